@@ -2,7 +2,7 @@
 """bench.py — headline benchmark of the spectrogram hot path (BASELINE.json metric:
 "STFT frames/sec + spectrogram Mpixels/sec at n_fft=2048, 1/2/4/8 MI355X").
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (the driver's form for N > 1)
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment makes this process a LAUNCHER: before anything touches the GPU
@@ -172,6 +172,17 @@ def launch_ranks(args, argv) -> int:
         raise
 
 
+def may_build(objdir) -> bool:
+    """Whether this process may write where __graft_entry__.build() writes even when everything is up to date: its lock file
+    <objdir>/.lock (or the directory that would hold it).  A tree built by another user, or mounted read-only, cannot be
+    built in; there bench.py runs the build that is there, and `import thesia_amd` still fails loudly if there is none."""
+    lock = os.path.join(objdir, ".lock")
+    d = lock
+    while not os.path.exists(d):
+        d = os.path.dirname(d)
+    return os.access(d, os.W_OK)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -186,6 +197,8 @@ def parse_args(argv=None):
     ap.add_argument("--no-full-cfg5", action="store_true", help="skip the strong-scaling anchor (all 1024 tracks of config 5 on one GPU)")
     ap.add_argument("--kernel", type=int, default=0, help="0 auto, 1 generic, 2 wave")
     ap.add_argument("--no-fused-image", action="store_true", help="quantise and raster as two kernels (A/B; the default fuses them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; rank 0's tracks; see dump_outputs)")
     return ap.parse_args(argv)
 
 
@@ -245,6 +258,7 @@ class Workload:
             if not any_row:
                 break
             tx += 1
+        self.geoms = geoms
         self.tile_px = sum(g.width * g.height for g in geoms)
         # every tile starts on a 256-byte boundary (the rasteriser stores 16 bytes per lane: an unaligned tile base
         # degrades it to 4-byte stores)
@@ -321,6 +335,50 @@ class Workload:
 
     def stft_only(self):
         self.plan.calc_spec_batch_dev(self.chan, self.minmax.data_ptr())
+
+
+DUMP_SAMPLE = 1 << 20        # elements per sampled array: spec and image 4 MB each, RGBA 16 MB (as float32)
+DUMP_SEED = 0x7E51A
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(torch, wl, out_dir):
+    """--dump-outputs: what the timed step left in its buffers, in the dense layout a caller of the path receives (no row
+    padding), as float32 .npy files.  The global dB range and every track's (min, max) are written whole; the dB spectrograms
+    (track, frame, bin), the u16 images (track, row, frame) and the level-0 RGBA tile pixels (track, pixel of the tiles in
+    `geoms` order, channel) as a fixed seeded sample of DUMP_SAMPLE positions, sorted, or whole when smaller.  The positions
+    depend only on the shapes, so two builds run with the same arguments are compared element for element."""
+    dev = wl.spec.device
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def positions(total):
+        if total <= DUMP_SAMPLE:
+            return np.arange(total, dtype=np.int64)
+        return np.sort(rng.choice(total, DUMP_SAMPLE, replace=False)).astype(np.int64)
+
+    def on_dev(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+    out = {"range_db": wl.range_db.cpu().numpy(), "minmax": wl.minmax.cpu().numpy()}
+    tr, fr, b = np.unravel_index(positions(wl.n_tracks * wl.T * wl.H), (wl.n_tracks, wl.T, wl.H))
+    out["spec_db_sample"] = wl.spec[on_dev(tr), on_dev(fr), on_dev(b)].cpu().numpy()
+    tr, row, fr = np.unravel_index(positions(wl.n_tracks * wl.H * wl.T), (wl.n_tracks, wl.H, wl.T))
+    img = wl.img[on_dev(tr), on_dev(row), on_dev(fr)].to(torch.int32) & 0xFFFF   # u16 held in an int16 tensor
+    out["image_u16_sample"] = img.cpu().numpy()
+    # tile pixel p of a track: tile k with first[k] <= p < first[k + 1], stored from slot[k] (tiles start on 64-pixel slots)
+    sizes = np.array([g.width * g.height for g in wl.geoms], dtype=np.int64)
+    first = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+    slot = np.concatenate([[0], np.cumsum(-(-sizes // 64) * 64)[:-1]])
+    tr, p = np.divmod(positions(wl.n_tracks * wl.tile_px), wl.tile_px)
+    k = np.searchsorted(first, p, side="right") - 1
+    out["tiles_rgba_sample"] = wl.rgba[on_dev(tr), on_dev(slot[k] + p - first[k])].cpu().numpy()
+    out = {name: a.astype(np.float32) for name, a in out.items()}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline(cmap_bytes, sr, n, win, hop, n_fft, target_s=15.0):
@@ -546,6 +604,8 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     if "WORLD_SIZE" not in os.environ:
         # launcher: N ranks as a child process, before anything here touches the GPU (TH_BENCH_FORCE_LAUNCHER=1 takes the
         # same route with N = 1: launcher -> torchrun -> rank -> RCCL process group, end to end on a one-GPU box)
@@ -562,7 +622,8 @@ def main():
         os.dup2(os.open(os.devnull, os.O_WRONLY), 1)
 
     import __graft_entry__ as ge
-    ge.build()  # no-op when up to date; serialised across ranks by a file lock
+    if may_build(ge.OBJDIR):
+        ge.build()  # no-op when up to date; serialised across ranks by a file lock
     import torch
     import thesia_amd as ta
 
@@ -627,6 +688,8 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device="cpu" if SHARE_GPU else dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:   # before anything below runs the step again or frees its buffers
+        dump_outputs(torch, wl, args.dump_outputs)
     # every rank must have quantised against the SAME global dB range (the path's one exchange): collect the ranks' [min_dB, max_dB]
     range_agrees = None
     if dist is not None:
