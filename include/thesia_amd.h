@@ -78,6 +78,7 @@ typedef enum {
 typedef struct th_ctx th_ctx;   /* device + stream + scratch */
 typedef struct th_plan th_plan; /* one SpectrogramAnalyzer cache entry */
 typedef struct th_tm th_tm;     /* TrackManager mirror */
+typedef struct th_tmg th_tmg;   /* TrackManager mirror over several devices of one process */
 
 /* ---------------------------------------------------------------- errors / info */
 TH_API const char *th_last_error(void);
@@ -458,6 +459,62 @@ TH_API int th_tm_mip_level(th_tm *tm, size_t id, uint32_t ch, uint32_t level_x, 
  * the pyramid passes (one per (axis length, level) some resident image needs; dropped with the last such image) and the
  * mip pyramids.  Any out pointer may be NULL. */
 TH_API int th_tm_lod_footprint(th_tm *tm, size_t *n_axis_tables, size_t *axis_table_bytes, size_t *mip_bytes);
+
+/* ---------------------------------------------------------------- TrackManager over several devices (one process) */
+/* th_tmg: the th_tm_* calls above, call for call, with a th_tmg * in place of the th_tm *; a multi-GPU host swaps one for
+ * the other.  Every result — updated ids, max_sr, db state, revisions, specs, images, tile bytes, batch offsets, render
+ * metadata — is bit-identical to that of ONE th_tm holding all the tracks after the same sequence of calls.
+ *   - Slots.  Each entry of `devices` is a slot with its own th_ctx and th_tm.  Duplicates are allowed ({0, 0}: two slots on
+ *     one card, which is how a one-GPU box runs the N-slot code).  th_tmg_create checks, in this order: devices != NULL,
+ *     1 <= n_devices <= 64, no negative entry (else TH_ERR_INVALID_ARG); a GPU at all (else TH_ERR_NO_DEVICE, no CPU
+ *     fallback); every entry < th_device_count (else TH_ERR_INVALID_ARG).
+ *   - Placement.  A track lives whole on one slot.  The new ids of an add_tracks batch (for an id given twice, its last
+ *     entry) are placed longest-first by weight = n_samples x n_channels, ties in input order, each on the slot with the
+ *     least resident weight, ties to the lowest slot (th_shard_assign starting from the resident loads).  A resident id
+ *     that is added again is replaced on its own slot.  Tracks never migrate; removals do not rebalance.
+ *   - The one coupling.  apply_track_list_changes, set_dB_range, set_setting and set_colormap fold every slot's channel
+ *     (min, max) in ascending (id, ch) order and every track's sample rate into one (min_dB, max_dB, max_sr), as one th_tm
+ *     does, and every slot quantises against it; when one slot must re-make all its images, every slot does.  updated_ids
+ *     is the ascending union over the slots.
+ *   - Concurrency.  The per-slot work of a mutator (staging, STFT, quantisation, pyramids) runs on one host thread per slot.
+ *     A slot's failure is reported on the caller's thread (th_last_error) with the slot and its device.  Tile getters run on
+ *     the caller's thread against the owning slot.  th_tmg has its own reader / writer lock: a tile reader never sees one
+ *     slot re-made while another is not.
+ *   - Transactions.  set_setting and add_tracks prepare on every slot, then commit everywhere or discard everywhere: a
+ *     failure leaves every slot exactly as it was (nothing added anywhere, revisions unchanged).
+ *   - Revisions.  One pair for the whole manager, moved exactly as one th_tm moves its own (lib.rs:192,221,243-245,265,284);
+ *     every slot stamps its tiles with it.
+ *   - Batched tiles.  get_spectrogram_tiles splits the requests by owner and serves the slots side by side; the records and
+ *     offsets are those of one th_tm (request order, 64-byte boundaries). */
+TH_API int th_tmg_create(const int *devices, size_t n_devices, th_tmg **out);
+TH_API int th_tmg_destroy(th_tmg *tmg);
+TH_API int th_tmg_n_devices(const th_tmg *tmg, size_t *n_devices);
+/* the slot (index into `devices`) that owns track id; TH_ERR_NOT_FOUND when it is not resident */
+TH_API int th_tmg_track_device(const th_tmg *tmg, size_t id, uint32_t *slot);
+TH_API int th_tmg_set_colormap(th_tmg *tmg, const uint8_t *rgba, size_t bytes);
+TH_API int th_tmg_set_setting(th_tmg *tmg, double win_ms, uint32_t t_overlap, uint32_t f_overlap, int freq_scale);
+TH_API int th_tmg_set_dB_range(th_tmg *tmg, float dB_range);
+TH_API int th_tmg_add_tracks(th_tmg *tmg, size_t n_tracks, const size_t *ids, const uint32_t *srs,
+                             const uint32_t *n_channels, const float *const *channels_flat, const size_t *n_samples);
+TH_API int th_tmg_remove_track(th_tmg *tmg, size_t id);
+TH_API int th_tmg_apply_track_list_changes(th_tmg *tmg, size_t *updated_ids, size_t cap, size_t *n_updated,
+                                           uint32_t *max_sr);
+TH_API int th_tmg_get_db_state(const th_tmg *tmg, float *min_dB, float *max_dB, uint32_t *max_sr);
+TH_API int th_tmg_spec_shape(const th_tmg *tmg, size_t id, uint32_t ch, size_t *n_frames, size_t *height);
+TH_API int th_tmg_img_shape(const th_tmg *tmg, size_t id, uint32_t ch, size_t *img_height, size_t *img_width);
+TH_API int th_tmg_copy_spec(th_tmg *tmg, size_t id, uint32_t ch, float *out, size_t capacity_floats);
+TH_API int th_tmg_copy_img(th_tmg *tmg, size_t id, uint32_t ch, uint16_t *out, size_t capacity_px);
+TH_API int th_tmg_revisions(const th_tmg *tmg, uint64_t *waveform_revision, uint64_t *spectrogram_revision);
+TH_API int th_tmg_get_spectrogram_tile(th_tmg *tmg, size_t id, uint32_t ch, uint32_t level_x, uint32_t level_y,
+                                       uint32_t tile_x, uint32_t tile_y, uint8_t *out, size_t out_capacity,
+                                       size_t *out_len);
+TH_API int th_tmg_get_spectrogram_tiles(th_tmg *tmg, const th_tile_request *reqs, size_t n, uint8_t *out,
+                                        size_t out_capacity, size_t *offsets /* n + 1 */, size_t *out_len);
+TH_API int th_tmg_get_waveform_tile(th_tmg *tmg, size_t id, uint32_t ch, uint32_t level, uint32_t tile_index,
+                                    uint8_t *out, size_t out_capacity, size_t *out_len);
+TH_API int th_tmg_get_audio_render_metadata(th_tmg *tmg, size_t id, uint32_t ch, double track_sec, int is_clipped,
+                                            th_render_metadata *out);
+TH_API int th_tmg_set_lod_source(th_tmg *tmg, int per_request);
 
 /* Test and measurement entry points (kernel selectors for A/B runs, per-launch kernel timing, replacing a resident image
  * with given pixels) are NOT part of this interface: include/thesia_amd_testing.h declares them; a thesia host binds none. */

@@ -203,6 +203,29 @@ _SIGS = {
     "th_tm_put_img": [vp, C.c_size_t, C.c_uint32, c_u16p, C.c_size_t, C.c_size_t],
     "th_tm_lod_footprint": [vp, c_szp, c_szp, c_szp],
     "th_tm_get_audio_render_metadata": [vp, C.c_size_t, C.c_uint32, C.c_double, C.c_int, C.POINTER(RenderMetadata)],
+    "th_tmg_create": [C.POINTER(C.c_int), C.c_size_t, C.POINTER(vp)],
+    "th_tmg_destroy": [vp],
+    "th_tmg_n_devices": [vp, c_szp],
+    "th_tmg_track_device": [vp, C.c_size_t, C.POINTER(C.c_uint32)],
+    "th_tmg_set_colormap": [vp, c_u8p, C.c_size_t],
+    "th_tmg_set_setting": [vp, C.c_double, C.c_uint32, C.c_uint32, C.c_int],
+    "th_tmg_set_dB_range": [vp, C.c_float],
+    "th_tmg_add_tracks": [vp, C.c_size_t, c_szp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(c_f32p),
+                          c_szp],
+    "th_tmg_remove_track": [vp, C.c_size_t],
+    "th_tmg_apply_track_list_changes": [vp, c_szp, C.c_size_t, c_szp, C.POINTER(C.c_uint32)],
+    "th_tmg_get_db_state": [vp, c_f32p, c_f32p, C.POINTER(C.c_uint32)],
+    "th_tmg_spec_shape": [vp, C.c_size_t, C.c_uint32, c_szp, c_szp],
+    "th_tmg_img_shape": [vp, C.c_size_t, C.c_uint32, c_szp, c_szp],
+    "th_tmg_copy_spec": [vp, C.c_size_t, C.c_uint32, c_f32p, C.c_size_t],
+    "th_tmg_copy_img": [vp, C.c_size_t, C.c_uint32, c_u16p, C.c_size_t],
+    "th_tmg_revisions": [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    "th_tmg_get_spectrogram_tile": [vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                    c_u8p, C.c_size_t, c_szp],
+    "th_tmg_get_spectrogram_tiles": [vp, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, c_szp, c_szp],
+    "th_tmg_get_waveform_tile": [vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, c_u8p, C.c_size_t, c_szp],
+    "th_tmg_get_audio_render_metadata": [vp, C.c_size_t, C.c_uint32, C.c_double, C.c_int, C.POINTER(RenderMetadata)],
+    "th_tmg_set_lod_source": [vp, C.c_int],
     "th_tile_cache_create": [C.c_size_t, C.POINTER(vp)],
     "th_tile_cache_destroy": [vp],
     "th_tile_cache_lookup": [vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), c_u8p, C.c_size_t,

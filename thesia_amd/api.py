@@ -725,3 +725,165 @@ class TrackManager:
         check(lib.th_tm_get_waveform_tile(self.handle, track_id, ch, level, tile_index, _ptr(out, c_u8p), out.size,
                                           C.byref(n)))
         return out[: n.value].tobytes()
+
+
+class MultiTrackManager:
+    """th_tmg: the TrackManager over several devices of one process (duplicates allowed: [0, 0] is two slots on one card).
+    Same method names as TrackManager; results are bit-identical to one TrackManager holding every track."""
+
+    def __init__(self, devices):
+        devs = [int(d) for d in devices]
+        arr = (C.c_int * max(len(devs), 1))(*devs)
+        h = vp()
+        check(lib.th_tmg_create(arr, len(devs), C.byref(h)))
+        self.handle, self.devices = h, devs
+        self._pin_ctx = None  # a context of devices[0], made on the first pinned tile batch (th_host_alloc needs one)
+        self._pin_free, self._pin_all, self._pin_lock = [], {}, threading.Lock()
+
+    PIN_POOL_MAX = TrackManager.PIN_POOL_MAX
+    _pin_checkout = TrackManager._pin_checkout  # (the same pool of pinned output buffers, allocated through self.ctx)
+    _pin_return = TrackManager._pin_return
+
+    @property
+    def ctx(self) -> Context:
+        with self._pin_lock:
+            if self._pin_ctx is None:
+                self._pin_ctx = Context(self.devices[0])
+            return self._pin_ctx
+
+    @property
+    def n_devices(self) -> int:
+        n = C.c_size_t()
+        check(lib.th_tmg_n_devices(self.handle, C.byref(n)))
+        return n.value
+
+    def device_of(self, track_id: int) -> int:
+        """The slot (index into `devices`) that owns the track."""
+        s = C.c_uint32()
+        check(lib.th_tmg_track_device(self.handle, track_id, C.byref(s)))
+        return s.value
+
+    def close(self):
+        if self.handle:
+            if self._pin_ctx is not None:
+                TrackManager._free_pinned(self)
+            check(lib.th_tmg_destroy(self.handle))
+            self.handle = None
+            if self._pin_ctx is not None:
+                self._pin_ctx.close()
+                self._pin_ctx = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def set_colormap(self, rgba: bytes):
+        a = np.frombuffer(bytes(rgba), np.uint8)
+        check(lib.th_tmg_set_colormap(self.handle, _ptr(a, c_u8p), a.size))
+
+    def set_setting(self, win_ms: float, t_overlap: int, f_overlap: int, freq_scale: int):
+        check(lib.th_tmg_set_setting(self.handle, win_ms, t_overlap, f_overlap, freq_scale))
+
+    def set_dB_range(self, dB_range: float):
+        check(lib.th_tmg_set_dB_range(self.handle, dB_range))
+
+    def add_tracks(self, tracks):
+        """tracks: iterable of (id, sr, planar ndarray [channels, samples])."""
+        tracks = [(i, sr, np.atleast_2d(_f32(w))) for i, sr, w in tracks]
+        n = len(tracks)
+        ids = (C.c_size_t * n)(*[t[0] for t in tracks])
+        srs = (C.c_uint32 * n)(*[t[1] for t in tracks])
+        nch = (C.c_uint32 * n)(*[t[2].shape[0] for t in tracks])
+        ns = (C.c_size_t * n)(*[t[2].shape[1] for t in tracks])
+        rows = [np.ascontiguousarray(t[2][c]) for t in tracks for c in range(t[2].shape[0])]
+        ptrs = (c_f32p * len(rows))(*[_ptr(r, c_f32p) for r in rows])
+        check(lib.th_tmg_add_tracks(self.handle, n, ids, srs, nch, ptrs, ns))
+
+    def remove_track(self, track_id: int):
+        check(lib.th_tmg_remove_track(self.handle, track_id))
+
+    def apply_track_list_changes(self):
+        cap = 4096
+        ids = (C.c_size_t * cap)()
+        n, sr = C.c_size_t(), C.c_uint32()
+        check(lib.th_tmg_apply_track_list_changes(self.handle, ids, cap, C.byref(n), C.byref(sr)))
+        return sorted(ids[i] for i in range(min(n.value, cap))), sr.value
+
+    def db_state(self):
+        lo, hi, sr = C.c_float(), C.c_float(), C.c_uint32()
+        check(lib.th_tmg_get_db_state(self.handle, C.byref(lo), C.byref(hi), C.byref(sr)))
+        return lo.value, hi.value, sr.value
+
+    def revisions(self):
+        w, s = C.c_uint64(), C.c_uint64()
+        check(lib.th_tmg_revisions(self.handle, C.byref(w), C.byref(s)))
+        return w.value, s.value
+
+    def spec(self, track_id: int, ch: int) -> np.ndarray:
+        t, h = C.c_size_t(), C.c_size_t()
+        check(lib.th_tmg_spec_shape(self.handle, track_id, ch, C.byref(t), C.byref(h)))
+        out = np.empty((t.value, h.value), np.float32)
+        check(lib.th_tmg_copy_spec(self.handle, track_id, ch, _ptr(out, c_f32p), out.size))
+        return out
+
+    def img(self, track_id: int, ch: int) -> np.ndarray:
+        h, w = C.c_size_t(), C.c_size_t()
+        check(lib.th_tmg_img_shape(self.handle, track_id, ch, C.byref(h), C.byref(w)))
+        out = np.empty((h.value, w.value), np.uint16)
+        check(lib.th_tmg_copy_img(self.handle, track_id, ch, _ptr(out, c_u16p), out.size))
+        return out
+
+    def get_spectrogram_tile(self, track_id: int, ch: int, level_x: int, level_y: int, tile_x: int,
+                             tile_y: int) -> bytes:
+        out = np.empty(SPECTROGRAM_TILE_MAX_BYTES, np.uint8)
+        n = C.c_size_t()
+        check(lib.th_tmg_get_spectrogram_tile(self.handle, track_id, ch, level_x, level_y, tile_x, tile_y,
+                                              _ptr(out, c_u8p), out.size, C.byref(n)))
+        return out[: n.value].tobytes()
+
+    def get_spectrogram_tiles(self, requests, pinned: bool = False):
+        """As TrackManager.get_spectrogram_tiles (th_tmg_get_spectrogram_tiles)."""
+        reqs = list(requests)
+        n = len(reqs)
+        arr = (_ffi.TileRequest * max(n, 1))(*[_ffi.TileRequest(*r, 0) for r in reqs])
+        offs = (C.c_size_t * (n + 1))()
+        need = C.c_size_t()
+        rc = lib.th_tmg_get_spectrogram_tiles(self.handle, arr, n, None, 0, offs, C.byref(need))
+        if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+            check(rc)
+        if n == 0 or need.value == 0:
+            return []
+        if pinned:
+            cap, pin = self._pin_checkout(need.value)
+            try:
+                check(lib.th_tmg_get_spectrogram_tiles(self.handle, arr, n, pin, cap, offs, C.byref(need)))
+                out = bytes((C.c_uint8 * need.value).from_address(pin.value))
+            finally:
+                self._pin_return(cap, pin)
+        else:
+            b = np.empty(need.value, np.uint8)
+            check(lib.th_tmg_get_spectrogram_tiles(self.handle, arr, n, b.ctypes.data_as(C.c_void_p), b.size, offs,
+                                                   C.byref(need)))
+            out = b.tobytes()
+        tiles = []
+        for i in range(n):
+            w, h = struct.unpack_from("<II", out, offs[i] + 8)
+            tiles.append(out[offs[i]: offs[i] + 40 + 4 * w * h])
+        return tiles
+
+    def set_lod_source(self, per_request: bool) -> None:
+        check(lib.th_tmg_set_lod_source(self.handle, int(per_request)))
+
+    def render_metadata(self, track_id: int, ch: int, track_sec: float, is_clipped: bool) -> dict:
+        m = _ffi.RenderMetadata()
+        check(lib.th_tmg_get_audio_render_metadata(self.handle, track_id, ch, track_sec, int(is_clipped), C.byref(m)))
+        return {k: getattr(m, k) for k, _ in m._fields_}
+
+    def get_waveform_tile(self, track_id: int, ch: int, level: int, tile_index: int) -> bytes:
+        out = np.empty(WAVEFORM_TILE_MAX_BYTES, np.uint8)
+        n = C.c_size_t()
+        check(lib.th_tmg_get_waveform_tile(self.handle, track_id, ch, level, tile_index, _ptr(out, c_u8p), out.size,
+                                           C.byref(n)))
+        return out[: n.value].tobytes()

@@ -163,12 +163,13 @@ void global_db_range(const float *mins, const float *maxs, size_t n, float dB_ra
 
 // Longest-processing-time-first assignment: units sorted by weight (descending, index ascending
 // on ties) go to the currently least-loaded rank (lowest rank on ties).  Equal weights reduce to
-// round-robin, e.g. 1024 equal tracks on 8 GPUs = 128 per GPU.
-void shard_assign(const uint64_t *weights, size_t n, uint32_t world, uint32_t *owner) {
+// round-robin, e.g. 1024 equal tracks on 8 GPUs = 128 per GPU.  With load0 the ranks start from those loads instead of 0.
+void shard_assign(const uint64_t *weights, size_t n, uint32_t world, uint32_t *owner, const uint64_t *load0) {
     std::vector<size_t> order(n);
     for (size_t i = 0; i < n; i++) order[i] = i;
     std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return weights[a] > weights[b]; });
     std::vector<uint64_t> load(world, 0);
+    if (load0) load.assign(load0, load0 + world);
     for (size_t i : order) {
         uint32_t best = 0;
         for (uint32_t r = 1; r < world; r++)

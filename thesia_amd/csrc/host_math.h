@@ -18,7 +18,8 @@ std::vector<float> calc_mel_fb(uint32_t sr, size_t n_fft, size_t n_mel, float fm
 void mel_fb_points(uint32_t sr, size_t n_fft, size_t n_mel, float fmin, float fmax, std::vector<float> &lin, std::vector<float> &mf);
 size_t mel_default_n_mel(uint32_t sr, size_t n_fft);
 void hz_range_to_idx(int freq_scale, float hz0, float hz1, uint32_t sr, size_t n, size_t *i0, size_t *i1);
-void shard_assign(const uint64_t *weights, size_t n, uint32_t world, uint32_t *owner);
+// load0 (world entries, may be NULL = all zero): the ranks' loads before these units (th_tmg: the resident tracks' weights)
+void shard_assign(const uint64_t *weights, size_t n, uint32_t world, uint32_t *owner, const uint64_t *load0 = nullptr);
 void global_db_range(const float *mins, const float *maxs, size_t n, float dB_range, float *mn, float *mx);
 
 // Tables of a Bluestein plan (stft_bluestein_kernel, kernels_stft.hip): interleaved (re, im) doubles.  nc = n_fft / 2 points,

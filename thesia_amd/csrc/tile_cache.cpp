@@ -67,6 +67,18 @@ void th_tile_cache::invalidate_spectrogram() {
     spectrogram_revision = bump(spectrogram_revision);
 }
 
+void th_tile_cache::set_revisions(uint64_t waveform, uint64_t spectrogram) {
+    std::lock_guard<std::mutex> lk(mu);
+    if (waveform != waveform_revision) {
+        waveform_revision = waveform;
+        lru.clear();
+        entries.clear();
+        entries.rehash(0);
+        bytes = 0;
+    }
+    spectrogram_revision = spectrogram;
+}
+
 void th_tile_cache::set_budget(size_t budget) {
     std::lock_guard<std::mutex> lk(mu);
     budget_bytes = budget;

@@ -52,6 +52,9 @@ struct th_tile_cache {
         invalidate_spectrogram();
     }
     void set_budget(size_t budget);
+    // th_tmg: every slot's cache carries the revisions of the whole manager (a changed waveform revision drops the tiles,
+    // as invalidate_waveform does)
+    void set_revisions(uint64_t waveform, uint64_t spectrogram);
 
     mutable std::mutex mu;  // the reference wraps the cache in an RwLock (lib.rs:38)
     std::list<Entry> lru;   // front = most recently used

@@ -30,6 +30,7 @@
 #include "host_math.h"
 #include "kernels.h"
 #include "tile_cache.h"
+#include "track_manager_internal.h"
 
 using namespace th;
 
@@ -639,10 +640,14 @@ int build_mips(th_tm *tm, const std::vector<Channel *> &chans) {
     return TH_OK;
 }
 
-// TrackManager::update_spec_imgs — core/mod.rs:168-230
-int update_spec_imgs(th_tm *tm, bool force_update_all, std::vector<size_t> *updated) {
+// TrackManager::update_spec_imgs — core/mod.rs:168-230.  `global` (th_tmg): the range and max_sr of the tracks of every slot,
+// folded by the caller, in place of this manager's own
+int update_spec_imgs(th_tm *tm, bool force_update_all, std::vector<size_t> *updated, const tmi::DbRange *global = nullptr) {
     float mn = INFINITY, mx = -INFINITY;
-    {
+    if (global) {
+        mn = global->min_dB;
+        mx = global->max_dB;
+    } else {
         std::vector<float> mins, maxs;
         for (auto &kv : tm->tracks)
             for (Channel &ch : kv.second.ch)
@@ -663,6 +668,7 @@ int update_spec_imgs(th_tm *tm, bool force_update_all, std::vector<size_t> *upda
     }
     uint32_t max_sr = 0;  // TrackList::max_sr, track.rs:371-376
     for (auto &kv : tm->tracks) max_sr = std::max(max_sr, kv.second.sr);
+    if (global) max_sr = global->max_sr;
     if (tm->max_sr != max_sr) {
         tm->max_sr = max_sr;
         need_update_all = true;
@@ -886,16 +892,10 @@ TH_API int th_tm_set_colormap(th_tm *tm, const uint8_t *rgba, size_t bytes) {
     TH_TRY
     TH_REQUIRE(tm && rgba, "NULL argument");
     std::unique_lock<std::shared_mutex> wl(tm->rw);
-    TH_HIP(hipSetDevice(tm->ctx->device));
-    // RenderTileCache::set_colormap keeps the old map for malformed input — render_tiles.rs:80-85
-    if (bytes >= 4 && bytes % 4 == 0) {
-        tm->colormap_rgba.assign(rgba, rgba + bytes);
-        int rc = upload_colormap(tm);
-        if (rc != TH_OK) return rc;
-    }
+    int rc = tmi::set_colormap_only(tm, rgba, bytes);
+    if (rc != TH_OK) return rc;
     tm->invalidate_spectrogram();
-    // init: TM.set_colormap_length(len / 4) → update_spec_imgs(force) — lib.rs:61, core/mod.rs:128-131
-    tm->colormap_length = (uint32_t)(bytes / 4);
+    // → update_spec_imgs(force) — lib.rs:61, core/mod.rs:128-131
     std::vector<size_t> upd;
     return writer_done(tm, update_spec_imgs(tm, true, &upd));
     TH_CATCH
@@ -907,31 +907,10 @@ TH_API int th_tm_set_setting(th_tm *tm, double win_ms, uint32_t t_overlap, uint3
     TH_REQUIRE(win_ms > 0. && t_overlap >= 1 && f_overlap >= 1, "invalid SpecSetting (lib.rs:275-277)");
     TH_REQUIRE(freq_scale == TH_FREQ_LINEAR || freq_scale == TH_FREQ_MEL, "bad freq_scale");
     std::unique_lock<std::shared_mutex> wl(tm->rw);
-    TH_HIP(hipSetDevice(tm->ctx->device));
-    // Transactional: plans and specs of the NEW setting are made first, into fresh buffers; the manager's own state
-    // changes only when all of it exists.  (The reference cannot fail here: realfft takes any even length.  This
-    // library plans n_fft = 2^a * odd with a >= 1 and odd <= 63, up to TH_MAX_N_FFT (th_plan_create): f_overlap = 3, 5, 6, 7 run
-    // on the generic kernel; e.g. f_overlap = 67 or an n_fft above 2^20 is refused and leaves everything as it was.)
-    const Setting st{win_ms, t_overlap, f_overlap, freq_scale};
-    std::vector<std::pair<uint32_t, Channel *>> chans;
-    for (auto &kv : tm->tracks)
-        for (Channel &ch : kv.second.ch) chans.push_back({kv.second.sr, &ch});
-    std::map<PlanKey, th_plan *> created;
-    std::vector<NewSpec> fresh;
-    int rc = compute_specs(tm, st, chans, created, &fresh);
-    if (rc != TH_OK) {
-        (void)hipStreamSynchronize(tm->ctx->stream);
-        free_new_specs(fresh);
-        for (auto &kv : created) th_plan_destroy(kv.second);
-        return rc;
-    }
-    tm->win_ms = win_ms;
-    tm->t_overlap = t_overlap;
-    tm->f_overlap = f_overlap;
-    tm->freq_scale = freq_scale;
-    for (auto &kv : created) tm->plans[kv.first] = kv.second;
-    commit_specs(fresh);
-    retain_plans(tm);  // spec_analyzer.retain(...)  core/mod.rs:111-112
+    tmi::StagedPtr staged;
+    int rc = tmi::prepare_setting(tm, win_ms, t_overlap, f_overlap, freq_scale, &staged);
+    if (rc != TH_OK) return rc;
+    tmi::commit(tm, std::move(staged));
     std::vector<size_t> upd;
     rc = update_spec_imgs(tm, true, &upd);
     tm->invalidate_spectrogram();  // lib.rs:284
@@ -967,122 +946,11 @@ TH_API int th_tm_add_tracks(th_tm *tm, size_t n_tracks, const size_t *ids, const
         }
     }
     std::unique_lock<std::shared_mutex> wl(tm->rw);
-    th_ctx *c = tm->ctx;
-    TH_HIP(hipSetDevice(c->device));
-    // Transactional: the new tracks are staged (audio upload, waveform pyramid, spec) beside the resident ones and
-    // swapped in when everything has succeeded.  A failure frees the staging area and changes nothing.
-    // Pipelined (round 6; the reference overlaps decode and calc_spec across rayon tasks, core/track.rs:211-239 -> core/mod.rs:
-    // 153-163): the tracks go up in GROUPS on a copy stream of the manager's own; the waveform pyramids and the STFT of group g run
-    // on the context stream (behind an event of the copy stream) while the host feeds group g + 1 to the copy engine — a pageable
-    // source keeps the calling thread inside hipMemcpyAsync for the length of the transfer, so the kernels of the group before
-    // cost nothing; nothing waits for the device until the end (one synchronisation, then the per-channel (min, max) read-back).
-    // Inputs stay borrowed until the call returns.
-    std::map<size_t, Track> staged;
-    std::map<PlanKey, th_plan *> created;
-    std::vector<NewSpec> fresh;
-    std::vector<PendingMinMax> pending;
-    TH_REQUIRE(tm->copy_stream != nullptr && tm->copy_ev != nullptr, "manager without its copy stream");  // (th_tm_create)
-    auto abort_staging = [&]() {
-        (void)hipStreamSynchronize(tm->copy_stream);
-        (void)hipStreamSynchronize(c->stream);
-        (void)finish_specs(tm, pending, &fresh, false);
-        free_new_specs(fresh);
-        for (auto &kv : staged) free_track(kv.second);
-        for (auto &kv : created) th_plan_destroy(kv.second);
-    };
-    int rc = TH_OK;
-    hipError_t e = hipSuccess;
-    std::vector<size_t> added;
-    const bool prof = getenv("TH_TM_PROF") != nullptr;
-    auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double tp0 = now();
-    // the same id twice in one call: the later one wins, as sequential adds would — only its data is uploaded
-    std::map<size_t, size_t> last_of;
-    std::vector<size_t> flat0(n_tracks, 0);
-    {
-        size_t flat = 0;
-        for (size_t t = 0; t < n_tracks; t++) {
-            last_of[ids[t]] = t;
-            flat0[t] = flat;
-            flat += n_channels[t];
-            added.push_back(ids[t]);
-        }
-    }
-    // groups of about 96 MB of samples (at least one track each): a group's launches cost ~0.2 ms of host time (descriptor tables,
-    // spec allocations: six groups of 32 MB were SLOWER than no pipeline, 6.0 against 5.1 ms for 32 tracks), the last group's
-    // kernels are the only ones nothing hides.  (Round 6, tried: the uploads on a helper thread so that this thread's launches do
-    // not hold up the copy engine — the launches then take 1.15 ms of host time instead of 0.67 and the call 5.2 instead of 4.9 ms:
-    // the runtime serialises the pageable copy path and the launches of the two threads.)
-    constexpr size_t GROUP_BYTES = (size_t)96 << 20;
-    const Setting st = setting_of(tm);
-    size_t t = 0;
-    double t_launch = 0.0;
-    while (t < n_tracks && e == hipSuccess && rc == TH_OK) {
-        std::vector<std::pair<uint32_t, Channel *>> chans;
-        std::vector<th_pyramid_desc> pdescs;
-        size_t bytes = 0;
-        for (; t < n_tracks && (bytes == 0 || bytes < GROUP_BYTES) && e == hipSuccess; t++) {
-            if (last_of[ids[t]] != t) continue;
-            Track &tr = staged[ids[t]];
-            tr.sr = srs[t];
-            tr.ch.assign(n_channels[t], Channel());
-            // resident waveform pyramid: levels up to the one whose single bin spans the channel (render_tiles.rs:232-259)
-            // (levels PYR_FIRST .. lv - 1: level 0 would be (x, x, x) per sample — half of the pyramid's bytes — and level 1 a
-            // quarter; tiles of both are served from the resident samples instead, th_pyramid_desc.first_level)
-            const size_t n = n_samples[t];
-            uint32_t lv = 1;
-            while (lv < PYR_MAX_LEVELS && ((uint64_t)1 << (lv - 1)) < n) lv++;
-            const size_t wav_f = (n + 63) / 64 * 64;  // (256-byte pieces: every view starts on a 256-byte boundary)
-            const size_t pyr_f = (std::max<size_t>(1, th_waveform_pyramid_offset(n, std::max(lv, PYR_FIRST)) - th_waveform_pyramid_offset(n, PYR_FIRST)) + 63) / 64 * 64;
-            e = hipMalloc(&tr.d_pool, (wav_f + pyr_f) * n_channels[t] * sizeof(float));
-            for (uint32_t k = 0; k < n_channels[t] && e == hipSuccess; k++) {
-                Channel &ch = tr.ch[k];
-                ch.n = n;
-                ch.pyr_levels = lv;
-                ch.d_wav = static_cast<float *>(tr.d_pool) + (size_t)k * (wav_f + pyr_f);
-                ch.d_pyr = ch.d_wav + wav_f;
-                e = hipMemcpyAsync(ch.d_wav, channels_flat[flat0[t] + k], ch.n * sizeof(float), hipMemcpyHostToDevice, tm->copy_stream);
-                bytes += ch.n * sizeof(float);
-                // (std::map nodes and this vector do not move any more: the pointer stays valid while later groups are staged)
-                chans.push_back({tr.sr, &ch});
-                pdescs.push_back(th_pyramid_desc{ch.d_wav, ch.d_pyr, ch.n, ch.pyr_levels, PYR_FIRST});
-            }
-        }
-        if (e != hipSuccess) break;
-        if (chans.empty()) continue;
-        const double tl0 = now();
-        e = hipEventRecord(tm->copy_ev, tm->copy_stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, tm->copy_ev, 0);
-        if (e != hipSuccess) break;
-        rc = th_waveform_pyramid_dev(c, pdescs.data(), pdescs.size());
-        if (rc == TH_OK) rc = compute_specs(tm, st, chans, created, &fresh, &pending);
-        t_launch += now() - tl0;
-    }
-    const double tp1 = now();
-    if (e == hipSuccess && rc == TH_OK) e = hipStreamSynchronize(tm->copy_stream);  // inputs are borrowed for this call only
-    if (e == hipSuccess && rc == TH_OK) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess || rc != TH_OK) {
-        abort_staging();
-        if (rc != TH_OK) return rc;
-        TH_HIP(e);
-    }
-    rc = finish_specs(tm, pending, &fresh, true);
-    if (prof) fprintf(stderr, "th_tm_add_tracks prof: staging + launches %.2f ms (of which pyramid / STFT launches %.2f), drain %.2f\n", tp1 - tp0, t_launch, now() - tp1);
-    if (rc != TH_OK) {
-        abort_staging();
-        return rc;
-    }
-    commit_specs(fresh);  // (into the staged channels)
-    for (auto &kv : created) tm->plans[kv.first] = kv.second;
-    for (auto &kv : staged) {
-        Track &dst = tm->tracks[kv.first];  // re-adding an id replaces it (reload_tracks, core/mod.rs:73-82)
-        free_track(dst);
-        dst = std::move(kv.second);
-        kv.second.d_pool = nullptr;
-    }
-    std::set<size_t> uniq(added.begin(), added.end());
-    tm->no_spec_img_ids.insert(tm->no_spec_img_ids.end(), uniq.begin(), uniq.end());  // core/mod.rs:70
-    tm->invalidate_all();                                                             // lib.rs:192
+    tmi::StagedPtr staged;
+    int rc = tmi::prepare_add(tm, n_tracks, ids, srs, n_channels, channels_flat, n_samples, &staged);
+    if (rc != TH_OK) return rc;
+    tmi::commit(tm, std::move(staged));
+    tm->invalidate_all();  // lib.rs:192
     return writer_done(tm, TH_OK);
     TH_CATCH
 }
@@ -1648,3 +1516,226 @@ TH_API int th_tm_mip_level(th_tm *tm, size_t id, uint32_t ch, uint32_t level_x, 
     return TH_OK;
     TH_CATCH
 }
+
+// ---------------------------------------------------------------------------------------------- steps th_tmg drives per slot
+namespace th {
+namespace tmi {
+
+struct Staged {
+    th_tm *tm = nullptr;
+    bool setting = false;  // set_setting: st + the specs of every resident channel; add_tracks: tracks (+ their specs), added
+    Setting st{};
+    std::map<PlanKey, th_plan *> created;
+    std::vector<NewSpec> fresh;
+    std::map<size_t, Track> tracks;
+    std::set<size_t> added;
+};
+
+void StagedDeleter::operator()(Staged *s) const {
+    if (!s) return;
+    if (!s->fresh.empty() || !s->tracks.empty() || !s->created.empty()) {  // not committed: discard
+        (void)hipSetDevice(s->tm->ctx->device);
+        (void)hipStreamSynchronize(s->tm->copy_stream);
+        (void)hipStreamSynchronize(s->tm->ctx->stream);
+        free_new_specs(s->fresh);
+        for (auto &kv : s->tracks) free_track(kv.second);
+        for (auto &kv : s->created) th_plan_destroy(kv.second);
+    }
+    delete s;
+}
+
+std::shared_mutex &rw_of(th_tm *tm) { return tm->rw; }
+
+void list_extrema(th_tm *tm, std::vector<ChanExtremum> *out) {
+    for (auto &kv : tm->tracks)
+        for (size_t k = 0; k < kv.second.ch.size(); k++)
+            if (kv.second.ch[k].has_spec) out->push_back(ChanExtremum{kv.first, (uint32_t)k, kv.second.ch[k].mn, kv.second.ch[k].mx});
+}
+
+void list_rates(th_tm *tm, std::vector<uint32_t> *out) {
+    for (auto &kv : tm->tracks) out->push_back(kv.second.sr);
+}
+
+// Transactional: plans and specs of the NEW setting are made first, into fresh buffers; the manager's own state changes only
+// in commit.  (The reference cannot fail here: realfft takes any even length.  This library plans n_fft = 2^a * odd with
+// a >= 1 and odd <= 63, up to TH_MAX_N_FFT (th_plan_create): f_overlap = 3, 5, 6, 7 run on the generic kernel; e.g.
+// f_overlap = 67 or an n_fft above 2^20 is refused and leaves everything as it was.)
+int prepare_setting(th_tm *tm, double win_ms, uint32_t t_overlap, uint32_t f_overlap, int freq_scale, StagedPtr *out) {
+    TH_HIP(hipSetDevice(tm->ctx->device));
+    StagedPtr stg(new Staged);
+    stg->tm = tm;
+    stg->setting = true;
+    stg->st = Setting{win_ms, t_overlap, f_overlap, freq_scale};
+    std::vector<std::pair<uint32_t, Channel *>> chans;
+    for (auto &kv : tm->tracks)
+        for (Channel &ch : kv.second.ch) chans.push_back({kv.second.sr, &ch});
+    const int rc = compute_specs(tm, stg->st, chans, stg->created, &stg->fresh);
+    if (rc != TH_OK) return rc;  // (stg discards what was made)
+    *out = std::move(stg);
+    return TH_OK;
+}
+
+int prepare_add(th_tm *tm, size_t n_tracks, const size_t *ids, const uint32_t *srs, const uint32_t *n_channels,
+                const float *const *channels_flat, const size_t *n_samples, StagedPtr *out) {
+    th_ctx *c = tm->ctx;
+    TH_HIP(hipSetDevice(c->device));
+    // Transactional: the new tracks are staged (audio upload, waveform pyramid, spec) beside the resident ones and
+    // swapped in when everything has succeeded.  A failure frees the staging area and changes nothing.
+    // Pipelined (round 6; the reference overlaps decode and calc_spec across rayon tasks, core/track.rs:211-239 -> core/mod.rs:
+    // 153-163): the tracks go up in GROUPS on a copy stream of the manager's own; the waveform pyramids and the STFT of group g run
+    // on the context stream (behind an event of the copy stream) while the host feeds group g + 1 to the copy engine — a pageable
+    // source keeps the calling thread inside hipMemcpyAsync for the length of the transfer, so the kernels of the group before
+    // cost nothing; nothing waits for the device until the end (one synchronisation, then the per-channel (min, max) read-back).
+    // Inputs stay borrowed until the call returns.
+    StagedPtr stg(new Staged);
+    stg->tm = tm;
+    std::map<size_t, Track> &staged = stg->tracks;
+    std::map<PlanKey, th_plan *> &created = stg->created;
+    std::vector<NewSpec> &fresh = stg->fresh;
+    std::vector<PendingMinMax> pending;
+    TH_REQUIRE(tm->copy_stream != nullptr && tm->copy_ev != nullptr, "manager without its copy stream");  // (th_tm_create)
+    auto abort_staging = [&]() {  // (the staged specs, tracks and plans go with stg)
+        (void)hipStreamSynchronize(tm->copy_stream);
+        (void)hipStreamSynchronize(c->stream);
+        (void)finish_specs(tm, pending, &fresh, false);
+        stg.reset();
+    };
+    int rc = TH_OK;
+    hipError_t e = hipSuccess;
+    std::vector<size_t> added;
+    const bool prof = getenv("TH_TM_PROF") != nullptr;
+    auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double tp0 = now();
+    // the same id twice in one call: the later one wins, as sequential adds would — only its data is uploaded
+    std::map<size_t, size_t> last_of;
+    std::vector<size_t> flat0(n_tracks, 0);
+    {
+        size_t flat = 0;
+        for (size_t t = 0; t < n_tracks; t++) {
+            last_of[ids[t]] = t;
+            flat0[t] = flat;
+            flat += n_channels[t];
+            added.push_back(ids[t]);
+        }
+    }
+    // groups of about 96 MB of samples (at least one track each): a group's launches cost ~0.2 ms of host time (descriptor tables,
+    // spec allocations: six groups of 32 MB were SLOWER than no pipeline, 6.0 against 5.1 ms for 32 tracks), the last group's
+    // kernels are the only ones nothing hides.  (Round 6, tried: the uploads on a helper thread so that this thread's launches do
+    // not hold up the copy engine — the launches then take 1.15 ms of host time instead of 0.67 and the call 5.2 instead of 4.9 ms:
+    // the runtime serialises the pageable copy path and the launches of the two threads.)
+    constexpr size_t GROUP_BYTES = (size_t)96 << 20;
+    const Setting st = setting_of(tm);
+    size_t t = 0;
+    double t_launch = 0.0;
+    while (t < n_tracks && e == hipSuccess && rc == TH_OK) {
+        std::vector<std::pair<uint32_t, Channel *>> chans;
+        std::vector<th_pyramid_desc> pdescs;
+        size_t bytes = 0;
+        for (; t < n_tracks && (bytes == 0 || bytes < GROUP_BYTES) && e == hipSuccess; t++) {
+            if (last_of[ids[t]] != t) continue;
+            Track &tr = staged[ids[t]];
+            tr.sr = srs[t];
+            tr.ch.assign(n_channels[t], Channel());
+            // resident waveform pyramid: levels up to the one whose single bin spans the channel (render_tiles.rs:232-259)
+            // (levels PYR_FIRST .. lv - 1: level 0 would be (x, x, x) per sample — half of the pyramid's bytes — and level 1 a
+            // quarter; tiles of both are served from the resident samples instead, th_pyramid_desc.first_level)
+            const size_t n = n_samples[t];
+            uint32_t lv = 1;
+            while (lv < PYR_MAX_LEVELS && ((uint64_t)1 << (lv - 1)) < n) lv++;
+            const size_t wav_f = (n + 63) / 64 * 64;  // (256-byte pieces: every view starts on a 256-byte boundary)
+            const size_t pyr_f = (std::max<size_t>(1, th_waveform_pyramid_offset(n, std::max(lv, PYR_FIRST)) - th_waveform_pyramid_offset(n, PYR_FIRST)) + 63) / 64 * 64;
+            e = hipMalloc(&tr.d_pool, (wav_f + pyr_f) * n_channels[t] * sizeof(float));
+            for (uint32_t k = 0; k < n_channels[t] && e == hipSuccess; k++) {
+                Channel &ch = tr.ch[k];
+                ch.n = n;
+                ch.pyr_levels = lv;
+                ch.d_wav = static_cast<float *>(tr.d_pool) + (size_t)k * (wav_f + pyr_f);
+                ch.d_pyr = ch.d_wav + wav_f;
+                e = hipMemcpyAsync(ch.d_wav, channels_flat[flat0[t] + k], ch.n * sizeof(float), hipMemcpyHostToDevice, tm->copy_stream);
+                bytes += ch.n * sizeof(float);
+                // (std::map nodes and this vector do not move any more: the pointer stays valid while later groups are staged)
+                chans.push_back({tr.sr, &ch});
+                pdescs.push_back(th_pyramid_desc{ch.d_wav, ch.d_pyr, ch.n, ch.pyr_levels, PYR_FIRST});
+            }
+        }
+        if (e != hipSuccess) break;
+        if (chans.empty()) continue;
+        const double tl0 = now();
+        e = hipEventRecord(tm->copy_ev, tm->copy_stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, tm->copy_ev, 0);
+        if (e != hipSuccess) break;
+        rc = th_waveform_pyramid_dev(c, pdescs.data(), pdescs.size());
+        if (rc == TH_OK) rc = compute_specs(tm, st, chans, created, &fresh, &pending);
+        t_launch += now() - tl0;
+    }
+    const double tp1 = now();
+    if (e == hipSuccess && rc == TH_OK) e = hipStreamSynchronize(tm->copy_stream);  // inputs are borrowed for this call only
+    if (e == hipSuccess && rc == TH_OK) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess || rc != TH_OK) {
+        abort_staging();
+        if (rc != TH_OK) return rc;
+        TH_HIP(e);
+    }
+    rc = finish_specs(tm, pending, &fresh, true);
+    if (prof) fprintf(stderr, "th_tm_add_tracks prof: staging + launches %.2f ms (of which pyramid / STFT launches %.2f), drain %.2f\n", tp1 - tp0, t_launch, now() - tp1);
+    if (rc != TH_OK) {
+        abort_staging();
+        return rc;
+    }
+    stg->added.insert(added.begin(), added.end());
+    *out = std::move(stg);
+    return TH_OK;
+}
+
+void commit(th_tm *tm, StagedPtr s) {
+    (void)hipSetDevice(tm->ctx->device);
+    if (s->setting) {
+        tm->win_ms = s->st.win_ms;
+        tm->t_overlap = s->st.t_overlap;
+        tm->f_overlap = s->st.f_overlap;
+        tm->freq_scale = s->st.freq_scale;
+        for (auto &kv : s->created) tm->plans[kv.first] = kv.second;
+        s->created.clear();
+        commit_specs(s->fresh);
+        retain_plans(tm);  // spec_analyzer.retain(...)  core/mod.rs:111-112
+        return;
+    }
+    commit_specs(s->fresh);  // (into the staged channels)
+    for (auto &kv : s->created) tm->plans[kv.first] = kv.second;
+    s->created.clear();
+    for (auto &kv : s->tracks) {
+        Track &dst = tm->tracks[kv.first];  // re-adding an id replaces it (reload_tracks, core/mod.rs:73-82)
+        free_track(dst);
+        dst = std::move(kv.second);
+        kv.second.d_pool = nullptr;
+    }
+    s->tracks.clear();
+    tm->no_spec_img_ids.insert(tm->no_spec_img_ids.end(), s->added.begin(), s->added.end());  // core/mod.rs:70
+}
+
+int requantise(th_tm *tm, const DbRange *global, bool force_update_all, bool images_only, std::vector<size_t> *updated) {
+    TH_HIP(hipSetDevice(tm->ctx->device));
+    const int rc = update_spec_imgs(tm, force_update_all, updated, global);
+    return images_only ? writer_done_images(tm, rc) : writer_done(tm, rc);
+}
+
+int set_colormap_only(th_tm *tm, const uint8_t *rgba, size_t bytes) {
+    TH_HIP(hipSetDevice(tm->ctx->device));
+    // RenderTileCache::set_colormap keeps the old map for malformed input — render_tiles.rs:80-85
+    if (bytes >= 4 && bytes % 4 == 0) {
+        tm->colormap_rgba.assign(rgba, rgba + bytes);
+        int rc = upload_colormap(tm);
+        if (rc != TH_OK) return rc;
+    }
+    // init: TM.set_colormap_length(len / 4) — lib.rs:61, core/mod.rs:128-131 (its update_spec_imgs(force) is the caller's)
+    tm->colormap_length = (uint32_t)(bytes / 4);
+    return TH_OK;
+}
+
+int settle(th_tm *tm) {
+    TH_HIP(hipSetDevice(tm->ctx->device));
+    return writer_done(tm, TH_OK);
+}
+
+}  // namespace tmi
+}  // namespace th

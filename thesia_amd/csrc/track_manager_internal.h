@@ -1,0 +1,58 @@
+// track_manager_internal.h — what th_tmg (track_manager_multi.hip) drives inside each slot's th_tm (track_manager.hip).
+// Not part of the C ABI.  None of these functions takes the manager's lock: the caller holds rw_of(tm) (or has the only
+// reference to the manager), exactly as the th_tm_* entry points do around the same steps.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <memory>
+#include <shared_mutex>
+#include <vector>
+
+#include "common.h"
+
+namespace th {
+namespace tmi {
+
+std::shared_mutex &rw_of(th_tm *tm);
+
+// The global values the image step quantises against (update_spec_imgs, core/mod.rs:169-185)
+struct DbRange {
+    float min_dB, max_dB;
+    uint32_t max_sr;
+};
+
+// (mn, mx) of every channel that has a spec, in ascending (id, ch) — the order update_spec_imgs folds them in
+struct ChanExtremum {
+    size_t id;
+    uint32_t ch;
+    float mn, mx;
+};
+void list_extrema(th_tm *tm, std::vector<ChanExtremum> *out);
+// sample rate of every resident track (TrackList::max_sr folds these)
+void list_rates(th_tm *tm, std::vector<uint32_t> *out);
+
+// Work staged beside the manager by a prepare step (plans, specs and, for add_tracks, whole tracks), not yet visible to it.
+// commit() swaps it in and cannot fail; destroying a Staged that was not committed frees all of it (the discard).
+struct Staged;
+struct StagedDeleter {
+    void operator()(Staged *s) const;
+};
+using StagedPtr = std::unique_ptr<Staged, StagedDeleter>;
+
+// set_setting (core/mod.rs:107-115): the plans and specs of the new setting for every resident channel
+int prepare_setting(th_tm *tm, double win_ms, uint32_t t_overlap, uint32_t f_overlap, int freq_scale, StagedPtr *out);
+// add_tracks (core/mod.rs:62-71): arguments as th_tm_add_tracks, already validated
+int prepare_add(th_tm *tm, size_t n_tracks, const size_t *ids, const uint32_t *srs, const uint32_t *n_channels,
+                const float *const *channels_flat, const size_t *n_samples, StagedPtr *out);
+void commit(th_tm *tm, StagedPtr staged);
+
+// update_spec_imgs against `global` (NULL: the manager's own tracks, as th_tm_* does), then the writer's final wait:
+// for the images only (apply_track_list_changes, set_dB_range) or for everything (set_setting, set_colormap)
+int requantise(th_tm *tm, const DbRange *global, bool force_update_all, bool images_only, std::vector<size_t> *updated);
+// set_colormap without its image step: the LUT (kept when malformed, render_tiles.rs:80-85) and colormap_length
+int set_colormap_only(th_tm *tm, const uint8_t *rgba, size_t bytes);
+// the writer's final wait (the context stream idle, host copies of uploads released)
+int settle(th_tm *tm);
+
+}  // namespace tmi
+}  // namespace th

@@ -1,0 +1,541 @@
+// track_manager_multi.hip — th_tmg: one TrackManager whose tracks live on several devices of one process.
+//
+// A slot = one th_ctx + one th_tm on one device (duplicates allowed).  A track lives whole on one slot.  The only coupling
+// between slots is the reference's global dB range and max_sr (core/mod.rs:169-185): the channels' (min, max) are already on
+// the host (finish_specs read them back), so the manager folds them here in the order one th_tm would and hands the result to
+// every slot's image step.  The per-slot work of a mutator runs on one host thread per slot, so N devices work at once.
+// Revisions are the manager's own and every slot's tile cache carries them, so tiles are stamped as one th_tm would stamp them.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <set>
+#include <shared_mutex>
+#include <string>
+#include <thread>
+#include <tuple>
+#include <vector>
+
+#include "common.h"
+#include "host_math.h"
+#include "tile_cache.h"
+#include "track_manager_internal.h"
+
+using namespace th;
+
+struct th_tmg {
+    struct Slot {
+        int device = 0;
+        th_ctx *ctx = nullptr;
+        th_tm *tm = nullptr;
+    };
+    std::vector<Slot> slots;
+    struct Placement {
+        uint32_t slot;
+        uint64_t weight;  // n_samples x n_channels
+    };
+    std::map<size_t, Placement> where;  // every resident track
+    float dB_range = 100.f;             // TrackManager::new, core/mod.rs:46-60
+    int lod_source = 0;
+    // the revision pair of the whole manager (only the counters of this cache are used: it never holds a tile); every
+    // slot's own cache is set to it after each mutator (sync_revisions)
+    th_tile_cache revs{0};
+    // writers take it exclusively, tile readers share it (th_tm::rw one level up): a reader never sees one slot re-made
+    // while another is not
+    mutable std::shared_mutex rw;
+};
+
+namespace {
+
+void sync_revisions(th_tmg *g) {
+    uint64_t w, s;
+    {
+        std::lock_guard<std::mutex> lk(g->revs.mu);
+        w = g->revs.waveform_revision;
+        s = g->revs.spectrogram_revision;
+    }
+    for (auto &sl : g->slots) {
+        th_tile_cache *c = nullptr;
+        if (th_tm_tile_cache(sl.tm, &c) == TH_OK) c->set_revisions(w, s);
+    }
+}
+
+std::vector<uint32_t> all_slots(const th_tmg *g) {
+    std::vector<uint32_t> v(g->slots.size());
+    for (size_t i = 0; i < v.size(); i++) v[i] = (uint32_t)i;
+    return v;
+}
+
+// fn(slot) for every slot of `which`, each on a thread of its own (the caller's thread takes the first).  th_last_error is
+// thread-local: a failure is re-raised on the caller's thread with its slot and device (the first failing slot in `which`
+// order; every slot has finished by then).
+template <class F>
+int for_slots(th_tmg *g, const std::vector<uint32_t> &which, F fn) {
+    const size_t n = which.size();
+    std::vector<int> rc(n, TH_OK);
+    std::vector<std::string> msg(n);
+    auto run = [&](size_t i) {
+        try {
+            rc[i] = fn(which[i]);
+        } catch (const std::bad_alloc &) {
+            rc[i] = fail(TH_ERR_OOM, "host allocation failed");
+        } catch (...) {
+            rc[i] = fail(TH_ERR_INTERNAL, "exception in slot work");
+        }
+        if (rc[i] != TH_OK) msg[i] = get_error();
+    };
+    std::vector<std::thread> thr;
+    size_t spawned = 1;
+    try {
+        for (; spawned < n; spawned++) thr.emplace_back(run, spawned);
+    } catch (...) {  // (no more threads: this one runs the rest)
+    }
+    if (n) run(0);
+    for (size_t i = spawned; i < n; i++) run(i);
+    for (auto &t : thr) t.join();
+    for (size_t i = 0; i < n; i++)
+        if (rc[i] != TH_OK) return fail(rc[i], "slot %u (device %d): %s", which[i], g->slots[which[i]].device, msg[i].c_str());
+    return TH_OK;
+}
+
+// The one coupling: every resident channel's (mn, mx) and every track's sr from all slots, folded in ascending (id, ch) —
+// the order one th_tm iterates — by the same global_db_range (so that even a NaN lands where it would there)
+tmi::DbRange global_range(th_tmg *g) {
+    std::vector<tmi::ChanExtremum> ext;
+    std::vector<uint32_t> rates;
+    for (auto &sl : g->slots) {
+        tmi::list_extrema(sl.tm, &ext);
+        tmi::list_rates(sl.tm, &rates);
+    }
+    std::sort(ext.begin(), ext.end(), [](const tmi::ChanExtremum &a, const tmi::ChanExtremum &b) {
+        return std::tie(a.id, a.ch) < std::tie(b.id, b.ch);
+    });
+    std::vector<float> mins(ext.size()), maxs(ext.size());
+    for (size_t i = 0; i < ext.size(); i++) {
+        mins[i] = ext[i].mn;
+        maxs[i] = ext[i].mx;
+    }
+    tmi::DbRange r{INFINITY, -INFINITY, 0};
+    global_db_range(mins.data(), maxs.data(), mins.size(), g->dB_range, &r.min_dB, &r.max_dB);
+    for (uint32_t sr : rates) r.max_sr = std::max(r.max_sr, sr);
+    return r;
+}
+
+// update_spec_imgs on every slot against the global values; *updated = the ascending union of the slots' ids
+int requantise_all(th_tmg *g, bool force_update_all, bool images_only, std::vector<size_t> *updated) {
+    const tmi::DbRange r = global_range(g);
+    std::vector<std::vector<size_t>> upd(g->slots.size());
+    const int rc = for_slots(g, all_slots(g), [&](uint32_t s) -> int {
+        std::unique_lock<std::shared_mutex> wl(tmi::rw_of(g->slots[s].tm));
+        return tmi::requantise(g->slots[s].tm, &r, force_update_all, images_only, &upd[s]);
+    });
+    if (updated) {
+        std::set<size_t> u;
+        for (auto &v : upd) u.insert(v.begin(), v.end());
+        updated->assign(u.begin(), u.end());
+    }
+    return rc;
+}
+
+// the slot of a resident track, or NULL
+const th_tmg::Placement *find_track(const th_tmg *g, size_t id) {
+    auto it = g->where.find(id);
+    return it == g->where.end() ? nullptr : &it->second;
+}
+
+}  // namespace
+
+TH_API int th_tmg_destroy(th_tmg *g) {
+    TH_TRY
+    if (!g) return TH_OK;
+    for (auto &sl : g->slots) {
+        if (sl.tm) (void)th_tm_destroy(sl.tm);
+        if (sl.ctx) (void)th_ctx_destroy(sl.ctx);
+    }
+    delete g;
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_tmg_create(const int *devices, size_t n_devices, th_tmg **out) {
+    TH_TRY
+    TH_REQUIRE(devices && out, "NULL argument");
+    TH_REQUIRE(n_devices >= 1 && n_devices <= 64, "n_devices must be 1 .. 64 (got %zu)", n_devices);
+    for (size_t i = 0; i < n_devices; i++) TH_REQUIRE(devices[i] >= 0, "devices[%zu] = %d is negative", i, devices[i]);
+    *out = nullptr;
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
+        return fail(TH_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    for (size_t i = 0; i < n_devices; i++)
+        TH_REQUIRE(devices[i] < n, "devices[%zu] = %d out of range (have %d)", i, devices[i], n);
+    std::unique_ptr<th_tmg, int (*)(th_tmg *)> g(new th_tmg(), th_tmg_destroy);
+    g->slots.resize(n_devices);
+    for (size_t i = 0; i < n_devices; i++) {
+        th_tmg::Slot &sl = g->slots[i];
+        sl.device = devices[i];
+        int rc = th_ctx_create(devices[i], nullptr, &sl.ctx);
+        if (rc == TH_OK) rc = th_tm_create(sl.ctx, &sl.tm);
+        if (rc != TH_OK) return fail(rc, "slot %zu (device %d): %s", i, devices[i], th_last_error());
+    }
+    sync_revisions(g.get());
+    *out = g.release();
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_tmg_n_devices(const th_tmg *g, size_t *n) {
+    TH_TRY
+    TH_REQUIRE(g && n, "NULL argument");
+    *n = g->slots.size();
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_tmg_track_device(const th_tmg *g, size_t id, uint32_t *slot) {
+    TH_TRY
+    TH_REQUIRE(g && slot, "NULL argument");
+    std::shared_lock<std::shared_mutex> rl(g->rw);
+    const th_tmg::Placement *p = find_track(g, id);
+    if (!p) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", id);
+    *slot = p->slot;
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_tmg_set_colormap(th_tmg *g, const uint8_t *rgba, size_t bytes) {
+    TH_TRY
+    TH_REQUIRE(g && rgba, "NULL argument");
+    std::unique_lock<std::shared_mutex> wl(g->rw);
+    int rc = for_slots(g, all_slots(g), [&](uint32_t s) -> int {
+        std::unique_lock<std::shared_mutex> sl(tmi::rw_of(g->slots[s].tm));
+        return tmi::set_colormap_only(g->slots[s].tm, rgba, bytes);
+    });
+    if (rc != TH_OK) return rc;
+    g->revs.invalidate_spectrogram();
+    sync_revisions(g);
+    return requantise_all(g, true, false, nullptr);
+    TH_CATCH
+}
+
+TH_API int th_tmg_set_setting(th_tmg *g, double win_ms, uint32_t t_overlap, uint32_t f_overlap, int freq_scale) {
+    TH_TRY
+    TH_REQUIRE(g, "tmg is NULL");
+    TH_REQUIRE(win_ms > 0. && t_overlap >= 1 && f_overlap >= 1, "invalid SpecSetting (lib.rs:275-277)");
+    TH_REQUIRE(freq_scale == TH_FREQ_LINEAR || freq_scale == TH_FREQ_MEL, "bad freq_scale");
+    std::unique_lock<std::shared_mutex> wl(g->rw);
+    // every slot prepares (new plans and specs beside the resident ones); all commit, or all discard
+    std::vector<tmi::StagedPtr> staged(g->slots.size());
+    int rc = for_slots(g, all_slots(g), [&](uint32_t s) -> int {
+        std::unique_lock<std::shared_mutex> sl(tmi::rw_of(g->slots[s].tm));
+        return tmi::prepare_setting(g->slots[s].tm, win_ms, t_overlap, f_overlap, freq_scale, &staged[s]);
+    });
+    if (rc != TH_OK) return rc;  // (staged: discarded on the way out)
+    for (size_t s = 0; s < staged.size(); s++) {
+        std::unique_lock<std::shared_mutex> sl(tmi::rw_of(g->slots[s].tm));
+        tmi::commit(g->slots[s].tm, std::move(staged[s]));
+    }
+    rc = requantise_all(g, true, false, nullptr);
+    g->revs.invalidate_spectrogram();  // lib.rs:284
+    sync_revisions(g);
+    return rc;
+    TH_CATCH
+}
+
+TH_API int th_tmg_set_dB_range(th_tmg *g, float dB_range) {
+    TH_TRY
+    TH_REQUIRE(g, "tmg is NULL");
+    TH_REQUIRE(dB_range > 0.f, "dB_range must be > 0 (lib.rs:259)");
+    std::unique_lock<std::shared_mutex> wl(g->rw);
+    g->dB_range = dB_range;
+    const int rc = requantise_all(g, true, true, nullptr);
+    g->revs.invalidate_spectrogram();  // lib.rs:265
+    sync_revisions(g);
+    return rc;
+    TH_CATCH
+}
+
+TH_API int th_tmg_add_tracks(th_tmg *g, size_t n_tracks, const size_t *ids, const uint32_t *srs, const uint32_t *n_channels,
+                             const float *const *channels_flat, const size_t *n_samples) {
+    TH_TRY
+    TH_REQUIRE(g && ids && srs && n_channels && channels_flat && n_samples, "NULL argument");
+    TH_REQUIRE(n_tracks >= 1, "no tracks (lib.rs:182)");
+    std::vector<size_t> flat0(n_tracks, 0);
+    {   // validate everything before anything is allocated (th_tm_add_tracks)
+        size_t flat = 0;
+        for (size_t t = 0; t < n_tracks; t++) {
+            TH_REQUIRE(srs[t] > 0 && n_channels[t] >= 1 && n_samples[t] >= 1, "track %zu: empty or invalid", ids[t]);
+            flat0[t] = flat;
+            for (uint32_t k = 0; k < n_channels[t]; k++, flat++)
+                TH_REQUIRE(channels_flat[flat], "track %zu channel %u: NULL data", ids[t], k);
+        }
+    }
+    std::unique_lock<std::shared_mutex> wl(g->rw);
+    const uint32_t n_slots = (uint32_t)g->slots.size();
+    // the same id twice in one call: the later one wins, as in th_tm_add_tracks — only it goes to a slot
+    std::map<size_t, size_t> last_of;
+    for (size_t t = 0; t < n_tracks; t++) last_of[ids[t]] = t;
+    // placement: a resident id stays on its slot; new ids longest-first (weight = n_samples x n_channels, ties in input
+    // order) to the slot with the least resident weight (ties: the lowest slot) — shard_assign from the resident loads
+    std::vector<uint64_t> load(n_slots, 0);
+    for (auto &kv : g->where) load[kv.second.slot] += kv.second.weight;
+    std::vector<size_t> fresh;  // input indices of the new ids
+    std::vector<uint64_t> weight(n_tracks, 0);
+    for (size_t t = 0; t < n_tracks; t++) {
+        weight[t] = (uint64_t)n_samples[t] * n_channels[t];
+        if (last_of[ids[t]] == t && !find_track(g, ids[t])) fresh.push_back(t);
+    }
+    std::vector<uint64_t> fw(fresh.size());
+    for (size_t i = 0; i < fresh.size(); i++) fw[i] = weight[fresh[i]];
+    std::vector<uint32_t> owner(fresh.size(), 0);
+    shard_assign(fw.data(), fw.size(), n_slots, owner.data(), load.data());
+    std::vector<uint32_t> slot_of(n_tracks, 0);
+    for (size_t i = 0; i < fresh.size(); i++) slot_of[fresh[i]] = owner[i];
+    // each slot's share of the batch, in input order
+    struct Batch {
+        std::vector<size_t> ids, ns;
+        std::vector<uint32_t> srs, nch;
+        std::vector<const float *> chans;
+    };
+    std::vector<Batch> batch(n_slots);
+    for (size_t t = 0; t < n_tracks; t++) {
+        if (last_of[ids[t]] != t) continue;
+        const th_tmg::Placement *p = find_track(g, ids[t]);
+        if (p) slot_of[t] = p->slot;
+        Batch &b = batch[slot_of[t]];
+        b.ids.push_back(ids[t]);
+        b.srs.push_back(srs[t]);
+        b.nch.push_back(n_channels[t]);
+        b.ns.push_back(n_samples[t]);
+        for (uint32_t k = 0; k < n_channels[t]; k++) b.chans.push_back(channels_flat[flat0[t] + k]);
+    }
+    std::vector<uint32_t> busy;
+    for (uint32_t s = 0; s < n_slots; s++)
+        if (!batch[s].ids.empty()) busy.push_back(s);
+    // every slot stages its tracks (upload, waveform pyramids, STFT); all commit, or all discard
+    std::vector<tmi::StagedPtr> staged(n_slots);
+    int rc = for_slots(g, busy, [&](uint32_t s) -> int {
+        const Batch &b = batch[s];
+        std::unique_lock<std::shared_mutex> sl(tmi::rw_of(g->slots[s].tm));
+        return tmi::prepare_add(g->slots[s].tm, b.ids.size(), b.ids.data(), b.srs.data(), b.nch.data(), b.chans.data(), b.ns.data(),
+                                &staged[s]);
+    });
+    if (rc != TH_OK) return rc;  // (staged: discarded on the way out)
+    for (uint32_t s : busy) {
+        std::unique_lock<std::shared_mutex> sl(tmi::rw_of(g->slots[s].tm));
+        tmi::commit(g->slots[s].tm, std::move(staged[s]));
+    }
+    for (size_t t = 0; t < n_tracks; t++)
+        if (last_of[ids[t]] == t) g->where[ids[t]] = th_tmg::Placement{slot_of[t], weight[t]};
+    g->revs.invalidate_all();  // lib.rs:192
+    sync_revisions(g);
+    for (uint32_t s : busy) {
+        rc = tmi::settle(g->slots[s].tm);
+        if (rc != TH_OK) return fail(rc, "slot %u (device %d): %s", s, g->slots[s].device, get_error());
+    }
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_tmg_remove_track(th_tmg *g, size_t id) {
+    TH_TRY
+    TH_REQUIRE(g, "tmg is NULL");
+    std::unique_lock<std::shared_mutex> wl(g->rw);
+    const th_tmg::Placement *p = find_track(g, id);
+    if (!p) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", id);
+    const uint32_t s = p->slot;
+    const int rc = th_tm_remove_track(g->slots[s].tm, id);
+    if (rc != TH_OK) return fail(rc, "slot %u (device %d): %s", s, g->slots[s].device, get_error());
+    g->where.erase(id);
+    g->revs.invalidate_all();  // lib.rs:221
+    sync_revisions(g);
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_tmg_apply_track_list_changes(th_tmg *g, size_t *updated_ids, size_t cap, size_t *n_updated, uint32_t *max_sr) {
+    TH_TRY
+    TH_REQUIRE(g, "tmg is NULL");
+    std::unique_lock<std::shared_mutex> wl(g->rw);
+    std::vector<size_t> upd;
+    const int rc = requantise_all(g, false, true, &upd);
+    if (rc != TH_OK) return rc;
+    if (n_updated) *n_updated = upd.size();
+    if (updated_ids)
+        for (size_t i = 0; i < upd.size() && i < cap; i++) updated_ids[i] = upd[i];
+    if (max_sr) {
+        float lo, hi;
+        (void)th_tm_get_db_state(g->slots[0].tm, &lo, &hi, max_sr);  // (every slot holds the global values)
+    }
+    if (!upd.empty()) {  // lib.rs:243-245
+        g->revs.invalidate_spectrogram();
+        sync_revisions(g);
+    }
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_tmg_get_db_state(const th_tmg *g, float *min_dB, float *max_dB, uint32_t *max_sr) {
+    TH_TRY
+    TH_REQUIRE(g, "tmg is NULL");
+    std::shared_lock<std::shared_mutex> rl(g->rw);
+    return th_tm_get_db_state(g->slots[0].tm, min_dB, max_dB, max_sr);  // (every slot holds the global values)
+    TH_CATCH
+}
+
+// ---------------------------------------------------------------------------------------------- readers: the owning slot
+#define TMG_OWNER(g, id, what, ...)                                                        \
+    TH_REQUIRE(g, "tmg is NULL");                                                          \
+    std::shared_lock<std::shared_mutex> rl((g)->rw);                                       \
+    const th_tmg::Placement *p_ = find_track(g, id);                                       \
+    if (!p_) return fail(TH_ERR_NOT_FOUND, what " does not exist", __VA_ARGS__);          \
+    th_tm *tm_ = (g)->slots[p_->slot].tm
+
+TH_API int th_tmg_spec_shape(const th_tmg *g, size_t id, uint32_t ch, size_t *n_frames, size_t *height) {
+    TH_TRY
+    TMG_OWNER(g, id, "Spectrogram %zu_%u", id, ch);
+    return th_tm_spec_shape(tm_, id, ch, n_frames, height);
+    TH_CATCH
+}
+
+TH_API int th_tmg_img_shape(const th_tmg *g, size_t id, uint32_t ch, size_t *img_height, size_t *img_width) {
+    TH_TRY
+    TMG_OWNER(g, id, "Spectrogram %zu_%u", id, ch);
+    return th_tm_img_shape(tm_, id, ch, img_height, img_width);
+    TH_CATCH
+}
+
+TH_API int th_tmg_copy_spec(th_tmg *g, size_t id, uint32_t ch, float *out, size_t capacity_floats) {
+    TH_TRY
+    TMG_OWNER(g, id, "Spectrogram %zu_%u", id, ch);
+    return th_tm_copy_spec(tm_, id, ch, out, capacity_floats);
+    TH_CATCH
+}
+
+TH_API int th_tmg_copy_img(th_tmg *g, size_t id, uint32_t ch, uint16_t *out, size_t capacity_px) {
+    TH_TRY
+    TMG_OWNER(g, id, "Spectrogram %zu_%u", id, ch);
+    return th_tm_copy_img(tm_, id, ch, out, capacity_px);
+    TH_CATCH
+}
+
+TH_API int th_tmg_revisions(const th_tmg *g, uint64_t *waveform_revision, uint64_t *spectrogram_revision) {
+    TH_TRY
+    TH_REQUIRE(g, "tmg is NULL");
+    std::lock_guard<std::mutex> lk(g->revs.mu);
+    if (waveform_revision) *waveform_revision = g->revs.waveform_revision;
+    if (spectrogram_revision) *spectrogram_revision = g->revs.spectrogram_revision;
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_tmg_get_spectrogram_tile(th_tmg *g, size_t id, uint32_t ch, uint32_t level_x, uint32_t level_y, uint32_t tile_x,
+                                       uint32_t tile_y, uint8_t *out, size_t out_capacity, size_t *out_len) {
+    TH_TRY
+    TMG_OWNER(g, id, "Spectrogram %zu_%u", id, ch);
+    return th_tm_get_spectrogram_tile(tm_, id, ch, level_x, level_y, tile_x, tile_y, out, out_capacity, out_len);
+    TH_CATCH
+}
+
+TH_API int th_tmg_get_waveform_tile(th_tmg *g, size_t id, uint32_t ch, uint32_t level, uint32_t tile_index, uint8_t *out,
+                                    size_t out_capacity, size_t *out_len) {
+    TH_TRY
+    TMG_OWNER(g, id, "Track %zu", id);
+    return th_tm_get_waveform_tile(tm_, id, ch, level, tile_index, out, out_capacity, out_len);
+    TH_CATCH
+}
+
+TH_API int th_tmg_get_audio_render_metadata(th_tmg *g, size_t id, uint32_t ch, double track_sec, int is_clipped,
+                                            th_render_metadata *out) {
+    TH_TRY
+    TMG_OWNER(g, id, "Track %zu", id);
+    return th_tm_get_audio_render_metadata(tm_, id, ch, track_sec, is_clipped, out);
+    TH_CATCH
+}
+
+// The batch split by owner, the slots served side by side.  Record sizes follow from the images' shapes
+// (spectrogram_tile_geometry), so the offsets are known before any slot runs: a batch owned by one slot goes to it whole
+// (its th_tm writes the caller's buffer directly when its device can reach it, else stages); otherwise each slot writes its
+// records into a staging buffer of its own and they are scattered to their places.
+TH_API int th_tmg_get_spectrogram_tiles(th_tmg *g, const th_tile_request *reqs, size_t n, uint8_t *out, size_t out_capacity,
+                                        size_t *offsets, size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(g && out_len && (n == 0 || (reqs && offsets)), "NULL argument");
+    *out_len = 0;
+    if (n == 0) {
+        if (offsets) offsets[0] = 0;
+        return TH_OK;
+    }
+    std::shared_lock<std::shared_mutex> rl(g->rw);
+    std::vector<uint32_t> owner(n);
+    size_t total = 0;
+    for (size_t i = 0; i < n; i++) {
+        const th_tile_request &r = reqs[i];
+        const th_tmg::Placement *p = find_track(g, r.id);
+        if (!p) return fail(TH_ERR_NOT_FOUND, "Spectrogram %zu_%u does not exist", r.id, r.ch);
+        owner[i] = p->slot;
+        size_t h = 0, w = 0;
+        int rc = th_tm_img_shape(g->slots[p->slot].tm, r.id, r.ch, &h, &w);
+        if (rc != TH_OK) return rc;
+        const TileGeom tg = spectrogram_tile_geometry(w, h, r.level_x, r.level_y, r.tile_x, r.tile_y);
+        offsets[i] = total;
+        total += (40 + tg.width * tg.height * 4 + 63) / 64 * 64;
+    }
+    offsets[n] = total;
+    *out_len = total;
+    if (out_capacity < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
+    std::vector<std::vector<size_t>> mine(g->slots.size());  // request indices per slot, in request order
+    for (size_t i = 0; i < n; i++) mine[owner[i]].push_back(i);
+    std::vector<uint32_t> busy;
+    for (uint32_t s = 0; s < g->slots.size(); s++)
+        if (!mine[s].empty()) busy.push_back(s);
+    if (busy.size() == 1) return th_tm_get_spectrogram_tiles(g->slots[busy[0]].tm, reqs, n, out, out_capacity, offsets, out_len);
+    return for_slots(g, busy, [&](uint32_t s) -> int {
+        const std::vector<size_t> &idx = mine[s];
+        std::vector<th_tile_request> sub(idx.size());
+        size_t bytes = 0;
+        for (size_t j = 0; j < idx.size(); j++) {
+            sub[j] = reqs[idx[j]];
+            bytes += offsets[idx[j] + 1] - offsets[idx[j]];
+        }
+        std::vector<uint8_t> stage(bytes);
+        std::vector<size_t> soff(idx.size() + 1);
+        size_t len = 0;
+        int rc = th_tm_get_spectrogram_tiles(g->slots[s].tm, sub.data(), sub.size(), stage.data(), stage.size(), soff.data(), &len);
+        if (rc != TH_OK) return rc;
+        for (size_t j = 0; j < idx.size(); j++) {  // (the record itself: 40-byte header + RGBA, not the padding after it)
+            uint32_t w, h;
+            std::memcpy(&w, stage.data() + soff[j] + 8, 4);
+            std::memcpy(&h, stage.data() + soff[j] + 12, 4);
+            std::memcpy(out + offsets[idx[j]], stage.data() + soff[j], 40 + (size_t)w * h * 4);
+        }
+        return TH_OK;
+    });
+    TH_CATCH
+}
+
+TH_API int th_tmg_set_lod_source(th_tmg *g, int per_request) {
+    TH_TRY
+    TH_REQUIRE(g, "tmg is NULL");
+    std::unique_lock<std::shared_mutex> wl(g->rw);
+    const int want = per_request ? 1 : 0;
+    if (want == g->lod_source) return TH_OK;
+    std::vector<int> done(g->slots.size(), 0);
+    const int rc = for_slots(g, all_slots(g), [&](uint32_t s) -> int {
+        const int r = th_tm_set_lod_source(g->slots[s].tm, want);
+        done[s] = r == TH_OK;
+        return r;
+    });
+    if (rc != TH_OK) {  // failure-atomic like th_tm_set_lod_source: the slots that switched go back
+        const std::string msg = get_error();
+        for (size_t s = 0; s < done.size(); s++)
+            if (done[s]) (void)th_tm_set_lod_source(g->slots[s].tm, g->lod_source);
+        return fail(rc, "%s", msg.c_str());
+    }
+    g->lod_source = want;
+    return TH_OK;
+    TH_CATCH
+}
