@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -383,49 +384,92 @@ void DeviceTable::release() {
 
 }  // namespace th
 
-bool th_plan::use_wave() const {
-    if (kernel_choice == 1) return false;
-    return th::stft_wave_supported(g) && (g.n_mel == 0 || d_mel_bt != nullptr);
-}
-// mel plans on the wave kernel: the filterbank fused into the FFT kernel's epilogue where its table fits (n_fft 1024 /
-// 2048 at the default launch shape), else amplitude out of the FFT kernel and the filterbank on the matrix cores
-int th_plan::long_plan() const {
-    if (kernel_choice == 14) return 1;
-    if (kernel_choice == 15) return 2;
+// Fills p.route from the plan's geometry, the tables th_plan_create built and the selector: the one place that decides which
+// kernels a launch runs.  The table-fit checks see p.g (phased = 0); the frame-loop checks behind phase_mode see the launch's.
+static void resolve_route(th_plan &p) {
+    using R = StftRoute;
+    const StftGeom &g = p.g;
+    const int k = p.kernel_choice, wv = p.wave_waves;
+    R r;
+    const bool wave = k != SEL_GENERIC && stft_wave_supported(g) && (g.n_mel == 0 || p.d_mel_bt != nullptr);
+    r.no_wave_kernel = k >= SEL_WAVE && !wave;
+    // n_fft 8192 .. 65536: the block or the subwave plan (stft_subwave_default: the sizes where the subwave plan is the default).
     // Mel plans at n_fft 16384 that have a moment table: the workgroup-per-frame kernel with the filterbank in its epilogue at EVERY
     // hop.  For linear rows the subwave plan is the faster one at hops other than n_fft / 4 (0.63 against 0.67 ms at 16320 / 4080,
     // the UI's 340 ms window), but it has no epilogue and would need the second kernel: 0.99 against 0.82 ms there, 1.23 against 1.04
     // at 12000 / 3000, 1.79 against 1.50 at 16320 / 2040 (64 ch x 30 s).  Selector 12 (the two kernels) keeps the size's default.
-    if (g.n_mel != 0 && g.log2_nc == 13 && d_mel_mom != nullptr && kernel_choice != 12) return 1;
-    return 0;
+    r.long_plan = k == SEL_BLOCK ? 1 : k == SEL_SUBWAVE ? 2
+                : (g.n_mel != 0 && g.log2_nc == 13 && p.d_mel_mom != nullptr && k != SEL_MEL_TWO_KERNELS) ? 1
+                : stft_subwave_default(g) ? 2 : 1;
+    // mel plans on the wave kernels: the filterbank fused into the FFT kernel's epilogue where one of its table forms applies, else
+    // amplitude rows out of the FFT kernel and a second mel kernel
+    bool fused = false, mom_small = false, bsum_fits = false;
+    if (g.n_mel != 0 && wave && k != SEL_MEL_AMP && k != SEL_MEL_MFMA) {
+        bsum_fits = k != SEL_MEL_PIECES && p.d_mel_bsum != nullptr && stft_wave_mel_fits(g, wv, p.mel_bsum_words, true);
+        const bool pieces_fit = p.d_mel_fuse != nullptr && stft_wave_mel_fits(g, wv, p.mel_fuse_words);
+        // n_fft 512 .. 2048 under more mels than an LDS table form holds (low sample rates under long windows, or f_overlap 2 / 4):
+        // the moment form with its table in global memory, as at n_fft 4096 (one-frame epilogue; any frame loop of the size).
+        // n_fft 512 (four frames per wave): where the banded rows table does not exist — filters wider than its 8 bins: 10 / 20 ms
+        // windows at 16 .. 48 kHz.  Selectors 12 / 8 keep the two kernels / the table forms.
+        if (g.log2_nc >= 8 && g.log2_nc <= 10 && p.d_mel_mom != nullptr && k != SEL_MEL_TWO_KERNELS && k != SEL_MEL_PIECES)
+            mom_small = g.log2_nc == 8 ? p.d_mel_rows == nullptr && stft_wave_multi_applies(g, 2) && stft_wave_multi_mel_fits(g, wv, 0)
+                                       : !bsum_fits && !pieces_fit && stft_wave_mel_fits(g, wv, 0, true);
+        if (g.log2_nc == 11)  // n_fft 4096 (round 6): the moment form as the FFT kernel's epilogue — no table in LDS (the eight slabs
+            // leave none), any mel count; instantiated for hop 1024 and for the even-offset grid-aligned shapes of the 96 / 88.2 kHz
+            // defaults (not when selector 4 switches that mode off)
+            fused = k != SEL_MEL_TWO_KERNELS && p.d_mel_mom != nullptr && stft_wave_mel_fits(g, wv, 1, true);
+        else if (g.log2_nc == 12 || g.log2_nc == 13)  // n_fft 8192 / 16384 (round 6): the same moment form in the epilogue of the
+            // workgroup-per-frame kernel, where that kernel is the plan that runs
+            fused = k != SEL_MEL_TWO_KERNELS && p.d_mel_mom != nullptr && stft_block_mel_fused_applies(g, r.long_plan);
+        else if (g.log2_nc == 8)  // n_fft 512 under narrow filters: the banded sums of mel_rows_kernel as the epilogue of the four-frames-per-wave kernel
+            fused = (p.d_mel_rows != nullptr && stft_wave_multi_mel_fits(g, wv, p.mel_rows_groups * (uint32_t)(MEL_ROWS_W + 1) * 64u)) || mom_small;
+        else
+            fused = bsum_fits || pieces_fit || mom_small;
+    }
+    const bool mel_amp = g.n_mel != 0 && wave && !fused;
+    if (fused)
+        r.mel_fused = (g.log2_nc >= 11 || mom_small) ? (stft_is_block_plan(g) ? R::MelFused::MomentLanes : R::MelFused::Moment)
+                    : g.log2_nc == 8 ? R::MelFused::Rows
+                    // frame pairs (round 5): two consecutive frames per pass over the table; selector 13 keeps the one-frame epilogue (A/B)
+                    : bsum_fits ? (k != SEL_MEL_ONE_FRAME && stft_wave_mel_pair_applies(g, wv, p.mel_bsum_reach) ? R::MelFused::BandedPairs : R::MelFused::Banded)
+                    : R::MelFused::Pieces;
+    if (mel_amp)
+        r.mel_second = (p.d_mel_rows != nullptr && k != SEL_MEL_MFMA) ? R::MelSecond::Rows
+                     : (g.log2_nc >= 11 && p.d_mel_bsum != nullptr && k != SEL_MEL_MFMA) ? R::MelSecond::BandRows : R::MelSecond::Mfma;
+    const int mode = r.out_mode();
+    // phased mode of the wave kernel (hop = 480-style framings): frames are loaded from the 128-sample grid below their first window
+    // sample (not with the fused mel epilogue unless selector 5 asks for it: measured no gain there, with or without idle gaps —
+    // 48 kHz / 347 mels 0.522 vs 0.521 ms, 44.1 kHz / 370 mels 0.513 vs 0.541 — the window then comes from LDS instead of
+    // registers and the mel kernel is not bound by its loads)
+    // (n_fft 4096 — the 40 ms default at 88.2 / 96 kHz — also with amplitude output for the matrix-core mel kernel)
+    if (wave && (!mel_amp || g.log2_nc == 11) && (!fused || k == SEL_PHASE_FUSED || g.log2_nc == 11) && k != SEL_NO_PHASE && p.d_wtab_phased != nullptr)
+        r.phase_mode = fused ? stft_wave_mel_phase_mode(g, wv) : stft_wave_phased_mode(g, wv);
+    StftGeom gl = g;  // the launch's geometry
+    gl.phased = (uint32_t)r.phase_mode;
+    r.waves = wv > 0 ? wv : stft_wave_default_waves(gl);
+    const bool multi = wave && stft_wave_multi_applies(gl, mode);
+    // (multi-frame kernel with staged loads and hop % 4 == 2: see stft_wave_multi_tail_guard)
+    if (multi && g.log2_nc == 8) r.tail_guard = stft_wave_multi_tail_guard(gl);
+    // boundary frames of channels with at least n_fft samples also go to the wave kernel (one-frame chunks with a
+    // reflect-indexed fetch): no second launch on the fast path.  Not on the matrix-core mel path (its amplitude rows
+    // are laid out for the interior jobs), not for channels shorter than n_fft (a single reflection is not enough there).
+    r.edges_in_wave = wave && !mel_amp && r.phase_mode == 0 && !stft_is_block_plan(g);
+    r.sweep = wave && k == SEL_SWEEP && p.wave_chunk == 0 && g.n_mel == 0 && r.phase_mode == 0 && stft_wave_sweep_applies(gl, wv, 0);
+    r.packed = k == SEL_PACKED;
+    // n_fft 512, linear dB: four frames per wave (stft_wave_multi.h).  The same plan with two frames per wave exists for
+    // n_fft 1024 (selector 6) but measures 0.72 ms against 0.64 for the one-frame plan on the bench tracks (it reloads
+    // every frame in full: 16 loads per iteration against 4), so 1024 keeps the one-frame kernel by default.
+    // (n_fft 32768, round 5: sixteen wave transforms + a combining pass, kernels_stft_long.hip; selector 14 keeps the block kernel)
+    if (!wave) r.main = p.bluestein() ? R::Main::Bluestein : R::Main::Generic;
+    else if (multi && (g.log2_nc == 8 || k == SEL_MULTI_1024)) r.main = R::Main::WaveMulti;
+    else if (!stft_is_block_plan(g)) r.main = R::Main::Wave;
+    else r.main = (mode != 2 && stft_subwave_applies(g) && p.d_twc != nullptr && r.long_plan == 2) ? R::Main::Subwave : R::Main::Block;
+    static const char *const main_name[] = {"stft_generic_kernel", "stft_bluestein_kernel", "stft_wave_kernel", "stft_wave_kernel",
+                                            "stft_block_kernel", "stft_subwave_kernel"};
+    static const char *const second_name[] = {"", "+mel_rows_kernel", "+mel_band_rows_kernel", "+mel_mfma_kernel"};
+    std::snprintf(r.name, sizeof r.name, "%s%s%s", main_name[(int)r.main], fused ? "(fused mel)" : "", second_name[(int)r.mel_second]);
+    p.route = r;
 }
-bool th_plan::use_mel_fused() const {
-    if (g.n_mel == 0 || !use_wave() || kernel_choice == 3 || kernel_choice == 7) return false;
-    // n_fft 4096 (round 6): the moment form of the filterbank as the FFT kernel's epilogue — no table in LDS (the eight slabs
-    // leave none), any mel count; instantiated for hop 1024 and for the even-offset grid-aligned shapes of the 96 / 88.2 kHz
-    // defaults (not when selector 4 switches that mode off).  Selector 12 keeps round 5's two kernels (A/B).
-    if (g.log2_nc == 11) return kernel_choice != 12 && d_mel_mom != nullptr && th::stft_wave_mel_fits(g, wave_waves, 1, true);
-    // n_fft 8192 / 16384 (round 6): the same moment form as the epilogue of the workgroup-per-frame kernel, where that kernel is the
-    // plan that runs (long_plan(): at 16384 a mel plan with a table takes the block kernel at every hop; not under selector 15); selector 12 keeps the two kernels
-    if (g.log2_nc == 12 || g.log2_nc == 13)
-        return kernel_choice != 12 && d_mel_mom != nullptr && th::stft_block_mel_fused_applies(g, long_plan());
-    // n_fft 512 under narrow filters: the banded sums of mel_rows_kernel as the epilogue of the four-frames-per-wave kernel
-    if (g.log2_nc == 8) return (d_mel_rows != nullptr && th::stft_wave_multi_mel_fits(g, wave_waves, mel_rows_groups * (uint32_t)(th::MEL_ROWS_W + 1) * 64u)) || use_mel_moment_small();
-    return mel_bsum_fits() || (d_mel_fuse != nullptr && th::stft_wave_mel_fits(g, wave_waves, mel_fuse_words)) || use_mel_moment_small();
-}
-// n_fft 1024 / 2048 under more mels than an LDS table form holds (512: low sample rates under long windows, or f_overlap 2 / 4): the moment form
-// with its table in global memory, as at n_fft 4096 (one-frame epilogue; any frame loop of the size).  Selectors 12 / 2 keep the two kernels.
-bool th_plan::use_mel_moment_small() const {
-    if (g.n_mel == 0 || g.log2_nc < 8 || g.log2_nc > 10 || d_mel_mom == nullptr || kernel_choice == 12 || kernel_choice == 8 || kernel_choice == 3 || kernel_choice == 7) return false;
-    // n_fft 512 (four frames per wave): where the banded rows table does not exist — filters wider than its 8 bins: 10 / 20 ms windows at 16 .. 48 kHz
-    if (g.log2_nc == 8) return d_mel_rows == nullptr && th::stft_wave_multi_applies(g, 2) && th::stft_wave_multi_mel_fits(g, wave_waves, 0);
-    if (mel_bsum_fits() || (d_mel_fuse != nullptr && th::stft_wave_mel_fits(g, wave_waves, mel_fuse_words))) return false;
-    return th::stft_wave_mel_fits(g, wave_waves, 0, true);
-}
-bool th_plan::mel_bsum_fits() const {
-    return kernel_choice != 8 && d_mel_bsum != nullptr && th::stft_wave_mel_fits(g, wave_waves, mel_bsum_words, true);
-}
-bool th_plan::use_mel_mfma() const { return g.n_mel != 0 && use_wave() && !use_mel_fused(); }
 
 static void plan_free(th_plan *p) {
     if (!p) return;
@@ -733,6 +777,7 @@ TH_API int th_plan_create(th_ctx *c, uint32_t sr, size_t win, size_t hop, size_t
         plan_free(p);
         return rc;
     }
+    resolve_route(*p);
     *out = p;
     return TH_OK;
     TH_CATCH
@@ -760,24 +805,14 @@ TH_API int th_plan_dims(const th_plan *p, size_t *n_freq, size_t *height) {
 TH_API int th_plan_set_kernel(th_plan *p, int which) {
     TH_TRY
     TH_REQUIRE(p, "plan is NULL");
-    // bits 0-7: 0 auto, 1 generic, 2 wave, 3 wave + matrix-core mel, 4 wave without the phased mode, 5 phased mode also with the
-    // fused mel epilogue, 6 wave with the two-frames-per-wave plan at n_fft 1024, 7 as 3 with the matrix-core kernel also where
-    // the banded-sum kernel for short rows under narrow filters is the default (n_fft 512), 8 fused mel epilogue in its pieces / gather
-    // form where the banded sums are the default, 9 wave kernel with the packed-f32 pipeline (stft_pk.h) on the launch shape it is
-    // instantiated for (n_fft 2048, hop = n_fft / 4, linear dB, default waves; elsewhere as 2), 11 wave kernel with the sweep chunk
-    // schedule (4-frame chunks dealt out in order) on large batches of that same shape (A/B; elsewhere as 2; 10 is reserved: as 2),
-    // 12 mel plans at n_fft 4096: the two kernels (FFT -> amplitude rows -> banded sums / matrix cores) where the moment-form
-    // epilogue is the default (hop 1024, the 96 / 88.2 kHz defaults: round 5's route, A/B; elsewhere as 2);
-    // 13 fused mel epilogue one frame at a time where the frame-pair form is the default (n_fft 2048 banded sums; A/B; elsewhere as 2);
-    // 14 the workgroup-per-frame Stockham kernel (stft_block_kernel) where stft_subwave_kernel is the default (A/B; elsewhere as 2);
-    // 15 stft_subwave_kernel wherever it exists (n_fft 8192 .. 32768) also where the block kernel is the default (A/B; elsewhere as 2);
-    // bits 8-15 (tuning): waves per workgroup
+    // bits 0-7: the kernel selector (th::StftSelector; include/thesia_amd_testing.h describes them), bits 8-15 (tuning): waves per
+    // workgroup, bits 16-23 (tuning): frames per chunk of the wave kernel
     const int k = which & 0xff, wv = (which >> 8) & 0xff;
     TH_REQUIRE(k >= 0 && k <= 15, "kernel selector must be 0 .. 15");
     TH_REQUIRE(wv == 0 || wv == 4 || wv == 6 || wv == 7 || wv == 8 || wv == 10 || wv == 12 || wv == 14 || wv == 16,
                "waves per workgroup must be 4, 6, 7, 8, 10, 12, 14 or 16");
     // the multi-frame plans (n_fft 512; n_fft 1024 under selector 6) are instantiated for 8, 12 and 16 waves only
-    const bool multi = p->g.n_mel == 0 ? (p->g.log2_nc == 8 || (p->g.log2_nc == 9 && k == 6)) : p->g.log2_nc == 8;
+    const bool multi = p->g.n_mel == 0 ? (p->g.log2_nc == 8 || (p->g.log2_nc == 9 && k == SEL_MULTI_1024)) : p->g.log2_nc == 8;
     if (multi && !(wv == 0 || wv == 8 || wv == 12 || wv == 16))
         return fail(TH_ERR_UNSUPPORTED, "the multi-frame wave kernel of n_fft %u runs with 8, 12 or 16 waves per workgroup, not %d",
                     p->g.n_fft, wv);
@@ -785,10 +820,10 @@ TH_API int th_plan_set_kernel(th_plan *p, int which) {
     // instead of a launch failure later
     if (!TH_AB_VARIANTS) {
         const char *what = nullptr;
-        if (k == 9) what = "selector 9 (packed-f32 pipeline)";
-        else if (k == 11) what = "selector 11 (sweep chunk schedule)";
-        else if (k == 14 && p->g.log2_nc >= 14) what = "selector 14 at n_fft 32768 / 65536 (workgroup-per-frame Stockham kernels)";
-        else if (k == 15 && p->g.log2_nc == 12) what = "selector 15 at n_fft 8192 (stft_subwave_kernel with four waves)";
+        if (k == SEL_PACKED) what = "selector 9 (packed-f32 pipeline)";
+        else if (k == SEL_SWEEP) what = "selector 11 (sweep chunk schedule)";
+        else if (k == SEL_BLOCK && p->g.log2_nc >= 14) what = "selector 14 at n_fft 32768 / 65536 (workgroup-per-frame Stockham kernels)";
+        else if (k == SEL_SUBWAVE && p->g.log2_nc == 12) what = "selector 15 at n_fft 8192 (stft_subwave_kernel with four waves)";
         else if (!multi && p->g.log2_nc >= 9 && p->g.log2_nc <= 11 && wv != 0 && !(p->g.log2_nc == 11 ? (wv == 7 || wv == 8) : wv == 12))
             what = "a waves-per-workgroup shape other than the size's own (n_fft 1024 / 2048: 12; n_fft 4096: 8 or 7)";
         if (what) return fail(TH_ERR_UNSUPPORTED, "%s is an A/B variant: build with -DTH_AB_VARIANTS=1 (scripts/build_variant.sh)", what);
@@ -796,6 +831,7 @@ TH_API int th_plan_set_kernel(th_plan *p, int which) {
     p->kernel_choice = k;
     p->wave_waves = wv;
     p->wave_chunk = (which >> 16) & 0xff;  // tuning: frames per chunk of the wave kernel (0 = default)
+    resolve_route(*p);
     return TH_OK;
     TH_CATCH
 }
@@ -814,19 +850,7 @@ TH_API int th_plan_mel_moments_info(const th_plan *p, uint32_t *n_groups, uint32
     TH_CATCH
 }
 
-TH_API const char *th_plan_kernel_name(const th_plan *p) {
-    if (!p) return "";
-    if (p->use_mel_fused()) return th::stft_is_block_plan(p->g) ? "stft_block_kernel(fused mel)" : "stft_wave_kernel(fused mel)";
-    if (p->use_mel_mfma() && p->d_mel_rows != nullptr && p->kernel_choice != 7) return "stft_wave_kernel+mel_rows_kernel";
-    // (n_fft 32768, round 5: sixteen wave transforms + a combining pass, kernels_stft_long.hip; selector 14 keeps the block kernel)
-    const bool subwave = th::stft_subwave_applies(p->g) && p->d_twc != nullptr && (p->long_plan() == 2 || (p->long_plan() == 0 && th::stft_subwave_default(p->g)));
-    if (p->use_mel_mfma() && p->g.log2_nc >= 11 && p->d_mel_bsum != nullptr && p->kernel_choice != 7)
-        return subwave ? "stft_subwave_kernel+mel_band_rows_kernel" : th::stft_is_block_plan(p->g) ? "stft_block_kernel+mel_band_rows_kernel" : "stft_wave_kernel+mel_band_rows_kernel";
-    if (p->use_mel_mfma()) return subwave ? "stft_subwave_kernel+mel_mfma_kernel" : th::stft_is_block_plan(p->g) ? "stft_block_kernel+mel_mfma_kernel" : "stft_wave_kernel+mel_mfma_kernel";
-    if (p->use_wave() && subwave) return "stft_subwave_kernel";
-    if (p->use_wave() && th::stft_is_block_plan(p->g)) return "stft_block_kernel";
-    return p->use_wave() ? "stft_wave_kernel" : p->bluestein() ? "stft_bluestein_kernel" : "stft_generic_kernel";
-}
+TH_API const char *th_plan_kernel_name(const th_plan *p) { return p ? p->route.name : ""; }
 
 TH_API size_t th_pitch_f32(size_t n) { return (n + 31) / 32 * 32; }
 TH_API size_t th_pitch_u16(size_t n) { return (n + 63) / 64 * 64; }
@@ -854,57 +878,65 @@ static int calc_spec_batch_impl(th_plan *p, const th_chan_desc *chans, size_t n_
     TH_REQUIRE(chans, "chans is NULL");
     TH_REQUIRE(n_chan < (1u << 24), "too many channels");
     th_ctx *c = p->ctx;
-    const bool wave = p->use_wave();
-    const bool mel_mfma = p->use_mel_mfma(), mel_fused = p->use_mel_fused();
-    if (p->kernel_choice >= 2 && !wave)
-        return fail(TH_ERR_UNSUPPORTED, "the wave kernels cover n_fft 512 .. 32768");
+    const StftRoute &r = p->route;
+    const bool wave = r.wave(), mel_mfma = r.mel_second != StftRoute::MelSecond::None;
+    if (r.no_wave_kernel) return fail(TH_ERR_UNSUPPORTED, "the wave kernels cover n_fft 512 .. 32768");
     StftGeom g = p->g;       // main launch
     StftGeom ge = p->g;      // edge launch (generic kernel)
+    g.phased = (uint32_t)r.phase_mode;
+    const bool phased = r.phase_mode != 0;
     // wave kernel: chunk of consecutive frames one wave walks (the first frame of a chunk loads
     // n_fft samples, the rest only hop new ones).  32 amortises that well on large batches; small
     // batches (one track) get shorter chunks so that every wave of the chip has work.
     // interior frames [fa, fb) of a channel: the frame's whole n_fft-sample span [e0, e0 + n_fft), e0 = f*hop - win/2 -
     // pad_left, lies inside the channel (the wave kernel loads it unconditionally); the others are boundary frames
-    // phased mode of the wave kernel (hop = 480-style framings): frames are loaded from the 128-sample grid below their
-    // first window sample; chunks must start on frames that sit exactly on the grid (every fourth)
-    // (not with the fused mel epilogue unless selector 5 asks for it: measured no gain there, with or without idle gaps —
-    // 48 kHz / 347 mels 0.522 vs 0.521 ms, 44.1 kHz / 370 mels 0.513 vs 0.541 — the window then comes from LDS instead of
-    // registers and the mel kernel is not bound by its loads)
-    // (n_fft 4096 — the 40 ms default at 88.2 / 96 kHz — also with amplitude output for the matrix-core mel kernel)
-    const int phase_mode = (wave && (!mel_mfma || g.log2_nc == 11) && (!mel_fused || p->kernel_choice == 5 || g.log2_nc == 11) && p->kernel_choice != 4 && p->d_wtab_phased != nullptr)
-                               ? (mel_fused ? th::stft_wave_mel_phase_mode(g, p->wave_waves) : th::stft_wave_phased_mode(g, p->wave_waves)) : 0;
-    const bool phased = phase_mode != 0;
-    g.phased = (uint32_t)phase_mode;
-    const int waves = p->wave_waves > 0 ? p->wave_waves : stft_wave_default_waves(g);
-    // (multi-frame kernel with staged loads and hop % 4 == 2: see stft_wave_multi_tail_guard)
-    const uint64_t tail_guard = (wave && !phased && th::stft_wave_multi_applies(g, mel_mfma ? 1 : (mel_fused ? 2 : 0)) && g.log2_nc == 8)
-                                    ? th::stft_wave_multi_tail_guard(g) : 0;
-    auto interior = [&g, phased, phase_mode, tail_guard](const th_chan_desc &d, uint64_t T, uint64_t &fa, uint64_t &fb) {
+    // phased mode: chunks must start on frames that sit exactly on the 128-sample grid (every fourth)
+    auto interior = [&g, &r, phased](const th_chan_desc &d, uint64_t T, uint64_t &fa, uint64_t &fb) {
         if (phased) {
             const int64_t N = (int64_t)d.n_samples, half = (int64_t)(g.win / 2);
             auto delta = [&](int64_t f) { return (((f * (int64_t)g.hop - half) % 128) + 128) % 128; };
             auto start = [&](int64_t f) { return f * (int64_t)g.hop - half - delta(f); };
             int64_t a = 0, b = (int64_t)T;
-            while (a < b && (start(a) < 0 || (phase_mode == 1 && delta(a) != 0))) a++;  // phased chunks start on the grid
+            while (a < b && (start(a) < 0 || (r.phase_mode == 1 && delta(a) != 0))) a++;  // phased chunks start on the grid
             while (b > a && start(b - 1) + (int64_t)g.n_fft > N) b--;
             fa = (uint64_t)a;
             fb = (uint64_t)b;
             return;
         }
-        const uint64_t lead = g.win / 2 + g.pad_left, N = d.n_samples > tail_guard ? d.n_samples - tail_guard : 0;
+        const uint64_t lead = g.win / 2 + g.pad_left, N = d.n_samples > r.tail_guard ? d.n_samples - r.tail_guard : 0;
         fa = (lead + g.hop - 1) / g.hop;                                  // first f with e0 >= 0
         fb = N + lead >= g.n_fft ? (N + lead - g.n_fft) / g.hop + 1 : 0;  // one past the last f with e0 + n_fft <= N
         fa = std::min<uint64_t>(fa, T);
         fb = std::min<uint64_t>(std::max(fb, fa), T);
     };
-    // boundary frames of channels with at least n_fft samples also go to the wave kernel (one-frame chunks with a
-    // reflect-indexed fetch): no second launch on the fast path.  Not on the matrix-core mel path (its amplitude rows
-    // are laid out for the interior jobs), not for channels shorter than n_fft (a single reflection is not enough there).
-    const bool edges_in_wave = wave && !mel_mfma && !phased && !th::stft_is_block_plan(g);
     bool sweep = false;
     if (wave) {
         uint64_t total = 0;
         for (size_t i = 0; i < n_chan; i++) total += chans[i].n_frames;
+        // chunks of `len` frames over the batch's interior frames (+ with_edges: one per boundary frame the wave launch takes)
+        auto n_chunks = [&](uint64_t len, bool with_edges) {
+            uint64_t n = 0;
+            for (size_t i = 0; i < n_chan; i++) {
+                uint64_t fa, fb;
+                interior(chans[i], chans[i].n_frames, fa, fb);
+                n += (fb - fa + len - 1) / len;
+                if (with_edges && chans[i].n_samples >= g.n_fft) n += chans[i].n_frames - (fb - fa);
+            }
+            return n;
+        };
+        // The launch ends when the last chunk does and every slot (wave, or workgroup) walks its chunks one after the other, so
+        // what counts is rounds x chunk length: the length around `want` (at least `lo`) whose chunk count fills the last round best
+        auto best_chunk = [&](uint64_t want, uint64_t lo, uint64_t slots) {
+            uint64_t best = want, best_cost = ~0ull;
+            for (uint64_t cand = std::max<uint64_t>(lo, want - want / 4); cand <= want + want / 4; cand++) {
+                const uint64_t cost = (n_chunks(cand, false) + slots - 1) / slots * cand;  // frames a slot walks through, at worst
+                if (cost < best_cost || (cost == best_cost && cand > best)) {
+                    best_cost = cost;
+                    best = cand;
+                }
+            }
+            return best;
+        };
         // about TH_CHUNKS_PER_WAVE chunks per wave (at most 32 frames each): the launch ends when the last chunk does,
         // so a chunk is the granularity of the load balance, while every chunk costs one full fetch and one atomic on the
         // queue head (served at ~8 ns each device-wide).  Measured inside bench.py's step: 4 per wave (29 frames)
@@ -912,7 +944,7 @@ static int calc_spec_batch_impl(th_plan *p, const th_chan_desc *chans, size_t n_
 #if !defined(TH_CHUNKS_PER_WAVE)
 #define TH_CHUNKS_PER_WAVE 4
 #endif
-        const uint64_t n_waves = (uint64_t)c->n_cu * (uint64_t)waves;
+        const uint64_t n_waves = (uint64_t)c->n_cu * (uint64_t)r.waves;
         uint64_t chunk;
         if (th::stft_is_block_plan(g) && g.log2_nc <= 14) {
             // Workgroup-per-frame plans (n_fft 8192 .. 32768): what runs side by side is one workgroup per CU (two at n_fft 8192),
@@ -922,57 +954,17 @@ static int calc_spec_batch_impl(th_plan *p, const th_chan_desc *chans, size_t n_
             // 0.84-0.92 ms, 32768 8 -> 43 1.26 -> 1.21, 8192 30 -> 60-90 0.70 -> 0.64-0.69; n_fft 65536 measures 5 % slower with
             // longer chunks and keeps the rule below)
             const uint64_t slots = (uint64_t)c->n_cu * (g.log2_nc == 12 ? 2u : 1u);
-            const uint64_t want = std::min<uint64_t>(128, std::max<uint64_t>(1, total / (slots * 2)));  // (a single track: one frame per chunk, every CU busy)
-            uint64_t best = want, best_cost = ~0ull;
-            for (uint64_t cand = std::max<uint64_t>(1, want - want / 4); cand <= want + want / 4; cand++) {
-                uint64_t n = 0;
-                for (size_t i = 0; i < n_chan; i++) {
-                    uint64_t fa, fb;
-                    interior(chans[i], chans[i].n_frames, fa, fb);
-                    n += (fb - fa + cand - 1) / cand;
-                }
-                const uint64_t cost = (n + slots - 1) / slots * cand;
-                if (cost < best_cost || (cost == best_cost && cand > best)) {
-                    best_cost = cost;
-                    best = cand;
-                }
-            }
-            chunk = best;
+            // (a single track: one frame per chunk, every CU busy)
+            chunk = best_chunk(std::min<uint64_t>(128, std::max<uint64_t>(1, total / (slots * 2))), 1, slots);
         } else if (total <= n_waves * 32) {
             // small batch (one track ...): one chunk per wave, all of them assigned statically — the kernel then never
             // touches the queue (3072 waves finding it empty is 25 us of serialised atomics on a 20 us job)
             chunk = std::max<uint64_t>(1, (total + n_waves - 1) / n_waves);
-            for (;; chunk++) {
-                uint64_t n = 0;
-                for (size_t i = 0; i < n_chan; i++) {
-                    uint64_t fa, fb;
-                    interior(chans[i], chans[i].n_frames, fa, fb);
-                    n += (fb - fa + chunk - 1) / chunk;
-                    if (edges_in_wave && chans[i].n_samples >= g.n_fft) n += chans[i].n_frames - (fb - fa);
-                }
-                if (n <= n_waves || chunk >= 32) break;
-            }
+            while (chunk < 32 && n_chunks(chunk, r.edges_in_wave) > n_waves) chunk++;
         } else {
-            // The launch ends when the last chunk does and every wave walks its chunks one after the other, so what counts
-            // is rounds x chunk length: pick the chunk length (around total / (waves x TH_CHUNKS_PER_WAVE), at most 40
-            // frames) whose chunk count fills the last round best.  Bench workload: 29 frames would be 12416 chunks = 4.04
+            // around total / (waves x TH_CHUNKS_PER_WAVE), 12 to 40 frames.  Bench workload: 29 frames would be 12416 chunks = 4.04
             // rounds of 3072 waves, i.e. a fifth round for 128 stragglers: 0.520 ms; 30-32 frames 0.507 (r02_chunks).
-            const uint64_t want = std::min<uint64_t>(32, std::max<uint64_t>(12, total / (n_waves * TH_CHUNKS_PER_WAVE)));
-            uint64_t best = 0, best_cost = ~0ull;
-            for (uint64_t cand = std::max<uint64_t>(12, want - want / 4); cand <= want + want / 4; cand++) {
-                uint64_t n = 0;
-                for (size_t i = 0; i < n_chan; i++) {
-                    uint64_t fa, fb;
-                    interior(chans[i], chans[i].n_frames, fa, fb);
-                    n += (fb - fa + cand - 1) / cand;
-                }
-                const uint64_t cost = (n + n_waves - 1) / n_waves * cand;  // frames a wave walks through, at worst
-                if (cost < best_cost || (cost == best_cost && cand > best)) {
-                    best_cost = cost;
-                    best = cand;
-                }
-            }
-            chunk = best;
+            chunk = best_chunk(std::min<uint64_t>(32, std::max<uint64_t>(12, total / (n_waves * TH_CHUNKS_PER_WAVE))), 12, n_waves);
         }
         g.frames_per_tile = p->wave_chunk > 0 ? (uint32_t)p->wave_chunk : (uint32_t)chunk;
         // The sweep schedule (kernels_stft.hip: 4-frame chunks dealt out in order, next chunk prefetched) — round 4, selector 11
@@ -983,8 +975,7 @@ static int calc_spec_batch_impl(th_plan *p, const th_chan_desc *chans, size_t n_
         // seven times longer chunk table per call, which a pipelined step hides and a lone call does not.  With the packed-f32
         // pipeline (-39 % VALU instructions, +-0) that makes three independent changes of what the kernel DOES per frame that do
         // not change what a launch TAKES: it runs at the package power cap, where time follows flops + bytes, and neither moved.
-        sweep = total > n_waves * 32 && p->wave_chunk == 0 && p->kernel_choice == 11 && !mel_mfma && !mel_fused &&
-                g.n_mel == 0 && phase_mode == 0 && th::stft_wave_sweep_applies(g, p->wave_waves, 0);
+        sweep = r.sweep && total > n_waves * 32;
         if (sweep) g.frames_per_tile = 4;
         // (an earlier launch of this plan that dropped a chunk: found here when the stream has gone idle — no stall otherwise —
         // and in th_calc_spec_host behind its synchronisation)
@@ -992,7 +983,7 @@ static int calc_spec_batch_impl(th_plan *p, const th_chan_desc *chans, size_t n_
             const int src = sweep_check(p);
             if (src != TH_OK) return src;
         }
-        if (phase_mode == 1) g.frames_per_tile = std::max<uint32_t>(4, (g.frames_per_tile + 3) / 4 * 4);  // chunks start on the grid
+        if (r.phase_mode == 1) g.frames_per_tile = std::max<uint32_t>(4, (g.frames_per_tile + 3) / 4 * 4);  // chunks start on the grid
     } else {
         g.frames_per_tile = 8;
         // (short transforms — n_fft 256 and below, the generic kernel's only full plans: a tile of 8 frames is one round of its frames-side-by-side
@@ -1051,7 +1042,7 @@ static int calc_spec_batch_impl(th_plan *p, const th_chan_desc *chans, size_t n_
                 mel_start.push_back((uint32_t)mel_tiles);
                 mel_tiles += (fb - fa + MEL_TILE_FRAMES - 1) / MEL_TILE_FRAMES;
             }
-            if (edges_in_wave && d.n_samples >= g.n_fft) {
+            if (r.edges_in_wave && d.n_samples >= g.n_fft) {
                 add(jobs, tile_start, tiles, g, d, (uint32_t)T, 0, (uint32_t)fa, (uint32_t)i, true);
                 add(jobs, tile_start, tiles, g, d, (uint32_t)T, (uint32_t)fb, (uint32_t)T, (uint32_t)i, true);
             } else {
@@ -1112,7 +1103,7 @@ static int calc_spec_batch_impl(th_plan *p, const th_chan_desc *chans, size_t n_
     if (rc != TH_OK) return rc;
     {   // n_fft >= 32768: the generic kernel's frame buffers live in global scratch (all frames of a plan without a fast
         // kernel, or the boundary frames of the n_fft 32768 block plan)
-        const size_t need = !wave ? (p->bluestein() ? th::stft_bluestein_scratch_bytes(g, (uint32_t)tiles, c->n_cu) : th::stft_generic_scratch_bytes(g, (uint32_t)tiles, c->n_cu))
+        const size_t need = !wave ? (r.main == StftRoute::Main::Bluestein ? th::stft_bluestein_scratch_bytes(g, (uint32_t)tiles, c->n_cu) : th::stft_generic_scratch_bytes(g, (uint32_t)tiles, c->n_cu))
                                   : (edge.empty() ? 0 : th::stft_generic_scratch_bytes(ge, (uint32_t)edge_tiles, c->n_cu));
         if (need) {
             if (need > p->gen_scratch.cap) TH_HIP(hipStreamSynchronize(c->stream));  // (a launch may still use the old buffer)
@@ -1130,45 +1121,43 @@ static int calc_spec_batch_impl(th_plan *p, const th_chan_desc *chans, size_t n_
     if (timed) TH_HIP(hipEventRecord(p->ev_k0[slot], c->stream));
     if (wave) {
         th::WaveOut wo;
-        wo.mode = mel_mfma ? 1 : (mel_fused ? 2 : 0);
-        // n_fft 512, linear dB: four frames per wave (stft_wave_multi.h).  The same plan with two frames per wave exists for
-        // n_fft 1024 (selector 6) but measures 0.72 ms against 0.64 for the one-frame plan on the bench tracks (it reloads
-        // every frame in full: 16 loads per iteration against 4), so 1024 keeps the one-frame kernel by default.
-        wo.multi = (th::stft_wave_multi_applies(g, wo.mode) && (g.log2_nc == 8 || p->kernel_choice == 6)) ? 1 : 0;
-        wo.packed = p->kernel_choice == 9 ? 1 : 0;
+        wo.mode = r.out_mode();
+        wo.multi = r.main == StftRoute::Main::WaveMulti ? 1 : 0;
+        wo.packed = r.packed ? 1 : 0;
         wo.sweep = sweep ? 1 : 0;
-        wo.long_plan = p->long_plan();
+        wo.long_plan = r.long_plan;
         wo.subwave_twc = p->d_twc;
-        if (mel_fused && (g.log2_nc >= 11 || p->use_mel_moment_small())) {  // moment form: the table stays in global memory (scalar + 16-byte lane loads)
-            wo.mel_moment = g.log2_nc >= 11 ? 0u : 1u;
-            wo.mel_tab = p->d_mel_mom;
-            wo.mel_words = 0;
-            wo.mel_slots = 0;
-            wo.mel_groups = p->mel_mom_groups;
-            wo.n_mel = g.n_mel;
-        } else if (mel_fused && g.log2_nc == 8) {  // (the per-mel table of the banded sums, kernels.h)
-            wo.mel_tab = p->d_mel_rows;
-            wo.mel_groups = p->mel_rows_groups;
-            wo.mel_words = p->mel_rows_groups * (uint32_t)(th::MEL_ROWS_W + 1) * 64u;
-            wo.n_mel = g.n_mel;
-        } else if (mel_fused && p->mel_bsum_fits()) {  // banded sums (mel_slots = 0 tells the kernel)
-            wo.mel_tab = p->d_mel_bsum;
-            wo.mel_words = p->mel_bsum_words;
-            wo.mel_slots = 0;
-            wo.mel_groups = p->mel_bsum_groups;
-            for (uint32_t gq = 0; gq < 8; gq++) {
-                wo.band_off[gq] = p->mel_bsum_hdr[2 * gq];
-                wo.band_n[gq] = p->mel_bsum_hdr[2 * gq + 1];
-            }
-            wo.n_mel = g.n_mel;
-            // frame pairs (round 5): two consecutive frames per pass over the table; selector 13 keeps the one-frame epilogue (A/B)
-            wo.mel_pair = (p->kernel_choice != 13 && th::stft_wave_mel_pair_applies(g, p->wave_waves, p->mel_bsum_reach)) ? 1u : 0u;
-        } else if (mel_fused) {
-            wo.mel_tab = p->d_mel_fuse;
-            wo.mel_words = p->mel_fuse_words;
-            wo.mel_slots = p->mel_fuse_slots;
-            wo.mel_groups = p->mel_fuse_groups;
-            wo.n_mel = g.n_mel;
+        if (r.mel_fused != StftRoute::MelFused::None) wo.n_mel = g.n_mel;
+        switch (r.mel_fused) {
+            case StftRoute::MelFused::None: break;
+            case StftRoute::MelFused::Moment:
+            case StftRoute::MelFused::MomentLanes:  // moment form: the table stays in global memory (scalar + 16-byte lane loads)
+                wo.mel_moment = r.mel_fused == StftRoute::MelFused::Moment && g.log2_nc < 11 ? 1u : 0u;  // (n_fft 4096 and up: their only form)
+                wo.mel_tab = p->d_mel_mom;
+                wo.mel_groups = p->mel_mom_groups;
+                break;
+            case StftRoute::MelFused::Rows:  // (the per-mel table of the banded sums, kernels.h)
+                wo.mel_tab = p->d_mel_rows;
+                wo.mel_groups = p->mel_rows_groups;
+                wo.mel_words = p->mel_rows_groups * (uint32_t)(th::MEL_ROWS_W + 1) * 64u;
+                break;
+            case StftRoute::MelFused::Banded:
+            case StftRoute::MelFused::BandedPairs:  // banded sums (mel_slots = 0 tells the kernel)
+                wo.mel_tab = p->d_mel_bsum;
+                wo.mel_words = p->mel_bsum_words;
+                wo.mel_groups = p->mel_bsum_groups;
+                for (uint32_t gq = 0; gq < 8; gq++) {
+                    wo.band_off[gq] = p->mel_bsum_hdr[2 * gq];
+                    wo.band_n[gq] = p->mel_bsum_hdr[2 * gq + 1];
+                }
+                wo.mel_pair = r.mel_fused == StftRoute::MelFused::BandedPairs ? 1u : 0u;
+                break;
+            case StftRoute::MelFused::Pieces:
+                wo.mel_tab = p->d_mel_fuse;
+                wo.mel_words = p->mel_fuse_words;
+                wo.mel_slots = p->mel_fuse_slots;
+                wo.mel_groups = p->mel_fuse_groups;
+                break;
         }
         // min / max: the wave kernel stores one pair per chunk and its last workgroup folds them into the channel slots
         float *chunk_mm = nullptr;
@@ -1195,23 +1184,23 @@ static int calc_spec_batch_impl(th_plan *p, const th_chan_desc *chans, size_t n_
         p->queue_dirty = true;
         TH_HIP(launch_stft_wave(g, (const ChanJob *)p->jobs.dptr, (const uint32_t *)p->tile_start.dptr,
                                 (uint32_t)jobs.size(), (uint32_t)tiles, phased ? p->d_wtab_phased : p->d_wtab, p->d_tw, chunk_mm, p->d_queue_head,
-                                c->n_cu, waves, wo, c->stream));
+                                c->n_cu, r.waves, wo, c->stream));
         if (timed) TH_HIP(hipEventRecord(p->ev_k1[slot], c->stream));
         // fold the per-chunk (min, max) pairs into the channel slots and rewind the chunk queue
         range_done = d_range != nullptr && all_in_wave && n_post == 1 && n_chan == 1;
         TH_HIP(launch_wave_post((const th::WavePostJob *)p->post_jobs.dptr, n_post, chunk_mm, d_minmax, all_in_wave,
                                 p->d_queue_head, dB_range, range_done ? d_range : nullptr, c->stream));
         p->queue_dirty = false;
-        if (mel_mfma && p->d_mel_rows != nullptr && p->kernel_choice != 7)
+        if (r.mel_second == StftRoute::MelSecond::Rows)
             TH_HIP(launch_mel_rows((const MelJob *)p->mel_jobs.dptr, (const uint32_t *)p->mel_tile_start.dptr,
                                    (uint32_t)mel_jobs.size(), (uint32_t)mel_tiles, amp_pitch, p->d_mel_rows, p->mel_rows_groups,
                                    g.n_mel, d_minmax, c->n_cu, c->stream));
-        else if (mel_mfma && g.log2_nc >= 11 && p->d_mel_bsum != nullptr && p->kernel_choice != 7)
+        else if (r.mel_second == StftRoute::MelSecond::BandRows)
             TH_HIP(launch_mel_band_rows((const MelJob *)p->mel_jobs.dptr, (const uint32_t *)p->mel_tile_start.dptr,
                                         (uint32_t)mel_jobs.size(), (uint32_t)mel_tiles, amp_pitch, g.n_freq, p->d_mel_bsum,
                                         p->mel_bsum_words, p->mel_bsum_groups, p->mel_bsum_hdr, g.n_mel, d_minmax, c->n_cu,
                                         c->stream));
-        else if (mel_mfma)
+        else if (r.mel_second == StftRoute::MelSecond::Mfma)
             TH_HIP(launch_mel_mfma((const MelJob *)p->mel_jobs.dptr, (const uint32_t *)p->mel_tile_start.dptr,
                                    (uint32_t)mel_jobs.size(), (uint32_t)mel_tiles, amp_pitch, p->d_mel_bt, p->d_mel_band,
                                    p->d_mel_slice, p->mel_slices, p->mel_zero_block, g.n_mel, d_minmax, c->stream));
@@ -1220,7 +1209,7 @@ static int calc_spec_batch_impl(th_plan *p, const th_chan_desc *chans, size_t n_
                                        (uint32_t)edge.size(), (uint32_t)edge_tiles, p->d_window, p->d_tw, p->d_mel_fb,
                                        p->d_mel_lo, p->d_mel_hi, d_minmax, c->stream, p->gen_scratch.dptr, c->n_cu));
     } else {
-        if (p->bluestein())
+        if (r.main == StftRoute::Main::Bluestein)
             TH_HIP(launch_stft_bluestein(g, (const ChanJob *)p->jobs.dptr, (const uint32_t *)p->tile_start.dptr, (uint32_t)jobs.size(),
                                          (uint32_t)tiles, p->d_window, p->d_bs_chirp, p->d_bs_bhat, p->d_bs_twm, p->d_bs_tws, p->d_mel_fb,
                                          p->d_mel_lo, p->d_mel_hi, d_minmax, c->stream, p->gen_scratch.dptr, c->n_cu));
@@ -1307,7 +1296,7 @@ TH_API int th_plan_kernel_ms_history(th_plan *p, float *out_ms, size_t capacity,
     }
     // (selector 11, A/B builds: a pipelined caller never lets the stream go idle between launches, so the launch path's check for a
     // dropped chunk never runs there — this call has just waited for the launches it reports, check here as well: ADVICE r5)
-    if (n > 0 && p->kernel_choice == 11) {
+    if (n > 0 && p->route.sweep) {
         TH_HIP(hipStreamSynchronize(p->ctx->stream));
         const int src = sweep_check(p);
         if (src != TH_OK) return src;
@@ -1357,7 +1346,7 @@ TH_API int th_calc_spec_host(th_plan *p, const float *wav, size_t n_samples, flo
         rc = th_calc_spec_batch_dev(p, &d, 1, d_mm);
         if (rc == TH_OK) {
             float mm[2];
-            if (hipok(hipStreamSynchronize(c->stream), "sync") && (p->kernel_choice != 11 || (rc = sweep_check(p)) == TH_OK) &&
+            if (hipok(hipStreamSynchronize(c->stream), "sync") && (!p->route.sweep || (rc = sweep_check(p)) == TH_OK) &&
                 hipok(hipMemcpy(out_spec, d_spec, T * g.height * sizeof(float), hipMemcpyDeviceToHost), "download") &&
                 hipok(hipMemcpy(mm, d_mm, sizeof mm, hipMemcpyDeviceToHost), "download minmax")) {
                 if (out_min) *out_min = mm[0];

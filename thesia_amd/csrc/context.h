@@ -22,6 +22,52 @@ struct DeviceTable {
     void release();
 };
 
+// th_plan_set_kernel's selectors (bits 0-7), described in include/thesia_amd_testing.h.  Product builds refuse the A/B-only
+// ones there (9, 11, 14 at n_fft 32768 / 65536, 15 at n_fft 8192, and wave counts other than a size's own).
+enum StftSelector : int {
+    SEL_AUTO = 0,
+    SEL_GENERIC = 1,
+    SEL_WAVE = 2,              // every selector from here on asks for a wave kernel
+    SEL_MEL_AMP = 3,           // amplitude rows + a second mel kernel
+    SEL_NO_PHASE = 4,
+    SEL_PHASE_FUSED = 5,
+    SEL_MULTI_1024 = 6,
+    SEL_MEL_MFMA = 7,          // as 3, the matrix-core kernel also where 3 runs mel_rows / mel_band_rows
+    SEL_MEL_PIECES = 8,
+    SEL_PACKED = 9,
+    SEL_RESERVED = 10,         // as 2
+    SEL_SWEEP = 11,
+    SEL_MEL_TWO_KERNELS = 12,
+    SEL_MEL_ONE_FRAME = 13,
+    SEL_BLOCK = 14,
+    SEL_SUBWAVE = 15,
+};
+
+// Which kernels a plan launches, and how: everything about a th_calc_spec_batch_dev launch that the batch does not change.
+// resolve_route (api.hip) fills it from the plan's geometry, its tables and its kernel selector — at th_plan_create and at every
+// th_plan_set_kernel — and nothing else reads the selector.
+struct StftRoute {
+    enum class Main : uint8_t { Generic, Bluestein, Wave, WaveMulti, Block, Subwave };
+    // the mel filterbank in the main kernel's epilogue (mel_fuse.h): moment form with its table in global memory, the same as
+    // per-lane constants of the block kernel, mel_rows_kernel's table (n_fft 512), banded sums one frame or two at a time, pieces / gather
+    enum class MelFused : uint8_t { None, Moment, MomentLanes, Rows, Banded, BandedPairs, Pieces };
+    enum class MelSecond : uint8_t { None, Rows, BandRows, Mfma };  // the mel kernel behind amplitude rows
+    Main main = Main::Generic;
+    MelFused mel_fused = MelFused::None;
+    MelSecond mel_second = MelSecond::None;
+    bool no_wave_kernel = false;   // a selector >= 2 asked for a wave kernel this plan has none of: th_calc_spec_batch_dev fails
+    int phase_mode = 0;            // StftGeom::phased of the launch (grid-aligned frame loop; window table d_wtab_phased when != 0)
+    int waves = 0;                 // waves per workgroup of the wave kernels
+    uint32_t tail_guard = 0;       // stft_wave_multi_tail_guard, or 0
+    bool edges_in_wave = false;    // boundary frames of channels of at least n_fft samples run inside the wave launch
+    int long_plan = 1;             // WaveOut::long_plan: 1 stft_block_kernel, 2 stft_subwave_kernel (read at n_fft 8192 and above)
+    bool sweep = false;            // selector 11's sweep schedule exists for this plan (the launch adds: the batch is large enough)
+    bool packed = false;           // selector 9: WaveOut::packed
+    char name[48] = "";            // th_plan_kernel_name
+    bool wave() const { return main != Main::Generic && main != Main::Bluestein; }
+    int out_mode() const { return mel_second != MelSecond::None ? 1 : mel_fused != MelFused::None ? 2 : 0; }  // WaveOut::mode
+};
+
 }  // namespace th
 
 struct th_ctx {
@@ -64,7 +110,7 @@ struct th_plan {
     th_ctx *ctx = nullptr;
     uint32_t sr = 0;
     int freq_scale = 0;
-    int kernel_choice = 0;  // 0 auto, 1 generic, 2 wave, 3 wave with the matrix-core mel kernel (no fused epilogue), 4 wave without the phased mode
+    int kernel_choice = 0;  // th_plan_set_kernel's selector (th::StftSelector); read by resolve_route only
     int wave_waves = 0;     // tuning: waves per workgroup of the wave kernel (0 = default)
     int wave_chunk = 0;     // tuning: frames per chunk of the wave kernel (0 = default)
     // th_plan_time_kernel: a ring of event pairs around the STFT kernel launch (no synchronisation while recording)
@@ -82,7 +128,6 @@ struct th_plan {
     bool queue_dirty = false;          // a wave launch went out whose rewind did not: the next launch zeroes the head first
     th::cf32 *d_wtab = nullptr;  // wave kernel: 0.5 * zero-padded window as (even, odd) pairs
     th::cf32 *d_wtab_phased = nullptr;  // phased mode: 48 zero pairs + the table with the window at offset 0 (NULL: not applicable)
-    bool use_wave() const;
     float *d_mel_fb = nullptr;
     uint32_t *d_mel_lo = nullptr, *d_mel_hi = nullptr;
     std::vector<float> h_mel_fb;
@@ -98,10 +143,6 @@ struct th_plan {
     th::DeviceTable chunk_mm;                            // (min, max) per chunk of the wave kernel's last launch
     th::DeviceTable gen_scratch;                         // n_fft >= 32768: frame buffers of the generic kernel (global scratch)
     th::DeviceTable post_jobs;                           // per-channel tile ranges for wave_post_kernel
-    bool use_mel_mfma() const;   // mel plan: amplitude rows + mel_mfma_kernel
-    bool use_mel_fused() const;  // mel plan: filterbank fused into the wave kernel's epilogue (mel_fuse.h)
-    bool use_mel_moment_small() const;  // n_fft 1024 / 2048 mel plan whose table forms do not fit LDS: the moment-form epilogue (round 6)
-    int long_plan() const;       // n_fft 8192 .. 65536: 0 = the size's default plan, 1 = stft_block_kernel, 2 = stft_subwave_kernel (WaveOut::long_plan)
     // fused mel epilogue: device copy of the mel_fuse.h word table
     uint32_t *d_mel_fuse = nullptr;
     uint32_t mel_fuse_words = 0, mel_fuse_slots = 0, mel_fuse_groups = 0;
@@ -114,8 +155,8 @@ struct th_plan {
     uint32_t *d_mel_mom = nullptr;
     uint32_t mel_mom_groups = 0, mel_mom_taps = 0;
     double mel_mom_max_dev = 0.0, mel_mom_max_amp = 0.0;
-    bool mel_bsum_fits() const;
     th::DeviceTable jobs, tile_start;            // main launch: jobs + first chunk of every job (generic kernel) or the
                                                  // per-chunk (job, first frame) table (wave kernels)
     th::DeviceTable edge_jobs, edge_tile_start;  // boundary frames handed to the generic kernel
+    th::StftRoute route;                         // resolve_route (api.hip)
 };

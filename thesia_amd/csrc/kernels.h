@@ -95,7 +95,7 @@ struct WaveOut {
     // mel counts above what an LDS table holds.  (n_fft 4096 .. 16384 mel plans are always this form.)
     uint32_t mel_moment = 0;
     const cf32 *subwave_twc = nullptr;  // DEVICE: stft_subwave_build_twc's table (n_fft 32768 plans)
-    int long_plan = 0;  // n_fft 8192 .. 32768: 0 = the default of the size (stft_subwave_default), 1 = stft_block_kernel, 2 = stft_subwave_kernel
+    int long_plan = 1;  // n_fft 8192 .. 65536: 1 = stft_block_kernel, 2 = stft_subwave_kernel (the host resolves the size's default: stft_subwave_default)
 };
 // ---- kernels_stft_long.hip: n_fft 8192 / 16384 / 32768 as 4 / 8 / 16 wave transforms + one combining pass (interior frames, as the block kernel)
 bool stft_subwave_applies(const StftGeom &g);

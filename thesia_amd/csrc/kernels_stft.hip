@@ -2289,10 +2289,10 @@ bool stft_wave_supported(const StftGeom &g) {
 }
 bool stft_is_block_plan(const StftGeom &g) { return g.log2_nc >= 12; }
 // mel rows in the block kernel's own epilogue (moment form): n_fft 8192 / 16384 where stft_block_kernel is what runs
-// (long_plan: 0 the size's default plan, 1 block kernel, 2 subwave plan — WaveOut::long_plan)
+// (long_plan: 1 block kernel, 2 subwave plan — WaveOut::long_plan)
 bool stft_block_mel_fused_applies(const StftGeom &g, int long_plan) {
     if (g.odd_m1 != 0 || g.phased != 0 || (g.log2_nc != 12 && g.log2_nc != 13)) return false;
-    return long_plan == 1 || (long_plan == 0 && !stft_subwave_default(g));
+    return long_plan == 1;
 }
 // amplitude floats a lane of that epilogue may address (the exchange buffer), and the most groups it takes
 uint32_t stft_block_mel_max_index(const StftGeom &g) { return 2u * (g.nc + g.nc / 16u + 2u) - 64u; }
@@ -2697,7 +2697,7 @@ hipError_t launch_stft_wave(const StftGeom &g, const ChanJob *d_jobs, const uint
         }
         if (out.mode > 1) return hipErrorInvalidValue;
         // round 5: R wave transforms + one combining pass (kernels_stft_long.hip): the default at n_fft 32768, selector 15 elsewhere
-        if (stft_subwave_applies(g) && out.subwave_twc != nullptr && (out.long_plan == 2 || (out.long_plan == 0 && stft_subwave_default(g))))
+        if (stft_subwave_applies(g) && out.subwave_twc != nullptr && out.long_plan == 2)
             return launch_stft_subwave(g, d_jobs, d_tile_start, n_tiles, d_wtab, d_tw, out.subwave_twc, out.mode == 1 ? nullptr : d_minmax, out.mode == 1, n_cu, s);
         if (out.mode == 1) {  // amplitude rows, no (min, max)
             if (g.log2_nc == 12) return launch_block<12, 1>(g, d_jobs, d_tile_start, n_tiles, d_wtab, d_tw, nullptr, s);
