@@ -29,8 +29,10 @@
  *   - The caller owns every host buffer it passes.  Inputs are borrowed for the call only.
  *     Outputs go to caller buffers with a capacity; the written length is returned.
  *   - The library owns device memory behind opaque handles with explicit destroy.
- *   - "_dev" entries take DEVICE pointers, enqueue on the context's HIP stream and do not
- *     synchronise unless they return data to the host.  All other entries take HOST pointers.
+ *   - "_dev" entries take DEVICE pointers and enqueue on the context's HIP stream.  A call that returns data to the
+ *     host synchronises that stream; so does a first call, or one whose descriptors changed, when it uploads its
+ *     descriptor tables or grows a scratch buffer.  A repeat call with the same descriptors only enqueues.
+ *     All other entries take HOST pointers.
  *   - Compute entries (th_calc_spec_*, th_tm_* mutators) may assume exclusive access, like the
  *     reference's single write-lock worker (interface.rs:12-56).  th_tm_* tile getters run
  *     concurrently with each other (each request has its own HIP stream and pinned staging buffer)
