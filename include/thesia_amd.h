@@ -319,6 +319,37 @@ typedef struct {
 TH_API int th_channel_stats_dev(th_ctx *ctx, const th_stats_desc *descs, size_t n, float *out_sum_squares,
                                 float *out_abs_max);
 
+/* Loudness of whole tracks — StatCalculator::calc (dynamics/stats.rs:56-86), the AudioStats behind get_global_lufs, get_rms_dB and
+ * get_max_peak_dB (lib.rs:463-489).  global_lufs: EBU R128 integrated loudness as the ebur128 crate computes it with Mode::all()
+ * (histogram gating: 0.1 LU bins; K-weighting in f64; default channel map: 4 ch L R Ls Rs, 5 ch L R C Ls Rs, otherwise channel 3 and
+ * channels from 6 on unused, Ls / Rs weigh 1.41); -inf when no 400 ms block passes the gates.  rms_dB = 10 log10(sum of squares over
+ * all channels / (n_channels n_samples)) and max_peak_dB = 20 log10(max |x|), both in f32 (0 gives -inf, NaN stays NaN; no samples
+ * give rms_dB = NaN, max_peak = 0, max_peak_dB = -inf). */
+typedef struct {
+    double global_lufs;
+    float rms_dB;
+    float max_peak;
+    float max_peak_dB;
+    uint32_t reserved[3];
+} th_audio_stats;
+typedef struct {
+    const float *const *channels; /* HOST array of n_channels DEVICE pointers (n_samples f32 each) */
+    uint64_t n_samples;
+    uint32_t n_channels;          /* >= 1 */
+    uint32_t sr;                  /* 16 .. 2 822 400 (the rates EbuR128::new accepts), else TH_ERR_UNSUPPORTED */
+    double *block_energy;         /* DEVICE, may be NULL: receives the th_loudness_n_blocks values E_k of the momentary (400 ms, hop
+                                   * 100 ms) series, E_k = sum_c w_c sum_(block) y_c^2 / block length, in stream order */
+} th_audio_desc;
+/* A batch of tracks; out_host[n].  Returns to the host: synchronises the context's stream. */
+TH_API int th_audio_stats_dev(th_ctx *ctx, const th_audio_desc *descs, size_t n, th_audio_stats *out_host);
+/* The host arithmetic around it (no GPU).  th_k_weighting: the 4th-order K-weighting section at rate sr, b[5] and a[5] (a[0] = 1),
+ * designed as libebur128 does; TH_ERR_UNSUPPORTED outside 16 .. 2 822 400 Hz.  th_loudness_n_blocks: (n - 4 s100) / s100 + 1 blocks
+ * of 4 s100 samples, s100 = (sr + 5) / 10, or 0 when n < 4 s100.  th_gated_loudness: integrated LUFS of a block-energy series
+ * (histogram-mode absolute and relative gates; NaN energies never count). */
+TH_API int th_k_weighting(uint32_t sr, double b[5], double a[5]);
+TH_API int th_loudness_n_blocks(size_t n_samples, uint32_t sr, size_t *n_blocks);
+TH_API int th_gated_loudness(const double *block_energies, size_t n, double *lufs);
+
 /* Waveform pyramid: every decimation level of a channel from one pass over the audio.  Level L
  * (samples per bin 2^L, exactly the bins encode_waveform_tile emits for that level — render_tiles.rs:232-279)
  * has th_waveform_pyramid_bins(n, L) = ceil(n / 2^L) bins of (min, max, mean) f32 and starts at float offset
@@ -443,6 +474,11 @@ typedef struct {
 } th_render_metadata;
 TH_API int th_tm_get_audio_render_metadata(th_tm *tm, size_t id, uint32_t ch, double track_sec, int is_clipped,
                                            th_render_metadata *out);
+/* AudioStats of a resident track (get_global_lufs / get_rms_dB / get_max_peak_dB, lib.rs:463-489): computed by th_tm_add_tracks from
+ * the uploaded samples, replaced when the id is added again, dropped by remove_track, untouched by every other call.  A reader: no
+ * GPU work.  TH_ERR_NOT_FOUND when the id is not resident (the reference then answers -inf); a track whose rate the ebur128 crate
+ * refuses (outside 16 .. 2 822 400 Hz) has global_lufs = NaN. */
+TH_API int th_tm_get_audio_stats(th_tm *tm, size_t id, th_audio_stats *out);
 /* the RenderTileCache in front of get_waveform_tile (lib.rs:350-366): borrowed, owned by tm */
 TH_API int th_tm_tile_cache(th_tm *tm, th_tile_cache **out);
 /* Spectrogram tiles with level_x or level_y > 0 (resize_spectrogram_tile, render_tiles.rs:354-393).
@@ -517,6 +553,7 @@ TH_API int th_tmg_get_waveform_tile(th_tmg *tmg, size_t id, uint32_t ch, uint32_
 TH_API int th_tmg_get_audio_render_metadata(th_tmg *tmg, size_t id, uint32_t ch, double track_sec, int is_clipped,
                                             th_render_metadata *out);
 TH_API int th_tmg_set_lod_source(th_tmg *tmg, int per_request);
+TH_API int th_tmg_get_audio_stats(th_tmg *tmg, size_t id, th_audio_stats *out);
 
 /* Test and measurement entry points (kernel selectors for A/B runs, per-launch kernel timing, replacing a resident image
  * with given pixels) are NOT part of this interface: include/thesia_amd_testing.h declares them; a thesia host binds none. */

@@ -69,6 +69,16 @@ class StatsDesc(C.Structure):
     _fields_ = [("wav", C.c_void_p), ("n_samples", C.c_uint64)]
 
 
+class AudioStats(C.Structure):  # th_audio_stats
+    _fields_ = [("global_lufs", C.c_double), ("rms_dB", C.c_float), ("max_peak", C.c_float), ("max_peak_dB", C.c_float),
+                ("reserved", C.c_uint32 * 3)]
+
+
+class AudioDesc(C.Structure):  # th_audio_desc
+    _fields_ = [("channels", C.POINTER(C.c_void_p)), ("n_samples", C.c_uint64), ("n_channels", C.c_uint32), ("sr", C.c_uint32),
+                ("block_energy", C.c_void_p)]
+
+
 class PyramidDesc(C.Structure):
     _fields_ = [("wav", C.c_void_p), ("out", C.c_void_p), ("n_samples", C.c_uint64), ("n_levels", C.c_uint32),
                 ("first_level", C.c_uint32)]
@@ -194,6 +204,12 @@ _SIGS = {
     "th_plan_last_kernel_ms": [vp, C.POINTER(C.c_float)],
     "th_plan_kernel_ms_history": [vp, c_f32p, C.c_size_t, c_szp],
     "th_channel_stats_dev": [vp, C.POINTER(StatsDesc), C.c_size_t, c_f32p, c_f32p],
+    "th_audio_stats_dev": [vp, C.POINTER(AudioDesc), C.c_size_t, C.POINTER(AudioStats)],
+    "th_k_weighting": [C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)],
+    "th_loudness_n_blocks": [C.c_size_t, C.c_uint32, c_szp],
+    "th_gated_loudness": [C.POINTER(C.c_double), C.c_size_t, C.POINTER(C.c_double)],
+    "th_tm_get_audio_stats": [vp, C.c_size_t, C.POINTER(AudioStats)],
+    "th_tmg_get_audio_stats": [vp, C.c_size_t, C.POINTER(AudioStats)],
     "th_waveform_pyramid_bins": [C.c_uint64, C.c_uint32],
     "th_waveform_pyramid_offset": [C.c_uint64, C.c_uint32],
     "th_waveform_pyramid_dev": [vp, C.POINTER(PyramidDesc), C.c_size_t],

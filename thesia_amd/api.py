@@ -133,6 +133,31 @@ def waveform_tile_geometry(n_samples: int, level: int, tile_index: int):
 
 
 # ------------------------------------------------------------------ device context
+def _audio_stats_dict(o) -> dict:
+    return {"global_lufs": o.global_lufs, "rms_dB": o.rms_dB, "max_peak": o.max_peak, "max_peak_dB": o.max_peak_dB}
+
+
+def k_weighting(sr: int):
+    """-> (b[5], a[5]) of the K-weighting section at rate sr (host arithmetic)"""
+    b, a = (C.c_double * 5)(), (C.c_double * 5)()
+    check(lib.th_k_weighting(sr, b, a))
+    return np.array(b[:]), np.array(a[:])
+
+
+def loudness_n_blocks(n_samples: int, sr: int) -> int:
+    n = C.c_size_t()
+    check(lib.th_loudness_n_blocks(n_samples, sr, C.byref(n)))
+    return n.value
+
+
+def gated_loudness(block_energies) -> float:
+    """integrated LUFS of a block-energy series (host arithmetic)"""
+    e = np.ascontiguousarray(block_energies, dtype=np.float64)
+    out = C.c_double()
+    check(lib.th_gated_loudness(e.ctypes.data_as(C.POINTER(C.c_double)), e.size, C.byref(out)))
+    return out.value
+
+
 class DeviceBuffer:
     """hipMalloc'd buffer owned through the C ABI (th_dev_alloc / th_dev_free)."""
 
@@ -359,6 +384,21 @@ class Context:
         ss, pk = np.empty(len(arr), np.float32), np.empty(len(arr), np.float32)
         check(lib.th_channel_stats_dev(self.handle, arr, len(arr), _ptr(ss, c_f32p), _ptr(pk, c_f32p)))
         return ss, pk
+
+    # ---- loudness (StatCalculator::calc, dynamics/stats.rs:56-86)
+    def audio_stats_dev(self, tracks):
+        """tracks: [(channel device pointers, n_samples, sr, block_energy device pointer or 0)] -> [dict] of th_audio_stats
+        (global_lufs, rms_dB, max_peak, max_peak_dB); the block energies land in the given device buffers"""
+        descs = (_ffi.AudioDesc * len(tracks))()
+        keep = []
+        for d, (chans, n, sr, be) in zip(descs, tracks):
+            arr = (C.c_void_p * len(chans))(*chans)
+            keep.append(arr)
+            d.channels = C.cast(arr, C.POINTER(C.c_void_p))
+            d.n_samples, d.n_channels, d.sr, d.block_energy = n, len(chans), sr, be or None
+        out = (_ffi.AudioStats * max(len(tracks), 1))()
+        check(lib.th_audio_stats_dev(self.handle, descs, len(tracks), out))
+        return [_audio_stats_dict(o) for o in out[:len(tracks)]]
 
     # ---- waveform pyramid: all levels of a channel in one pass over the audio
     def waveform_pyramid_dev(self, descs):
@@ -713,6 +753,12 @@ class TrackManager:
         check(lib.th_tm_get_audio_render_metadata(self.handle, track_id, ch, track_sec, int(is_clipped), C.byref(m)))
         return {k: getattr(m, k) for k, _ in m._fields_}
 
+    def audio_stats(self, track_id: int) -> dict:
+        """AudioStats of a resident track (get_global_lufs / get_rms_dB / get_max_peak_dB, lib.rs:463-489)."""
+        o = _ffi.AudioStats()
+        check(lib.th_tm_get_audio_stats(self.handle, track_id, C.byref(o)))
+        return _audio_stats_dict(o)
+
     def tile_cache(self) -> TileCache:
         """The RenderTileCache in front of get_waveform_tile (borrowed; owned by the manager)."""
         h = vp()
@@ -875,6 +921,11 @@ class MultiTrackManager:
 
     def set_lod_source(self, per_request: bool) -> None:
         check(lib.th_tmg_set_lod_source(self.handle, int(per_request)))
+
+    def audio_stats(self, track_id: int) -> dict:
+        o = _ffi.AudioStats()
+        check(lib.th_tmg_get_audio_stats(self.handle, track_id, C.byref(o)))
+        return _audio_stats_dict(o)
 
     def render_metadata(self, track_id: int, ch: int, track_sec: float, is_clipped: bool) -> dict:
         m = _ffi.RenderMetadata()

@@ -1844,3 +1844,199 @@ TH_API int th_encode_waveform_tile_dev(th_ctx *c, const float *d_wav, size_t n_s
     return TH_OK;
     TH_CATCH
 }
+
+// ------------------------------------------------------------------------------------------ loudness (StatCalculator::calc)
+TH_API int th_k_weighting(uint32_t sr, double b[5], double a[5]) {
+    TH_TRY
+    TH_REQUIRE(b && a, "NULL argument");
+    if (!loudness_rate_ok(sr)) return fail(TH_ERR_UNSUPPORTED, "sample rate %u outside [16, 2822400]", sr);
+    k_weighting(sr, b, a);
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_loudness_n_blocks(size_t n_samples, uint32_t sr, size_t *n_blocks) {
+    TH_TRY
+    TH_REQUIRE(n_blocks, "NULL argument");
+    if (!loudness_rate_ok(sr)) return fail(TH_ERR_UNSUPPORTED, "sample rate %u outside [16, 2822400]", sr);
+    *n_blocks = loudness_n_blocks(n_samples, sr);
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_gated_loudness(const double *block_energies, size_t n, double *lufs) {
+    TH_TRY
+    TH_REQUIRE(lufs && (n == 0 || block_energies), "NULL argument");
+    *lufs = gated_loudness(block_energies, n);
+    return TH_OK;
+    TH_CATCH
+}
+
+namespace th {
+
+LoudnessBatch::~LoudnessBatch() {
+    if (d_own) {
+        (void)hipSetDevice(ctx->device);
+        (void)hipFree(d_own);
+    }
+}
+
+int loudness_enqueue(th_ctx *c, const th_audio_desc *descs, size_t n, bool own_memory, bool allow_bad_rate, LoudnessBatch *b) {
+    b->ctx = c;
+    std::vector<uint32_t> rate_of(n, 0);
+    std::vector<const LoudnessRate *> rates;
+    std::vector<LoudJob> jobs;
+    std::vector<LoudTrackJob> tjobs;
+    size_t n_states = 0, n_blocks = 0;
+    uint32_t max_chunks = 0, max_fchunks = 0, lds_floats = 4;
+    uint64_t max_blocks = 0;
+    for (size_t t = 0; t < n; t++) {
+        const th_audio_desc &d = descs[t];
+        TH_REQUIRE(d.n_channels >= 1 && d.channels, "track %zu: no channels", t);
+        TH_REQUIRE(d.n_samples < (1ull << 40), "track %zu: too many samples", t);
+        const bool ok = loudness_rate_ok(d.sr);
+        if (!ok && !allow_bad_rate) return fail(TH_ERR_UNSUPPORTED, "track %zu: sample rate %u outside [16, 2822400]", t, d.sr);
+        // (a refused rate: the sums only, over chunks of a 48 kHz geometry)
+        const LoudnessRate &R = loudness_rate(ok ? d.sr : 48000);
+        size_t ri = 0;
+        while (ri < rates.size() && rates[ri] != &R) ri++;
+        if (ri == rates.size()) rates.push_back(&R);
+        const uint64_t nb = ok ? loudness_n_blocks(d.n_samples, d.sr) : 0;
+        const uint64_t nseg = (d.n_samples + R.s100 - 1) / R.s100;
+        TH_REQUIRE(nseg * R.n_sub < (1ull << 31), "track %zu: too many samples", t);
+        const uint32_t nch = (uint32_t)(nseg * R.n_sub), nf = nb ? (uint32_t)((nb + 3) * R.n_sub) : 0u;
+        b->ch0.push_back(jobs.size());
+        b->blk0.push_back(n_blocks);
+        b->srs.push_back(d.sr);
+        b->ns.push_back(d.n_samples);
+        for (uint32_t k = 0; k < d.n_channels; k++) {
+            TH_REQUIRE(d.n_samples == 0 || d.channels[k], "track %zu channel %u: NULL device pointer", t, k);
+            LoudJob j{};
+            j.wav = d.channels[k];
+            j.n = d.n_samples;
+            j.rate = (uint32_t)ri;
+            j.n_chunks = nch;
+            j.n_fchunks = nf;
+            j.aligned16 = (reinterpret_cast<uintptr_t>(d.channels[k]) & 15u) == 0;
+            jobs.push_back(j);
+            n_states += nf;
+        }
+        LoudTrackJob tj{};
+        tj.n_blocks = nb;
+        for (uint32_t k = 0; k < 8; k++) tj.w[k] = loudness_channel_weight(k, d.n_channels);
+        tj.n_ch = d.n_channels;
+        tj.n_sub = R.n_sub;
+        tj.n_fchunks = nf;
+        tj.L = 4 * R.s100;
+        tjobs.push_back(tj);
+        n_blocks += nb;
+        max_chunks = std::max(max_chunks, nch);
+        max_fchunks = std::max(max_fchunks, nf);
+        max_blocks = std::max<uint64_t>(max_blocks, nb);
+        lds_floats = std::max(lds_floats, R.cl + 4);
+    }
+    TH_REQUIRE(jobs.size() <= 65535 && n <= 65535, "at most 65535 channels and tracks per call");
+    b->n_ch = jobs.size();
+    b->n_blocks = n_blocks;
+    // device layout: [jobs][rates][track jobs] | [sums n_ch][peaks n_ch (u32, padded)][block energies] | [states 8 / chunk][energies]
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t o_rates = up(jobs.size() * sizeof(LoudJob)), o_tj = o_rates + up(rates.size() * sizeof(LoudnessRate));
+    const size_t o_sums = o_tj + up(tjobs.size() * sizeof(LoudTrackJob));
+    const size_t sums_bytes = b->n_ch * 8 + (b->n_ch * 4 + 7) / 8 * 8;
+    const size_t o_blk = o_sums + sums_bytes, o_z = up(o_blk + n_blocks * 8), o_q = o_z + n_states * 64;
+    const size_t total = o_q + n_states * 8 + 8;
+    TH_HIP(hipSetDevice(c->device));
+    unsigned char *dm;
+    if (own_memory) {
+        TH_HIP(hipMalloc(&b->d_own, total));
+        dm = static_cast<unsigned char *>(b->d_own);
+    } else {
+        TH_HIP(hipStreamSynchronize(c->stream));  // (the last call's launches may still read the tables)
+        const int rc = c->loud_mem.ensure(total);
+        if (rc != TH_OK) return rc;
+        dm = static_cast<unsigned char *>(c->loud_mem.dptr);
+    }
+    b->d_sums = reinterpret_cast<double *>(dm + o_sums);
+    double *d_blk = reinterpret_cast<double *>(dm + o_blk), *d_z = reinterpret_cast<double *>(dm + o_z), *d_q = reinterpret_cast<double *>(dm + o_q);
+    uint32_t *d_pk = reinterpret_cast<uint32_t *>(dm + o_sums + b->n_ch * 8);
+    size_t si = 0;
+    for (size_t t = 0, jc = 0; t < n; t++) {
+        const size_t q0 = si;
+        for (uint32_t k = 0; k < descs[t].n_channels; k++, jc++) {
+            LoudJob &j = jobs[jc];
+            j.z = d_z + 8 * si;
+            j.q = d_q + si;
+            j.sumsq = b->d_sums + jc;
+            j.peak = d_pk + jc;
+            si += j.n_fchunks;
+        }
+        tjobs[t].q = d_q + q0;
+        tjobs[t].out = d_blk + b->blk0[t];
+    }
+    std::vector<unsigned char> h(o_sums, 0);
+    std::memcpy(h.data(), jobs.data(), jobs.size() * sizeof(LoudJob));
+    for (size_t r = 0; r < rates.size(); r++) std::memcpy(h.data() + o_rates + r * sizeof(LoudnessRate), rates[r], sizeof(LoudnessRate));
+    std::memcpy(h.data() + o_tj, tjobs.data(), tjobs.size() * sizeof(LoudTrackJob));
+    TH_HIP(hipMemcpy(dm, h.data(), o_sums, hipMemcpyHostToDevice));  // (nothing on the stream reads this memory yet)
+    TH_HIP(hipMemsetAsync(b->d_sums, 0, sums_bytes, c->stream));      // sums = 0, peaks = +0.0
+    TH_HIP(launch_loudness(reinterpret_cast<const LoudJob *>(dm), (uint32_t)jobs.size(), max_chunks, max_fchunks,
+                           reinterpret_cast<const LoudnessRate *>(dm + o_rates), lds_floats, reinterpret_cast<const LoudTrackJob *>(dm + o_tj),
+                           (uint32_t)n, max_blocks, c->stream));
+    for (size_t t = 0; t < n; t++)
+        if (descs[t].block_energy && tjobs[t].n_blocks)
+            TH_HIP(hipMemcpyAsync(descs[t].block_energy, tjobs[t].out, tjobs[t].n_blocks * 8, hipMemcpyDeviceToDevice, c->stream));
+    return TH_OK;
+}
+
+int loudness_collect(LoudnessBatch *b, bool sync_stream) {
+    th_ctx *c = b->ctx;
+    TH_HIP(hipSetDevice(c->device));
+    const size_t sums_bytes = b->n_ch * 8 + (b->n_ch * 4 + 7) / 8 * 8;
+    b->h_sums.assign(sums_bytes / 8 + b->n_blocks, 0.0);
+    if (sync_stream) {
+        TH_HIP(hipMemcpyAsync(b->h_sums.data(), b->d_sums, sums_bytes + b->n_blocks * 8, hipMemcpyDeviceToHost, c->stream));
+        TH_HIP(hipStreamSynchronize(c->stream));
+    } else {
+        TH_HIP(hipMemcpy(b->h_sums.data(), b->d_sums, sums_bytes + b->n_blocks * 8, hipMemcpyDeviceToHost));
+    }
+    return TH_OK;
+}
+
+void loudness_result(const LoudnessBatch &b, size_t t, th_audio_stats *out) {
+    *out = th_audio_stats{};
+    const size_t c0 = b.ch0[t], c1 = t + 1 < b.ch0.size() ? b.ch0[t + 1] : b.n_ch;
+    const size_t sums_words = (b.n_ch * 8 + (b.n_ch * 4 + 7) / 8 * 8) / 8;
+    const uint32_t *pk = reinterpret_cast<const uint32_t *>(b.h_sums.data() + b.n_ch);
+    // StatCalculator::calc (stats.rs:62-77): f32 sums of the channels' f32 sums of squares, f32 division, log_for_dB (amin = 0)
+    float ss = 0.0f, peak = 0.0f;
+    for (size_t k = c0; k < c1; k++) {
+        ss += (float)b.h_sums[k];
+        float p;
+        std::memcpy(&p, &pk[k], 4);
+        peak = std::max(peak, p);
+    }
+    const float mean_sq = ss / (float)((double)(c1 - c0) * (double)b.ns[t]);
+    // (the logarithms in f64, rounded once: within half an ulp of the exact f32 result, where log10f itself may be off by one)
+    out->rms_dB = mean_sq == 0.0f ? -INFINITY : (float)(10.0 * std::log10((double)mean_sq));
+    out->max_peak = peak;
+    out->max_peak_dB = peak == 0.0f ? -INFINITY : (float)(20.0 * std::log10((double)peak));
+    const size_t nb = (t + 1 < b.blk0.size() ? b.blk0[t + 1] : b.n_blocks) - b.blk0[t];
+    out->global_lufs = loudness_rate_ok(b.srs[t]) ? gated_loudness(b.h_sums.data() + sums_words + b.blk0[t], nb) : NAN;
+}
+
+}  // namespace th
+
+TH_API int th_audio_stats_dev(th_ctx *c, const th_audio_desc *descs, size_t n, th_audio_stats *out_host) {
+    TH_TRY
+    TH_REQUIRE(c, "ctx is NULL");
+    if (n == 0) return TH_OK;
+    TH_REQUIRE(descs && out_host, "NULL argument");
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    LoudnessBatch b;
+    int rc = loudness_enqueue(c, descs, n, false, false, &b);
+    if (rc == TH_OK) rc = loudness_collect(&b, true);
+    if (rc != TH_OK) return rc;
+    for (size_t t = 0; t < n; t++) loudness_result(b, t, &out_host[t]);
+    return TH_OK;
+    TH_CATCH
+}

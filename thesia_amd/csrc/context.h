@@ -80,7 +80,7 @@ struct th_ctx {
     // (tile encoders → batched launchers) can hold it across the whole request.
     std::recursive_mutex mu;
     th::DeviceTable img_jobs, img_start, raster_jobs, raster_start, wave_jobs, wave_start, colormap, tile_out, lod_tabs, lod_tmp,
-        pyr_jobs, pyr_sums, fused_jobs, fused_start, fused_ptrs;
+        pyr_jobs, pyr_sums, fused_jobs, fused_start, fused_ptrs, loud_mem;
     // the descriptor batches the img / raster tables were built from (identical batch -> tables reused as they are)
     std::vector<unsigned char> img_descs_key, raster_descs_key, fused_key;
     uint32_t img_tiles_key = 0, raster_blocks_key = 0, fused_blocks_key = 0;
@@ -103,6 +103,7 @@ struct th_ctx {
         lod_tmp.release();
         pyr_jobs.release();
         pyr_sums.release();
+        loud_mem.release();
     }
 };
 
@@ -160,3 +161,28 @@ struct th_plan {
     th::DeviceTable edge_jobs, edge_tile_start;  // boundary frames handed to the generic kernel
     th::StftRoute route;                         // resolve_route (api.hip)
 };
+
+namespace th {
+// A batch of th_audio_desc tracks on a context's stream (th_audio_stats_dev; th_tm_add_tracks: one per group of tracks).
+// loudness_enqueue uploads the tables (synchronously, into `scratch` after the stream has drained, or into a fresh allocation of
+// the batch's own) and enqueues the passes; loudness_collect reads the results back once the stream has got that far.
+struct LoudnessBatch {
+    th_ctx *ctx = nullptr;
+    void *d_own = nullptr;     // the batch's own device memory (NULL: the context's loud_mem)
+    double *d_sums = nullptr;  // n_ch sums of squares, then n_ch peaks (u32), then the block energies of every track
+    size_t n_ch = 0, n_blocks = 0;
+    std::vector<size_t> ch0, blk0;  // per track: first channel, first block
+    std::vector<uint32_t> srs;
+    std::vector<uint64_t> ns;
+    std::vector<double> h_blocks;
+    std::vector<double> h_sums;
+    LoudnessBatch() = default;
+    LoudnessBatch(const LoudnessBatch &) = delete;
+    LoudnessBatch &operator=(const LoudnessBatch &) = delete;
+    ~LoudnessBatch();
+};
+// allow_bad_rate: a track at a rate outside [16, 2 822 400] gets its sums only (global_lufs = NaN) instead of TH_ERR_UNSUPPORTED
+int loudness_enqueue(th_ctx *c, const th_audio_desc *descs, size_t n, bool own_memory, bool allow_bad_rate, LoudnessBatch *b);
+int loudness_collect(LoudnessBatch *b, bool sync_stream);
+void loudness_result(const LoudnessBatch &b, size_t t, th_audio_stats *out);
+}  // namespace th

@@ -6,6 +6,9 @@
 #include <cmath>
 #include <cstring>
 #include <limits>
+#include <map>
+#include <memory>
+#include <mutex>
 
 namespace th {
 
@@ -325,6 +328,205 @@ BluesteinTables bluestein_tables(size_t n_fft, size_t M) {
     }
     t.bhat = std::move(x);
     return t;
+}
+
+// ---------------------------------------------------------------------------------------------- integrated loudness
+// StatCalculator::calc (dynamics/stats.rs:56-86) is EbuR128::new(n_ch, sr, Mode::all()) + add_frames_planar_f32 +
+// loudness_global() of the ebur128 crate 0.1.10 (Cargo.lock:1192), a port of libebur128.  What follows is libebur128's
+// arithmetic; the crate's own source is not pinned here.
+
+// ebur128_init_filter: the high shelf and the high-pass of ITU-R BS.1770-4 designed for `sr`, multiplied into one section
+void k_weighting(uint32_t sr, double b[5], double a[5]) {
+    const double pi = 3.14159265358979323846;
+    double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
+    double K = std::tan(pi * f0 / (double)sr);
+    const double Vh = std::pow(10.0, G / 20.0);
+    const double Vb = std::pow(Vh, 0.4996667741545416);
+    double pb[3], pa[3] = {1.0, 0.0, 0.0};
+    const double rb[3] = {1.0, -2.0, 1.0};
+    double ra[3] = {1.0, 0.0, 0.0};
+    const double a0 = 1.0 + K / Q + K * K;
+    pb[0] = (Vh + Vb * K / Q + K * K) / a0;
+    pb[1] = 2.0 * (K * K - Vh) / a0;
+    pb[2] = (Vh - Vb * K / Q + K * K) / a0;
+    pa[1] = 2.0 * (K * K - 1.0) / a0;
+    pa[2] = (1.0 - K / Q + K * K) / a0;
+    f0 = 38.13547087602444;
+    Q = 0.5003270373238773;
+    K = std::tan(pi * f0 / (double)sr);
+    ra[1] = 2.0 * (K * K - 1.0) / (1.0 + K / Q + K * K);
+    ra[2] = (1.0 - K / Q + K * K) / (1.0 + K / Q + K * K);
+    b[0] = pb[0] * rb[0];
+    b[1] = pb[0] * rb[1] + pb[1] * rb[0];
+    b[2] = pb[0] * rb[2] + pb[1] * rb[1] + pb[2] * rb[0];
+    b[3] = pb[1] * rb[2] + pb[2] * rb[1];
+    b[4] = pb[2] * rb[2];
+    a[0] = pa[0] * ra[0];
+    a[1] = pa[0] * ra[1] + pa[1] * ra[0];
+    a[2] = pa[0] * ra[2] + pa[1] * ra[1] + pa[2] * ra[0];
+    a[3] = pa[1] * ra[2] + pa[2] * ra[1];
+    a[4] = pa[2] * ra[2];
+}
+
+// the first block is complete after 400 ms, every further one 100 ms later
+size_t loudness_n_blocks(size_t n, uint32_t sr) {
+    const size_t s100 = loudness_s100(sr), L = 4 * s100;
+    return (s100 == 0 || n < L) ? 0 : (n - L) / s100 + 1;
+}
+
+// ebur128_init_channel_map: 4 channels L R Ls Rs, 5 channels L R C Ls Rs, otherwise L R C unused Ls Rs unused...
+double loudness_channel_weight(uint32_t c, uint32_t n_ch) {
+    if (n_ch == 4) return c < 2 ? 1.0 : 1.41;
+    if (n_ch == 5) return c < 3 ? 1.0 : 1.41;
+    if (c < 3) return 1.0;
+    if (c == 4 || c == 5) return 1.41;
+    return 0.0;
+}
+
+namespace {
+struct LoudnessHistogram {
+    double boundaries[1001], energies[1000];
+    LoudnessHistogram() {
+        for (int i = 0; i < 1001; i++) boundaries[i] = std::pow(10.0, ((double)i / 10.0 - 70.0 + 0.691) / 10.0);
+        for (int i = 0; i < 1000; i++) energies[i] = std::pow(10.0, ((double)i / 10.0 - 69.95 + 0.691) / 10.0);
+    }
+    // find_histogram_index: the largest j <= 999 with e >= boundaries[j] (e >= boundaries[0])
+    size_t index(double e) const {
+        size_t lo = 0, hi = 1000;
+        do {
+            const size_t mid = (lo + hi) / 2;
+            if (e >= boundaries[mid]) lo = mid;
+            else hi = mid;
+        } while (hi - lo != 1);
+        return lo;
+    }
+};
+const LoudnessHistogram &loudness_histogram() {
+    static const LoudnessHistogram h;
+    return h;
+}
+}  // namespace
+
+// ebur128_calc_gating_block's histogram update + ebur128_gated_loudness (histogram mode)
+double gated_loudness(const double *E, size_t n) {
+    const LoudnessHistogram &h = loudness_histogram();
+    std::vector<uint64_t> hist(1000, 0);
+    for (size_t k = 0; k < n; k++)
+        if (E[k] >= h.boundaries[0]) hist[h.index(E[k])]++;  // (NaN compares false: never counted)
+    double rel = 0.0;
+    uint64_t cnt = 0;
+    for (size_t j = 0; j < 1000; j++) {
+        rel += (double)hist[j] * h.energies[j];
+        cnt += hist[j];
+    }
+    if (!cnt) return -std::numeric_limits<double>::infinity();
+    rel /= (double)cnt;
+    rel *= std::pow(10.0, -10.0 / 10.0);  // relative_gate_factor
+    size_t start = 0;
+    if (rel >= h.boundaries[0]) {
+        start = h.index(rel);
+        if (rel > h.energies[start]) start++;
+    }
+    double sum = 0.0;
+    cnt = 0;
+    for (size_t j = start; j < 1000; j++) {
+        sum += (double)hist[j] * h.energies[j];
+        cnt += hist[j];
+    }
+    if (!cnt) return -std::numeric_limits<double>::infinity();
+    sum /= (double)cnt;
+    return 10.0 * std::log10(sum) - 0.691;
+}
+
+void kw_transition(const double a[5], double A[16]) {
+    std::fill(A, A + 16, 0.0);
+    for (int j = 0; j < 4; j++) A[j] = -a[j + 1];
+    A[4] = A[9] = A[14] = 1.0;
+}
+
+void mat4_pow(const double A[16], uint64_t n, double out[16]) {
+    double r[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}, p[16], t[16];
+    std::memcpy(p, A, sizeof p);
+    auto mul = [&](const double *x, const double *y, double *z) {
+        for (int i = 0; i < 4; i++)
+            for (int j = 0; j < 4; j++) z[4 * i + j] = (x[4 * i] * y[j] + x[4 * i + 1] * y[4 + j]) + (x[4 * i + 2] * y[8 + j] + x[4 * i + 3] * y[12 + j]);
+    };
+    for (; n; n >>= 1) {
+        if (n & 1) {
+            mul(r, p, t);
+            std::memcpy(r, t, sizeof r);
+        }
+        if (n > 1) {
+            mul(p, p, t);
+            std::memcpy(p, t, sizeof p);
+        }
+    }
+    std::memcpy(out, r, sizeof r);
+}
+
+namespace {
+struct DD {
+    double hi, lo;
+};
+DD dd_fold(DD acc, double c, DD w) {  // acc + c * w, c exact
+    const double p = c * w.hi, pe = std::fma(c, w.hi, -p) + c * w.lo;
+    const double s = acc.hi + p, bb = s - acc.hi, e = (acc.hi - (s - bb)) + (p - bb) + acc.lo + pe;
+    const double h = s + e;
+    return DD{h, e - (h - s)};
+}
+}  // namespace
+
+const LoudnessRate &loudness_rate(uint32_t sr) {
+    static std::mutex mu;
+    static std::map<uint32_t, std::unique_ptr<LoudnessRate>> cache;
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = cache.find(sr);
+    if (it != cache.end()) return *it->second;
+    std::unique_ptr<LoudnessRate> R(new LoudnessRate{});
+    k_weighting(sr, R->b, R->a);
+    R->sr = sr;
+    R->s100 = (uint32_t)loudness_s100(sr);
+    R->n_sub = (R->s100 + LOUDNESS_CHUNK_MAX - 1) / LOUDNESS_CHUNK_MAX;
+    R->cl = (R->s100 + R->n_sub - 1) / R->n_sub;
+    R->cl_last = R->s100 - (R->n_sub - 1) * R->cl;
+    R->m = (R->cl + 63) / 64;
+    if (R->m % 2 == 0) R->m++;
+    for (int w = 0; w < 2; w++) {
+        const uint32_t len = w ? R->cl_last : R->cl, nl = (len + R->m - 1) / R->m;
+        R->e_lane[w] = 64 - nl;
+        R->r[w] = len - (nl - 1) * R->m;
+    }
+    // columns of A^k for k = 1, 2, ...: w <- A w, the filter's own recurrence with zero input, in double-double
+    DD W[4][4];  // W[col][row]
+    for (int c = 0; c < 4; c++)
+        for (int r = 0; r < 4; r++) W[c][r] = DD{c == r ? 1.0 : 0.0, 0.0};
+    auto put = [&](double (*dst)[2]) {
+        for (int r = 0; r < 4; r++)
+            for (int c = 0; c < 4; c++) {
+                dst[4 * r + c][0] = W[c][r].hi;
+                dst[4 * r + c][1] = W[c][r].lo;
+            }
+    };
+    const uint64_t kmax = std::max<uint64_t>((uint64_t)R->m << 5, R->cl);
+    for (uint64_t k = 1; k <= kmax; k++) {
+        for (int c = 0; c < 4; c++) {
+            DD v0{0.0, 0.0};
+            for (int j = 0; j < 4; j++) v0 = dd_fold(v0, -R->a[j + 1], W[c][j]);
+            W[c][3] = W[c][2];
+            W[c][2] = W[c][1];
+            W[c][1] = W[c][0];
+            W[c][0] = v0;
+        }
+        for (int j = 0; j < 6; j++)
+            if (k == ((uint64_t)R->m << j)) put(R->scan[j]);
+        for (int w = 0; w < 2; w++) {
+            if (k == R->r[w]) put(R->rpow[w]);
+            if (k == (w ? R->cl_last : R->cl)) put(R->step[w]);
+        }
+    }
+    const LoudnessRate &ref = *R;
+    cache[sr] = std::move(R);
+    return ref;
 }
 
 }  // namespace th

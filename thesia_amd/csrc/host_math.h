@@ -49,6 +49,38 @@ struct LodAxisHost {
 };
 void build_lod_axis(double origin, double extent, size_t n_out, long lo, long hi, LodAxisHost &ax);
 
+// ---- integrated loudness (StatCalculator::calc, dynamics/stats.rs:56-86: the ebur128 crate 0.1.10, a port of libebur128 —
+// PARITY UNPINNED) and the momentary block series behind it
+constexpr uint32_t LOUDNESS_MIN_SR = 16, LOUDNESS_MAX_SR = 2822400;  // the rates EbuR128::new accepts
+inline bool loudness_rate_ok(uint32_t sr) { return sr >= LOUDNESS_MIN_SR && sr <= LOUDNESS_MAX_SR; }
+// the K-weighting filter as one 4th-order section (the shelf times the high-pass), in libebur128's arithmetic
+void k_weighting(uint32_t sr, double b[5], double a[5]);
+inline size_t loudness_s100(uint32_t sr) { return (sr + 5) / 10; }  // samples per 100 ms; a gating block is 4 of them
+size_t loudness_n_blocks(size_t n_samples, uint32_t sr);
+// weight of channel c of n_ch in a block energy under the default channel map (L R C: 1, Ls Rs: 1.41, unused: 0)
+double loudness_channel_weight(uint32_t c, uint32_t n_ch);
+// histogram-mode gating of the block energies (absolute gate -70 LUFS, relative gate -10 LU, 0.1 LU bins) -> integrated LUFS
+double gated_loudness(const double *block_energies, size_t n);
+// The filter's recurrence on its state S = (v1, v2, v3, v4) over a run of samples is S' = A^len S + z, z = the run from zero state.
+// A: the 4x4 (row-major) transition of one sample with zero input; mat4_pow: A^n by squaring, in f64.
+void kw_transition(const double a[5], double A[16]);
+void mat4_pow(const double A[16], uint64_t n, double out[16]);
+// What the loudness kernels (kernels_loudness.hip) need of one rate.  A 100 ms segment is cut into n_sub chunks of cl samples (the
+// last one cl_last) of at most LOUDNESS_CHUNK_MAX; a chunk is one wave, whose lane l runs samples [len - (64 - l) m, len - (63 - l) m)
+// of it (m odd: the lanes' LDS reads hit 32 different banks); lanes below e_lane[w] are empty, lane e_lane[w] runs r[w] samples
+// (w = 0: a chunk of cl samples, 1: of cl_last).  The powers of A are double-double (hi, lo) pairs, made by iterating the
+// recurrence itself: the DF-II transition is far from normal (|A^75| = 3.2e3 at 48 kHz, 4.7e4 at 192 kHz) and its powers by
+// squaring, or products of them with a state in f64, lose up to 6 digits of the state.
+constexpr uint32_t LOUDNESS_CHUNK_MAX = 4800;
+struct LoudnessRate {
+    double b[5], a[5];
+    double scan[6][16][2];  // A^(m 2^j): the lane scan's step j
+    double rpow[2][16][2];  // A^r[w]: the chunk's start state through the first non-empty lane
+    double step[2][16][2];  // A^cl, A^cl_last: the carry from chunk to chunk
+    uint32_t sr, s100, n_sub, cl, cl_last, m, e_lane[2], r[2], pad_;
+};
+const LoudnessRate &loudness_rate(uint32_t sr);  // (cached per rate; sr must satisfy loudness_rate_ok)
+
 inline bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
 inline unsigned ilog2(size_t n) {
     unsigned l = 0;

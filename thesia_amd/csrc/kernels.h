@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "../../include/thesia_amd.h"
+#include "host_math.h"
 #include "stft_core.h"
 
 // Measured-and-dropped kernel variants: the packed-f32 pipeline (selector 9), the sweep chunk schedule (11), the
@@ -286,5 +287,29 @@ hipError_t launch_pyramid_base(const PyrJob *d_jobs, uint32_t n_jobs, uint64_t m
 hipError_t launch_pyramid_up(const PyrJob *d_jobs, uint32_t n_jobs, uint64_t max_samples, uint32_t level, uint32_t parity,
                              hipStream_t s);
 uint32_t waveform_blocks_for(uint32_t level, uint32_t bin_count);
+
+
+// ---- kernels_loudness.hip: K-weighted chunk energies, per-channel sum of squares and peak, 400 ms block energies
+struct LoudJob {           // one channel
+    const float *wav;
+    double *z;             // n_fchunks x 8: double-double states (4 hi, 4 lo), the chunks' zero-state end states, then their start states
+    double *q;             // n_fchunks chunk energies (sum of y^2)
+    double *sumsq;         // += sum of x^2 over all samples (zeroed by the caller)
+    uint32_t *peak;        // max |x| as float bits (zeroed by the caller)
+    uint64_t n;
+    uint32_t rate;         // index into the LoudnessRate table
+    uint32_t n_chunks;     // chunks that hold samples (the sums)
+    uint32_t n_fchunks;    // chunks the 400 ms blocks cover: (n_blocks + 3) n_sub, or 0
+    uint32_t aligned16;
+};
+struct LoudTrackJob {      // one track
+    const double *q;       // channel c's chunk energies at q + c n_fchunks
+    double *out;           // n_blocks block energies
+    uint64_t n_blocks;
+    double w[8];           // channel weights (channel c >= 7: w[7])
+    uint32_t n_ch, n_sub, n_fchunks, L;
+};
+hipError_t launch_loudness(const LoudJob *d_jobs, uint32_t n_jobs, uint32_t max_chunks, uint32_t max_fchunks, const LoudnessRate *d_rates,
+                           uint32_t lds_floats, const LoudTrackJob *d_tjobs, uint32_t n_tracks, uint64_t max_blocks, hipStream_t s);
 
 }  // namespace th

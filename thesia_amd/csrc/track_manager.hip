@@ -93,6 +93,7 @@ struct Track {
     // ONE device allocation for the samples and waveform pyramids of all channels (round 6: two hipMalloc per channel were 0.7 ms
     // of a 32-track add); Channel::d_wav / d_pyr are views into it and live exactly as long as the track
     void *d_pool = nullptr;
+    th_audio_stats stats{};  // AudioStats (StatCalculator::calc, dynamics/stats.rs:56-86) of the samples as they were added
 };
 
 using PlanKey = std::tuple<uint32_t, size_t, size_t, size_t, int>;  // sr, win, hop, n_fft, scale
@@ -1439,6 +1440,17 @@ TH_API int th_tm_get_waveform_tile(th_tm *tm, size_t id, uint32_t ch, uint32_t l
     TH_CATCH
 }
 
+TH_API int th_tm_get_audio_stats(th_tm *tm, size_t id, th_audio_stats *out) {
+    TH_TRY
+    TH_REQUIRE(tm && out, "NULL argument");
+    std::shared_lock<std::shared_mutex> rl(tm->rw);
+    auto it = tm->tracks.find(id);
+    if (it == tm->tracks.end()) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", id);
+    *out = it->second.stats;
+    return TH_OK;
+    TH_CATCH
+}
+
 // get_audio_render_metadata — lib.rs:321-340 → RenderTileCache::metadata (render_tiles.rs:101-122)
 TH_API int th_tm_get_audio_render_metadata(th_tm *tm, size_t id, uint32_t ch, double track_sec, int is_clipped,
                                            th_render_metadata *out) {
@@ -1603,6 +1615,8 @@ int prepare_add(th_tm *tm, size_t n_tracks, const size_t *ids, const uint32_t *s
     int rc = TH_OK;
     hipError_t e = hipSuccess;
     std::vector<size_t> added;
+    std::vector<std::unique_ptr<LoudnessBatch>> loud;      // one per group (freed after the synchronisation below)
+    std::vector<std::pair<size_t, size_t>> loud_ids;       // (id, its group), in the order of the groups' descriptors
     const bool prof = getenv("TH_TM_PROF") != nullptr;
     auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double tp0 = now();
@@ -1630,6 +1644,8 @@ int prepare_add(th_tm *tm, size_t n_tracks, const size_t *ids, const uint32_t *s
     while (t < n_tracks && e == hipSuccess && rc == TH_OK) {
         std::vector<std::pair<uint32_t, Channel *>> chans;
         std::vector<th_pyramid_desc> pdescs;
+        std::vector<th_audio_desc> adescs;
+        std::vector<std::vector<const float *>> aptrs;
         size_t bytes = 0;
         for (; t < n_tracks && (bytes == 0 || bytes < GROUP_BYTES) && e == hipSuccess; t++) {
             if (last_of[ids[t]] != t) continue;
@@ -1657,6 +1673,12 @@ int prepare_add(th_tm *tm, size_t n_tracks, const size_t *ids, const uint32_t *s
                 chans.push_back({tr.sr, &ch});
                 pdescs.push_back(th_pyramid_desc{ch.d_wav, ch.d_pyr, ch.n, ch.pyr_levels, PYR_FIRST});
             }
+            if (e == hipSuccess) {
+                aptrs.emplace_back();
+                for (const Channel &ch : tr.ch) aptrs.back().push_back(ch.d_wav);
+                adescs.push_back(th_audio_desc{nullptr, (uint64_t)n, n_channels[t], srs[t], nullptr});
+                loud_ids.emplace_back(ids[t], loud.size());
+            }
         }
         if (e != hipSuccess) break;
         if (chans.empty()) continue;
@@ -1665,6 +1687,11 @@ int prepare_add(th_tm *tm, size_t n_tracks, const size_t *ids, const uint32_t *s
         if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, tm->copy_ev, 0);
         if (e != hipSuccess) break;
         rc = th_waveform_pyramid_dev(c, pdescs.data(), pdescs.size());
+        if (rc == TH_OK) {  // the group's loudness, behind its pyramid (read back at the one synchronisation below)
+            for (size_t i = 0; i < adescs.size(); i++) adescs[i].channels = aptrs[i].data();
+            loud.emplace_back(new LoudnessBatch);
+            rc = loudness_enqueue(c, adescs.data(), adescs.size(), true, true, loud.back().get());
+        }
         if (rc == TH_OK) rc = compute_specs(tm, st, chans, created, &fresh, &pending);
         t_launch += now() - tl0;
     }
@@ -1677,6 +1704,11 @@ int prepare_add(th_tm *tm, size_t n_tracks, const size_t *ids, const uint32_t *s
         TH_HIP(e);
     }
     rc = finish_specs(tm, pending, &fresh, true);
+    for (size_t g = 0, i = 0; rc == TH_OK && g < loud.size(); g++) {
+        rc = loudness_collect(loud[g].get(), false);
+        for (size_t k = 0; rc == TH_OK && i < loud_ids.size() && loud_ids[i].second == g; i++, k++)
+            loudness_result(*loud[g], k, &staged[loud_ids[i].first].stats);
+    }
     if (prof) fprintf(stderr, "th_tm_add_tracks prof: staging + launches %.2f ms (of which pyramid / STFT launches %.2f), drain %.2f\n", tp1 - tp0, t_launch, now() - tp1);
     if (rc != TH_OK) {
         abort_staging();

@@ -448,6 +448,13 @@ TH_API int th_tmg_get_waveform_tile(th_tmg *g, size_t id, uint32_t ch, uint32_t 
     TH_CATCH
 }
 
+TH_API int th_tmg_get_audio_stats(th_tmg *g, size_t id, th_audio_stats *out) {
+    TH_TRY
+    TMG_OWNER(g, id, "Track %zu", id);
+    return th_tm_get_audio_stats(tm_, id, out);
+    TH_CATCH
+}
+
 TH_API int th_tmg_get_audio_render_metadata(th_tmg *g, size_t id, uint32_t ch, double track_sec, int is_clipped,
                                             th_render_metadata *out) {
     TH_TRY
