@@ -33,6 +33,15 @@
  *     host synchronises that stream; so does a first call, or one whose descriptors changed, when it uploads its
  *     descriptor tables or grows a scratch buffer.  A repeat call with the same descriptors only enqueues.
  *     All other entries take HOST pointers.
+ *   - Alignment.  A DEVICE pointer — an argument, a struct field or an entry of a pointer array marked DEVICE — needs the
+ *     alignment of its element type and no more (f32: 4 bytes, u16: 2, bytes: 1), unless its declaration says otherwise:
+ *     th_dev_copy 16 bytes (pointers and size); rgba, tiles[] and d_colormap 4 bytes (one RGBA8 pixel / LUT entry);
+ *     block_energy 8 bytes (f64).  So a channel may be a row of a planar channels x samples array of any length, spec
+ *     rows and images sub-rectangles of wider arrays, outputs packed back to back.  Faster paths (8- and 16-byte
+ *     accesses) are taken where base, pitch and origin allow them; the values written do not depend on the alignment,
+ *     except where a sum is taken in another order (th_channel_stats_dev's sum of squares, th_audio_stats_dev's rms_dB:
+ *     within their stated accuracy either way).  The entries check it: a device pointer below its stated alignment is
+ *     refused with TH_ERR_INVALID_ARG before anything is launched, and th_last_error() names the argument.
  *   - Compute entries (th_calc_spec_*, th_tm_* mutators) may assume exclusive access, like the
  *     reference's single write-lock worker (interface.rs:12-56).  th_tm_* tile getters run
  *     concurrently with each other (each request has its own HIP stream and pinned staging buffer)
@@ -257,7 +266,7 @@ TH_API int th_spec_to_img_batch_dev_ranged(th_ctx *ctx, const th_img_desc *descs
  * n_frames image (th_spectrogram_tile_geometry with levels 0) at [tx * n_tiles_y + ty]: a dense width x height RGBA8 array,
  * top row = highest frequency, 4-byte aligned (16-byte aligned bases are faster); NULL entries are skipped.
  * d_range != NULL: [min_dB, max_dB] on the DEVICE (th_global_db_range_dev), else the host values.  d_colormap: DEVICE RGBA8
- * LUT of n_colors entries (1 .. 65536); the quantiser's colormap_len is n_colors. */
+ * LUT of n_colors entries (1 .. 65536), 4-byte aligned; the quantiser's colormap_len is n_colors. */
 typedef struct {
     th_img_desc img;
     uint8_t *const *tiles; /* HOST array of DEVICE pointers */
@@ -288,7 +297,7 @@ typedef struct {
     uint32_t reserved;
 } th_raster_desc;
 /* Batched level-0 colormap raster of many tile rectangles in one launch (device → device).
- * d_colormap: DEVICE RGBA8, n_colors entries. */
+ * d_colormap: DEVICE RGBA8, n_colors entries, 4-byte aligned. */
 TH_API int th_raster_tiles_dev(th_ctx *ctx, const th_raster_desc *descs, size_t n, const uint8_t *d_colormap,
                                uint32_t n_colors);
 
@@ -337,7 +346,7 @@ typedef struct {
     uint64_t n_samples;
     uint32_t n_channels;          /* >= 1 */
     uint32_t sr;                  /* 16 .. 2 822 400 (the rates EbuR128::new accepts), else TH_ERR_UNSUPPORTED */
-    double *block_energy;         /* DEVICE, may be NULL: receives the th_loudness_n_blocks values E_k of the momentary (400 ms, hop
+    double *block_energy;         /* DEVICE, 8-byte aligned, may be NULL: receives the th_loudness_n_blocks values E_k of the momentary (400 ms, hop
                                    * 100 ms) series, E_k = sum_c w_c sum_(block) y_c^2 / block length, in stream order */
 } th_audio_desc;
 /* A batch of tracks; out_host[n].  Returns to the host: synchronises the context's stream. */

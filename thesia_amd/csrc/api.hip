@@ -877,6 +877,12 @@ static int calc_spec_batch_impl(th_plan *p, const th_chan_desc *chans, size_t n_
     if (n_chan == 0) return TH_OK;
     TH_REQUIRE(chans, "chans is NULL");
     TH_REQUIRE(n_chan < (1u << 24), "too many channels");
+    TH_REQUIRE_ALIGNED(d_minmax, 4, "d_minmax must be 4-byte aligned");
+    TH_REQUIRE_ALIGNED(d_range, 4, "d_range must be 4-byte aligned");
+    for (size_t i = 0; i < n_chan; i++) {
+        TH_REQUIRE_ALIGNED(chans[i].wav, 4, "channel %zu: wav must be 4-byte aligned", i);
+        TH_REQUIRE_ALIGNED(chans[i].spec, 4, "channel %zu: spec must be 4-byte aligned", i);
+    }
     th_ctx *c = p->ctx;
     const StftRoute &r = p->route;
     const bool wave = r.wave(), mel_mfma = r.mel_second != StftRoute::MelSecond::None;
@@ -1241,6 +1247,8 @@ TH_API int th_minmax_reduce_dev(th_ctx *c, const float *d_minmax, size_t n_chan,
     TH_REQUIRE(c && d_out, "NULL argument");
     TH_REQUIRE(n_chan == 0 || d_minmax, "d_minmax is NULL");
     TH_REQUIRE(n_chan < (1ull << 31), "too many channels");
+    TH_REQUIRE_ALIGNED(d_minmax, 4, "d_minmax must be 4-byte aligned");
+    TH_REQUIRE_ALIGNED(d_out, 4, "d_out must be 4-byte aligned");
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     TH_HIP(hipSetDevice(c->device));
     TH_HIP(launch_minmax_reduce(d_minmax, (uint32_t)n_chan, d_out, 0.0f, nullptr, c->stream));
@@ -1255,6 +1263,9 @@ TH_API int th_minmax_reduce_range_dev(th_ctx *c, const float *d_minmax, size_t n
     TH_REQUIRE(c && d_range, "NULL argument");
     TH_REQUIRE(n_chan == 0 || d_minmax, "d_minmax is NULL");
     TH_REQUIRE(n_chan < (1ull << 31), "too many channels");
+    TH_REQUIRE_ALIGNED(d_minmax, 4, "d_minmax must be 4-byte aligned");
+    TH_REQUIRE_ALIGNED(d_min_negmax, 4, "d_min_negmax must be 4-byte aligned");
+    TH_REQUIRE_ALIGNED(d_range, 4, "d_range must be 4-byte aligned");
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     TH_HIP(hipSetDevice(c->device));
     TH_HIP(launch_minmax_reduce(d_minmax, (uint32_t)n_chan, d_min_negmax, dB_range, d_range, c->stream));
@@ -1367,6 +1378,11 @@ static int spec_to_img_impl(th_ctx *c, const th_img_desc *descs, size_t n, float
     TH_REQUIRE(c, "ctx is NULL");
     if (n == 0) return TH_OK;
     TH_REQUIRE(descs, "descs is NULL");
+    TH_REQUIRE_ALIGNED(d_range, 4, "d_range must be 4-byte aligned");
+    for (size_t i = 0; i < n; i++) {
+        TH_REQUIRE_ALIGNED(descs[i].spec, 4, "desc %zu: spec must be 4-byte aligned", i);
+        TH_REQUIRE_ALIGNED(descs[i].img, 2, "desc %zu: img must be 2-byte aligned", i);
+    }
     const bool all_neg_inf = !d_range && (min_dB == max_dB) && std::isinf(max_dB) && max_dB < 0;  // drawing.rs:16-18
     if (!all_neg_inf && !d_range) TH_REQUIRE(std::isfinite(min_dB), "min_dB must be finite (drawing.rs:19)");
     if (!all_neg_inf) {
@@ -1445,6 +1461,12 @@ TH_API int th_spec_to_img_raster_batch_dev(th_ctx *c, const th_img_tiles_desc *d
     if (n == 0) return TH_OK;
     TH_REQUIRE(descs && d_colormap && n_colors >= 1, "NULL descs / colormap or empty colormap");
     TH_REQUIRE(n_colors <= 65536, "colormaps of more than 65536 entries are not supported");
+    TH_REQUIRE_ALIGNED(d_colormap, 4, "d_colormap must be 4-byte aligned");
+    TH_REQUIRE_ALIGNED(d_range, 4, "d_range must be 4-byte aligned");
+    for (size_t i = 0; i < n; i++) {  // (on every call: an identical batch skips the table building below)
+        TH_REQUIRE_ALIGNED(descs[i].img.spec, 4, "desc %zu: spec must be 4-byte aligned", i);
+        TH_REQUIRE_ALIGNED(descs[i].img.img, 2, "desc %zu: img must be 2-byte aligned", i);
+    }
     const bool all_neg_inf = !d_range && (min_dB == max_dB) && std::isinf(max_dB) && max_dB < 0;  // drawing.rs:16-18
     if (!all_neg_inf && !d_range) TH_REQUIRE(std::isfinite(min_dB), "min_dB must be finite (drawing.rs:19)");
     // key of the batch: the descriptors and every tile pointer (identical batch -> the device tables are reused as they are)
@@ -1512,6 +1534,8 @@ TH_API int th_spec_to_img_raster_batch_dev(th_ctx *c, const th_img_tiles_desc *d
 TH_API int th_global_db_range_dev(th_ctx *c, const float *d_min_negmax, float dB_range, float *d_range) {
     TH_TRY
     TH_REQUIRE(c && d_min_negmax && d_range, "NULL argument");
+    TH_REQUIRE_ALIGNED(d_min_negmax, 4, "d_min_negmax must be 4-byte aligned");
+    TH_REQUIRE_ALIGNED(d_range, 4, "d_range must be 4-byte aligned");
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     TH_HIP(hipSetDevice(c->device));
     TH_HIP(launch_db_range(d_min_negmax, dB_range, d_range, c->stream));
@@ -1533,6 +1557,7 @@ TH_API int th_raster_tiles_dev(th_ctx *c, const th_raster_desc *descs, size_t n,
     if (n == 0) return TH_OK;
     TH_REQUIRE(descs && d_colormap && n_colors >= 1, "NULL descs/colormap or empty colormap");
     TH_REQUIRE(n_colors <= 65536, "colormaps of more than 65536 entries are not supported");
+    TH_REQUIRE_ALIGNED(d_colormap, 4, "d_colormap must be 4-byte aligned");
     {   // same batch as the previous call: the device tables are still valid
         std::lock_guard<std::recursive_mutex> lk(c->mu);
         if (c->raster_descs_key.size() == n * sizeof(th_raster_desc) &&
@@ -1553,7 +1578,8 @@ TH_API int th_raster_tiles_dev(th_ctx *c, const th_raster_desc *descs, size_t n,
         const uint64_t px = (uint64_t)d.width * d.height;
         TH_REQUIRE(px < (1ull << 31), "desc %zu: tile too large", i);
         TH_REQUIRE(px == 0 || (d.img && d.rgba), "desc %zu: NULL device pointer", i);
-        TH_REQUIRE((reinterpret_cast<uintptr_t>(d.rgba) & 3u) == 0, "desc %zu: rgba must be 4-byte aligned", i);
+        TH_REQUIRE_ALIGNED(d.rgba, 4, "desc %zu: rgba must be 4-byte aligned", i);
+        TH_REQUIRE_ALIGNED(d.img, 2, "desc %zu: img must be 2-byte aligned", i);
         TH_REQUIRE(d.img_pitch == 0 || d.img_pitch >= d.img_width, "desc %zu: img_pitch < img_width", i);
         const uint32_t qpr = (d.width + 3) / 4;
         const uint32_t inv = qpr > 1 ? (uint32_t)((1ull << 32) / qpr) + 1u : 0u;  // exact for q * qpr < 2^32
@@ -1594,6 +1620,7 @@ TH_API int th_encode_spectrogram_tile_dev(th_ctx *c, const uint16_t *d_img, size
     TH_REQUIRE(colormap_rgba && colormap_bytes >= 4 && colormap_bytes % 4 == 0, "colormap must be a non-empty RGBA8 array");
     TH_REQUIRE(img_width < (1ull << 31) && img_height < (1ull << 31), "image too large");
     TH_REQUIRE(img_pitch == 0 || (img_pitch >= img_width && img_pitch < (1ull << 31)), "img_pitch < img_width");
+    TH_REQUIRE_ALIGNED(d_img, 2, "d_img must be 2-byte aligned");
     const TileGeom g = spectrogram_tile_geometry(img_width, img_height, level_x, level_y, tile_x, tile_y);
     const size_t need = 40 + g.width * g.height * 4;
     *out_len = need;
@@ -1696,6 +1723,8 @@ TH_API int th_waveform_tiles_dev(th_ctx *c, const th_wave_desc *descs, size_t n)
         TH_REQUIRE(d.bin_count <= TH_WAVEFORM_TILE_BINS, "desc %zu: bin_count > 1024", i);
         TH_REQUIRE(d.level < 40, "desc %zu: level %u too large", i, d.level);
         TH_REQUIRE(d.bin_count == 0 || (d.wav && d.bins), "desc %zu: NULL device pointer", i);
+        TH_REQUIRE_ALIGNED(d.wav, 4, "desc %zu: wav must be 4-byte aligned", i);
+        TH_REQUIRE_ALIGNED(d.bins, 4, "desc %zu: bins must be 4-byte aligned", i);
         if (d.bin_count) {
             const uint64_t spb = 1ull << d.level;
             TH_REQUIRE(d.start < d.n_samples && d.start + (uint64_t)(d.bin_count - 1) * spb < d.n_samples,
@@ -1731,6 +1760,7 @@ TH_API int th_channel_stats_dev(th_ctx *c, const th_stats_desc *descs, size_t n,
     uint64_t max_samples = 0;
     for (size_t i = 0; i < n; i++) {
         TH_REQUIRE(descs[i].n_samples == 0 || descs[i].wav, "desc %zu: NULL device pointer", i);
+        TH_REQUIRE_ALIGNED(descs[i].wav, 4, "desc %zu: wav must be 4-byte aligned", i);
         TH_REQUIRE(descs[i].n_samples < (1ull << 40), "desc %zu: too many samples", i);
         jobs[i] = StatsJob{descs[i].wav, descs[i].n_samples, (reinterpret_cast<uintptr_t>(descs[i].wav) & 15u) == 0, 0};
         max_samples = std::max<uint64_t>(max_samples, descs[i].n_samples);
@@ -1777,6 +1807,8 @@ TH_API int th_waveform_pyramid_dev(th_ctx *c, const th_pyramid_desc *descs, size
         const th_pyramid_desc &d = descs[i];
         TH_REQUIRE(d.n_levels <= PYR_MAX_LEVELS, "desc %zu: more than %u levels", i, PYR_MAX_LEVELS);
         TH_REQUIRE(d.n_samples == 0 || d.n_levels == 0 || (d.wav && d.out), "desc %zu: NULL device pointer", i);
+        TH_REQUIRE_ALIGNED(d.wav, 4, "desc %zu: wav must be 4-byte aligned", i);
+        TH_REQUIRE_ALIGNED(d.out, 4, "desc %zu: out must be 4-byte aligned", i);
         TH_REQUIRE(d.n_samples < (1ull << 40), "desc %zu: too many samples", i);
         PyrJob &j = jobs[i];
         j = PyrJob{};
@@ -1818,6 +1850,7 @@ TH_API int th_encode_waveform_tile_dev(th_ctx *c, const float *d_wav, size_t n_s
                                        size_t *out_len) {
     TH_TRY
     TH_REQUIRE(c && out && out_len, "NULL argument");
+    TH_REQUIRE_ALIGNED(d_wav, 4, "d_wav must be 4-byte aligned");
     size_t start, bins, spb;
     waveform_tile_geometry(n_samples, level, tile_index, &start, &bins, &spb);
     const size_t need = 24 + bins * 12;
@@ -1894,6 +1927,7 @@ int loudness_enqueue(th_ctx *c, const th_audio_desc *descs, size_t n, bool own_m
         const th_audio_desc &d = descs[t];
         TH_REQUIRE(d.n_channels >= 1 && d.channels, "track %zu: no channels", t);
         TH_REQUIRE(d.n_samples < (1ull << 40), "track %zu: too many samples", t);
+        TH_REQUIRE_ALIGNED(d.block_energy, 8, "track %zu: block_energy must be 8-byte aligned", t);
         const bool ok = loudness_rate_ok(d.sr);
         if (!ok && !allow_bad_rate) return fail(TH_ERR_UNSUPPORTED, "track %zu: sample rate %u outside [16, 2822400]", t, d.sr);
         // (a refused rate: the sums only, over chunks of a 48 kHz geometry)
@@ -1911,6 +1945,7 @@ int loudness_enqueue(th_ctx *c, const th_audio_desc *descs, size_t n, bool own_m
         b->ns.push_back(d.n_samples);
         for (uint32_t k = 0; k < d.n_channels; k++) {
             TH_REQUIRE(d.n_samples == 0 || d.channels[k], "track %zu channel %u: NULL device pointer", t, k);
+            TH_REQUIRE_ALIGNED(d.channels[k], 4, "track %zu channel %u: channels[] must be 4-byte aligned", t, k);
             LoudJob j{};
             j.wav = d.channels[k];
             j.n = d.n_samples;

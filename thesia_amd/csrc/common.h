@@ -40,7 +40,12 @@ inline int fail(int code, const char *fmt, ...) {
         if (!(cond)) return th::fail(TH_ERR_INVALID_ARG, __VA_ARGS__);    \
     } while (0)
 
-#define TH_HIP(call)                                                      \
+// A DEVICE pointer below the alignment its declaration states (include/thesia_amd.h, Conventions: that of its element
+// type unless said otherwise) is refused before anything is launched; the message names the argument.
+#define TH_REQUIRE_ALIGNED(ptr, bytes, ...) \
+    TH_REQUIRE((reinterpret_cast<uintptr_t>(ptr) & (uintptr_t)((bytes) - 1)) == 0, __VA_ARGS__)
+
+#define TH_HIP(call)                                                    \
     do {                                                                  \
         hipError_t e_ = (call);                                           \
         if (e_ != hipSuccess)                                             \
