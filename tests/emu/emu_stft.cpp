@@ -14,6 +14,7 @@
 #include "../../thesia_amd/csrc/stft_block.h"
 #include "../../thesia_amd/csrc/mel_fuse.h"
 #include "../../thesia_amd/csrc/host_math.h"  // bluestein_tables (host_math.cpp is compiled into the emulator)
+#include "../../thesia_amd/csrc/stft_plan.h"  // the plan tables and the launch planner, as th_plan_create / th_calc_spec_batch_dev call them
 
 using namespace th;
 
@@ -247,14 +248,7 @@ extern "C" __attribute__((visibility("default"))) int emu_stft_wave_multi(const 
     g.nc = n_fft / 2;
     g.n_freq = n_fft / 2 + 1;
     g.height = g.n_freq;
-    std::vector<cf32> tw(n_fft), wtab(g.nc);
-    for (uint32_t i = 0; i < n_fft; i++) {
-        const double a = -2.0 * M_PI * (double)i / (double)n_fft;
-        tw[i] = {(float)std::cos(a), (float)std::sin(a)};
-    }
-    std::vector<float> wpad(n_fft, 0.0f);
-    for (uint32_t i = 0; i < win; i++) wpad[g.pad_left + i] = 0.5f * WAVE_PRESCALE * window[i];
-    for (uint32_t n = 0; n < g.nc; n++) wtab[n] = {wpad[2 * n], wpad[2 * n + 1]};
+    const std::vector<cf32> tw = build_twiddles(n_fft), wtab = build_wave_window(window, win, n_fft, 0).wtab;  // the plan's own tables
     std::vector<uint32_t> interior;
     for (uint32_t f = 0; f < n_frames; f++) {
         const int64_t e0 = (int64_t)f * hop - (int64_t)(win / 2) - (int64_t)g.pad_left;
@@ -305,14 +299,7 @@ static int emu_stft_wave_impl(const float *wav, uint32_t n_samples, uint32_t win
     g.nc = n_fft / 2;
     g.n_freq = n_fft / 2 + 1;
     g.height = g.n_freq;
-    std::vector<cf32> tw(n_fft), wtab(g.nc);
-    for (uint32_t i = 0; i < n_fft; i++) {
-        const double a = -2.0 * M_PI * (double)i / (double)n_fft;
-        tw[i] = {(float)std::cos(a), (float)std::sin(a)};
-    }
-    std::vector<float> wpad(n_fft, 0.0f);
-    for (uint32_t i = 0; i < win; i++) wpad[g.pad_left + i] = 0.5f * WAVE_PRESCALE * window[i];  // as api.hip builds the table
-    for (uint32_t n = 0; n < g.nc; n++) wtab[n] = {wpad[2 * n], wpad[2 * n + 1]};
+    const std::vector<cf32> tw = build_twiddles(n_fft), wtab = build_wave_window(window, win, n_fft, 0).wtab;  // the plan's own tables
     for (uint32_t f = 0; f < n_frames; f++) {
         float *row = out + (size_t)f * g.n_freq;
         const int64_t e0 = (int64_t)f * hop - (int64_t)(win / 2) - (int64_t)g.pad_left;
@@ -612,3 +599,98 @@ extern "C" __attribute__((visibility("default"))) int emu_stft_bluestein(const f
     return (int)M;
 }
 
+
+// ---- the plan's host tables and the launch planner (stft_plan.h), for tests/test_plan_host.py.  A call builds the product's
+// structures and keeps them as byte blobs behind a handle; emu_blob copies one out (returns its size; copies when cap suffices).
+struct EmuBlobs {
+    std::vector<std::vector<unsigned char>> b;
+    template <class T>
+    void add(const std::vector<T> &v) {
+        const unsigned char *p = reinterpret_cast<const unsigned char *>(v.data());
+        b.emplace_back(p, p + v.size() * sizeof(T));
+    }
+};
+extern "C" __attribute__((visibility("default"))) uint64_t emu_blob(const void *h, uint32_t which, void *out, uint64_t cap) {
+    const EmuBlobs *e = static_cast<const EmuBlobs *>(h);
+    if (!e || which >= e->b.size()) return ~0ull;
+    const std::vector<unsigned char> &v = e->b[which];
+    if (out && cap >= v.size() && !v.empty()) std::memcpy(out, v.data(), v.size());
+    return v.size();
+}
+extern "C" __attribute__((visibility("default"))) void emu_blob_free(void *h) { delete static_cast<EmuBlobs *>(h); }
+
+// plan_stft_launch on channels of n_samples[i] samples (frame counts as th_stft_n_frames gives them; dense spec rows).
+// route: {main, mel_fused, mel_second, phase_mode, waves, tail_guard, edges_in_wave, block_plan, sweep} (StftRoute's values).
+// Blobs (u64 unless said): 0 {err, frames_per_tile, phased, sweep, tiles, edge_tiles, mel_tiles, amp_rows, all_in_wave, edge
+// frames_per_tile}; 1 jobs and 2 edge jobs, rows of {n_samples, n_frames, f_begin, f_end, mm_index, edge}; 3 tile_start (u32);
+// 4 edge_start (u32); 5 chunk_tab (u32); 6 mel jobs, rows of {f_begin, f_end, mm_index}; 7 mel_start (u32); 8 amp_row0;
+// 9 post jobs, rows of {t0, t1, mm_index}
+extern "C" __attribute__((visibility("default"))) void *emu_plan_launch(uint32_t win, uint32_t hop, uint32_t n_fft, uint32_t n_mel, const int32_t *route,
+                                                                        uint32_t n_cu, int32_t wave_chunk, const uint64_t *n_samples, uint64_t n_chan) {
+    StftGeom g = stft_geom(win, hop, n_fft);
+    if (n_mel) g.n_mel = g.height = n_mel;
+    StftRoute r;
+    r.main = (StftRoute::Main)route[0];
+    r.mel_fused = (StftRoute::MelFused)route[1];
+    r.mel_second = (StftRoute::MelSecond)route[2];
+    r.phase_mode = route[3];
+    r.waves = route[4];
+    r.tail_guard = (uint32_t)route[5];
+    r.edges_in_wave = route[6] != 0;
+    r.block_plan = route[7] != 0;
+    r.sweep = route[8] != 0;
+    static float dummy[2];  // (the planner copies the pointers and reads nothing through them)
+    std::vector<th_chan_desc> ch(n_chan);
+    for (uint64_t i = 0; i < n_chan; i++) ch[i] = th_chan_desc{dummy, dummy, n_samples[i], stft_n_frames(n_samples[i], win, hop), 0};
+    const StftLaunch l = plan_stft_launch(g, r, n_cu, wave_chunk, ch.data(), ch.size());
+    EmuBlobs *e = new EmuBlobs;
+    e->add(std::vector<uint64_t>{(uint64_t)l.err, l.g.frames_per_tile, l.g.phased, l.sweep, l.tiles, l.edge_tiles, l.mel_tiles, l.amp_rows,
+                                 l.all_in_wave, l.ge.frames_per_tile});
+    for (const std::vector<ChanJob> *v : {&l.jobs, &l.edge}) {
+        std::vector<uint64_t> rows;
+        for (const ChanJob &j : *v) rows.insert(rows.end(), {j.n_samples, j.n_frames, j.f_begin, j.f_end, j.mm_index, j.edge});
+        e->add(rows);
+    }
+    e->add(l.tile_start);
+    e->add(l.edge_start);
+    e->add(l.chunk_tab);
+    std::vector<uint64_t> mj, pj;
+    for (const MelJob &j : l.mel_jobs) mj.insert(mj.end(), {j.f_begin, j.f_end, j.mm_index});
+    for (const WavePostJob &j : l.post) pj.insert(pj.end(), {j.t0, j.t1, j.mm_index});
+    e->add(mj);
+    e->add(l.mel_start);
+    e->add(l.amp_row0);
+    e->add(pj);
+    return e;
+}
+
+// The mel tables th_plan_create builds from calc_mel_fb(sr, n_fft, n_mel) (n_mel = 0: the default count).  Blobs: 0 the dense
+// filterbank (f32, [n_freq][n_mel]); 1 {n_mel, kblocks, ntiles, zero_block, n_slices, mel_rows ok, mel_rows groups} (u32);
+// 2 lo, 3 hi, 4 band, 5 slice (u32); 6 the operand-order blocks (f32); 7 the mel_rows table (u32)
+extern "C" __attribute__((visibility("default"))) void *emu_mel_tables(uint32_t sr, uint32_t n_fft, uint32_t n_mel) {
+    if (n_mel == 0) n_mel = (uint32_t)mel_default_n_mel(sr, n_fft);
+    const uint32_t n_freq = n_fft / 2 + 1;
+    const std::vector<float> fb = calc_mel_fb(sr, n_fft, n_mel, 0.f, -1.f, true);
+    const MelRangeHost rg = build_mel_ranges(fb.data(), n_freq, n_mel);
+    const MelMfmaHost mt = build_mel_mfma(fb.data(), rg, n_freq, n_mel);
+    const MelRowsHost mr = build_mel_rows(fb.data(), rg, n_freq, n_mel);
+    EmuBlobs *e = new EmuBlobs;
+    e->add(fb);
+    e->add(std::vector<uint32_t>{n_mel, mt.kblocks, mt.ntiles, mt.zero_block, mt.n_slices, mr.ok ? 1u : 0u, mr.n_groups});
+    e->add(rg.lo);
+    e->add(rg.hi);
+    e->add(mt.band);
+    e->add(mt.slice);
+    e->add(mt.bt);
+    e->add(mr.words);
+    return e;
+}
+
+// The wave kernels' window tables from a normalised window.  Blobs (f32): 0 wtab, 1 the phased / dynamic table (empty in mode 0)
+extern "C" __attribute__((visibility("default"))) void *emu_wave_window(const float *window, uint32_t win, uint32_t n_fft, int32_t phased_mode) {
+    const WaveWindowHost ww = build_wave_window(window, win, n_fft, phased_mode);
+    EmuBlobs *e = new EmuBlobs;
+    e->add(ww.wtab);
+    e->add(ww.phased);
+    return e;
+}

@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -164,7 +165,7 @@ TH_API int th_ctx_create_ex(int device, void *hip_stream, int use_given_stream, 
         return fail(TH_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
     TH_REQUIRE(device >= 0 && device < n, "device %d out of range (have %d)", device, n);
     TH_HIP(hipSetDevice(device));
-    th_ctx *c = new th_ctx();
+    std::unique_ptr<th_ctx> c(new th_ctx());
     c->device = device;
     {
         int n_cu = 0;
@@ -176,17 +177,11 @@ TH_API int th_ctx_create_ex(int device, void *hip_stream, int use_given_stream, 
         c->own_stream = false;
     } else {
         hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-        if (e != hipSuccess) {
-            delete c;
-            return fail(TH_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(e));
-        }
+        if (e != hipSuccess) return fail(TH_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(e));
         c->own_stream = true;
     }
-    if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) {
-        delete c;
-        return fail(TH_ERR_HIP, "hipEventCreate failed");
-    }
-    *out = c;
+    if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) return fail(TH_ERR_HIP, "hipEventCreate failed");
+    *out = c.release();
     return TH_OK;
     TH_CATCH
 }
@@ -196,10 +191,6 @@ TH_API int th_ctx_destroy(th_ctx *c) {
     if (!c) return TH_OK;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    c->release_scratch();
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return TH_OK;
     TH_CATCH
@@ -391,6 +382,7 @@ static void resolve_route(th_plan &p) {
     const StftGeom &g = p.g;
     const int k = p.kernel_choice, wv = p.wave_waves;
     R r;
+    r.block_plan = stft_is_block_plan(g);
     const bool wave = k != SEL_GENERIC && stft_wave_supported(g) && (g.n_mel == 0 || p.d_mel_bt != nullptr);
     r.no_wave_kernel = k >= SEL_WAVE && !wave;
     // n_fft 8192 .. 65536: the block or the subwave plan (stft_subwave_default: the sizes where the subwave plan is the default).
@@ -428,7 +420,7 @@ static void resolve_route(th_plan &p) {
     }
     const bool mel_amp = g.n_mel != 0 && wave && !fused;
     if (fused)
-        r.mel_fused = (g.log2_nc >= 11 || mom_small) ? (stft_is_block_plan(g) ? R::MelFused::MomentLanes : R::MelFused::Moment)
+        r.mel_fused = (g.log2_nc >= 11 || mom_small) ? (r.block_plan ? R::MelFused::MomentLanes : R::MelFused::Moment)
                     : g.log2_nc == 8 ? R::MelFused::Rows
                     // frame pairs (round 5): two consecutive frames per pass over the table; selector 13 keeps the one-frame epilogue (A/B)
                     : bsum_fits ? (k != SEL_MEL_ONE_FRAME && stft_wave_mel_pair_applies(g, wv, p.mel_bsum_reach) ? R::MelFused::BandedPairs : R::MelFused::Banded)
@@ -453,7 +445,7 @@ static void resolve_route(th_plan &p) {
     // boundary frames of channels with at least n_fft samples also go to the wave kernel (one-frame chunks with a
     // reflect-indexed fetch): no second launch on the fast path.  Not on the matrix-core mel path (its amplitude rows
     // are laid out for the interior jobs), not for channels shorter than n_fft (a single reflection is not enough there).
-    r.edges_in_wave = wave && !mel_amp && r.phase_mode == 0 && !stft_is_block_plan(g);
+    r.edges_in_wave = wave && !mel_amp && r.phase_mode == 0 && !r.block_plan;
     r.sweep = wave && k == SEL_SWEEP && p.wave_chunk == 0 && g.n_mel == 0 && r.phase_mode == 0 && stft_wave_sweep_applies(gl, wv, 0);
     r.packed = k == SEL_PACKED;
     // n_fft 512, linear dB: four frames per wave (stft_wave_multi.h).  The same plan with two frames per wave exists for
@@ -462,50 +454,13 @@ static void resolve_route(th_plan &p) {
     // (n_fft 32768, round 5: sixteen wave transforms + a combining pass, kernels_stft_long.hip; selector 14 keeps the block kernel)
     if (!wave) r.main = p.bluestein() ? R::Main::Bluestein : R::Main::Generic;
     else if (multi && (g.log2_nc == 8 || k == SEL_MULTI_1024)) r.main = R::Main::WaveMulti;
-    else if (!stft_is_block_plan(g)) r.main = R::Main::Wave;
+    else if (!r.block_plan) r.main = R::Main::Wave;
     else r.main = (mode != 2 && stft_subwave_applies(g) && p.d_twc != nullptr && r.long_plan == 2) ? R::Main::Subwave : R::Main::Block;
     static const char *const main_name[] = {"stft_generic_kernel", "stft_bluestein_kernel", "stft_wave_kernel", "stft_wave_kernel",
                                             "stft_block_kernel", "stft_subwave_kernel"};
     static const char *const second_name[] = {"", "+mel_rows_kernel", "+mel_band_rows_kernel", "+mel_mfma_kernel"};
     std::snprintf(r.name, sizeof r.name, "%s%s%s", main_name[(int)r.main], fused ? "(fused mel)" : "", second_name[(int)r.mel_second]);
     p.route = r;
-}
-
-static void plan_free(th_plan *p) {
-    if (!p) return;
-    for (hipEvent_t e : p->ev_k0) (void)hipEventDestroy(e);
-    for (hipEvent_t e : p->ev_k1) (void)hipEventDestroy(e);
-    if (p->d_wtab) (void)hipFree(p->d_wtab);
-    if (p->d_wtab_phased) (void)hipFree(p->d_wtab_phased);
-    if (p->d_queue_head) (void)hipFree(p->d_queue_head);
-    if (p->d_mel_bt) (void)hipFree(p->d_mel_bt);
-    if (p->d_mel_band) (void)hipFree(p->d_mel_band);
-    if (p->d_mel_slice) (void)hipFree(p->d_mel_slice);
-    if (p->d_mel_rows) (void)hipFree(p->d_mel_rows);
-    if (p->d_mel_fuse) (void)hipFree(p->d_mel_fuse);
-    if (p->d_mel_bsum) (void)hipFree(p->d_mel_bsum);
-    if (p->d_mel_mom) (void)hipFree(p->d_mel_mom);
-    p->amp_buf.release();
-    p->chunk_mm.release();
-    p->post_jobs.release();
-    p->mel_jobs.release();
-    p->mel_tile_start.release();
-    if (p->d_window) (void)hipFree(p->d_window);
-    if (p->d_bs_chirp) (void)hipFree(p->d_bs_chirp);
-    if (p->d_bs_bhat) (void)hipFree(p->d_bs_bhat);
-    if (p->d_bs_twm) (void)hipFree(p->d_bs_twm);
-    if (p->d_bs_tws) (void)hipFree(p->d_bs_tws);
-    if (p->d_tw) (void)hipFree(p->d_tw);
-    if (p->d_twc) (void)hipFree(p->d_twc);
-    if (p->d_mel_fb) (void)hipFree(p->d_mel_fb);
-    if (p->d_mel_lo) (void)hipFree(p->d_mel_lo);
-    if (p->d_mel_hi) (void)hipFree(p->d_mel_hi);
-    p->jobs.release();
-    p->gen_scratch.release();
-    p->tile_start.release();
-    p->edge_jobs.release();
-    p->edge_tile_start.release();
-    delete p;
 }
 
 TH_API int th_plan_create(th_ctx *c, uint32_t sr, size_t win, size_t hop, size_t n_fft, int freq_scale,
@@ -532,196 +487,93 @@ TH_API int th_plan_create(th_ctx *c, uint32_t sr, size_t win, size_t hop, size_t
         return fail(TH_ERR_UNSUPPORTED, "n_fft=%zu: supported is every even n_fft from 2 to %u", n_fft, (unsigned)TH_MAX_N_FFT);
     TH_HIP(hipSetDevice(c->device));
 
-    th_plan *p = new th_plan();
+    std::unique_ptr<th_plan> owner(new th_plan());  // (a failure below frees the plan and what it has uploaded so far)
+    th_plan *p = owner.get();
     p->ctx = c;
     p->sr = sr;
     p->freq_scale = freq_scale;
     StftGeom &g = p->g;
-    g.hop = (uint32_t)hop;
-    g.win = (uint32_t)win;
-    g.n_fft = (uint32_t)n_fft;
-    g.pad_left = (uint32_t)((n_fft - win) / 2);
-    g.nc = (uint32_t)(n_fft / 2);
-    g.odd_m1 = (uint32_t)odd_part - 1u;
-    g.log2_nc = ilog2(g.nc / (uint32_t)odd_part);  // log2 of the power-of-two part of nc
-    g.n_freq = (uint32_t)(n_fft / 2 + 1);
-    g.n_mel = 0;
-    g.height = g.n_freq;
-    g.frames_per_tile = 8;  // generic kernel; the wave kernel's tile is set at launch
+    g = stft_geom(win, hop, n_fft);
 
-    // window (windows.rs) and twiddles W_{n_fft}^i (double → f32)
+    // every table is built on the host (stft_plan.h, mel_fuse.h, host_math.h) and uploaded as it is:
+    // window (windows.rs), twiddles W_{n_fft}^i and the wave kernels' window tables (grid-aligned forms: kernels_stft.hip)
     const std::vector<float> w = normalized_hann(win, n_fft);
-    std::vector<cf32> tw(n_fft);
-    for (size_t i = 0; i < n_fft; i++) {
-        const double a = -2.0 * M_PI * (double)i / (double)n_fft;
-        tw[i].re = (float)std::cos(a);
-        tw[i].im = (float)std::sin(a);
-    }
-    int rc = TH_OK;
-    auto up = [&](void **d, const void *h, size_t bytes) -> int {
-        TH_HIP(hipMalloc(d, bytes));
-        TH_HIP(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
-        return TH_OK;
-    };
+    const std::vector<cf32> tw = build_twiddles(n_fft);
     {
-        // wave-kernel window table: wtab[n] = 0.5 * (wpad[2n], wpad[2n+1]), wpad = zero-padded window
-        // (the 1/2 of the real-FFT split pass and the kernel's 2^32 pre-scale (stft_wave.h: WAVE_PRESCALE, undone in the
-        // dB conversion) are folded in here; exact, powers of two)
-        const float half = 0.5f * th::WAVE_PRESCALE;
-        std::vector<float> wpad(n_fft, 0.f);
-        for (size_t i = 0; i < win; i++) wpad[g.pad_left + i] = half * w[i];
-        rc = up((void **)&p->d_wtab, wpad.data(), wpad.size() * sizeof(float));
-        // grid-aligned modes of the wave kernel (kernels_stft.hip): the window at offset 0 instead of pad_left.
-        // phased (hop 480): behind 48 zero pairs (read 0, 96, 64 or 32 samples lower);  dynamic (e.g. hop 441): behind 64
-        // zero pairs, followed by the same with every pair shifted by one sample (odd offsets)
-        const int pm = th::stft_wave_phased_mode(g, 0);
-        if (rc == TH_OK && pm == 1) {
-            std::vector<float> w4(96 + n_fft, 0.f);
-            for (size_t i = 0; i < win; i++) w4[96 + i] = half * w[i];
-            rc = up((void **)&p->d_wtab_phased, w4.data(), w4.size() * sizeof(float));
-        } else if (rc == TH_OK && (pm == 2 || pm == 3)) {  // (3 reads the even table only: the same buffer)
-            std::vector<float> t0(n_fft + 2, 0.f), w2(2 * (128 + n_fft), 0.f);
-            for (size_t i = 0; i < win; i++) t0[i] = half * w[i];
-            for (size_t i = 0; i < n_fft; i++) {
-                w2[128 + i] = t0[i];                       // even table: pairs (t0[2n], t0[2n+1])
-                w2[128 + n_fft + 128 + i] = t0[i + 1];     // odd table:  pairs (t0[2n+1], t0[2n+2])
-            }
-            rc = up((void **)&p->d_wtab_phased, w2.data(), w2.size() * sizeof(float));
-        }
+        const WaveWindowHost ww = build_wave_window(w.data(), win, n_fft, th::stft_wave_phased_mode(g, 0));
+        TH_CHECK(p->d_wtab.fill(ww.wtab));
+        if (!ww.phased.empty()) TH_CHECK(p->d_wtab_phased.fill(ww.phased));
     }
-    if (rc == TH_OK) rc = up((void **)&p->d_window, w.data(), w.size() * sizeof(float));
-    if (rc == TH_OK) {
+    TH_CHECK(p->d_window.fill(w));
+    {
         const uint32_t zero[4] = {0, 0, 0, 0};  // [0] chunk queue head (rewound by wave_post_kernel after every launch), [1..3] spare
-        rc = up((void **)&p->d_queue_head, zero, sizeof zero);
+        TH_CHECK(p->d_queue_head.fill(zero, sizeof zero));
     }
-    if (rc == TH_OK) rc = up((void **)&p->d_tw, tw.data(), tw.size() * sizeof(cf32));
-    if (rc == TH_OK && odd_part > th::STFT_MAX_DIRECT_ODD) {  // Bluestein plan: chirp, FFT_M(b), twiddles of the M-point passes and of the split pass (doubles)
+    TH_CHECK(p->d_tw.fill(tw));
+    if (odd_part > th::STFT_MAX_DIRECT_ODD) {  // Bluestein plan: chirp, FFT_M(b), twiddles of the M-point passes and of the split pass (doubles)
         const BluesteinTables bt = bluestein_tables(n_fft, th::stft_bluestein_m(g));
-        rc = up((void **)&p->d_bs_chirp, bt.chirp.data(), bt.chirp.size() * sizeof(double));
-        if (rc == TH_OK) rc = up((void **)&p->d_bs_bhat, bt.bhat.data(), bt.bhat.size() * sizeof(double));
-        if (rc == TH_OK) rc = up((void **)&p->d_bs_twm, bt.twm.data(), bt.twm.size() * sizeof(double));
-        if (rc == TH_OK) rc = up((void **)&p->d_bs_tws, bt.tws.data(), bt.tws.size() * sizeof(double));
+        TH_CHECK(p->d_bs_chirp.fill(bt.chirp));
+        TH_CHECK(p->d_bs_bhat.fill(bt.bhat));
+        TH_CHECK(p->d_bs_twm.fill(bt.twm));
+        TH_CHECK(p->d_bs_tws.fill(bt.tws));
     }
-    if (rc == TH_OK && th::stft_subwave_applies(g)) {  // n_fft 32768: per-thread constants of stft_subwave_kernel's combining pass
+    if (th::stft_subwave_applies(g)) {  // n_fft 32768: per-thread constants of stft_subwave_kernel's combining pass
         std::vector<cf32> twc(th::stft_subwave_twc_len(g));
         th::stft_subwave_build_twc(g, tw.data(), twc.data());
-        rc = up((void **)&p->d_twc, twc.data(), twc.size() * sizeof(cf32));
+        TH_CHECK(p->d_twc.fill(twc));
     }
-    if (rc == TH_OK && freq_scale == TH_FREQ_MEL) {
+    if (freq_scale == TH_FREQ_MEL) {
         if (n_mel == 0) n_mel = mel_default_n_mel(sr, n_fft);  // calc_mel_fb_default, lib.rs:91-103
-        if (n_mel == 0 || n_mel > 65535) {
-            plan_free(p);
-            return fail(TH_ERR_INVALID_ARG, "n_mel=%zu out of range", n_mel);
-        }
+        if (n_mel == 0 || n_mel > 65535) return fail(TH_ERR_INVALID_ARG, "n_mel=%zu out of range", n_mel);
         // the dense (F x n_mel) filterbank of calc_mel_fb (src-common/src/lib.rs:46-89) is what the generic kernel reads: at the
         // default mel counts of very long windows it no longer fits anything (n_fft 131072 at 48 kHz: 65537 x ~22000 floats)
-        if ((double)(n_fft / 2 + 1) * (double)n_mel * sizeof(float) > (double)((size_t)1 << 30)) {
-            plan_free(p);
+        if ((double)(n_fft / 2 + 1) * (double)n_mel * sizeof(float) > (double)((size_t)1 << 30))
             return fail(TH_ERR_UNSUPPORTED, "mel filterbank of %zu bins x %zu mels exceeds 1 GiB", n_fft / 2 + 1, n_mel);
-        }
         g.n_mel = (uint32_t)n_mel;
         g.height = (uint32_t)n_mel;
         p->h_mel_fb = calc_mel_fb(sr, n_fft, n_mel, 0.f, -1.f, true);
-        std::vector<uint32_t> lo(n_mel, 0), hi(n_mel, 0);
-        for (size_t m = 0; m < n_mel; m++) {
-            uint32_t a = g.n_freq, b = 0;
-            for (uint32_t f = 0; f < g.n_freq; f++)
-                if (p->h_mel_fb[(size_t)f * n_mel + m] != 0.f) {
-                    a = std::min(a, f);
-                    b = f + 1;
-                }
-            lo[m] = b ? a : 0;
-            hi[m] = b;
-        }
+        const float *fb = p->h_mel_fb.data();
+        const MelRangeHost rg = build_mel_ranges(fb, g.n_freq, g.n_mel);
         if (th::stft_wave_supported(g)) {   // (no wave / block kernel for this geometry: the generic kernel reads none of these)
             // MFMA mel path tables (kernels_mel.hip; any mel count since round 4 — the Mel default of long windows, e.g. 5571 mels
-            // at n_fft 32768 / 48 kHz, used to fall back to the generic kernel: 12 ms where the linear plan takes 2): for every N tile j of 16 mels the band of K blocks (16 bins each)
-            // that hold non-zeros, and the filterbank of those blocks in operand order: lane (kq = lane / 16,
-            // li = lane % 16), step s -> fb[16 kb + 4 kq + s][16 j + li]
-            const uint32_t nt = (uint32_t)((n_mel + 15) / 16);
-            const uint32_t kb_n = (g.n_freq + 15) / 16;
-            std::vector<uint32_t> band(3 * (size_t)nt, 0);
-            std::vector<float> bt;
-            auto fbv = [&](uint32_t f, size_t m) { return (f < g.n_freq && m < n_mel) ? p->h_mel_fb[(size_t)f * n_mel + m] : 0.f; };
-            for (uint32_t j = 0; j < nt; j++) {
-                // the tile's K band from the per-mel non-zero ranges [lo, hi) found above (the dense scan over
-                // every (bin, mel) of every tile was ~90 M filterbank reads at the 5571-mel default of n_fft 32768)
-                uint32_t klo = kb_n, khi = 0;
-                for (size_t m = 16 * (size_t)j; m < std::min<size_t>(16 * (size_t)j + 16, n_mel); m++)
-                    if (hi[m]) {
-                        klo = std::min(klo, lo[m] / 16);
-                        khi = std::max(khi, (hi[m] + 15) / 16);
-                    }
-                if (!khi) klo = 0;
-                band[3 * j] = klo;
-                band[3 * j + 1] = khi;
-                band[3 * j + 2] = (uint32_t)(bt.size() / 256);
-                for (uint32_t kb = klo; kb < khi; kb++)
-                    for (uint32_t lane = 0; lane < 64; lane++)
-                        for (uint32_t st = 0; st < 4; st++) bt.push_back(fbv(16 * kb + 4 * (lane >> 4) + st, 16 * (size_t)j + (lane & 15u)));
-            }
-            p->mel_zero_block = (uint32_t)(bt.size() / 256);
-            bt.insert(bt.end(), 256, 0.f);
-            p->mel_kblocks = kb_n;
-            p->mel_ntiles = nt;
-            // slices of the tile range (grid y): contiguous, about equal numbers of 4-K-block groups
-#if !defined(TH_MEL_SLICES)
-#define TH_MEL_SLICES 6
-#endif
-            std::vector<uint32_t> slice{0};
-            {
-                uint64_t total = 0;
-                for (uint32_t j = 0; j < nt; j++) total += (band[3 * j + 1] - band[3 * j] + 3) / 4 + 1;  // + epilogue
-                const uint32_t want = std::min<uint32_t>(TH_MEL_SLICES, nt);
-                uint64_t acc_g = 0;
-                for (uint32_t j = 0; j < nt; j++) {
-                    acc_g += (band[3 * j + 1] - band[3 * j] + 3) / 4 + 1;
-                    if (slice.size() < want && acc_g * want >= total * slice.size() && j + 1 < nt) slice.push_back(j + 1);
-                }
-                slice.push_back(nt);
-            }
-            p->mel_slices = (uint32_t)slice.size() - 1;
-            {   // short rows under narrow filters (n_fft 512 at the default mel counts): the per-mel table of mel_rows_kernel
-                uint32_t widest = 0;
-                for (size_t m = 0; m < n_mel; m++) widest = std::max(widest, hi[m] - lo[m]);
-                const uint32_t ng = (uint32_t)((n_mel + 63) / 64);
-                // (only n_fft 512 plans on the wave kernel ever read it — ADVICE r3: n_fft 128 / 256 used to pay the upload too)
-                if (g.log2_nc == 8 && th::stft_wave_supported(g) && kb_n <= (uint32_t)th::MEL_ROWS_NKB && g.n_freq - 1 + th::MEL_ROWS_W <= 16 * th::MEL_ROWS_NKB + 4 &&  // (reads stay in the LDS row)
-                    widest <= (uint32_t)th::MEL_ROWS_W && ng <= (uint32_t)th::MEL_ROWS_MAX_GROUPS) {
-                    constexpr uint32_t W = th::MEL_ROWS_W;
-                    std::vector<uint32_t> tab((size_t)ng * (W + 1) * 64, 0u);
-                    for (size_t m = 0; m < n_mel; m++) {
-                        const size_t at = (m / 64) * (W + 1) * 64 + m % 64;
-                        tab[at] = lo[m];
-                        for (uint32_t t = 0; t < W && lo[m] + t < hi[m]; t++)
-                            std::memcpy(&tab[at + (1 + t) * 64], &p->h_mel_fb[(size_t)(lo[m] + t) * n_mel + m], 4);
-                    }
-                    p->mel_rows_groups = ng;
-                    rc = up((void **)&p->d_mel_rows, tab.data(), tab.size() * sizeof(uint32_t));
+            // at n_fft 32768 / 48 kHz, used to fall back to the generic kernel: 12 ms where the linear plan takes 2)
+            const MelMfmaHost mt = build_mel_mfma(fb, rg, g.n_freq, g.n_mel);
+            p->mel_zero_block = mt.zero_block;
+            p->mel_kblocks = mt.kblocks;
+            p->mel_ntiles = mt.ntiles;
+            p->mel_slices = mt.n_slices;
+            // short rows under narrow filters (n_fft 512 at the default mel counts): the per-mel table of mel_rows_kernel
+            // (only n_fft 512 plans on the wave kernel ever read it — ADVICE r3: n_fft 128 / 256 used to pay the upload too)
+            if (g.log2_nc == 8) {
+                const MelRowsHost mr = build_mel_rows(fb, rg, g.n_freq, g.n_mel);
+                if (mr.ok) {
+                    p->mel_rows_groups = mr.n_groups;
+                    TH_CHECK(p->d_mel_rows.fill(mr.words));
                 }
             }
-            if (rc == TH_OK) rc = up((void **)&p->d_mel_bt, bt.data(), bt.size() * sizeof(float));
-            if (rc == TH_OK) rc = up((void **)&p->d_mel_band, band.data(), band.size() * sizeof(uint32_t));
-            if (rc == TH_OK) rc = up((void **)&p->d_mel_slice, slice.data(), slice.size() * sizeof(uint32_t));
+            TH_CHECK(p->d_mel_bt.fill(mt.bt));
+            TH_CHECK(p->d_mel_band.fill(mt.band));
+            TH_CHECK(p->d_mel_slice.fill(mt.slice));
         }
-        if (rc == TH_OK && th::stft_wave_supported(g) && n_mel <= 512) {  // (the fused forms: lane = mel in at most 8 groups of 64)
+        if (th::stft_wave_supported(g) && n_mel <= 512) {  // (the fused forms: lane = mel in at most 8 groups of 64)
             // fused mel epilogue of the wave kernel: piece / gather tables, when the filterbank has the expected structure
-            const th::MelFuseHost mf = th::build_mel_fuse(p->h_mel_fb.data(), g.n_freq, (uint32_t)n_mel, th::stft_wave_mel_max_pieces(g));
-            if (rc == TH_OK && g.log2_nc == 11) {
+            const th::MelFuseHost mf = th::build_mel_fuse(fb, g.n_freq, (uint32_t)n_mel, th::stft_wave_mel_max_pieces(g));
+            auto keep_band = [&](const th::MelBandHost &mb) {
+                p->mel_bsum_words = (uint32_t)mb.words.size();
+                std::copy(mb.words.begin(), mb.words.begin() + 16, p->mel_bsum_hdr);
+                p->mel_bsum_groups = mb.n_groups;
+                return p->d_mel_bsum.fill(mb.words);
+            };
+            if (g.log2_nc == 11) {
                 // n_fft 4096 (two kernels): the same banded table for mel_band_rows_kernel, where it fits LDS beside four rows
                 // (the paired layout as in the wave kernels; with dword reads the bank-spread table had measured 3 % SLOWER here, 2.08 ->
                 // 2.15 ms at the 96 kHz default, profiles/r04_ab_mel_bank_spread.txt — the paired one is 1 % faster than the plain table)
-                const th::MelBandHost mb = th::build_mel_band(p->h_mel_fb.data(), g.n_freq, (uint32_t)n_mel, 1u << 16, false, TH_MEL_ROWS_PAIRED != 0);
-                if (mb.ok && th::mel_band_rows_fits(g.n_freq, (uint32_t)mb.words.size())) {
-                    p->mel_bsum_words = (uint32_t)mb.words.size();
-                    std::copy(mb.words.begin(), mb.words.begin() + 16, p->mel_bsum_hdr);
-                    p->mel_bsum_groups = mb.n_groups;
-                    rc = up((void **)&p->d_mel_bsum, mb.words.data(), mb.words.size() * sizeof(uint32_t));
-                }
+                const th::MelBandHost mb = th::build_mel_band(fb, g.n_freq, (uint32_t)n_mel, 1u << 16, false, TH_MEL_ROWS_PAIRED != 0);
+                if (mb.ok && th::mel_band_rows_fits(g.n_freq, (uint32_t)mb.words.size())) TH_CHECK(keep_band(mb));
             }
-            if (rc == TH_OK && (g.log2_nc == 9 || g.log2_nc == 10)) {
+            if (g.log2_nc == 9 || g.log2_nc == 10) {
                 // (the wave kernels of n_fft 1024 / 2048 read the table's paired layout, mel_banded<true>)
-                const th::MelBandHost mb = th::build_mel_band(p->h_mel_fb.data(), g.n_freq, (uint32_t)n_mel, 1u << 16, TH_MEL_BAND_SPREAD != 0, TH_MEL_BAND_PAIRED != 0);
+                const th::MelBandHost mb = th::build_mel_band(fb, g.n_freq, (uint32_t)n_mel, 1u << 16, TH_MEL_BAND_SPREAD != 0, TH_MEL_BAND_PAIRED != 0);
                 // Measured against the pieces / gather form (same box, alternating; taps = the sum over the groups of their
                 // widest filter): n_fft 2048 — 56 / 60 / 64 taps (256 mels, the 44.1 / 48 kHz defaults) 6 / 8 / 10 % faster; 72 taps
                 // (128 mels) 4 % faster in the register-reuse kernel (hop a multiple of 128: config 4), 6 % slower in the full-reload
@@ -732,28 +584,25 @@ TH_API int th_plan_create(th_ctx *c, uint32_t sr, size_t win, size_t hop, size_t
                 const uint32_t taps = mb.taps_unshifted;
                 const uint32_t max_taps = g.log2_nc == 9 ? TH_MEL_BAND_TAPS_1024 : (g.hop % 128 == 0 ? TH_MEL_BAND_TAPS_2048 + 8u : TH_MEL_BAND_TAPS_2048);
                 if (mb.ok && taps <= max_taps) {
-                    p->mel_bsum_words = (uint32_t)mb.words.size();
-                    std::copy(mb.words.begin(), mb.words.begin() + 16, p->mel_bsum_hdr);
-                    p->mel_bsum_groups = mb.n_groups;
                     p->mel_bsum_reach = mb.reach;
-                    rc = up((void **)&p->d_mel_bsum, mb.words.data(), mb.words.size() * sizeof(uint32_t));
+                    TH_CHECK(keep_band(mb));
                 }
             }
-            if (mf.ok && rc == TH_OK) {
+            if (mf.ok) {
                 p->mel_fuse_words = (uint32_t)mf.words.size();
                 p->mel_fuse_slots = mf.n_slots;
                 p->mel_fuse_groups = mf.n_groups;
-                rc = up((void **)&p->d_mel_fuse, mf.words.data(), mf.words.size() * sizeof(uint32_t));
+                TH_CHECK(p->d_mel_fuse.fill(mf.words));
             }
         }
         // (n_fft 1024 / 2048: only where no LDS table form exists — more than 512 mels)
         const bool small_mom = ((g.log2_nc == 9 || g.log2_nc == 10) && p->d_mel_bsum == nullptr && p->d_mel_fuse == nullptr) || (g.log2_nc == 8 && p->d_mel_rows == nullptr);
-        if (rc == TH_OK && (g.log2_nc == 11 || g.log2_nc == 12 || g.log2_nc == 13 || small_mom) && th::stft_wave_supported(g)) {
+        if ((g.log2_nc == 11 || g.log2_nc == 12 || g.log2_nc == 13 || small_mom) && th::stft_wave_supported(g)) {
             // n_fft 4096 (the wave kernel) and 8192 / 16384 (the workgroup-per-frame kernel): the moment form (lane = segment of the
             // triangle points; mel_fuse.h) for the fused epilogue, any mel count
             std::vector<float> lin, mfp;
             mel_fb_points(sr, n_fft, n_mel, 0.f, -1.f, lin, mfp);
-            const th::MelMomHost mm = th::build_mel_moments(p->h_mel_fb.data(), lin.data(), mfp.data(), g.n_freq, (uint32_t)n_mel,
+            const th::MelMomHost mm = th::build_mel_moments(fb, lin.data(), mfp.data(), g.n_freq, (uint32_t)n_mel,
                                                             g.log2_nc == 8 ? th::stft_wave_multi_amp_pitch() : g.log2_nc <= 11 ? 2u * (g.nc + g.nc / 16u) : th::stft_block_mel_max_index(g), g.log2_nc <= 11 && TH_MEL_BAND_SPREAD != 0);
             // (the workgroup-per-frame kernels walk a batch of groups in lockstep: a lane reads up to the table's widest group's
             // taps behind its first bin — inside the exchange buffer)
@@ -766,19 +615,15 @@ TH_API int th_plan_create(th_ctx *c, uint32_t sr, size_t win, size_t hop, size_t
                 p->mel_mom_taps = mm.taps;
                 p->mel_mom_max_dev = mm.max_dev;
                 p->mel_mom_max_amp = mm.max_amp;
-                rc = up((void **)&p->d_mel_mom, tab.data(), tab.size() * sizeof(uint32_t));
+                TH_CHECK(p->d_mel_mom.fill(tab));
             }
         }
-        if (rc == TH_OK) rc = up((void **)&p->d_mel_fb, p->h_mel_fb.data(), p->h_mel_fb.size() * sizeof(float));
-        if (rc == TH_OK) rc = up((void **)&p->d_mel_lo, lo.data(), lo.size() * sizeof(uint32_t));
-        if (rc == TH_OK) rc = up((void **)&p->d_mel_hi, hi.data(), hi.size() * sizeof(uint32_t));
-    }
-    if (rc != TH_OK) {
-        plan_free(p);
-        return rc;
+        TH_CHECK(p->d_mel_fb.fill(p->h_mel_fb));
+        TH_CHECK(p->d_mel_lo.fill(rg.lo));
+        TH_CHECK(p->d_mel_hi.fill(rg.hi));
     }
     resolve_route(*p);
-    *out = p;
+    *out = owner.release();
     return TH_OK;
     TH_CATCH
 }
@@ -788,7 +633,7 @@ TH_API int th_plan_destroy(th_plan *p) {
     if (!p) return TH_OK;
     (void)hipSetDevice(p->ctx->device);
     (void)hipStreamSynchronize(p->ctx->stream);
-    plan_free(p);
+    delete p;
     return TH_OK;
     TH_CATCH
 }
@@ -869,6 +714,51 @@ static int sweep_check(th_plan *p) {
     return fail(TH_ERR_INTERNAL, "sweep schedule (kernel selector 11): a wave gave up waiting for its chunk block; rows of the last launch are unwritten");
 }
 
+// What the wave kernel of this plan writes, and the mel table its epilogue reads: the route's choices as launch arguments
+static th::WaveOut wave_out(const th_plan &p, const StftGeom &g, bool sweep) {
+    const StftRoute &r = p.route;
+    th::WaveOut wo;
+    wo.mode = r.out_mode();
+    wo.multi = r.main == StftRoute::Main::WaveMulti ? 1 : 0;
+    wo.packed = r.packed ? 1 : 0;
+    wo.sweep = sweep ? 1 : 0;
+    wo.long_plan = r.long_plan;
+    wo.subwave_twc = p.d_twc;
+    if (r.mel_fused != StftRoute::MelFused::None) wo.n_mel = g.n_mel;
+    switch (r.mel_fused) {
+        case StftRoute::MelFused::None: break;
+        case StftRoute::MelFused::Moment:
+        case StftRoute::MelFused::MomentLanes:  // moment form: the table stays in global memory (scalar + 16-byte lane loads)
+            wo.mel_moment = r.mel_fused == StftRoute::MelFused::Moment && g.log2_nc < 11 ? 1u : 0u;  // (n_fft 4096 and up: their only form)
+            wo.mel_tab = p.d_mel_mom;
+            wo.mel_groups = p.mel_mom_groups;
+            break;
+        case StftRoute::MelFused::Rows:  // (the per-mel table of the banded sums, kernels.h)
+            wo.mel_tab = p.d_mel_rows;
+            wo.mel_groups = p.mel_rows_groups;
+            wo.mel_words = p.mel_rows_groups * (uint32_t)(th::MEL_ROWS_W + 1) * 64u;
+            break;
+        case StftRoute::MelFused::Banded:
+        case StftRoute::MelFused::BandedPairs:  // banded sums (mel_slots = 0 tells the kernel)
+            wo.mel_tab = p.d_mel_bsum;
+            wo.mel_words = p.mel_bsum_words;
+            wo.mel_groups = p.mel_bsum_groups;
+            for (uint32_t gq = 0; gq < 8; gq++) {
+                wo.band_off[gq] = p.mel_bsum_hdr[2 * gq];
+                wo.band_n[gq] = p.mel_bsum_hdr[2 * gq + 1];
+            }
+            wo.mel_pair = r.mel_fused == StftRoute::MelFused::BandedPairs ? 1u : 0u;
+            break;
+        case StftRoute::MelFused::Pieces:
+            wo.mel_tab = p.d_mel_fuse;
+            wo.mel_words = p.mel_fuse_words;
+            wo.mel_slots = p.mel_fuse_slots;
+            wo.mel_groups = p.mel_fuse_groups;
+            break;
+    }
+    return wo;
+}
+
 static int calc_spec_batch_impl(th_plan *p, const th_chan_desc *chans, size_t n_chan, float *d_minmax, float dB_range,
                                 float *d_range) {
     TH_TRY
@@ -887,187 +777,28 @@ static int calc_spec_batch_impl(th_plan *p, const th_chan_desc *chans, size_t n_
     const StftRoute &r = p->route;
     const bool wave = r.wave(), mel_mfma = r.mel_second != StftRoute::MelSecond::None;
     if (r.no_wave_kernel) return fail(TH_ERR_UNSUPPORTED, "the wave kernels cover n_fft 512 .. 32768");
-    StftGeom g = p->g;       // main launch
-    StftGeom ge = p->g;      // edge launch (generic kernel)
-    g.phased = (uint32_t)r.phase_mode;
-    const bool phased = r.phase_mode != 0;
-    // wave kernel: chunk of consecutive frames one wave walks (the first frame of a chunk loads
-    // n_fft samples, the rest only hop new ones).  32 amortises that well on large batches; small
-    // batches (one track) get shorter chunks so that every wave of the chip has work.
-    // interior frames [fa, fb) of a channel: the frame's whole n_fft-sample span [e0, e0 + n_fft), e0 = f*hop - win/2 -
-    // pad_left, lies inside the channel (the wave kernel loads it unconditionally); the others are boundary frames
-    // phased mode: chunks must start on frames that sit exactly on the 128-sample grid (every fourth)
-    auto interior = [&g, &r, phased](const th_chan_desc &d, uint64_t T, uint64_t &fa, uint64_t &fb) {
-        if (phased) {
-            const int64_t N = (int64_t)d.n_samples, half = (int64_t)(g.win / 2);
-            auto delta = [&](int64_t f) { return (((f * (int64_t)g.hop - half) % 128) + 128) % 128; };
-            auto start = [&](int64_t f) { return f * (int64_t)g.hop - half - delta(f); };
-            int64_t a = 0, b = (int64_t)T;
-            while (a < b && (start(a) < 0 || (r.phase_mode == 1 && delta(a) != 0))) a++;  // phased chunks start on the grid
-            while (b > a && start(b - 1) + (int64_t)g.n_fft > N) b--;
-            fa = (uint64_t)a;
-            fb = (uint64_t)b;
-            return;
-        }
-        const uint64_t lead = g.win / 2 + g.pad_left, N = d.n_samples > r.tail_guard ? d.n_samples - r.tail_guard : 0;
-        fa = (lead + g.hop - 1) / g.hop;                                  // first f with e0 >= 0
-        fb = N + lead >= g.n_fft ? (N + lead - g.n_fft) / g.hop + 1 : 0;  // one past the last f with e0 + n_fft <= N
-        fa = std::min<uint64_t>(fa, T);
-        fb = std::min<uint64_t>(std::max(fb, fa), T);
-    };
-    bool sweep = false;
-    if (wave) {
-        uint64_t total = 0;
-        for (size_t i = 0; i < n_chan; i++) total += chans[i].n_frames;
-        // chunks of `len` frames over the batch's interior frames (+ with_edges: one per boundary frame the wave launch takes)
-        auto n_chunks = [&](uint64_t len, bool with_edges) {
-            uint64_t n = 0;
-            for (size_t i = 0; i < n_chan; i++) {
-                uint64_t fa, fb;
-                interior(chans[i], chans[i].n_frames, fa, fb);
-                n += (fb - fa + len - 1) / len;
-                if (with_edges && chans[i].n_samples >= g.n_fft) n += chans[i].n_frames - (fb - fa);
-            }
-            return n;
-        };
-        // The launch ends when the last chunk does and every slot (wave, or workgroup) walks its chunks one after the other, so
-        // what counts is rounds x chunk length: the length around `want` (at least `lo`) whose chunk count fills the last round best
-        auto best_chunk = [&](uint64_t want, uint64_t lo, uint64_t slots) {
-            uint64_t best = want, best_cost = ~0ull;
-            for (uint64_t cand = std::max<uint64_t>(lo, want - want / 4); cand <= want + want / 4; cand++) {
-                const uint64_t cost = (n_chunks(cand, false) + slots - 1) / slots * cand;  // frames a slot walks through, at worst
-                if (cost < best_cost || (cost == best_cost && cand > best)) {
-                    best_cost = cost;
-                    best = cand;
-                }
-            }
-            return best;
-        };
-        // about TH_CHUNKS_PER_WAVE chunks per wave (at most 32 frames each): the launch ends when the last chunk does,
-        // so a chunk is the granularity of the load balance, while every chunk costs one full fetch and one atomic on the
-        // queue head (served at ~8 ns each device-wide).  Measured inside bench.py's step: 4 per wave (29 frames)
-        // 0.50-0.515 ms, 6 (19) 0.52, 8 (14) 0.54, 12 (9) 0.69; 32-frame chunks 0.53.
-#if !defined(TH_CHUNKS_PER_WAVE)
-#define TH_CHUNKS_PER_WAVE 4
-#endif
-        const uint64_t n_waves = (uint64_t)c->n_cu * (uint64_t)r.waves;
-        uint64_t chunk;
-        if (th::stft_is_block_plan(g) && g.log2_nc <= 14) {
-            // Workgroup-per-frame plans (n_fft 8192 .. 32768): what runs side by side is one workgroup per CU (two at n_fft 8192),
-            // not twelve waves, and a chunk start costs a workgroup launch + its set-up (30-50 us: tables / constants, the first
-            // frame) or, in the persistent subwave kernel, a full reload of the resident samples.  About two chunks per slot, the
-            // length that fills the last round best (round 5, profiles/r05_ab_block_chunks.txt: n_fft 16384 15 -> 44 frames 0.96 ->
-            // 0.84-0.92 ms, 32768 8 -> 43 1.26 -> 1.21, 8192 30 -> 60-90 0.70 -> 0.64-0.69; n_fft 65536 measures 5 % slower with
-            // longer chunks and keeps the rule below)
-            const uint64_t slots = (uint64_t)c->n_cu * (g.log2_nc == 12 ? 2u : 1u);
-            // (a single track: one frame per chunk, every CU busy)
-            chunk = best_chunk(std::min<uint64_t>(128, std::max<uint64_t>(1, total / (slots * 2))), 1, slots);
-        } else if (total <= n_waves * 32) {
-            // small batch (one track ...): one chunk per wave, all of them assigned statically — the kernel then never
-            // touches the queue (3072 waves finding it empty is 25 us of serialised atomics on a 20 us job)
-            chunk = std::max<uint64_t>(1, (total + n_waves - 1) / n_waves);
-            while (chunk < 32 && n_chunks(chunk, r.edges_in_wave) > n_waves) chunk++;
-        } else {
-            // around total / (waves x TH_CHUNKS_PER_WAVE), 12 to 40 frames.  Bench workload: 29 frames would be 12416 chunks = 4.04
-            // rounds of 3072 waves, i.e. a fifth round for 128 stragglers: 0.520 ms; 30-32 frames 0.507 (r02_chunks).
-            chunk = best_chunk(std::min<uint64_t>(32, std::max<uint64_t>(12, total / (n_waves * TH_CHUNKS_PER_WAVE))), 12, n_waves);
-        }
-        g.frames_per_tile = p->wave_chunk > 0 ? (uint32_t)p->wave_chunk : (uint32_t)chunk;
-        // The sweep schedule (kernels_stft.hip: 4-frame chunks dealt out in order, next chunk prefetched) — round 4, selector 11
-        // only: its memory skeleton streams 3-10 % faster (scripts/ubench/stft_skeleton.hip mode 8), the kernel does not: inside
-        // bench.py's step 0.492 / 0.497 / 0.496 ms against 0.495 / 0.495 / 0.494 for the default schedule on one box, alternating,
-        // and 8 % slower alone with 1 ms gaps (profiles/r04_ab_sweep.txt) — of which the kernel itself is 1 % (rocprofv3 trace:
-        // 480 us against 475, profiles/r04_ab_sweep_kernel_level.txt); the rest is this function building and uploading a
-        // seven times longer chunk table per call, which a pipelined step hides and a lone call does not.  With the packed-f32
-        // pipeline (-39 % VALU instructions, +-0) that makes three independent changes of what the kernel DOES per frame that do
-        // not change what a launch TAKES: it runs at the package power cap, where time follows flops + bytes, and neither moved.
-        sweep = r.sweep && total > n_waves * 32;
-        if (sweep) g.frames_per_tile = 4;
-        // (an earlier launch of this plan that dropped a chunk: found here when the stream has gone idle — no stall otherwise —
-        // and in th_calc_spec_host behind its synchronisation)
-        if (sweep && hipStreamQuery(c->stream) == hipSuccess) {
-            const int src = sweep_check(p);
-            if (src != TH_OK) return src;
-        }
-        if (r.phase_mode == 1) g.frames_per_tile = std::max<uint32_t>(4, (g.frames_per_tile + 3) / 4 * 4);  // chunks start on the grid
-    } else {
-        g.frames_per_tile = 8;
-        // (short transforms — n_fft 256 and below, the generic kernel's only full plans: a tile of 8 frames is one round of its frames-side-by-side
-        // loop, and the workgroup's set-up and (min, max) fold then cost as much as the frames; up to 64 frames a tile where the batch still fills the chip)
-        if (g.nc <= 256 && g.odd_m1 == 0) {
-            uint64_t all = 0;
-            for (size_t i = 0; i < n_chan; i++) all += chans[i].n_frames;
-            const uint64_t want = all / ((uint64_t)c->n_cu * 16u);
-            g.frames_per_tile = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(8, want / 8 * 8));
-        }
+    // everything the batch decides (stft_plan.h): launch geometry, jobs and chunk / tile tables, edge and mel jobs
+    StftLaunch l = plan_stft_launch(p->g, r, c->n_cu, p->wave_chunk, chans, n_chan);
+    if (l.err != TH_OK) return fail(l.err, "%s", l.err_text.c_str());
+    const StftGeom &g = l.g, &ge = l.ge;  // main launch; edge launch (generic kernel)
+    const bool phased = r.phase_mode != 0, sweep = l.sweep, all_in_wave = l.all_in_wave;
+    std::vector<ChanJob> &jobs = l.jobs, &edge = l.edge;
+    const uint64_t tiles = l.tiles, edge_tiles = l.edge_tiles, mel_tiles = l.mel_tiles;
+    // (selector 11: an earlier launch of this plan that dropped a chunk is found here when the stream has gone idle — no stall
+    // otherwise — and in th_calc_spec_host behind its synchronisation)
+    if (sweep && hipStreamQuery(c->stream) == hipSuccess) {
+        const int src = sweep_check(p);
+        if (src != TH_OK) return src;
     }
-    ge.frames_per_tile = 1;
-    // main jobs: the wave kernel takes the interior frames [fa, fb) of every channel (all windowed
-    // samples inside the signal); the generic kernel takes the boundary frames (reflect padding,
-    // stft.rs:50-95) — or every frame when the wave kernel does not cover this plan.
-    std::vector<ChanJob> jobs, edge;
-    std::vector<uint32_t> tile_start, edge_start;
-    uint64_t tiles = 0, edge_tiles = 0;
     // mel on the matrix cores: the wave kernel stores |X| rows (pitch amp_pitch) into plan-owned
     // scratch, mel_mfma_kernel contracts them with the filterbank into the caller's spec
     const uint32_t amp_pitch = (uint32_t)th_pitch_f32((size_t)p->mel_kblocks * 16);
-    std::vector<MelJob> mel_jobs;
-    std::vector<uint32_t> mel_start;
-    std::vector<uint64_t> amp_row0(n_chan, 0);
-    uint64_t mel_tiles = 0, amp_rows = 0;
-    auto add = [](std::vector<ChanJob> &v, std::vector<uint32_t> &st, uint64_t &n_tiles, const StftGeom &gg,
-                  const th_chan_desc &d, uint32_t T, uint32_t fb0, uint32_t fe0, uint32_t slot, bool wave_edge = false) {
-        if (fb0 >= fe0) return;
-        const uint32_t pitch = d.spec_pitch ? (uint32_t)d.spec_pitch : gg.height;
-        v.push_back(ChanJob{d.wav, d.spec, (uint32_t)d.n_samples, T, fb0, fe0, slot, pitch, wave_edge ? 1u : 0u, 0u});
-        st.push_back((uint32_t)n_tiles);
-        const uint32_t fpt = wave_edge ? 1u : gg.frames_per_tile;
-        n_tiles += (fe0 - fb0 + fpt - 1) / fpt;
-    };
-    for (size_t i = 0; i < n_chan; i++) {
-        const th_chan_desc &d = chans[i];
-        TH_REQUIRE(d.wav && d.spec, "channel %zu: NULL device pointer", i);
-        TH_REQUIRE(d.n_samples >= 1 && d.n_samples < (1ull << 31) - 2 * g.n_fft, "channel %zu: n_samples=%llu out of range",
-                   i, (unsigned long long)d.n_samples);
-        const size_t T = stft_n_frames(d.n_samples, g.win, g.hop);
-        TH_REQUIRE(d.n_frames == T, "channel %zu: n_frames=%llu but the framing gives %zu", i,
-                   (unsigned long long)d.n_frames, T);
-        TH_REQUIRE(d.spec_pitch == 0 || (d.spec_pitch >= g.height && d.spec_pitch < (1ull << 31)),
-                   "channel %zu: spec_pitch %llu < height %u", i, (unsigned long long)d.spec_pitch, g.height);
-        if (!wave) {
-            add(jobs, tile_start, tiles, g, d, (uint32_t)T, 0, (uint32_t)T, (uint32_t)i);
-        } else {
-            uint64_t fa, fb;
-            interior(d, T, fa, fb);
-            add(jobs, tile_start, tiles, g, d, (uint32_t)T, (uint32_t)fa, (uint32_t)fb, (uint32_t)i);
-            if (mel_mfma && fa < fb) {
-                amp_row0[i] = amp_rows;
-                amp_rows += T;
-                mel_jobs.push_back(MelJob{nullptr, d.spec, (uint32_t)fa, (uint32_t)fb,
-                                          (uint32_t)(d.spec_pitch ? d.spec_pitch : g.height), (uint32_t)i});
-                mel_start.push_back((uint32_t)mel_tiles);
-                mel_tiles += (fb - fa + MEL_TILE_FRAMES - 1) / MEL_TILE_FRAMES;
-            }
-            if (r.edges_in_wave && d.n_samples >= g.n_fft) {
-                add(jobs, tile_start, tiles, g, d, (uint32_t)T, 0, (uint32_t)fa, (uint32_t)i, true);
-                add(jobs, tile_start, tiles, g, d, (uint32_t)T, (uint32_t)fb, (uint32_t)T, (uint32_t)i, true);
-            } else {
-                add(edge, edge_start, edge_tiles, ge, d, (uint32_t)T, 0, (uint32_t)fa, (uint32_t)i);
-                add(edge, edge_start, edge_tiles, ge, d, (uint32_t)T, (uint32_t)fb, (uint32_t)T, (uint32_t)i);
-            }
-        }
-        TH_REQUIRE(tiles < (1ull << 31) && edge_tiles < (1ull << 31), "batch too large for one launch");
-    }
-    tile_start.push_back((uint32_t)tiles);
-    edge_start.push_back((uint32_t)edge_tiles);
-
-    mel_start.push_back((uint32_t)mel_tiles);
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     TH_HIP(hipSetDevice(c->device));
     int rc = TH_OK;
     bool range_done = false;
-    if (mel_mfma && amp_rows) {
-        const size_t need = (size_t)amp_rows * amp_pitch * sizeof(float);
+    if (mel_mfma && l.amp_rows) {
+        const size_t need = (size_t)l.amp_rows * amp_pitch * sizeof(float);
         if (need > p->amp_buf.cap || p->amp_zeroed < need) {
             TH_HIP(hipStreamSynchronize(c->stream));
             rc = p->amp_buf.ensure(need);
@@ -1079,32 +810,22 @@ static int calc_spec_batch_impl(th_plan *p, const th_chan_desc *chans, size_t n_
         float *amp = static_cast<float *>(p->amp_buf.dptr);
         size_t mj = 0;
         for (ChanJob &j : jobs) {  // interior jobs are in channel order, one per channel with interior frames
-            j.spec = amp + amp_row0[j.mm_index] * amp_pitch;
+            j.spec = amp + l.amp_row0[j.mm_index] * amp_pitch;
             j.spec_pitch = amp_pitch;
-            mel_jobs[mj++].amp = j.spec;
+            l.mel_jobs[mj++].amp = j.spec;
         }
-        rc = p->mel_jobs.upload(c->stream, mel_jobs.data(), mel_jobs.size() * sizeof(MelJob));
-        if (rc == TH_OK) rc = p->mel_tile_start.upload(c->stream, mel_start.data(), mel_start.size() * sizeof(uint32_t));
+        rc = p->mel_jobs.upload(c->stream, l.mel_jobs.data(), l.mel_jobs.size() * sizeof(MelJob));
+        if (rc == TH_OK) rc = p->mel_tile_start.upload(c->stream, l.mel_start.data(), l.mel_start.size() * sizeof(uint32_t));
         if (rc != TH_OK) return rc;
     }
     rc = p->jobs.upload(c->stream, jobs.data(), jobs.size() * sizeof(ChanJob));
-    if (wave) {
-        // the wave kernels look a chunk up directly: (job, first frame) per chunk (cursor_at, kernels_stft.hip)
-        std::vector<uint32_t> chunk_tab((size_t)tiles * 2);
-        for (size_t j = 0; j < jobs.size(); j++) {
-            const uint32_t fpt = jobs[j].edge ? 1u : g.frames_per_tile;
-            for (uint32_t t = tile_start[j]; t < tile_start[j + 1]; t++) {
-                chunk_tab[2 * (size_t)t] = (uint32_t)j;
-                chunk_tab[2 * (size_t)t + 1] = jobs[j].f_begin + (t - tile_start[j]) * fpt;
-            }
-        }
-        if (rc == TH_OK) rc = p->tile_start.upload(c->stream, chunk_tab.data(), chunk_tab.size() * sizeof(uint32_t));
-    } else if (rc == TH_OK) {
-        rc = p->tile_start.upload(c->stream, tile_start.data(), tile_start.size() * sizeof(uint32_t));
+    if (rc == TH_OK) {  // the wave kernels look a chunk up directly; the generic kernel finds its job from the jobs' first tiles
+        const std::vector<uint32_t> &tab = wave ? l.chunk_tab : l.tile_start;
+        rc = p->tile_start.upload(c->stream, tab.data(), tab.size() * sizeof(uint32_t));
     }
     if (rc == TH_OK && !edge.empty()) {
         rc = p->edge_jobs.upload(c->stream, edge.data(), edge.size() * sizeof(ChanJob));
-        if (rc == TH_OK) rc = p->edge_tile_start.upload(c->stream, edge_start.data(), edge_start.size() * sizeof(uint32_t));
+        if (rc == TH_OK) rc = p->edge_tile_start.upload(c->stream, l.edge_start.data(), l.edge_start.size() * sizeof(uint32_t));
     }
     if (rc != TH_OK) return rc;
     {   // n_fft >= 32768: the generic kernel's frame buffers live in global scratch (all frames of a plan without a fast
@@ -1117,54 +838,15 @@ static int calc_spec_batch_impl(th_plan *p, const th_chan_desc *chans, size_t n_
             if (rc != TH_OK) return rc;
         }
     }
-    // (min, max) slots: when every frame of every channel is in the wave launch, its last workgroup initialises and fills
-    // them (no init launch); otherwise initialise here and let every kernel add with atomics
-    const bool all_in_wave = wave && !mel_mfma && edge.empty() && tiles > 0;
+    // (min, max) slots: the wave launch's follow-up fills them when every frame was in it (StftLaunch::all_in_wave);
+    // otherwise initialise here and let every kernel add with atomics
     if (!all_in_wave) TH_HIP(launch_minmax_init(d_minmax, (uint32_t)n_chan, c->stream));
     // optional timing of the dominant kernel alone (th_plan_time_kernel): two events on the launch stream
     const bool timed = p->time_kernel && !p->ev_k0.empty();
     const size_t slot = (size_t)(p->timed_launches % th_plan::TIMER_SLOTS);
     if (timed) TH_HIP(hipEventRecord(p->ev_k0[slot], c->stream));
     if (wave) {
-        th::WaveOut wo;
-        wo.mode = r.out_mode();
-        wo.multi = r.main == StftRoute::Main::WaveMulti ? 1 : 0;
-        wo.packed = r.packed ? 1 : 0;
-        wo.sweep = sweep ? 1 : 0;
-        wo.long_plan = r.long_plan;
-        wo.subwave_twc = p->d_twc;
-        if (r.mel_fused != StftRoute::MelFused::None) wo.n_mel = g.n_mel;
-        switch (r.mel_fused) {
-            case StftRoute::MelFused::None: break;
-            case StftRoute::MelFused::Moment:
-            case StftRoute::MelFused::MomentLanes:  // moment form: the table stays in global memory (scalar + 16-byte lane loads)
-                wo.mel_moment = r.mel_fused == StftRoute::MelFused::Moment && g.log2_nc < 11 ? 1u : 0u;  // (n_fft 4096 and up: their only form)
-                wo.mel_tab = p->d_mel_mom;
-                wo.mel_groups = p->mel_mom_groups;
-                break;
-            case StftRoute::MelFused::Rows:  // (the per-mel table of the banded sums, kernels.h)
-                wo.mel_tab = p->d_mel_rows;
-                wo.mel_groups = p->mel_rows_groups;
-                wo.mel_words = p->mel_rows_groups * (uint32_t)(th::MEL_ROWS_W + 1) * 64u;
-                break;
-            case StftRoute::MelFused::Banded:
-            case StftRoute::MelFused::BandedPairs:  // banded sums (mel_slots = 0 tells the kernel)
-                wo.mel_tab = p->d_mel_bsum;
-                wo.mel_words = p->mel_bsum_words;
-                wo.mel_groups = p->mel_bsum_groups;
-                for (uint32_t gq = 0; gq < 8; gq++) {
-                    wo.band_off[gq] = p->mel_bsum_hdr[2 * gq];
-                    wo.band_n[gq] = p->mel_bsum_hdr[2 * gq + 1];
-                }
-                wo.mel_pair = r.mel_fused == StftRoute::MelFused::BandedPairs ? 1u : 0u;
-                break;
-            case StftRoute::MelFused::Pieces:
-                wo.mel_tab = p->d_mel_fuse;
-                wo.mel_words = p->mel_fuse_words;
-                wo.mel_slots = p->mel_fuse_slots;
-                wo.mel_groups = p->mel_fuse_groups;
-                break;
-        }
+        const th::WaveOut wo = wave_out(*p, g, sweep);
         // min / max: the wave kernel stores one pair per chunk and its last workgroup folds them into the channel slots
         float *chunk_mm = nullptr;
         if (d_minmax != nullptr && wo.mode != 1 && tiles) {
@@ -1173,15 +855,10 @@ static int calc_spec_batch_impl(th_plan *p, const th_chan_desc *chans, size_t n_
             chunk_mm = static_cast<float *>(p->chunk_mm.dptr);
         }
         uint32_t n_post = 0;
-        if (chunk_mm) {  // per-channel tile ranges for wave_post_kernel: a channel's jobs (interior, head, tail) are consecutive
-            std::vector<th::WavePostJob> pj;
-            for (size_t j = 0; j < jobs.size(); j++) {
-                if (!pj.empty() && pj.back().mm_index == jobs[j].mm_index) pj.back().t1 = tile_start[j + 1];
-                else pj.push_back(th::WavePostJob{tile_start[j], tile_start[j + 1], jobs[j].mm_index, 0u});
-            }
-            rc = p->post_jobs.upload(c->stream, pj.data(), pj.size() * sizeof(th::WavePostJob));
+        if (chunk_mm) {  // per-channel tile ranges for wave_post_kernel
+            rc = p->post_jobs.upload(c->stream, l.post.data(), l.post.size() * sizeof(th::WavePostJob));
             if (rc != TH_OK) return rc;
-            n_post = (uint32_t)pj.size();
+            n_post = (uint32_t)l.post.size();
         }
         // The chunk queue head is rewound by wave_post_kernel right behind the wave kernel.  Should anything between the
         // two launches fail (the event record, the post launch itself), queue_dirty stays set and the next launch zeroes
@@ -1199,16 +876,16 @@ static int calc_spec_batch_impl(th_plan *p, const th_chan_desc *chans, size_t n_
         p->queue_dirty = false;
         if (r.mel_second == StftRoute::MelSecond::Rows)
             TH_HIP(launch_mel_rows((const MelJob *)p->mel_jobs.dptr, (const uint32_t *)p->mel_tile_start.dptr,
-                                   (uint32_t)mel_jobs.size(), (uint32_t)mel_tiles, amp_pitch, p->d_mel_rows, p->mel_rows_groups,
+                                   (uint32_t)l.mel_jobs.size(), (uint32_t)mel_tiles, amp_pitch, p->d_mel_rows, p->mel_rows_groups,
                                    g.n_mel, d_minmax, c->n_cu, c->stream));
         else if (r.mel_second == StftRoute::MelSecond::BandRows)
             TH_HIP(launch_mel_band_rows((const MelJob *)p->mel_jobs.dptr, (const uint32_t *)p->mel_tile_start.dptr,
-                                        (uint32_t)mel_jobs.size(), (uint32_t)mel_tiles, amp_pitch, g.n_freq, p->d_mel_bsum,
+                                        (uint32_t)l.mel_jobs.size(), (uint32_t)mel_tiles, amp_pitch, g.n_freq, p->d_mel_bsum,
                                         p->mel_bsum_words, p->mel_bsum_groups, p->mel_bsum_hdr, g.n_mel, d_minmax, c->n_cu,
                                         c->stream));
         else if (r.mel_second == StftRoute::MelSecond::Mfma)
             TH_HIP(launch_mel_mfma((const MelJob *)p->mel_jobs.dptr, (const uint32_t *)p->mel_tile_start.dptr,
-                                   (uint32_t)mel_jobs.size(), (uint32_t)mel_tiles, amp_pitch, p->d_mel_bt, p->d_mel_band,
+                                   (uint32_t)l.mel_jobs.size(), (uint32_t)mel_tiles, amp_pitch, p->d_mel_bt, p->d_mel_band,
                                    p->d_mel_slice, p->mel_slices, p->mel_zero_block, g.n_mel, d_minmax, c->stream));
         if (!edge.empty())  // boundary frames the wave kernel did not take: generic kernel (reflect padding; mel included)
             TH_HIP(launch_stft_generic(ge, (const ChanJob *)p->edge_jobs.dptr, (const uint32_t *)p->edge_tile_start.dptr,
@@ -1338,20 +1015,15 @@ TH_API int th_calc_spec_host(th_plan *p, const float *wav, size_t n_samples, flo
     if ((size_t)T * g.height > cap) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu floats", (size_t)T * g.height);
     th_ctx *c = p->ctx;
     TH_HIP(hipSetDevice(c->device));
-    float *d_wav = nullptr, *d_spec = nullptr, *d_mm = nullptr;
+    DeviceBuf<float> d_wav, d_spec, d_mm;
     int rc = TH_OK;
-    auto cleanup = [&]() {
-        if (d_wav) (void)hipFree(d_wav);
-        if (d_spec) (void)hipFree(d_spec);
-        if (d_mm) (void)hipFree(d_mm);
-    };
     auto hipok = [&](hipError_t e, const char *what) {
         if (e != hipSuccess && rc == TH_OK) rc = fail(e == hipErrorOutOfMemory ? TH_ERR_OOM : TH_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
         return e == hipSuccess;
     };
-    if (hipok(hipMalloc((void **)&d_wav, n_samples * sizeof(float)), "hipMalloc wav") &&
-        hipok(hipMalloc((void **)&d_spec, std::max<size_t>(1, T * g.height) * sizeof(float)), "hipMalloc spec") &&
-        hipok(hipMalloc((void **)&d_mm, 2 * sizeof(float)), "hipMalloc minmax") &&
+    if (hipok(d_wav.alloc(n_samples * sizeof(float)), "hipMalloc wav") &&
+        hipok(d_spec.alloc(std::max<size_t>(1, T * g.height) * sizeof(float)), "hipMalloc spec") &&
+        hipok(d_mm.alloc(2 * sizeof(float)), "hipMalloc minmax") &&
         hipok(hipMemcpy(d_wav, wav, n_samples * sizeof(float), hipMemcpyHostToDevice), "upload")) {
         th_chan_desc d{d_wav, d_spec, n_samples, T, 0};
         rc = th_calc_spec_batch_dev(p, &d, 1, d_mm);
@@ -1365,7 +1037,6 @@ TH_API int th_calc_spec_host(th_plan *p, const float *wav, size_t n_samples, flo
             }
         }
     }
-    cleanup();
     return rc;
     TH_CATCH
 }
@@ -1908,10 +1579,7 @@ TH_API int th_gated_loudness(const double *block_energies, size_t n, double *luf
 namespace th {
 
 LoudnessBatch::~LoudnessBatch() {
-    if (d_own) {
-        (void)hipSetDevice(ctx->device);
-        (void)hipFree(d_own);
-    }
+    if (d_own) (void)hipSetDevice(ctx->device);  // (d_own goes behind this body)
 }
 
 int loudness_enqueue(th_ctx *c, const th_audio_desc *descs, size_t n, bool own_memory, bool allow_bad_rate, LoudnessBatch *b) {
@@ -1983,8 +1651,8 @@ int loudness_enqueue(th_ctx *c, const th_audio_desc *descs, size_t n, bool own_m
     TH_HIP(hipSetDevice(c->device));
     unsigned char *dm;
     if (own_memory) {
-        TH_HIP(hipMalloc(&b->d_own, total));
-        dm = static_cast<unsigned char *>(b->d_own);
+        TH_HIP(b->d_own.alloc(total));
+        dm = b->d_own;
     } else {
         TH_HIP(hipStreamSynchronize(c->stream));  // (the last call's launches may still read the tables)
         const int rc = c->loud_mem.ensure(total);

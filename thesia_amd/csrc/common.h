@@ -45,6 +45,13 @@ inline int fail(int code, const char *fmt, ...) {
 #define TH_REQUIRE_ALIGNED(ptr, bytes, ...) \
     TH_REQUIRE((reinterpret_cast<uintptr_t>(ptr) & (uintptr_t)((bytes) - 1)) == 0, __VA_ARGS__)
 
+// a call that returns a TH_* status: pass a failure on (the callee has set the message)
+#define TH_CHECK(call)                \
+    do {                              \
+        const int rc_ = (call);       \
+        if (rc_ != TH_OK) return rc_; \
+    } while (0)
+
 #define TH_HIP(call)                                                    \
     do {                                                                  \
         hipError_t e_ = (call);                                           \

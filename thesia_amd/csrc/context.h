@@ -8,8 +8,48 @@
 
 #include "common.h"
 #include "stft_core.h"
+#include "stft_plan.h"  // StftRoute
 
 namespace th {
+
+// One hipMalloc allocation, freed with its owner (move-only).  The device it was allocated on must be current when it goes:
+// th_plan_destroy / th_ctx_destroy set it before they delete, th_plan_create before its first allocation.
+template <class T>
+struct DeviceBuf {
+    T *ptr = nullptr;
+    DeviceBuf() = default;
+    DeviceBuf(const DeviceBuf &) = delete;
+    DeviceBuf &operator=(const DeviceBuf &) = delete;
+    DeviceBuf(DeviceBuf &&o) noexcept : ptr(o.ptr) { o.ptr = nullptr; }
+    DeviceBuf &operator=(DeviceBuf &&o) noexcept {
+        if (this != &o) {
+            reset();
+            ptr = o.ptr;
+            o.ptr = nullptr;
+        }
+        return *this;
+    }
+    ~DeviceBuf() { reset(); }
+    void reset() {
+        if (ptr) (void)hipFree(ptr);
+        ptr = nullptr;
+    }
+    T *get() const { return ptr; }
+    operator T *() const { return ptr; }
+    hipError_t alloc(size_t bytes) {
+        reset();
+        return hipMalloc((void **)&ptr, bytes);
+    }
+    int fill(const void *h, size_t bytes) {  // allocate and fill from host
+        reset();
+        void **d = (void **)&ptr;
+        TH_HIP(hipMalloc(d, bytes));
+        TH_HIP(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
+        return TH_OK;
+    }
+    template <class V>
+    int fill(const std::vector<V> &h) { return fill(h.data(), h.size() * sizeof(V)); }
+};
 
 // Small device buffer holding a descriptor table; remembers the last uploaded bytes so that
 // re-sending an identical table (bench loops, repeated tile requests) costs nothing.
@@ -19,53 +59,11 @@ struct DeviceTable {
     std::vector<unsigned char> last;
     int ensure(size_t bytes);
     int upload(hipStream_t s, const void *src, size_t bytes);
-    void release();
-};
-
-// th_plan_set_kernel's selectors (bits 0-7), described in include/thesia_amd_testing.h.  Product builds refuse the A/B-only
-// ones there (9, 11, 14 at n_fft 32768 / 65536, 15 at n_fft 8192, and wave counts other than a size's own).
-enum StftSelector : int {
-    SEL_AUTO = 0,
-    SEL_GENERIC = 1,
-    SEL_WAVE = 2,              // every selector from here on asks for a wave kernel
-    SEL_MEL_AMP = 3,           // amplitude rows + a second mel kernel
-    SEL_NO_PHASE = 4,
-    SEL_PHASE_FUSED = 5,
-    SEL_MULTI_1024 = 6,
-    SEL_MEL_MFMA = 7,          // as 3, the matrix-core kernel also where 3 runs mel_rows / mel_band_rows
-    SEL_MEL_PIECES = 8,
-    SEL_PACKED = 9,
-    SEL_RESERVED = 10,         // as 2
-    SEL_SWEEP = 11,
-    SEL_MEL_TWO_KERNELS = 12,
-    SEL_MEL_ONE_FRAME = 13,
-    SEL_BLOCK = 14,
-    SEL_SUBWAVE = 15,
-};
-
-// Which kernels a plan launches, and how: everything about a th_calc_spec_batch_dev launch that the batch does not change.
-// resolve_route (api.hip) fills it from the plan's geometry, its tables and its kernel selector — at th_plan_create and at every
-// th_plan_set_kernel — and nothing else reads the selector.
-struct StftRoute {
-    enum class Main : uint8_t { Generic, Bluestein, Wave, WaveMulti, Block, Subwave };
-    // the mel filterbank in the main kernel's epilogue (mel_fuse.h): moment form with its table in global memory, the same as
-    // per-lane constants of the block kernel, mel_rows_kernel's table (n_fft 512), banded sums one frame or two at a time, pieces / gather
-    enum class MelFused : uint8_t { None, Moment, MomentLanes, Rows, Banded, BandedPairs, Pieces };
-    enum class MelSecond : uint8_t { None, Rows, BandRows, Mfma };  // the mel kernel behind amplitude rows
-    Main main = Main::Generic;
-    MelFused mel_fused = MelFused::None;
-    MelSecond mel_second = MelSecond::None;
-    bool no_wave_kernel = false;   // a selector >= 2 asked for a wave kernel this plan has none of: th_calc_spec_batch_dev fails
-    int phase_mode = 0;            // StftGeom::phased of the launch (grid-aligned frame loop; window table d_wtab_phased when != 0)
-    int waves = 0;                 // waves per workgroup of the wave kernels
-    uint32_t tail_guard = 0;       // stft_wave_multi_tail_guard, or 0
-    bool edges_in_wave = false;    // boundary frames of channels of at least n_fft samples run inside the wave launch
-    int long_plan = 1;             // WaveOut::long_plan: 1 stft_block_kernel, 2 stft_subwave_kernel (read at n_fft 8192 and above)
-    bool sweep = false;            // selector 11's sweep schedule exists for this plan (the launch adds: the batch is large enough)
-    bool packed = false;           // selector 9: WaveOut::packed
-    char name[48] = "";            // th_plan_kernel_name
-    bool wave() const { return main != Main::Generic && main != Main::Bluestein; }
-    int out_mode() const { return mel_second != MelSecond::None ? 1 : mel_fused != MelFused::None ? 2 : 0; }  // WaveOut::mode
+    void release();  // (for callers that free early; the destructor does the same)
+    DeviceTable() = default;
+    DeviceTable(const DeviceTable &) = delete;
+    DeviceTable &operator=(const DeviceTable &) = delete;
+    ~DeviceTable() { release(); }
 };
 
 }  // namespace th
@@ -84,26 +82,10 @@ struct th_ctx {
     // the descriptor batches the img / raster tables were built from (identical batch -> tables reused as they are)
     std::vector<unsigned char> img_descs_key, raster_descs_key, fused_key;
     uint32_t img_tiles_key = 0, raster_blocks_key = 0, fused_blocks_key = 0;
-    void release_scratch() {
-        img_descs_key.clear();
-        raster_descs_key.clear();
-        fused_key.clear();
-        fused_jobs.release();
-        fused_start.release();
-        fused_ptrs.release();
-        img_jobs.release();
-        img_start.release();
-        raster_jobs.release();
-        raster_start.release();
-        wave_jobs.release();
-        wave_start.release();
-        colormap.release();
-        tile_out.release();
-        lod_tabs.release();
-        lod_tmp.release();
-        pyr_jobs.release();
-        pyr_sums.release();
-        loud_mem.release();
+    ~th_ctx() {  // (th_ctx_destroy: device current, stream idle; the scratch tables above go after this body)
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (own_stream && stream) (void)hipStreamDestroy(stream);
     }
 };
 
@@ -120,24 +102,24 @@ struct th_plan {
     uint64_t timed_launches = 0;
     std::vector<hipEvent_t> ev_k0, ev_k1;
     th::StftGeom g{};
-    float *d_window = nullptr;
-    th::cf32 *d_tw = nullptr;
+    th::DeviceBuf<float> d_window;
+    th::DeviceBuf<th::cf32> d_tw;
     // Bluestein plans (an odd factor of n_fft above 63; stft_bluestein_kernel): complex-double tables, NULL otherwise
-    double *d_bs_chirp = nullptr, *d_bs_bhat = nullptr, *d_bs_twm = nullptr, *d_bs_tws = nullptr;
+    th::DeviceBuf<double> d_bs_chirp, d_bs_bhat, d_bs_twm, d_bs_tws;
     bool bluestein() const { return d_bs_chirp != nullptr; }
-    uint32_t *d_queue_head = nullptr;  // wave kernel: chunk queue head (rewound by wave_post_kernel after every launch)
+    th::DeviceBuf<uint32_t> d_queue_head;  // wave kernel: chunk queue head (rewound by wave_post_kernel after every launch)
     bool queue_dirty = false;          // a wave launch went out whose rewind did not: the next launch zeroes the head first
-    th::cf32 *d_wtab = nullptr;  // wave kernel: 0.5 * zero-padded window as (even, odd) pairs
-    th::cf32 *d_wtab_phased = nullptr;  // phased mode: 48 zero pairs + the table with the window at offset 0 (NULL: not applicable)
-    float *d_mel_fb = nullptr;
-    uint32_t *d_mel_lo = nullptr, *d_mel_hi = nullptr;
+    th::DeviceBuf<th::cf32> d_wtab;  // wave kernel: 0.5 * zero-padded window as (even, odd) pairs
+    th::DeviceBuf<th::cf32> d_wtab_phased;  // phased mode: 48 zero pairs + the table with the window at offset 0 (NULL: not applicable)
+    th::DeviceBuf<float> d_mel_fb;
+    th::DeviceBuf<uint32_t> d_mel_lo, d_mel_hi;
     std::vector<float> h_mel_fb;
     // MFMA mel path: filterbank packed per (N tile of 16 mels, K block of 16 bins) in operand order (256 floats per
     // block, band blocks only, + one all-zero block), per-tile band {klo, khi, first block}
-    float *d_mel_bt = nullptr;
-    uint32_t *d_mel_band = nullptr, *d_mel_slice = nullptr;  // + slices of the tile range with ~equal K-group counts
+    th::DeviceBuf<float> d_mel_bt;
+    th::DeviceBuf<uint32_t> d_mel_band, d_mel_slice;  // + slices of the tile range with ~equal K-group counts
     uint32_t mel_kblocks = 0, mel_ntiles = 0, mel_zero_block = 0, mel_slices = 0;
-    uint32_t *d_mel_rows = nullptr;  // short rows under narrow filters: the per-mel table of mel_rows_kernel (kernels.h)
+    th::DeviceBuf<uint32_t> d_mel_rows;  // short rows under narrow filters: the per-mel table of mel_rows_kernel (kernels.h)
     uint32_t mel_rows_groups = 0;
     th::DeviceTable amp_buf, mel_jobs, mel_tile_start;  // amplitude scratch + job tables of mel_mfma_kernel
     size_t amp_zeroed = 0;                               // bytes of amp_buf known to be zero-initialised
@@ -145,21 +127,25 @@ struct th_plan {
     th::DeviceTable gen_scratch;                         // n_fft >= 32768: frame buffers of the generic kernel (global scratch)
     th::DeviceTable post_jobs;                           // per-channel tile ranges for wave_post_kernel
     // fused mel epilogue: device copy of the mel_fuse.h word table
-    uint32_t *d_mel_fuse = nullptr;
+    th::DeviceBuf<uint32_t> d_mel_fuse;
     uint32_t mel_fuse_words = 0, mel_fuse_slots = 0, mel_fuse_groups = 0;
     // the same epilogue as banded sums, lane = mel (build_mel_band): the default where its table fits; selector 8 keeps the pieces
-    uint32_t *d_mel_bsum = nullptr;
+    th::DeviceBuf<uint32_t> d_mel_bsum;
     uint32_t mel_bsum_words = 0, mel_bsum_groups = 0, mel_bsum_hdr[16] = {};  // (header: offset and taps per group)
-    th::cf32 *d_twc = nullptr;  // n_fft 32768: the combining pass's per-thread constants (kernels_stft_long.hip)
+    th::DeviceBuf<th::cf32> d_twc;  // n_fft 32768: the combining pass's per-thread constants (kernels_stft_long.hip)
     uint32_t mel_bsum_reach = 0;  // one past the highest amplitude index the banded sums read (MelBandHost::reach)
     // n_fft 4096 mel plans (round 6): the moment form of the filterbank in the FFT kernel's epilogue (build_mel_moments, mel_fuse.h)
-    uint32_t *d_mel_mom = nullptr;
+    th::DeviceBuf<uint32_t> d_mel_mom;
     uint32_t mel_mom_groups = 0, mel_mom_taps = 0;
     double mel_mom_max_dev = 0.0, mel_mom_max_amp = 0.0;
     th::DeviceTable jobs, tile_start;            // main launch: jobs + first chunk of every job (generic kernel) or the
                                                  // per-chunk (job, first frame) table (wave kernels)
     th::DeviceTable edge_jobs, edge_tile_start;  // boundary frames handed to the generic kernel
     th::StftRoute route;                         // resolve_route (api.hip)
+    ~th_plan() {  // (th_plan_destroy, or th_plan_create giving up: the context's device is current)
+        for (hipEvent_t e : ev_k0) (void)hipEventDestroy(e);
+        for (hipEvent_t e : ev_k1) (void)hipEventDestroy(e);
+    }
 };
 
 namespace th {
@@ -168,7 +154,7 @@ namespace th {
 // the batch's own) and enqueues the passes; loudness_collect reads the results back once the stream has got that far.
 struct LoudnessBatch {
     th_ctx *ctx = nullptr;
-    void *d_own = nullptr;     // the batch's own device memory (NULL: the context's loud_mem)
+    DeviceBuf<unsigned char> d_own;  // the batch's own device memory (NULL: the context's loud_mem)
     double *d_sums = nullptr;  // n_ch sums of squares, then n_ch peaks (u32), then the block energies of every track
     size_t n_ch = 0, n_blocks = 0;
     std::vector<size_t> ch0, blk0;  // per track: first channel, first block

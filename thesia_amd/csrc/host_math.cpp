@@ -2,8 +2,12 @@
 // (paths relative to the reference checkout).
 #include "host_math.h"
 
+#include "stft_plan.h"
+
 #include <algorithm>
 #include <cmath>
+#include <cstdarg>
+#include <cstdio>
 #include <cstring>
 #include <limits>
 #include <map>
@@ -528,5 +532,327 @@ const LoudnessRate &loudness_rate(uint32_t sr) {
     cache[sr] = std::move(R);
     return ref;
 }
+
+// ------------------------------------------------------------------------------------------ plan tables (stft_plan.h)
+StftGeom stft_geom(size_t win, size_t hop, size_t n_fft) {
+    size_t odd_part = n_fft;
+    while (odd_part > 1 && odd_part % 2 == 0) odd_part /= 2;
+    StftGeom g{};
+    g.hop = (uint32_t)hop;
+    g.win = (uint32_t)win;
+    g.n_fft = (uint32_t)n_fft;
+    g.pad_left = (uint32_t)((n_fft - win) / 2);
+    g.nc = (uint32_t)(n_fft / 2);
+    g.odd_m1 = (uint32_t)odd_part - 1u;
+    g.log2_nc = ilog2(g.nc / (uint32_t)odd_part);  // log2 of the power-of-two part of nc
+    g.n_freq = (uint32_t)(n_fft / 2 + 1);
+    g.n_mel = 0;
+    g.height = g.n_freq;
+    g.frames_per_tile = 8;  // generic kernel; the wave kernel's tile is set at launch
+    return g;
+}
+
+std::vector<cf32> build_twiddles(size_t n_fft) {
+    std::vector<cf32> tw(n_fft);
+    for (size_t i = 0; i < n_fft; i++) {
+        const double a = -2.0 * M_PI * (double)i / (double)n_fft;
+        tw[i].re = (float)std::cos(a);
+        tw[i].im = (float)std::sin(a);
+    }
+    return tw;
+}
+
+WaveWindowHost build_wave_window(const float *w, size_t win, size_t n_fft, int phased_mode) {
+    WaveWindowHost out;
+    const float half = 0.5f * WAVE_PRESCALE;
+    const size_t pad_left = (n_fft - win) / 2;
+    auto at = [](std::vector<cf32> &v, size_t i) -> float & { return (i & 1) ? v[i / 2].im : v[i / 2].re; };  // float i of the pairs
+    out.wtab.assign(n_fft / 2, cf32{0.f, 0.f});
+    for (size_t i = 0; i < win; i++) at(out.wtab, pad_left + i) = half * w[i];
+    if (phased_mode == 1) {
+        out.phased.assign((96 + n_fft) / 2, cf32{0.f, 0.f});
+        for (size_t i = 0; i < win; i++) at(out.phased, 96 + i) = half * w[i];
+    } else if (phased_mode == 2 || phased_mode == 3) {
+        std::vector<float> t0(n_fft + 2, 0.f);
+        for (size_t i = 0; i < win; i++) t0[i] = half * w[i];
+        out.phased.assign(128 + n_fft, cf32{0.f, 0.f});
+        for (size_t i = 0; i < n_fft; i++) {
+            at(out.phased, 128 + i) = t0[i];                    // even table: pairs (t0[2n], t0[2n+1])
+            at(out.phased, 128 + n_fft + 128 + i) = t0[i + 1];  // odd table:  pairs (t0[2n+1], t0[2n+2])
+        }
+    }
+    return out;
+}
+
+MelRangeHost build_mel_ranges(const float *fb, uint32_t n_freq, uint32_t n_mel) {
+    MelRangeHost out;
+    out.lo.assign(n_mel, 0);
+    out.hi.assign(n_mel, 0);
+    for (size_t m = 0; m < n_mel; m++) {
+        uint32_t a = n_freq, b = 0;
+        for (uint32_t f = 0; f < n_freq; f++)
+            if (fb[(size_t)f * n_mel + m] != 0.f) {
+                a = std::min(a, f);
+                b = f + 1;
+            }
+        out.lo[m] = b ? a : 0;
+        out.hi[m] = b;
+    }
+    return out;
+}
+
+MelMfmaHost build_mel_mfma(const float *fb, const MelRangeHost &rg, uint32_t n_freq, uint32_t n_mel) {
+    MelMfmaHost out;
+    const uint32_t nt = (n_mel + 15) / 16, kb_n = (n_freq + 15) / 16;
+    std::vector<uint32_t> &band = out.band;
+    std::vector<float> &bt = out.bt;
+    band.assign(3 * (size_t)nt, 0);
+    auto fbv = [&](uint32_t f, size_t m) { return (f < n_freq && m < n_mel) ? fb[(size_t)f * n_mel + m] : 0.f; };
+    for (uint32_t j = 0; j < nt; j++) {
+        // the tile's K band from the per-mel non-zero ranges [lo, hi) (the dense scan over every (bin, mel) of
+        // every tile was ~90 M filterbank reads at the 5571-mel default of n_fft 32768)
+        uint32_t klo = kb_n, khi = 0;
+        for (size_t m = 16 * (size_t)j; m < std::min<size_t>(16 * (size_t)j + 16, n_mel); m++)
+            if (rg.hi[m]) {
+                klo = std::min(klo, rg.lo[m] / 16);
+                khi = std::max(khi, (rg.hi[m] + 15) / 16);
+            }
+        if (!khi) klo = 0;
+        band[3 * j] = klo;
+        band[3 * j + 1] = khi;
+        band[3 * j + 2] = (uint32_t)(bt.size() / 256);
+        for (uint32_t kb = klo; kb < khi; kb++)
+            for (uint32_t lane = 0; lane < 64; lane++)
+                for (uint32_t st = 0; st < 4; st++) bt.push_back(fbv(16 * kb + 4 * (lane >> 4) + st, 16 * (size_t)j + (lane & 15u)));
+    }
+    out.zero_block = (uint32_t)(bt.size() / 256);
+    bt.insert(bt.end(), 256, 0.f);
+    out.kblocks = kb_n;
+    out.ntiles = nt;
+    std::vector<uint32_t> &slice = out.slice;
+    slice.assign(1, 0u);
+    uint64_t total = 0;
+    for (uint32_t j = 0; j < nt; j++) total += (band[3 * j + 1] - band[3 * j] + 3) / 4 + 1;  // + epilogue
+    const uint32_t want = std::min<uint32_t>(TH_MEL_SLICES, nt);
+    uint64_t acc_g = 0;
+    for (uint32_t j = 0; j < nt; j++) {
+        acc_g += (band[3 * j + 1] - band[3 * j] + 3) / 4 + 1;
+        if (slice.size() < want && acc_g * want >= total * slice.size() && j + 1 < nt) slice.push_back(j + 1);
+    }
+    slice.push_back(nt);
+    out.n_slices = (uint32_t)slice.size() - 1;
+    return out;
+}
+
+MelRowsHost build_mel_rows(const float *fb, const MelRangeHost &rg, uint32_t n_freq, uint32_t n_mel) {
+    MelRowsHost out;
+    constexpr uint32_t W = MEL_ROWS_W;
+    uint32_t widest = 0;
+    for (size_t m = 0; m < n_mel; m++) widest = std::max(widest, rg.hi[m] - rg.lo[m]);
+    const uint32_t ng = (n_mel + 63) / 64, kb_n = (n_freq + 15) / 16;
+    if (!(kb_n <= (uint32_t)MEL_ROWS_NKB && n_freq - 1 + W <= 16 * MEL_ROWS_NKB + 4 &&  // (reads stay in the LDS row)
+          widest <= W && ng <= (uint32_t)MEL_ROWS_MAX_GROUPS))
+        return out;
+    out.words.assign((size_t)ng * (W + 1) * 64, 0u);
+    for (size_t m = 0; m < n_mel; m++) {
+        const size_t at = (m / 64) * (W + 1) * 64 + m % 64;
+        out.words[at] = rg.lo[m];
+        for (uint32_t t = 0; t < W && rg.lo[m] + t < rg.hi[m]; t++)
+            std::memcpy(&out.words[at + (1 + t) * 64], &fb[(size_t)(rg.lo[m] + t) * n_mel + m], 4);
+    }
+    out.n_groups = ng;
+    out.ok = true;
+    return out;
+}
+
+// ------------------------------------------------------------------------------------------ launch plan (stft_plan.h)
+static void launch_fail(StftLaunch &l, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+static void launch_fail(StftLaunch &l, const char *fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    l.err = TH_ERR_INVALID_ARG;
+    l.err_text = buf;
+}
+#define TH_LAUNCH_REQUIRE(cond, ...)      \
+    do {                                  \
+        if (!(cond)) {                    \
+            launch_fail(l, __VA_ARGS__);  \
+            return l;                     \
+        }                                 \
+    } while (0)
+
+StftLaunch plan_stft_launch(const StftGeom &pg, const StftRoute &r, uint32_t n_cu, int wave_chunk, const th_chan_desc *chans, size_t n_chan) {
+    StftLaunch l;
+    StftGeom &g = l.g, &ge = l.ge;
+    g = ge = pg;
+    g.phased = (uint32_t)r.phase_mode;
+    const bool wave = r.wave(), mel_second = r.mel_second != StftRoute::MelSecond::None, phased = r.phase_mode != 0;
+    // wave kernel: chunk of consecutive frames one wave walks (the first frame of a chunk loads
+    // n_fft samples, the rest only hop new ones).  32 amortises that well on large batches; small
+    // batches (one track) get shorter chunks so that every wave of the chip has work.
+    // interior frames [fa, fb) of a channel: the frame's whole n_fft-sample span [e0, e0 + n_fft), e0 = f*hop - win/2 -
+    // pad_left, lies inside the channel (the wave kernel loads it unconditionally); the others are boundary frames
+    // phased mode: chunks must start on frames that sit exactly on the 128-sample grid (every fourth)
+    auto interior = [&g, &r, phased](const th_chan_desc &d, uint64_t T, uint64_t &fa, uint64_t &fb) {
+        if (phased) {
+            const int64_t N = (int64_t)d.n_samples, half = (int64_t)(g.win / 2);
+            auto delta = [&](int64_t f) { return (((f * (int64_t)g.hop - half) % 128) + 128) % 128; };
+            auto start = [&](int64_t f) { return f * (int64_t)g.hop - half - delta(f); };
+            int64_t a = 0, b = (int64_t)T;
+            while (a < b && (start(a) < 0 || (r.phase_mode == 1 && delta(a) != 0))) a++;  // phased chunks start on the grid
+            while (b > a && start(b - 1) + (int64_t)g.n_fft > N) b--;
+            fa = (uint64_t)a;
+            fb = (uint64_t)b;
+            return;
+        }
+        const uint64_t lead = g.win / 2 + g.pad_left, N = d.n_samples > r.tail_guard ? d.n_samples - r.tail_guard : 0;
+        fa = (lead + g.hop - 1) / g.hop;                                  // first f with e0 >= 0
+        fb = N + lead >= g.n_fft ? (N + lead - g.n_fft) / g.hop + 1 : 0;  // one past the last f with e0 + n_fft <= N
+        fa = std::min<uint64_t>(fa, T);
+        fb = std::min<uint64_t>(std::max(fb, fa), T);
+    };
+    if (wave) {
+        uint64_t total = 0;
+        for (size_t i = 0; i < n_chan; i++) total += chans[i].n_frames;
+        // chunks of `len` frames over the batch's interior frames (+ with_edges: one per boundary frame the wave launch takes)
+        auto n_chunks = [&](uint64_t len, bool with_edges) {
+            uint64_t n = 0;
+            for (size_t i = 0; i < n_chan; i++) {
+                uint64_t fa, fb;
+                interior(chans[i], chans[i].n_frames, fa, fb);
+                n += (fb - fa + len - 1) / len;
+                if (with_edges && chans[i].n_samples >= g.n_fft) n += chans[i].n_frames - (fb - fa);
+            }
+            return n;
+        };
+        // The launch ends when the last chunk does and every slot (wave, or workgroup) walks its chunks one after the other, so
+        // what counts is rounds x chunk length: the length around `want` (at least `lo`) whose chunk count fills the last round best
+        auto best_chunk = [&](uint64_t want, uint64_t lo, uint64_t slots) {
+            uint64_t best = want, best_cost = ~0ull;
+            for (uint64_t cand = std::max<uint64_t>(lo, want - want / 4); cand <= want + want / 4; cand++) {
+                const uint64_t cost = (n_chunks(cand, false) + slots - 1) / slots * cand;  // frames a slot walks through, at worst
+                if (cost < best_cost || (cost == best_cost && cand > best)) {
+                    best_cost = cost;
+                    best = cand;
+                }
+            }
+            return best;
+        };
+        const uint64_t n_waves = (uint64_t)n_cu * (uint64_t)r.waves;
+        uint64_t chunk;
+        if (r.block_plan && g.log2_nc <= 14) {
+            // Workgroup-per-frame plans (n_fft 8192 .. 32768): what runs side by side is one workgroup per CU (two at n_fft 8192),
+            // not twelve waves, and a chunk start costs a workgroup launch + its set-up (30-50 us: tables / constants, the first
+            // frame) or, in the persistent subwave kernel, a full reload of the resident samples.  About two chunks per slot, the
+            // length that fills the last round best (round 5, profiles/r05_ab_block_chunks.txt: n_fft 16384 15 -> 44 frames 0.96 ->
+            // 0.84-0.92 ms, 32768 8 -> 43 1.26 -> 1.21, 8192 30 -> 60-90 0.70 -> 0.64-0.69; n_fft 65536 measures 5 % slower with
+            // longer chunks and keeps the rule below)
+            const uint64_t slots = (uint64_t)n_cu * (g.log2_nc == 12 ? 2u : 1u);
+            // (a single track: one frame per chunk, every CU busy)
+            chunk = best_chunk(std::min<uint64_t>(128, std::max<uint64_t>(1, total / (slots * 2))), 1, slots);
+        } else if (total <= n_waves * 32) {
+            // small batch (one track ...): one chunk per wave, all of them assigned statically — the kernel then never
+            // touches the queue (3072 waves finding it empty is 25 us of serialised atomics on a 20 us job)
+            chunk = std::max<uint64_t>(1, (total + n_waves - 1) / n_waves);
+            while (chunk < 32 && n_chunks(chunk, r.edges_in_wave) > n_waves) chunk++;
+        } else {
+            // around total / (waves x TH_CHUNKS_PER_WAVE), 12 to 40 frames.  Bench workload: 29 frames would be 12416 chunks = 4.04
+            // rounds of 3072 waves, i.e. a fifth round for 128 stragglers: 0.520 ms; 30-32 frames 0.507 (r02_chunks).
+            chunk = best_chunk(std::min<uint64_t>(32, std::max<uint64_t>(12, total / (n_waves * TH_CHUNKS_PER_WAVE))), 12, n_waves);
+        }
+        g.frames_per_tile = wave_chunk > 0 ? (uint32_t)wave_chunk : (uint32_t)chunk;
+        // The sweep schedule (kernels_stft.hip: 4-frame chunks dealt out in order, next chunk prefetched) — round 4, selector 11
+        // only: its memory skeleton streams 3-10 % faster (scripts/ubench/stft_skeleton.hip mode 8), the kernel does not: inside
+        // bench.py's step 0.492 / 0.497 / 0.496 ms against 0.495 / 0.495 / 0.494 for the default schedule on one box, alternating,
+        // and 8 % slower alone with 1 ms gaps (profiles/r04_ab_sweep.txt) — of which the kernel itself is 1 % (rocprofv3 trace:
+        // 480 us against 475, profiles/r04_ab_sweep_kernel_level.txt); the rest is this function building and uploading a
+        // seven times longer chunk table per call, which a pipelined step hides and a lone call does not.  With the packed-f32
+        // pipeline (-39 % VALU instructions, +-0) that makes three independent changes of what the kernel DOES per frame that do
+        // not change what a launch TAKES: it runs at the package power cap, where time follows flops + bytes, and neither moved.
+        l.sweep = r.sweep && total > n_waves * 32;
+        if (l.sweep) g.frames_per_tile = 4;
+        if (r.phase_mode == 1) g.frames_per_tile = std::max<uint32_t>(4, (g.frames_per_tile + 3) / 4 * 4);  // chunks start on the grid
+    } else {
+        g.frames_per_tile = 8;
+        // (short transforms — n_fft 256 and below, the generic kernel's only full plans: a tile of 8 frames is one round of its frames-side-by-side
+        // loop, and the workgroup's set-up and (min, max) fold then cost as much as the frames; up to 64 frames a tile where the batch still fills the chip)
+        if (g.nc <= 256 && g.odd_m1 == 0) {
+            uint64_t all = 0;
+            for (size_t i = 0; i < n_chan; i++) all += chans[i].n_frames;
+            const uint64_t want = all / ((uint64_t)n_cu * 16u);
+            g.frames_per_tile = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(8, want / 8 * 8));
+        }
+    }
+    ge.frames_per_tile = 1;
+    if (mel_second) l.amp_row0.assign(n_chan, 0);
+    auto add = [](std::vector<ChanJob> &v, std::vector<uint32_t> &st, uint64_t &n_tiles, const StftGeom &gg,
+                  const th_chan_desc &d, uint32_t T, uint32_t fb0, uint32_t fe0, uint32_t slot, bool wave_edge = false) {
+        if (fb0 >= fe0) return;
+        const uint32_t pitch = d.spec_pitch ? (uint32_t)d.spec_pitch : gg.height;
+        v.push_back(ChanJob{d.wav, d.spec, (uint32_t)d.n_samples, T, fb0, fe0, slot, pitch, wave_edge ? 1u : 0u, 0u});
+        st.push_back((uint32_t)n_tiles);
+        const uint32_t fpt = wave_edge ? 1u : gg.frames_per_tile;
+        n_tiles += (fe0 - fb0 + fpt - 1) / fpt;
+    };
+    for (size_t i = 0; i < n_chan; i++) {
+        const th_chan_desc &d = chans[i];
+        TH_LAUNCH_REQUIRE(d.wav && d.spec, "channel %zu: NULL device pointer", i);
+        TH_LAUNCH_REQUIRE(d.n_samples >= 1 && d.n_samples < (1ull << 31) - 2 * g.n_fft, "channel %zu: n_samples=%llu out of range",
+                          i, (unsigned long long)d.n_samples);
+        const size_t T = stft_n_frames(d.n_samples, g.win, g.hop);
+        TH_LAUNCH_REQUIRE(d.n_frames == T, "channel %zu: n_frames=%llu but the framing gives %zu", i,
+                          (unsigned long long)d.n_frames, T);
+        TH_LAUNCH_REQUIRE(d.spec_pitch == 0 || (d.spec_pitch >= g.height && d.spec_pitch < (1ull << 31)),
+                          "channel %zu: spec_pitch %llu < height %u", i, (unsigned long long)d.spec_pitch, g.height);
+        if (!wave) {
+            add(l.jobs, l.tile_start, l.tiles, g, d, (uint32_t)T, 0, (uint32_t)T, (uint32_t)i);
+        } else {
+            uint64_t fa, fb;
+            interior(d, T, fa, fb);
+            add(l.jobs, l.tile_start, l.tiles, g, d, (uint32_t)T, (uint32_t)fa, (uint32_t)fb, (uint32_t)i);
+            if (mel_second && fa < fb) {
+                l.amp_row0[i] = l.amp_rows;
+                l.amp_rows += T;
+                l.mel_jobs.push_back(MelJob{nullptr, d.spec, (uint32_t)fa, (uint32_t)fb,
+                                            (uint32_t)(d.spec_pitch ? d.spec_pitch : g.height), (uint32_t)i});
+                l.mel_start.push_back((uint32_t)l.mel_tiles);
+                l.mel_tiles += (fb - fa + MEL_TILE_FRAMES - 1) / MEL_TILE_FRAMES;
+            }
+            // boundary frames of channels with at least n_fft samples also go to the wave kernel where the route says so; a
+            // single reflection is not enough for shorter channels
+            if (r.edges_in_wave && d.n_samples >= g.n_fft) {
+                add(l.jobs, l.tile_start, l.tiles, g, d, (uint32_t)T, 0, (uint32_t)fa, (uint32_t)i, true);
+                add(l.jobs, l.tile_start, l.tiles, g, d, (uint32_t)T, (uint32_t)fb, (uint32_t)T, (uint32_t)i, true);
+            } else {
+                add(l.edge, l.edge_start, l.edge_tiles, ge, d, (uint32_t)T, 0, (uint32_t)fa, (uint32_t)i);
+                add(l.edge, l.edge_start, l.edge_tiles, ge, d, (uint32_t)T, (uint32_t)fb, (uint32_t)T, (uint32_t)i);
+            }
+        }
+        TH_LAUNCH_REQUIRE(l.tiles < (1ull << 31) && l.edge_tiles < (1ull << 31), "batch too large for one launch");
+    }
+    l.tile_start.push_back((uint32_t)l.tiles);
+    l.edge_start.push_back((uint32_t)l.edge_tiles);
+    l.mel_start.push_back((uint32_t)l.mel_tiles);
+    if (wave) {
+        l.chunk_tab.resize((size_t)l.tiles * 2);
+        for (size_t j = 0; j < l.jobs.size(); j++) {
+            const uint32_t fpt = l.jobs[j].edge ? 1u : g.frames_per_tile;
+            for (uint32_t t = l.tile_start[j]; t < l.tile_start[j + 1]; t++) {
+                l.chunk_tab[2 * (size_t)t] = (uint32_t)j;
+                l.chunk_tab[2 * (size_t)t + 1] = l.jobs[j].f_begin + (t - l.tile_start[j]) * fpt;
+            }
+            if (!l.post.empty() && l.post.back().mm_index == l.jobs[j].mm_index) l.post.back().t1 = l.tile_start[j + 1];
+            else l.post.push_back(WavePostJob{l.tile_start[j], l.tile_start[j + 1], l.jobs[j].mm_index, 0u});
+        }
+    }
+    // (min, max) slots: when every frame of every channel is in the wave launch, its last workgroup initialises and fills
+    // them (no init launch); otherwise the caller initialises them and every kernel adds with atomics
+    l.all_in_wave = wave && !mel_second && l.edge.empty() && l.tiles > 0;
+    return l;
+}
+#undef TH_LAUNCH_REQUIRE
 
 }  // namespace th

@@ -9,6 +9,7 @@
 #include "../../include/thesia_amd.h"
 #include "host_math.h"
 #include "stft_core.h"
+#include "stft_plan.h"  // WavePostJob, MelJob, MEL_TILE_FRAMES, MEL_ROWS_*
 
 // Measured-and-dropped kernel variants: the packed-f32 pipeline (selector 9), the sweep chunk schedule (11), the
 // workgroup-per-frame Stockham kernels of n_fft 32768 / 65536 (14), the subwave plan at n_fft 8192 (15) and launch shapes other
@@ -71,9 +72,6 @@ int stft_wave_default_waves(const StftGeom &g);
 // needs no initialisation: every frame of the channel was in the wave launch) and rewinds the queue (d_queue_head[0],
 // zero before the first launch; the kernel counts from 0 behind its statically assigned first round of chunks: a wave's
 // first chunk is its own index, TH_SCHED_ADVANCE adds the grid's wave count to what it pulls).
-struct WavePostJob {
-    uint32_t t0, t1, mm_index, reserved;
-};
 // d_range (may be NULL; single-job launches with store only): [min_dB, max_dB] of the one channel, clamped by dB_range
 hipError_t launch_wave_post(const WavePostJob *d_pj, uint32_t n_pj, const float *d_chunk_mm, float *d_mm_slots, bool store,
                             uint32_t *d_queue_head, float dB_range, float *d_range, hipStream_t s);
@@ -127,24 +125,11 @@ hipError_t launch_stft_wave(const StftGeom &g, const ChanJob *d_jobs, const uint
                             uint32_t n_tiles, const cf32 *d_wtab, const cf32 *d_tw, float *d_minmax,
                             uint32_t *d_queue_head, uint32_t n_cu, int waves, const WaveOut &out, hipStream_t s);
 
-// ---- kernels_mel.hip: mel filterbank contraction on the matrix cores (spectrogram.rs:207)
-struct MelJob {
-    const float *amp;  // n_frames x amp_pitch linear amplitudes |X| (columns >= n_freq are zero)
-    float *spec;       // n_frames x spec_pitch dB mel spectrogram
-    uint32_t f_begin, f_end, spec_pitch, mm_index;
-};
-#if !defined(TH_MEL_MT)
-#define TH_MEL_MT 2
-#endif
-constexpr int MEL_MT = TH_MEL_MT;                         // 16-frame row tiles per wave
-constexpr uint32_t MEL_TILE_FRAMES = 64 * MEL_MT;         // 4 waves x MEL_MT x 16 frames per workgroup
+// ---- kernels_mel.hip: mel filterbank contraction on the matrix cores (MelJob: stft_plan.h)
 hipError_t launch_mel_mfma(const MelJob *d_jobs, const uint32_t *d_tile_start, uint32_t n_jobs, uint32_t n_tiles,
                            uint32_t amp_pitch, const float *d_bt, const uint32_t *d_tile_band, const uint32_t *d_slice_start,
                            uint32_t n_slices, uint32_t zero_block, uint32_t n_mel, float *d_minmax, hipStream_t s);
-// short rows (at most MEL_ROWS_NKB * 16 bins: n_fft 512) under narrow filters (at most MEL_ROWS_W bins each, at most
-// 64 * MEL_ROWS_MAX_GROUPS mels): banded sums, lane = mel.  d_tab: [n_groups][1 + MEL_ROWS_W][64] words — the first bin of
-// mel 64 g + lane, then its weights (float bits, zero past the filter's end and for mels >= n_mel)
-constexpr int MEL_ROWS_NKB = 17, MEL_ROWS_W = 8, MEL_ROWS_MAX_GROUPS = 8;
+// short rows under narrow filters (n_fft 512): banded sums, lane = mel (d_tab: build_mel_rows, stft_plan.h)
 hipError_t launch_mel_rows(const MelJob *d_jobs, const uint32_t *d_tile_start, uint32_t n_jobs, uint32_t n_tiles,
                            uint32_t amp_pitch, const uint32_t *d_tab, uint32_t n_groups, uint32_t n_mel, float *d_minmax,
                            uint32_t n_cu, hipStream_t s);

@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>  // (hipcc compiles the plain C++ sources as HIP too: they get the qualifiers from here)
 #define TH_HD __host__ __device__ __forceinline__
 #else
 #define TH_HD inline
