@@ -22,6 +22,9 @@
  *   encode_waveform_tile              render_tiles.rs:232-279 → th_encode_waveform_tile_dev, th_waveform_tiles_dev
  *   TrackManager (update_specs, update_spec_imgs, ...) core/mod.rs:33-230 → th_tm_*
  *   tile commands                     src-tauri/src/lib.rs:342-389 → th_tm_get_waveform_tile, th_tm_get_spectrogram_tile
+ *   set_common_normalize / set_common_guard_clipping  lib.rs:287-319 (track.rs:152-171,329-337, audio.rs:50-63,133-179,
+ *     dynamics/{normalize,guardclipping,limiter,envelope,stats}.rs) → th_tm_set_common_normalize, th_tm_set_common_guard_clipping,
+ *     th_tm_get_track_dynamics, th_tm_get_guard_clip_stats, th_tm_get_limiter_gain; th_normalize_gain, th_limiter_params
  *
  * Conventions
  *   - Every function returns th_status (0 = ok, <0 = error) and never throws or aborts;
@@ -507,6 +510,68 @@ TH_API int th_tm_mip_level(th_tm *tm, size_t id, uint32_t ch, uint32_t level_x, 
  * mip pyramids.  Any out pointer may be NULL. */
 TH_API int th_tm_lod_footprint(th_tm *tm, size_t *n_axis_tables, size_t *axis_table_bytes, size_t *mip_bytes);
 
+/* ---------------------------------------------------------------- common normalisation and clip guarding */
+/* set_common_normalize / set_common_guard_clipping — lib.rs:287-319 -> track.rs:152-171,329-337,432-436 -> audio.rs:50-63,133-179
+ * -> dynamics/{normalize,guardclipping,limiter,envelope,stats}.rs, on the resident audio.  A track keeps its ORIGINAL samples as
+ * they were added; its AUDIO (what the spectrogram is made from and th_tm_get_audio_stats describes) is derived from them:
+ *   gain = th_normalize_gain(kind, target, stats of the original).  gain == 1 or not finite (Off, a silent track, a NaN target):
+ *   the audio IS the original — no second copy, result GlobalGain(1), default guard stats (AudioTrack::apply_gain, track.rs:158-170).
+ *   Otherwise y = gain * x in f32 and the guard: TH_GUARD_CLIP keeps y as the before-clip audio (which the waveform is then drawn
+ *   from) and clamps to [-1, 1]; TH_GUARD_REDUCE_GLOBAL_LEVEL scales by 1 / peak when the peak is above 1; TH_GUARD_LIMITER runs
+ *   PerfectLimiter::with_default (threshold 1, attack 5 ms, hold 15 ms, release 40 ms, three box filters) when the peak is above 1.
+ * Defaults: TH_NORM_OFF and TH_GUARD_REDUCE_GLOBAL_LEVEL (track.rs:203-204); with them every other call returns what it returned
+ * before these entries existed and no extra device memory is held.  th_tm_add_tracks derives new tracks under the common
+ * settings.  A setter re-derives every track, recomputes pyramids, stats, specs and images, and bumps both revisions once
+ * (invalidate_all); like set_setting it is transactional.  An unknown kind / mode: TH_ERR_INVALID_ARG, nothing changed.
+ * The limiter needs sr >= 100 (an attack of at least one sample), else TH_ERR_UNSUPPORTED. */
+#define TH_NORM_OFF 0
+#define TH_NORM_LUFS 1
+#define TH_NORM_RMS_DB 2
+#define TH_NORM_PEAK_DB 3
+#define TH_GUARD_CLIP 0
+#define TH_GUARD_REDUCE_GLOBAL_LEVEL 1
+#define TH_GUARD_LIMITER 2
+/* which GuardClippingResult a track holds (guardclipping.rs:24-29) */
+#define TH_GUARD_RESULT_GLOBAL_GAIN 0
+#define TH_GUARD_RESULT_BEFORE_CLIP 1
+#define TH_GUARD_RESULT_GAIN_SEQUENCE 2
+/* Host only.  th_normalize_gain: 10f32.powf((target - stat) / 20) in f32, stat = global_lufs (cast to f32 first), rms_dB or
+ * max_peak_dB of the ORIGINAL (normalize.rs:23-45); Off gives 1.  th_limiter_params: what PerfectLimiter::with_default(sr) runs
+ * with — attack = round(5 sr / 1000), hold_length = round(20 sr / 1000) (half away from zero), release_samples = 40 sr / 1000 and
+ * the three box lengths of BoxStackFilter::set(attack) (envelope.rs:229-265; their sum is attack + 2). */
+typedef struct {
+    uint32_t attack, hold_length;
+    double release_samples;
+    uint32_t box_len[3];
+    uint32_t reserved;
+} th_limiter_desc;
+TH_API int th_normalize_gain(int kind, float target, const th_audio_stats *orig, float *gain);
+TH_API int th_limiter_params(uint32_t sr, th_limiter_desc *out);
+typedef struct {
+    float normalize_gain;       /* the gain that was used (1 when the audio is the original) */
+    int32_t guard_result;       /* TH_GUARD_RESULT_* */
+    float global_gain;          /* GlobalGain's value (1 under the other results) */
+    uint32_t draws_before_clip; /* 1: waveform tiles come from the before-clip audio (channel_for_drawing, audio.rs:70-78) */
+} th_track_dynamics;
+typedef struct { /* GuardClippingStats, stats.rs:111-174 */
+    float max_reduction_gain_dB;
+    uint32_t reserved;
+    uint64_t reduction_cnt;
+} th_guard_clip_stats;
+TH_API int th_tm_set_common_normalize(th_tm *tm, int kind, float target);
+TH_API int th_tm_set_common_guard_clipping(th_tm *tm, int mode);
+TH_API int th_tm_get_common_dynamics(th_tm *tm, int *kind, float *target, int *mode); /* any out pointer may be NULL */
+TH_API int th_tm_get_track_dynamics(th_tm *tm, size_t id, th_track_dynamics *out);
+/* the entries format_guard_clip_stats selects (audio.rs:94-111): one per channel under TH_GUARD_CLIP, else one.  *n = entries
+ * there are; TH_ERR_BUFFER_TOO_SMALL when cap is less (out may then be NULL) */
+TH_API int th_tm_get_guard_clip_stats(th_tm *tm, size_t id, th_guard_clip_stats *out, size_t cap, size_t *n);
+/* guard_clipping_gain (audio.rs:80-92): *n = 0 when the track holds no gain sequence, 1 ([1.0]) when no gain is below 1, else
+ * n_samples f32 gains.  TH_ERR_BUFFER_TOO_SMALL when cap is less than *n (out may then be NULL) */
+TH_API int th_tm_get_limiter_gain(th_tm *tm, size_t id, float *out, size_t cap, size_t *n);
+/* n_samples f32 of one channel: which = 0 the audio (what the spectrogram is made from), 1 the audio the waveform is drawn from
+ * (channel_for_drawing), 2 the original */
+TH_API int th_tm_copy_audio(th_tm *tm, size_t id, uint32_t ch, int which, float *out, size_t cap);
+
 /* ---------------------------------------------------------------- TrackManager over several devices (one process) */
 /* th_tmg: the th_tm_* calls above, call for call, with a th_tmg * in place of the th_tm *; a multi-GPU host swaps one for
  * the other.  Every result — updated ids, max_sr, db state, revisions, specs, images, tile bytes, batch offsets, render
@@ -563,6 +628,14 @@ TH_API int th_tmg_get_audio_render_metadata(th_tmg *tmg, size_t id, uint32_t ch,
                                             th_render_metadata *out);
 TH_API int th_tmg_set_lod_source(th_tmg *tmg, int per_request);
 TH_API int th_tmg_get_audio_stats(th_tmg *tmg, size_t id, th_audio_stats *out);
+/* the common normalisation and clip guard: every slot prepares, then all commit or all discard; one global dB range is folded */
+TH_API int th_tmg_set_common_normalize(th_tmg *tmg, int kind, float target);
+TH_API int th_tmg_set_common_guard_clipping(th_tmg *tmg, int mode);
+TH_API int th_tmg_get_common_dynamics(th_tmg *tmg, int *kind, float *target, int *mode);
+TH_API int th_tmg_get_track_dynamics(th_tmg *tmg, size_t id, th_track_dynamics *out);
+TH_API int th_tmg_get_guard_clip_stats(th_tmg *tmg, size_t id, th_guard_clip_stats *out, size_t cap, size_t *n);
+TH_API int th_tmg_get_limiter_gain(th_tmg *tmg, size_t id, float *out, size_t cap, size_t *n);
+TH_API int th_tmg_copy_audio(th_tmg *tmg, size_t id, uint32_t ch, int which, float *out, size_t cap);
 
 /* Test and measurement entry points (kernel selectors for A/B runs, per-launch kernel timing, replacing a resident image
  * with given pixels) are NOT part of this interface: include/thesia_amd_testing.h declares them; a thesia host binds none. */

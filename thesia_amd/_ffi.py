@@ -79,6 +79,20 @@ class AudioDesc(C.Structure):  # th_audio_desc
                 ("block_energy", C.c_void_p)]
 
 
+class LimiterDesc(C.Structure):  # th_limiter_desc
+    _fields_ = [("attack", C.c_uint32), ("hold_length", C.c_uint32), ("release_samples", C.c_double), ("box_len", C.c_uint32 * 3),
+                ("reserved", C.c_uint32)]
+
+
+class TrackDynamics(C.Structure):  # th_track_dynamics
+    _fields_ = [("normalize_gain", C.c_float), ("guard_result", C.c_int32), ("global_gain", C.c_float),
+                ("draws_before_clip", C.c_uint32)]
+
+
+class GuardClipStats(C.Structure):  # th_guard_clip_stats
+    _fields_ = [("max_reduction_gain_dB", C.c_float), ("reserved", C.c_uint32), ("reduction_cnt", C.c_uint64)]
+
+
 class PyramidDesc(C.Structure):
     _fields_ = [("wav", C.c_void_p), ("out", C.c_void_p), ("n_samples", C.c_uint64), ("n_levels", C.c_uint32),
                 ("first_level", C.c_uint32)]
@@ -242,6 +256,22 @@ _SIGS = {
     "th_tmg_get_waveform_tile": [vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, c_u8p, C.c_size_t, c_szp],
     "th_tmg_get_audio_render_metadata": [vp, C.c_size_t, C.c_uint32, C.c_double, C.c_int, C.POINTER(RenderMetadata)],
     "th_tmg_set_lod_source": [vp, C.c_int],
+    "th_normalize_gain": [C.c_int, C.c_float, C.POINTER(AudioStats), c_f32p],
+    "th_limiter_params": [C.c_uint32, C.POINTER(LimiterDesc)],
+    "th_tm_set_common_normalize": [vp, C.c_int, C.c_float],
+    "th_tm_set_common_guard_clipping": [vp, C.c_int],
+    "th_tm_get_common_dynamics": [vp, C.POINTER(C.c_int), c_f32p, C.POINTER(C.c_int)],
+    "th_tm_get_track_dynamics": [vp, C.c_size_t, C.POINTER(TrackDynamics)],
+    "th_tm_get_guard_clip_stats": [vp, C.c_size_t, C.POINTER(GuardClipStats), C.c_size_t, c_szp],
+    "th_tm_get_limiter_gain": [vp, C.c_size_t, c_f32p, C.c_size_t, c_szp],
+    "th_tm_copy_audio": [vp, C.c_size_t, C.c_uint32, C.c_int, c_f32p, C.c_size_t],
+    "th_tmg_set_common_normalize": [vp, C.c_int, C.c_float],
+    "th_tmg_set_common_guard_clipping": [vp, C.c_int],
+    "th_tmg_get_common_dynamics": [vp, C.POINTER(C.c_int), c_f32p, C.POINTER(C.c_int)],
+    "th_tmg_get_track_dynamics": [vp, C.c_size_t, C.POINTER(TrackDynamics)],
+    "th_tmg_get_guard_clip_stats": [vp, C.c_size_t, C.POINTER(GuardClipStats), C.c_size_t, c_szp],
+    "th_tmg_get_limiter_gain": [vp, C.c_size_t, c_f32p, C.c_size_t, c_szp],
+    "th_tmg_copy_audio": [vp, C.c_size_t, C.c_uint32, C.c_int, c_f32p, C.c_size_t],
     "th_tile_cache_create": [C.c_size_t, C.POINTER(vp)],
     "th_tile_cache_destroy": [vp],
     "th_tile_cache_lookup": [vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), c_u8p, C.c_size_t,

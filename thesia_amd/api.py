@@ -19,6 +19,9 @@ from ._ffi import (ChanDesc, ImgDesc, RasterDesc, ThError, TileGeom, WaveDesc, c
                    lib, vp)
 
 LINEAR, MEL = 0, 1
+NORM_OFF, NORM_LUFS, NORM_RMS_DB, NORM_PEAK_DB = 0, 1, 2, 3
+GUARD_CLIP, GUARD_REDUCE_GLOBAL_LEVEL, GUARD_LIMITER = 0, 1, 2
+GUARD_RESULT_GLOBAL_GAIN, GUARD_RESULT_BEFORE_CLIP, GUARD_RESULT_GAIN_SEQUENCE = 0, 1, 2
 WAVEFORM_TILE_MAX_BYTES = 24 + 1024 * 12
 SPECTROGRAM_TILE_MAX_BYTES = 40 + 520 * 520 * 4
 
@@ -135,6 +138,75 @@ def waveform_tile_geometry(n_samples: int, level: int, tile_index: int):
 # ------------------------------------------------------------------ device context
 def _audio_stats_dict(o) -> dict:
     return {"global_lufs": o.global_lufs, "rms_dB": o.rms_dB, "max_peak": o.max_peak, "max_peak_dB": o.max_peak_dB}
+
+
+def normalize_gain(kind: int, target: float, stats: dict) -> float:
+    """the normalise gain of NormalizeTarget (kind, target) from the AudioStats of the original (normalize.rs:23-45), as f32"""
+    o = _ffi.AudioStats(stats["global_lufs"], stats["rms_dB"], stats["max_peak"], stats["max_peak_dB"])
+    g = C.c_float()
+    check(lib.th_normalize_gain(kind, target, C.byref(o), C.byref(g)))
+    return np.float32(g.value)
+
+
+def limiter_params(sr: int) -> dict:
+    """what PerfectLimiter::with_default(sr) runs with: attack, hold_length, release_samples, box_len[3]"""
+    o = _ffi.LimiterDesc()
+    check(lib.th_limiter_params(sr, C.byref(o)))
+    return {"attack": o.attack, "hold_length": o.hold_length, "release_samples": o.release_samples, "box_len": list(o.box_len)}
+
+
+class _DynamicsMethods:
+    """set_common_normalize / set_common_guard_clipping and what they leave to read (th_tm_* and th_tmg_*: _PFX)"""
+
+    def _dyn(self, name):
+        return getattr(lib, self._PFX + name)
+
+    def set_common_normalize(self, kind: int, target: float = 0.0):
+        check(self._dyn("set_common_normalize")(self.handle, kind, target))
+
+    def set_common_guard_clipping(self, mode: int):
+        check(self._dyn("set_common_guard_clipping")(self.handle, mode))
+
+    def common_dynamics(self):
+        """-> (normalize kind, target, guard-clipping mode)"""
+        k, t, m = C.c_int(), C.c_float(), C.c_int()
+        check(self._dyn("get_common_dynamics")(self.handle, C.byref(k), C.byref(t), C.byref(m)))
+        return k.value, t.value, m.value
+
+    def track_dynamics(self, track_id: int) -> dict:
+        o = _ffi.TrackDynamics()
+        check(self._dyn("get_track_dynamics")(self.handle, track_id, C.byref(o)))
+        return {"normalize_gain": np.float32(o.normalize_gain), "guard_result": o.guard_result,
+                "global_gain": np.float32(o.global_gain), "draws_before_clip": bool(o.draws_before_clip)}
+
+    def guard_clip_stats(self, track_id: int):
+        """the GuardClippingStats format_guard_clip_stats selects: [(max_reduction_gain_dB, reduction_cnt)]"""
+        n = C.c_size_t()
+        rc = self._dyn("get_guard_clip_stats")(self.handle, track_id, None, 0, C.byref(n))
+        if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+            check(rc)
+        out = (_ffi.GuardClipStats * max(n.value, 1))()
+        check(self._dyn("get_guard_clip_stats")(self.handle, track_id, out, n.value, C.byref(n)))
+        return [(np.float32(out[i].max_reduction_gain_dB), int(out[i].reduction_cnt)) for i in range(n.value)]
+
+    def limiter_gain(self, track_id: int):
+        """guard_clipping_gain (audio.rs:80-92): None, [1.0], or the n_samples gains"""
+        n = C.c_size_t()
+        rc = self._dyn("get_limiter_gain")(self.handle, track_id, None, 0, C.byref(n))
+        if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+            check(rc)
+        if n.value == 0:
+            return None
+        out = np.empty(n.value, np.float32)
+        check(self._dyn("get_limiter_gain")(self.handle, track_id, _ptr(out, c_f32p), out.size, C.byref(n)))
+        return out
+
+    def audio(self, track_id: int, ch: int, which: int = 0) -> np.ndarray:
+        """one channel's samples: which = 0 the audio, 1 what the waveform is drawn from, 2 the original"""
+        m = self.render_metadata(track_id, ch, 0.0, False)
+        out = np.empty(m["sample_count"], np.float32)
+        check(self._dyn("copy_audio")(self.handle, track_id, ch, which, _ptr(out, c_f32p), out.size))
+        return out
 
 
 def k_weighting(sr: int):
@@ -574,8 +646,9 @@ class TileCache:
                 "spectrogram_revision": sr.value, "hits": h.value, "misses": m.value}
 
 
-class TrackManager:
+class TrackManager(_DynamicsMethods):
     """th_tm: mirror of core/mod.rs TrackManager with HBM-resident audio / specs / images."""
+    _PFX = "th_tm_"
 
     def __init__(self, ctx: Context):
         h = vp()
@@ -773,9 +846,10 @@ class TrackManager:
         return out[: n.value].tobytes()
 
 
-class MultiTrackManager:
+class MultiTrackManager(_DynamicsMethods):
     """th_tmg: the TrackManager over several devices of one process (duplicates allowed: [0, 0] is two slots on one card).
     Same method names as TrackManager; results are bit-identical to one TrackManager holding every track."""
+    _PFX = "th_tmg_"
 
     def __init__(self, devices):
         devs = [int(d) for d in devices]

@@ -1576,6 +1576,28 @@ TH_API int th_gated_loudness(const double *block_energies, size_t n, double *luf
     TH_CATCH
 }
 
+TH_API int th_normalize_gain(int kind, float target, const th_audio_stats *orig, float *gain) {
+    TH_TRY
+    TH_REQUIRE(orig && gain, "NULL argument");
+    TH_REQUIRE(normalize_gain(kind, target, orig->global_lufs, orig->rms_dB, orig->max_peak_dB, gain), "unknown normalize kind %d", kind);
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_limiter_params(uint32_t sr, th_limiter_desc *out) {
+    TH_TRY
+    TH_REQUIRE(out, "NULL argument");
+    LimiterParams p{};
+    if (!limiter_params(sr, &p)) return fail(TH_ERR_UNSUPPORTED, "sample rate %u: the limiter's attack would be 0 samples", sr);
+    *out = th_limiter_desc{};
+    out->attack = p.attack;
+    out->hold_length = p.hold_length;
+    out->release_samples = p.release_samples;
+    for (int i = 0; i < 3; i++) out->box_len[i] = p.box_len[i];
+    return TH_OK;
+    TH_CATCH
+}
+
 namespace th {
 
 LoudnessBatch::~LoudnessBatch() {

@@ -855,4 +855,60 @@ StftLaunch plan_stft_launch(const StftGeom &pg, const StftRoute &r, uint32_t n_c
 }
 #undef TH_LAUNCH_REQUIRE
 
+// ---------------------------------------------------------------------------------------------- normalisation, limiter parameters
+// Normalize::normalize_default — dynamics/normalize.rs:23-45
+bool normalize_gain(int kind, float target, double global_lufs, float rms_dB, float max_peak_dB, float *gain) {
+    float stat;
+    switch (kind) {
+        case TH_NORM_OFF: *gain = 1.0f; return true;
+        case TH_NORM_LUFS: stat = (float)global_lufs; break;
+        case TH_NORM_RMS_DB: stat = rms_dB; break;
+        case TH_NORM_PEAK_DB: stat = max_peak_dB; break;
+        default: return false;
+    }
+    *gain = powf(10.0f, (target - stat) / 20.0f);
+    return true;
+}
+
+// PerfectLimiter::new(sr, 1., 5., 15., 40.) — limiter.rs:59-77; PeakHold::resize — envelope.rs:374-377;
+// BoxStackFilter::with_num_layers(attack, 3) -> set(attack) — envelope.rs:206-265
+bool limiter_params(uint32_t sr, LimiterParams *out) {
+    const double attack = std::round(5. * (double)sr / 1000.);  // f64::round: half away from zero
+    if (!(attack >= 1.)) return false;
+    out->attack = (uint32_t)attack;
+    out->hold_length = (uint32_t)std::round((double)sr * 20. / 1000.);
+    out->release_samples = 40. * (double)sr / 1000.;
+    // optimal_ratios(3) = HARDCODED_RATIOS[3..6], normalised by their sum (setup_layers)
+    double ratio[3] = {0.404078562416, 0.334851475794, 0.261069961789};
+    const double sum = ((0. + ratio[0]) + ratio[1]) + ratio[2];
+    for (double &r : ratio) r /= sum;
+    const size_t order = out->attack - 1;
+    size_t total = 0;
+    double err[3];
+    for (int i = 0; i < 3; i++) {
+        const double frac = ratio[i] * (double)order;
+        const size_t lo = (size_t)frac;
+        out->box_len[i] = (uint32_t)lo + 1;
+        err[i] = (double)lo - frac;
+        total += lo;
+    }
+    for (size_t k = total; k < order; k++) {  // the layer with the least length error grows (the first of equals)
+        int i_min = 0;
+        double mn = INFINITY;
+        for (int i = 0; i < 3; i++)
+            if (err[i] < mn) {
+                i_min = i;
+                mn = err[i];
+            }
+        out->box_len[i_min] += 1;
+        err[i_min] += 1.;
+    }
+    return true;
+}
+
+float db_from_amp(float x) {
+    if (std::isnan(x) || std::signbit(x)) return NAN;
+    return x == 0.0f ? -INFINITY : (float)(20.0 * std::log10((double)x));
+}
+
 }  // namespace th

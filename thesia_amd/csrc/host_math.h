@@ -81,6 +81,18 @@ struct LoudnessRate {
 };
 const LoudnessRate &loudness_rate(uint32_t sr);  // (cached per rate; sr must satisfy loudness_rate_ok)
 
+// ---- normalisation and clip guarding (dynamics/normalize.rs, limiter.rs, envelope.rs, stats.rs)
+// 10f32.powf((target - stat) / 20) in f32 (normalize.rs:29-43); kind: TH_NORM_* (Off: 1); false for an unknown kind
+bool normalize_gain(int kind, float target, double global_lufs, float rms_dB, float max_peak_dB, float *gain);
+// PerfectLimiter::with_default(sr) (limiter.rs:59-82): false when the attack would be 0 samples (sr < 100)
+struct LimiterParams {
+    uint32_t attack, hold_length, box_len[3];
+    double release_samples;
+};
+bool limiter_params(uint32_t sr, LimiterParams *out);
+// dB_from_amp_default of an f32 (decibel.rs:66-102, amin = 0): 20 log10 x, the logarithm in f64 and rounded once (as the AudioStats are)
+float db_from_amp(float x);
+
 inline bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
 inline unsigned ilog2(size_t n) {
     unsigned l = 0;

@@ -297,4 +297,36 @@ struct LoudTrackJob {      // one track
 hipError_t launch_loudness(const LoudJob *d_jobs, uint32_t n_jobs, uint32_t max_chunks, uint32_t max_fchunks, const LoudnessRate *d_rates,
                            uint32_t lds_floats, const LoudTrackJob *d_tjobs, uint32_t n_tracks, uint64_t max_blocks, hipStream_t s);
 
+// ---- kernels_dynamics.hip: normalise gain + clip guard (clip, global level, look-ahead limiter) of a batch of tracks
+struct DynApplyJob {        // one track: y = gain x in f32, then the clamp or a global gain
+    const float *x;         // channel c at x + c x_stride
+    float *aud;             // channel c at aud + c y_stride
+    float *before;          // Clip: gain x before the clamp (stride y_stride); else NULL
+    uint64_t x_stride, y_stride, n;
+    double g;               // scale: y <- clamp(f32(f64(y) g))   (reduce_global_level, audio.rs:145-159)
+    float gain;
+    uint32_t n_ch, clip, scale;
+    uint32_t *peak_bits;         // Clip: n_ch slots, max |gain x| as float bits (zeroed by the caller)
+    unsigned long long *cnt;     // Clip: n_ch slots, samples with |gain x| > 1 (zeroed by the caller)
+};
+hipError_t launch_dyn_apply(const DynApplyJob *d_jobs, uint32_t n_jobs, uint64_t max_n, hipStream_t s);
+constexpr uint32_t LIM_CHUNK = 256;  // samples per chunk of the release scan
+constexpr uint32_t LIM_BLOCK = 64;   // samples per block maximum of the peak hold (one wave)
+struct LimJob {             // one track through PerfectLimiter::process_inplace (limiter.rs:110-156); N = n + attack
+    const float *x;
+    float *aud;
+    float *gain_seq;        // n f32 gains
+    uint64_t x_stride, y_stride, n;
+    float *v;               // scratch, N: max over the channels of |gain x| (0 behind the track)
+    float *bm;              // scratch, ceil(N / LIM_BLOCK): block maxima of v
+    double *a, *b;          // scratch, N each: the envelope stages, ping-pong
+    double *sum;            // scratch, 4 per release chunk: the chunk's map (A, D, C) and its start state
+    double slew;            // 1 / (release_samples + 1)
+    float gain;
+    uint32_t n_ch, attack, hold, box_len[3];
+    uint32_t *min_bits;          // least gain as float bits (set to the bits of 1.0f by the caller)
+    unsigned long long *cnt;     // gains != 1 (zeroed by the caller)
+};
+hipError_t launch_limiter(const LimJob *h_jobs, const LimJob *d_jobs, uint32_t n_jobs, hipStream_t s);
+
 }  // namespace th

@@ -7,8 +7,9 @@
 // need_update_all, set_setting (:107-115), set_dB_range (:123-126), set_colormap_length (:128-131),
 // the revision bumps the command layer applies around them (lib.rs:192,221,244,265,284), and
 // get_waveform_tile / get_spectrogram_tile.
-// What is not: file decoding, normalisation / clip guarding (TrackList, out of scope — the path
-// starts at an in-memory planar f32 channel, audio.rs:65-78).
+// set_common_normalize / set_common_guard_clipping (lib.rs:287-319 -> track.rs:152-171,329-337 -> audio.rs:50-63,133-179): every
+// track keeps its original samples and derives its audio from them on the device (kernels_dynamics.hip).
+// What is not: file decoding (the path starts at an in-memory planar f32 channel, audio.rs:65-78).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -44,9 +45,11 @@ struct MipLevel {
 };
 
 struct Channel {
-    float *d_wav = nullptr;
+    float *d_wav = nullptr;      // the AUDIO (Audio::channel): what the spectrogram is made from
     size_t n = 0;
-    float *d_pyr = nullptr;      // resident waveform pyramid: every level's (min, max, mean) bins, th_waveform_pyramid_offset
+    float *d_draw = nullptr;     // what the waveform is drawn from (channel_for_drawing): d_wav, or the before-clip audio
+    float *d_pyr = nullptr;      // resident waveform pyramid of d_draw: every level's (min, max, mean) bins, th_waveform_pyramid_offset
+    float *d_orig = nullptr, *d_pyr_orig = nullptr;  // the samples as they were added and their pyramid (the track's pool)
     uint32_t pyr_levels = 0;     // levels 0 .. pyr_levels - 1 (the last one has a single bin)
     float *d_spec = nullptr;
     size_t T = 0, H = 0, spec_pitch = 0;   // rows padded to 128 B (th_pitch_f32)
@@ -93,7 +96,18 @@ struct Track {
     // ONE device allocation for the samples and waveform pyramids of all channels (round 6: two hipMalloc per channel were 0.7 ms
     // of a 32-track add); Channel::d_wav / d_pyr are views into it and live exactly as long as the track
     void *d_pool = nullptr;
-    th_audio_stats stats{};  // AudioStats (StatCalculator::calc, dynamics/stats.rs:56-86) of the samples as they were added
+    th_audio_stats stats{};       // AudioStats (StatCalculator::calc, dynamics/stats.rs:56-86) of the audio
+    th_audio_stats orig_stats{};  // ... of the samples as they were added: what the normalise gain is computed from
+    // The audio derived from the original under the common normalise target and clip guard (AudioTrack::apply_gain).  d_dyn == NULL:
+    // the audio IS the original (gain 1 or not finite) and nothing below is held.  One allocation: per channel the audio, in Clip mode
+    // the before-clip audio, and the pyramid of what is drawn; then the limiter's gain sequence.
+    void *d_dyn = nullptr;
+    float norm_gain = 1.0f;
+    int guard_result = TH_GUARD_RESULT_GLOBAL_GAIN;
+    float global_gain = 1.0f;
+    float *d_gain = nullptr;    // GainSequence: n gains (a view into d_dyn), or NULL when the limiter had nothing to do (all ones)
+    bool gain_below_one = false;
+    std::vector<th_guard_clip_stats> guard_stats;  // Audio::guard_clip_stats: one per channel, or one for a gain sequence
 };
 
 using PlanKey = std::tuple<uint32_t, size_t, size_t, size_t, int>;  // sr, win, hop, n_fft, scale
@@ -127,6 +141,10 @@ struct th_tm {
     // 0: LOD > 0 tiles are crops of the pre-built mip pyramid (default); 1: resampled per request from the level-0 image
     // (the reference's own flow; kept as the comparison path).  Levels the pyramid does not hold always use 1.
     int lod_source = 0;
+    // TrackList::new — track.rs:203-204
+    int norm_kind = TH_NORM_OFF;
+    float norm_target = 0.0f;
+    int guard_mode = TH_GUARD_REDUCE_GLOBAL_LEVEL;
     std::map<std::pair<uint32_t, uint32_t>, AxisTable> axis_tabs;  // (source length, level) -> taps
     th::DeviceTable mip_jobs;                                       // job table of the batched mip-pyramid passes
     th::DeviceTable mip_scratch;                                    // transposed images of one chunk of the batch
@@ -181,6 +199,9 @@ void free_track(Track &t) {
     t.ch.clear();
     if (t.d_pool) (void)hipFree(t.d_pool);
     t.d_pool = nullptr;
+    if (t.d_dyn) (void)hipFree(t.d_dyn);
+    t.d_dyn = nullptr;
+    t.d_gain = nullptr;
 }
 
 struct Setting {
@@ -1397,7 +1418,7 @@ TH_API int th_tm_get_waveform_tile(th_tm *tm, size_t id, uint32_t ch, uint32_t l
     put_u32(out + 16, tile_index);
     put_u32(out + 20, 0);
     if (bins) {
-        if (!c->d_wav || !c->pyr_levels) return fail(TH_ERR_INTERNAL, "channel %zu_%u has no waveform pyramid", id, ch);
+        if (!c->d_draw || !c->pyr_levels) return fail(TH_ERR_INTERNAL, "channel %zu_%u has no waveform pyramid", id, ch);
         // a level above the pyramid's last one still has exactly one bin, over the same samples
         const uint32_t lv = level < c->pyr_levels ? level : c->pyr_levels - 1;
         const size_t first_bin = lv == level ? (size_t)tile_index * 1024 : 0;
@@ -1412,7 +1433,7 @@ TH_API int th_tm_get_waveform_tile(th_tm *tm, size_t id, uint32_t ch, uint32_t l
             // sequential sum / len — one or two samples per bin)
             const size_t spb_lv = (size_t)1 << lv;
             const size_t s0 = lv == level ? start : 0, s1 = std::min<size_t>(c->n, s0 + bins * spb_lv);
-            TH_HIP(hipMemcpyAsync(sl.h_tile, c->d_wav + s0, (s1 - s0) * 4, hipMemcpyDeviceToHost, sl.stream));
+            TH_HIP(hipMemcpyAsync(sl.h_tile, c->d_draw + s0, (s1 - s0) * 4, hipMemcpyDeviceToHost, sl.stream));
             TH_HIP(hipStreamSynchronize(sl.stream));
             const float *x = reinterpret_cast<const float *>(sl.h_tile);
             for (size_t b = 0; b < bins; b++) {
@@ -1464,7 +1485,8 @@ TH_API int th_tm_get_audio_render_metadata(th_tm *tm, size_t id, uint32_t ch, do
     out->waveform_revision = tm->waveform_revision();
     out->spectrogram_revision = tm->spectrogram_revision();
     out->sample_rate = it->second.sr;
-    out->is_clipped = is_clipped ? 1u : 0u;
+    // (lib.rs:328: channel_for_drawing's flag; a host that guards clipping itself passes its own)
+    out->is_clipped = (is_clipped || it->second.guard_result == TH_GUARD_RESULT_BEFORE_CLIP) ? 1u : 0u;
     out->sample_count = c.n;
     out->track_sec = track_sec;
     out->spectrogram_height = c.d_img ? c.img_h : 0;  // (shape[0], shape[1]) of the u16 image, lib.rs:330-332
@@ -1529,6 +1551,278 @@ TH_API int th_tm_mip_level(th_tm *tm, size_t id, uint32_t ch, uint32_t level_x, 
     TH_CATCH
 }
 
+// ---------------------------------------------------------------------------------------------- normalise + clip guard
+namespace {
+
+size_t wav_floats(size_t n) { return (n + 63) / 64 * 64; }  // (256-byte pieces: every view starts on a 256-byte boundary)
+size_t pyr_floats(size_t n, uint32_t lv) {
+    return (std::max<size_t>(1, th_waveform_pyramid_offset(n, std::max(lv, PYR_FIRST)) - th_waveform_pyramid_offset(n, PYR_FIRST)) + 63) / 64 * 64;
+}
+
+// One track's audio derived from its original under (kind, target, mode) — AudioTrack::apply_gain, track.rs:158-170 — staged beside
+// the track until install()
+struct Derived {
+    bool active = false;  // false: gain 1 or not finite, the audio is the original
+    void *d_pool = nullptr;
+    float gain = 1.0f, global_gain = 1.0f;
+    int result = TH_GUARD_RESULT_GLOBAL_GAIN, mode = TH_GUARD_REDUCE_GLOBAL_LEVEL;
+    float *d_gain = nullptr;
+    bool limiting = false, gain_below_one = false;
+    std::vector<float *> aud, draw, pyr;
+    th_audio_stats stats{};
+    std::vector<th_guard_clip_stats> guard_stats;
+    size_t red0 = 0, loud_index = 0;  // its first reduction slot; its place in the loudness batch
+};
+struct DeriveBatch {
+    th_ctx *ctx = nullptr;
+    std::map<size_t, Derived> of;
+    DeviceBuf<unsigned char> d_tab, d_scratch;  // job tables and reduction slots; the limiter's scratch
+    std::unique_ptr<LoudnessBatch> loud;
+    size_t n_red = 0, o_cnt = 0;
+    DeriveBatch() = default;
+    DeriveBatch(const DeriveBatch &) = delete;
+    DeriveBatch &operator=(const DeriveBatch &) = delete;
+    ~DeriveBatch() {  // (the caller has drained the stream; pools that were installed are NULL here)
+        if (ctx) (void)hipSetDevice(ctx->device);
+        for (auto &kv : of)
+            if (kv.second.d_pool) (void)hipFree(kv.second.d_pool);
+    }
+};
+
+// Enqueue, on the context stream, the derived audio of `tracks` with its waveform pyramids and loudness passes.  Nothing waits.
+int derive_enqueue(th_tm *tm, const std::vector<std::pair<size_t, Track *>> &tracks, int kind, float target, int mode, DeriveBatch *b) {
+    th_ctx *c = tm->ctx;
+    b->ctx = c;
+    std::vector<DynApplyJob> ajobs;
+    std::vector<LimJob> ljobs;
+    std::vector<size_t> l_scratch;  // bytes of scratch of every limiter job
+    std::vector<uint32_t> red_init;
+    std::vector<th_pyramid_desc> pdescs;
+    std::vector<th_audio_desc> adescs;
+    std::vector<std::vector<const float *>> aptrs;
+    uint64_t max_n = 0;
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    for (auto &it : tracks) {
+        Track &tr = *it.second;
+        Derived &d = b->of[it.first];
+        d.mode = mode;
+        float gain = 1.0f;
+        TH_REQUIRE(normalize_gain(kind, target, tr.orig_stats.global_lufs, tr.orig_stats.rms_dB, tr.orig_stats.max_peak_dB, &gain),
+                   "unknown normalize kind %d", kind);
+        if (!std::isfinite(gain) || gain == 1.0f) continue;  // the audio is the original
+        const size_t n = tr.ch[0].n, n_ch = tr.ch.size(), wav_f = wav_floats(n), pyr_f = pyr_floats(n, tr.ch[0].pyr_levels);
+        // f32 multiplication by a positive gain is monotone: the peak of gain x is fl(gain max|x|) — no pass over the audio
+        const float peak = gain * tr.orig_stats.max_peak;
+        const bool clip = mode == TH_GUARD_CLIP;
+        d.limiting = mode == TH_GUARD_LIMITER && peak > 1.0f;
+        LimiterParams lp{};
+        if (d.limiting) {
+            if (!limiter_params(tr.sr, &lp)) return fail(TH_ERR_UNSUPPORTED, "track %zu: sample rate %u: the limiter's attack would be 0 samples", it.first, tr.sr);
+            if ((uint64_t)n + lp.attack >= (1ull << 31)) return fail(TH_ERR_UNSUPPORTED, "track %zu: too long for the limiter (2^31 samples)", it.first);
+        }
+        const size_t per_ch = wav_f * (clip ? 2 : 1) + pyr_f;
+        TH_HIP(hipMalloc(&d.d_pool, (per_ch * n_ch + (d.limiting ? wav_f : 0)) * sizeof(float)));
+        d.active = true;
+        d.gain = gain;
+        float *base = static_cast<float *>(d.d_pool);
+        aptrs.emplace_back();
+        for (size_t k = 0; k < n_ch; k++) {
+            d.aud.push_back(base + k * per_ch);
+            d.draw.push_back(clip ? base + k * per_ch + wav_f : base + k * per_ch);
+            d.pyr.push_back(base + k * per_ch + wav_f * (clip ? 2 : 1));
+            pdescs.push_back(th_pyramid_desc{d.draw[k], d.pyr[k], n, tr.ch[k].pyr_levels, PYR_FIRST});
+            aptrs.back().push_back(d.aud[k]);
+        }
+        d.loud_index = adescs.size();
+        adescs.push_back(th_audio_desc{nullptr, (uint64_t)n, (uint32_t)n_ch, tr.sr, nullptr});
+        const uint64_t x_stride = n_ch > 1 ? (uint64_t)(tr.ch[1].d_orig - tr.ch[0].d_orig) : 0;
+        d.red0 = red_init.size();
+        if (d.limiting) {
+            d.result = TH_GUARD_RESULT_GAIN_SEQUENCE;
+            d.d_gain = base + n_ch * per_ch;
+            LimJob j{};
+            j.x = tr.ch[0].d_orig;
+            j.aud = d.aud[0];
+            j.gain_seq = d.d_gain;
+            j.x_stride = x_stride;
+            j.y_stride = per_ch;
+            j.n = n;
+            j.slew = 1.0 / (lp.release_samples + 1.0);  // ExponentialRelease::with_initial_value (limiter.rs:24-31)
+            j.gain = gain;
+            j.n_ch = (uint32_t)n_ch;
+            j.attack = lp.attack;
+            j.hold = lp.hold_length;
+            for (int i = 0; i < 3; i++) j.box_len[i] = lp.box_len[i];
+            const size_t N = n + lp.attack;
+            l_scratch.push_back(up(N * 4) + up((N / LIM_BLOCK + 1) * 4) + 2 * up(N * 8) + up((N / LIM_CHUNK + 1) * 32));
+            ljobs.push_back(j);
+            red_init.push_back(0x3f800000u);  // the least gain starts at 1.0f
+        } else {
+            d.result = clip ? TH_GUARD_RESULT_BEFORE_CLIP : mode == TH_GUARD_LIMITER ? TH_GUARD_RESULT_GAIN_SEQUENCE : TH_GUARD_RESULT_GLOBAL_GAIN;
+            DynApplyJob j{};
+            j.x = tr.ch[0].d_orig;
+            j.aud = d.aud[0];
+            j.before = clip ? d.draw[0] : nullptr;
+            j.x_stride = x_stride;
+            j.y_stride = per_ch;
+            j.n = n;
+            j.gain = gain;
+            j.n_ch = (uint32_t)n_ch;
+            j.clip = clip;
+            if (mode == TH_GUARD_REDUCE_GLOBAL_LEVEL && peak > 1.0f) {  // audio.rs:145-159
+                j.scale = 1;
+                j.g = 1.0 / (double)peak;
+                d.global_gain = (float)j.g;
+            }
+            ajobs.push_back(j);
+            if (clip) red_init.insert(red_init.end(), n_ch, 0u);
+            max_n = std::max<uint64_t>(max_n, n);
+        }
+    }
+    if (adescs.empty()) return TH_OK;
+    // device tables: [apply jobs][limiter jobs][counts u64][peak / least-gain bits u32]
+    b->n_red = red_init.size();
+    const size_t o_lim = up(ajobs.size() * sizeof(DynApplyJob)), o_cnt = o_lim + up(ljobs.size() * sizeof(LimJob)), o_bits = o_cnt + up(b->n_red * 8);
+    const size_t tab_bytes = o_bits + up(b->n_red * 4);
+    b->o_cnt = o_cnt;
+    TH_HIP(b->d_tab.alloc(tab_bytes));
+    unsigned char *dt = b->d_tab;
+    // the limiter's scratch: groups of jobs under 1 GiB run one after the other on the stream and share one buffer
+    constexpr size_t SCRATCH_CAP = (size_t)1 << 30;
+    std::vector<std::pair<size_t, size_t>> groups;  // [first, last) limiter jobs
+    size_t scratch_bytes = 0;
+    for (size_t j0 = 0; j0 < ljobs.size();) {
+        size_t j1 = j0, bytes = 0;
+        while (j1 < ljobs.size() && (j1 == j0 || bytes + l_scratch[j1] <= SCRATCH_CAP)) bytes += l_scratch[j1++];
+        groups.push_back({j0, j1});
+        scratch_bytes = std::max(scratch_bytes, bytes);
+        j0 = j1;
+    }
+    if (scratch_bytes) TH_HIP(b->d_scratch.alloc(scratch_bytes));
+    {
+        size_t ri = 0, ai = 0, li = 0;
+        for (auto &it : tracks) {  // (the order the jobs were made in)
+            Derived &d = b->of[it.first];
+            if (!d.active) continue;
+            uint32_t *bits = reinterpret_cast<uint32_t *>(dt + o_bits) + ri;
+            unsigned long long *cnt = reinterpret_cast<unsigned long long *>(dt + o_cnt) + ri;
+            if (d.limiting) {
+                ljobs[li].min_bits = bits;
+                ljobs[li].cnt = cnt;
+                li++;
+                ri += 1;
+            } else {
+                if (ajobs[ai].clip) {
+                    ajobs[ai].peak_bits = bits;
+                    ajobs[ai].cnt = cnt;
+                    ri += ajobs[ai].n_ch;
+                }
+                ai++;
+            }
+        }
+        for (auto &g : groups) {
+            size_t off = 0;
+            for (size_t j = g.first; j < g.second; j++) {
+                unsigned char *p = b->d_scratch.get() + off;
+                const size_t N = ljobs[j].n + ljobs[j].attack;
+                ljobs[j].v = reinterpret_cast<float *>(p);
+                p += up(N * 4);
+                ljobs[j].bm = reinterpret_cast<float *>(p);
+                p += up((N / LIM_BLOCK + 1) * 4);
+                ljobs[j].a = reinterpret_cast<double *>(p);
+                p += up(N * 8);
+                ljobs[j].b = reinterpret_cast<double *>(p);
+                p += up(N * 8);
+                ljobs[j].sum = reinterpret_cast<double *>(p);
+                off += l_scratch[j];
+            }
+        }
+    }
+    std::vector<unsigned char> h(tab_bytes, 0);
+    if (!ajobs.empty()) std::memcpy(h.data(), ajobs.data(), ajobs.size() * sizeof(DynApplyJob));
+    if (!ljobs.empty()) std::memcpy(h.data() + o_lim, ljobs.data(), ljobs.size() * sizeof(LimJob));
+    if (b->n_red) std::memcpy(h.data() + o_bits, red_init.data(), b->n_red * 4);
+    TH_HIP(hipMemcpy(dt, h.data(), tab_bytes, hipMemcpyHostToDevice));  // (a fresh allocation: nothing on the stream reads it yet)
+    TH_HIP(launch_dyn_apply(reinterpret_cast<const DynApplyJob *>(dt), (uint32_t)ajobs.size(), max_n, c->stream));
+    for (auto &g : groups)
+        TH_HIP(launch_limiter(ljobs.data() + g.first, reinterpret_cast<const LimJob *>(dt + o_lim) + g.first, (uint32_t)(g.second - g.first), c->stream));
+    int rc = th_waveform_pyramid_dev(c, pdescs.data(), pdescs.size());
+    if (rc != TH_OK) return rc;
+    for (size_t i = 0; i < adescs.size(); i++) adescs[i].channels = aptrs[i].data();
+    b->loud.reset(new LoudnessBatch);
+    return loudness_enqueue(c, adescs.data(), adescs.size(), true, true, b->loud.get());
+}
+
+// after the stream has drained: the derived audio's stats and guard stats (GuardClippingStats, stats.rs:134-205)
+int derive_collect(const std::vector<std::pair<size_t, Track *>> &tracks, DeriveBatch *b) {
+    if (!b->loud) return TH_OK;
+    int rc = loudness_collect(b->loud.get(), false);
+    if (rc != TH_OK) return rc;
+    std::vector<unsigned long long> cnt(b->n_red);
+    std::vector<uint32_t> bits(b->n_red);
+    if (b->n_red) {
+        const size_t o_bits = b->o_cnt + (b->n_red * 8 + 255) / 256 * 256;
+        TH_HIP(hipMemcpy(cnt.data(), b->d_tab.get() + b->o_cnt, b->n_red * 8, hipMemcpyDeviceToHost));
+        TH_HIP(hipMemcpy(bits.data(), b->d_tab.get() + o_bits, b->n_red * 4, hipMemcpyDeviceToHost));
+    }
+    for (auto &it : tracks) {
+        Derived &d = b->of[it.first];
+        if (!d.active) continue;
+        loudness_result(*b->loud, d.loud_index, &d.stats);
+        const size_t n_ch = it.second->ch.size();
+        if (d.result == TH_GUARD_RESULT_BEFORE_CLIP) {  // from_wav_before_clip, per channel
+            for (size_t k = 0; k < n_ch; k++) {
+                float pk;
+                std::memcpy(&pk, &bits[d.red0 + k], 4);
+                th_guard_clip_stats st{};
+                if (pk > 1.0f) {
+                    st.max_reduction_gain_dB = db_from_amp(1.0f / pk);
+                    st.reduction_cnt = cnt[d.red0 + k];
+                }
+                d.guard_stats.push_back(st);
+            }
+        } else if (d.result == TH_GUARD_RESULT_GLOBAL_GAIN) {  // from_global_gain, for every channel
+            th_guard_clip_stats st{};
+            st.max_reduction_gain_dB = db_from_amp(d.global_gain);
+            d.guard_stats.assign(n_ch, st);
+        } else {  // from_gain_seq of the one gain row
+            th_guard_clip_stats st{};
+            if (d.limiting) {
+                float mn;
+                std::memcpy(&mn, &bits[d.red0], 4);
+                st.max_reduction_gain_dB = db_from_amp(mn);
+                st.reduction_cnt = cnt[d.red0];
+                d.gain_below_one = mn < 1.0f;
+            }
+            d.guard_stats.assign(1, st);
+        }
+    }
+    return TH_OK;
+}
+
+// the track takes its derived audio (or goes back to its original); the stream is idle
+void install_derived(Track &tr, Derived &d) {
+    if (tr.d_dyn) (void)hipFree(tr.d_dyn);
+    tr.d_dyn = d.d_pool;
+    d.d_pool = nullptr;
+    for (size_t k = 0; k < tr.ch.size(); k++) {
+        Channel &ch = tr.ch[k];
+        ch.d_wav = d.active ? d.aud[k] : ch.d_orig;
+        ch.d_draw = d.active ? d.draw[k] : ch.d_orig;
+        ch.d_pyr = d.active ? d.pyr[k] : ch.d_pyr_orig;
+    }
+    tr.norm_gain = d.gain;
+    tr.guard_result = d.result;
+    tr.global_gain = d.global_gain;
+    tr.d_gain = d.d_gain;
+    tr.gain_below_one = d.gain_below_one;
+    tr.stats = d.active ? d.stats : tr.orig_stats;
+    if (d.active) tr.guard_stats = std::move(d.guard_stats);
+    else tr.guard_stats.assign(tr.ch.size(), th_guard_clip_stats{});  // Audio::new: GlobalGain(1), default stats per channel
+}
+
+}  // namespace
+
 // ---------------------------------------------------------------------------------------------- steps th_tmg drives per slot
 namespace th {
 namespace tmi {
@@ -1541,11 +1835,19 @@ struct Staged {
     std::vector<NewSpec> fresh;
     std::map<size_t, Track> tracks;
     std::set<size_t> added;
+    // set_common_normalize / set_common_guard_clipping: the new settings, every track's derived audio, and the specs of the channels
+    // whose audio changes, computed from `views` (stand-ins that point at the staged audio)
+    bool dynamics = false;
+    int norm_kind = TH_NORM_OFF, guard_mode = TH_GUARD_REDUCE_GLOBAL_LEVEL;
+    float norm_target = 0.0f;
+    std::unique_ptr<DeriveBatch> derive;
+    std::list<Channel> views;
+    std::map<Channel *, Channel *> real_of;
 };
 
 void StagedDeleter::operator()(Staged *s) const {
     if (!s) return;
-    if (!s->fresh.empty() || !s->tracks.empty() || !s->created.empty()) {  // not committed: discard
+    if (!s->fresh.empty() || !s->tracks.empty() || !s->created.empty() || s->derive) {  // not committed: discard
         (void)hipSetDevice(s->tm->ctx->device);
         (void)hipStreamSynchronize(s->tm->copy_stream);
         (void)hipStreamSynchronize(s->tm->ctx->stream);
@@ -1585,6 +1887,57 @@ int prepare_setting(th_tm *tm, double win_ms, uint32_t t_overlap, uint32_t f_ove
     if (rc != TH_OK) return rc;  // (stg discards what was made)
     *out = std::move(stg);
     return TH_OK;
+}
+
+// set_common_normalize / set_common_guard_clipping (track.rs:329-337,432-436): every track re-derived from its resident original
+// into staged buffers, and the specs of every channel whose audio changes.  A track that is and stays its original is left alone
+// (its specs would come out the same bits).
+int prepare_dynamics(th_tm *tm, int kind, float target, int mode, StagedPtr *out) {
+    TH_REQUIRE(kind == TH_NORM_OFF || kind == TH_NORM_LUFS || kind == TH_NORM_RMS_DB || kind == TH_NORM_PEAK_DB, "unknown normalize kind %d", kind);
+    TH_REQUIRE(mode == TH_GUARD_CLIP || mode == TH_GUARD_REDUCE_GLOBAL_LEVEL || mode == TH_GUARD_LIMITER, "unknown guard-clipping mode %d", mode);
+    th_ctx *c = tm->ctx;
+    TH_HIP(hipSetDevice(c->device));
+    StagedPtr stg(new Staged);
+    stg->tm = tm;
+    stg->dynamics = true;
+    stg->norm_kind = kind;
+    stg->norm_target = target;
+    stg->guard_mode = mode;
+    stg->derive.reset(new DeriveBatch);
+    stg->derive->ctx = c;
+    std::vector<std::pair<size_t, Track *>> trs;
+    for (auto &kv : tm->tracks) trs.push_back({kv.first, &kv.second});
+    int rc = derive_enqueue(tm, trs, kind, target, mode, stg->derive.get());
+    if (rc == TH_OK) {
+        std::vector<std::pair<uint32_t, Channel *>> chans;
+        for (auto &kv : tm->tracks) {
+            const Derived &d = stg->derive->of[kv.first];
+            if (!d.active && !kv.second.d_dyn) continue;
+            for (size_t k = 0; k < kv.second.ch.size(); k++) {
+                Channel &real = kv.second.ch[k];
+                stg->views.emplace_back();
+                Channel &v = stg->views.back();
+                v.d_wav = d.active ? d.aud[k] : real.d_orig;
+                v.n = real.n;
+                stg->real_of[&v] = &real;
+                chans.push_back({kv.second.sr, &v});
+            }
+        }
+        rc = compute_specs(tm, setting_of(tm), chans, stg->created, &stg->fresh);
+    }
+    const hipError_t se = hipStreamSynchronize(c->stream);
+    if (rc != TH_OK) return rc;  // (stg discards what was made)
+    TH_HIP(se);
+    rc = derive_collect(trs, stg->derive.get());
+    if (rc != TH_OK) return rc;
+    *out = std::move(stg);
+    return TH_OK;
+}
+
+void get_common_dynamics(th_tm *tm, int *kind, float *target, int *mode) {
+    if (kind) *kind = tm->norm_kind;
+    if (target) *target = tm->norm_target;
+    if (mode) *mode = tm->guard_mode;
 }
 
 int prepare_add(th_tm *tm, size_t n_tracks, const size_t *ids, const uint32_t *srs, const uint32_t *n_channels,
@@ -1667,6 +2020,8 @@ int prepare_add(th_tm *tm, size_t n_tracks, const size_t *ids, const uint32_t *s
                 ch.pyr_levels = lv;
                 ch.d_wav = static_cast<float *>(tr.d_pool) + (size_t)k * (wav_f + pyr_f);
                 ch.d_pyr = ch.d_wav + wav_f;
+                ch.d_draw = ch.d_orig = ch.d_wav;
+                ch.d_pyr_orig = ch.d_pyr;
                 e = hipMemcpyAsync(ch.d_wav, channels_flat[flat0[t] + k], ch.n * sizeof(float), hipMemcpyHostToDevice, tm->copy_stream);
                 bytes += ch.n * sizeof(float);
                 // (std::map nodes and this vector do not move any more: the pointer stays valid while later groups are staged)
@@ -1692,7 +2047,8 @@ int prepare_add(th_tm *tm, size_t n_tracks, const size_t *ids, const uint32_t *s
             loud.emplace_back(new LoudnessBatch);
             rc = loudness_enqueue(c, adescs.data(), adescs.size(), true, true, loud.back().get());
         }
-        if (rc == TH_OK) rc = compute_specs(tm, st, chans, created, &fresh, &pending);
+        // (with a normalise target the specs come from the derived audio, which needs the stats first: below)
+        if (rc == TH_OK && tm->norm_kind == TH_NORM_OFF) rc = compute_specs(tm, st, chans, created, &fresh, &pending);
         t_launch += now() - tl0;
     }
     const double tp1 = now();
@@ -1709,6 +2065,28 @@ int prepare_add(th_tm *tm, size_t n_tracks, const size_t *ids, const uint32_t *s
         for (size_t k = 0; rc == TH_OK && i < loud_ids.size() && loud_ids[i].second == g; i++, k++)
             loudness_result(*loud[g], k, &staged[loud_ids[i].first].stats);
     }
+    for (auto &kv : staged) {
+        kv.second.orig_stats = kv.second.stats;
+        kv.second.guard_stats.assign(kv.second.ch.size(), th_guard_clip_stats{});
+    }
+    if (rc == TH_OK && tm->norm_kind != TH_NORM_OFF) {
+        // track.normalize(common_normalize, common_guard_clipping) — track.rs:217: one synchronisation between the stats and the rest
+        std::vector<std::pair<size_t, Track *>> trs;
+        for (auto &kv : staged) trs.push_back({kv.first, &kv.second});
+        DeriveBatch db;
+        rc = derive_enqueue(tm, trs, tm->norm_kind, tm->norm_target, tm->guard_mode, &db);
+        const hipError_t se = hipStreamSynchronize(c->stream);
+        if (rc == TH_OK && se != hipSuccess) rc = th::fail(TH_ERR_HIP, "%s", hipGetErrorString(se));
+        if (rc == TH_OK) rc = derive_collect(trs, &db);
+        if (rc == TH_OK) {
+            std::vector<std::pair<uint32_t, Channel *>> chans;
+            for (auto &kv : staged) {
+                install_derived(kv.second, db.of[kv.first]);
+                for (Channel &ch : kv.second.ch) chans.push_back({kv.second.sr, &ch});
+            }
+            rc = compute_specs(tm, st, chans, created, &fresh);
+        }
+    }
     if (prof) fprintf(stderr, "th_tm_add_tracks prof: staging + launches %.2f ms (of which pyramid / STFT launches %.2f), drain %.2f\n", tp1 - tp0, t_launch, now() - tp1);
     if (rc != TH_OK) {
         abort_staging();
@@ -1721,6 +2099,18 @@ int prepare_add(th_tm *tm, size_t n_tracks, const size_t *ids, const uint32_t *s
 
 void commit(th_tm *tm, StagedPtr s) {
     (void)hipSetDevice(tm->ctx->device);
+    if (s->dynamics) {
+        tm->norm_kind = s->norm_kind;
+        tm->norm_target = s->norm_target;
+        tm->guard_mode = s->guard_mode;
+        for (auto &kv : s->derive->of) install_derived(tm->tracks.at(kv.first), kv.second);
+        for (NewSpec &n : s->fresh) n.ch = s->real_of.at(n.ch);
+        commit_specs(s->fresh);
+        for (auto &kv : s->created) tm->plans[kv.first] = kv.second;
+        s->created.clear();
+        s->derive.reset();
+        return;
+    }
     if (s->setting) {
         tm->win_ms = s->st.win_ms;
         tm->t_overlap = s->st.t_overlap;
@@ -1771,3 +2161,111 @@ int settle(th_tm *tm) {
 
 }  // namespace tmi
 }  // namespace th
+
+// ---------------------------------------------------------------------------------------------- normalise + clip guard: the entries
+namespace {
+int set_common_dynamics(th_tm *tm, int kind, float target, int mode) {
+    tmi::StagedPtr staged;
+    int rc = tmi::prepare_dynamics(tm, kind, target, mode, &staged);
+    if (rc != TH_OK) return rc;
+    tmi::commit(tm, std::move(staged));
+    std::vector<size_t> upd;
+    rc = update_spec_imgs(tm, true, &upd);  // update_all_specs_imgs (forced)
+    tm->invalidate_all();
+    return writer_done(tm, rc);
+}
+}  // namespace
+
+TH_API int th_tm_set_common_normalize(th_tm *tm, int kind, float target) {
+    TH_TRY
+    TH_REQUIRE(tm, "tm is NULL");
+    std::unique_lock<std::shared_mutex> wl(tm->rw);
+    return set_common_dynamics(tm, kind, target, tm->guard_mode);
+    TH_CATCH
+}
+
+TH_API int th_tm_set_common_guard_clipping(th_tm *tm, int mode) {
+    TH_TRY
+    TH_REQUIRE(tm, "tm is NULL");
+    std::unique_lock<std::shared_mutex> wl(tm->rw);
+    return set_common_dynamics(tm, tm->norm_kind, tm->norm_target, mode);
+    TH_CATCH
+}
+
+TH_API int th_tm_get_common_dynamics(th_tm *tm, int *kind, float *target, int *mode) {
+    TH_TRY
+    TH_REQUIRE(tm, "tm is NULL");
+    std::shared_lock<std::shared_mutex> rl(tm->rw);
+    tmi::get_common_dynamics(tm, kind, target, mode);
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_tm_get_track_dynamics(th_tm *tm, size_t id, th_track_dynamics *out) {
+    TH_TRY
+    TH_REQUIRE(tm && out, "NULL argument");
+    std::shared_lock<std::shared_mutex> rl(tm->rw);
+    auto it = tm->tracks.find(id);
+    if (it == tm->tracks.end()) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", id);
+    const Track &tr = it->second;
+    *out = th_track_dynamics{};
+    out->normalize_gain = tr.norm_gain;
+    out->guard_result = tr.guard_result;
+    out->global_gain = tr.global_gain;
+    out->draws_before_clip = tr.guard_result == TH_GUARD_RESULT_BEFORE_CLIP;
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_tm_get_guard_clip_stats(th_tm *tm, size_t id, th_guard_clip_stats *out, size_t cap, size_t *n) {
+    TH_TRY
+    TH_REQUIRE(tm && n, "NULL argument");
+    std::shared_lock<std::shared_mutex> rl(tm->rw);
+    auto it = tm->tracks.find(id);
+    if (it == tm->tracks.end()) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", id);
+    const std::vector<th_guard_clip_stats> &gs = it->second.guard_stats;
+    // format_guard_clip_stats (audio.rs:94-111): every channel's entry under Clip, else the first
+    *n = tm->guard_mode == TH_GUARD_CLIP ? gs.size() : std::min<size_t>(1, gs.size());
+    if (cap < *n || (*n && !out)) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu entries", *n);
+    for (size_t i = 0; i < *n; i++) out[i] = gs[i];
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_tm_get_limiter_gain(th_tm *tm, size_t id, float *out, size_t cap, size_t *n) {
+    TH_TRY
+    TH_REQUIRE(tm && n, "NULL argument");
+    std::unique_lock<std::shared_mutex> wl(tm->rw);  // uses the context stream: exclusive, like th_tm_copy_spec
+    TH_HIP(hipSetDevice(tm->ctx->device));
+    auto it = tm->tracks.find(id);
+    if (it == tm->tracks.end()) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", id);
+    const Track &tr = it->second;
+    // guard_clipping_gain (audio.rs:80-92)
+    const bool seq = tr.guard_result == TH_GUARD_RESULT_GAIN_SEQUENCE, full = seq && tr.d_gain && tr.gain_below_one;
+    *n = !seq ? 0 : full ? tr.ch[0].n : 1;
+    if (cap < *n || (*n && !out)) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu floats", *n);
+    if (full) {
+        TH_HIP(hipMemcpyAsync(out, tr.d_gain, *n * sizeof(float), hipMemcpyDeviceToHost, tm->ctx->stream));
+        TH_HIP(hipStreamSynchronize(tm->ctx->stream));
+    } else if (seq) {
+        out[0] = 1.0f;
+    }
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_tm_copy_audio(th_tm *tm, size_t id, uint32_t ch, int which, float *out, size_t cap) {
+    TH_TRY
+    TH_REQUIRE(tm && out, "NULL argument");
+    TH_REQUIRE(which >= 0 && which <= 2, "which must be 0 (audio), 1 (drawn) or 2 (original)");
+    std::unique_lock<std::shared_mutex> wl(tm->rw);
+    TH_HIP(hipSetDevice(tm->ctx->device));
+    Channel *c = find_channel(tm, id, ch);
+    if (!c) return fail(TH_ERR_NOT_FOUND, "Track %zu channel %u does not exist", id, ch);
+    if (cap < c->n) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu floats", c->n);
+    const float *src = which == 0 ? c->d_wav : which == 1 ? c->d_draw : c->d_orig;
+    TH_HIP(hipMemcpyAsync(out, src, c->n * sizeof(float), hipMemcpyDeviceToHost, tm->ctx->stream));
+    TH_HIP(hipStreamSynchronize(tm->ctx->stream));
+    return TH_OK;
+    TH_CATCH
+}

@@ -44,6 +44,10 @@ int prepare_setting(th_tm *tm, double win_ms, uint32_t t_overlap, uint32_t f_ove
 // add_tracks (core/mod.rs:62-71): arguments as th_tm_add_tracks, already validated
 int prepare_add(th_tm *tm, size_t n_tracks, const size_t *ids, const uint32_t *srs, const uint32_t *n_channels,
                 const float *const *channels_flat, const size_t *n_samples, StagedPtr *out);
+// set_common_normalize / set_common_guard_clipping: every track's audio re-derived from its original, and the specs of the channels
+// it changes; TH_ERR_INVALID_ARG for an unknown kind or mode
+int prepare_dynamics(th_tm *tm, int kind, float target, int mode, StagedPtr *out);
+void get_common_dynamics(th_tm *tm, int *kind, float *target, int *mode);
 void commit(th_tm *tm, StagedPtr staged);
 
 // update_spec_imgs against `global` (NULL: the manager's own tracks, as th_tm_* does), then the writer's final wait:

@@ -524,6 +524,83 @@ TH_API int th_tmg_get_spectrogram_tiles(th_tmg *g, const th_tile_request *reqs, 
     TH_CATCH
 }
 
+// set_common_normalize / set_common_guard_clipping: every slot re-derives its tracks into staged buffers; all commit, or all discard
+namespace {
+int set_common_dynamics_all(th_tmg *g, int kind, float target, int mode) {
+    std::vector<tmi::StagedPtr> staged(g->slots.size());
+    int rc = for_slots(g, all_slots(g), [&](uint32_t s) -> int {
+        std::unique_lock<std::shared_mutex> sl(tmi::rw_of(g->slots[s].tm));
+        return tmi::prepare_dynamics(g->slots[s].tm, kind, target, mode, &staged[s]);
+    });
+    if (rc != TH_OK) return rc;  // (staged: discarded on the way out)
+    for (size_t s = 0; s < staged.size(); s++) {
+        std::unique_lock<std::shared_mutex> sl(tmi::rw_of(g->slots[s].tm));
+        tmi::commit(g->slots[s].tm, std::move(staged[s]));
+    }
+    rc = requantise_all(g, true, false, nullptr);
+    g->revs.invalidate_all();
+    sync_revisions(g);
+    return rc;
+}
+}  // namespace
+
+TH_API int th_tmg_set_common_normalize(th_tmg *g, int kind, float target) {
+    TH_TRY
+    TH_REQUIRE(g, "tmg is NULL");
+    std::unique_lock<std::shared_mutex> wl(g->rw);
+    int mode = 0;
+    tmi::get_common_dynamics(g->slots[0].tm, nullptr, nullptr, &mode);  // (every slot holds the common settings)
+    return set_common_dynamics_all(g, kind, target, mode);
+    TH_CATCH
+}
+
+TH_API int th_tmg_set_common_guard_clipping(th_tmg *g, int mode) {
+    TH_TRY
+    TH_REQUIRE(g, "tmg is NULL");
+    std::unique_lock<std::shared_mutex> wl(g->rw);
+    int kind = 0;
+    float target = 0.0f;
+    tmi::get_common_dynamics(g->slots[0].tm, &kind, &target, nullptr);
+    return set_common_dynamics_all(g, kind, target, mode);
+    TH_CATCH
+}
+
+TH_API int th_tmg_get_common_dynamics(th_tmg *g, int *kind, float *target, int *mode) {
+    TH_TRY
+    TH_REQUIRE(g, "tmg is NULL");
+    std::shared_lock<std::shared_mutex> rl(g->rw);
+    return th_tm_get_common_dynamics(g->slots[0].tm, kind, target, mode);
+    TH_CATCH
+}
+
+TH_API int th_tmg_get_track_dynamics(th_tmg *g, size_t id, th_track_dynamics *out) {
+    TH_TRY
+    TMG_OWNER(g, id, "Track %zu", id);
+    return th_tm_get_track_dynamics(tm_, id, out);
+    TH_CATCH
+}
+
+TH_API int th_tmg_get_guard_clip_stats(th_tmg *g, size_t id, th_guard_clip_stats *out, size_t cap, size_t *n) {
+    TH_TRY
+    TMG_OWNER(g, id, "Track %zu", id);
+    return th_tm_get_guard_clip_stats(tm_, id, out, cap, n);
+    TH_CATCH
+}
+
+TH_API int th_tmg_get_limiter_gain(th_tmg *g, size_t id, float *out, size_t cap, size_t *n) {
+    TH_TRY
+    TMG_OWNER(g, id, "Track %zu", id);
+    return th_tm_get_limiter_gain(tm_, id, out, cap, n);
+    TH_CATCH
+}
+
+TH_API int th_tmg_copy_audio(th_tmg *g, size_t id, uint32_t ch, int which, float *out, size_t cap) {
+    TH_TRY
+    TMG_OWNER(g, id, "Track %zu", id);
+    return th_tm_copy_audio(tm_, id, ch, which, out, cap);
+    TH_CATCH
+}
+
 TH_API int th_tmg_set_lod_source(th_tmg *g, int per_request) {
     TH_TRY
     TH_REQUIRE(g, "tmg is NULL");
