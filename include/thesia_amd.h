@@ -572,6 +572,57 @@ TH_API int th_tm_get_limiter_gain(th_tm *tm, size_t id, float *out, size_t cap, 
  * (channel_for_drawing), 2 the original */
 TH_API int th_tm_copy_audio(th_tm *tm, size_t id, uint32_t ch, int which, float *out, size_t cap);
 
+/* ---------------------------------------------------------------- spectrum of a time range */
+/* The per-channel spectrum over a time range, on the channel's own frequency axis (linear bins or the Mel bank): what upstream's
+ * planned "average FFT magnitude", "region selection" and "export as figures" need.  No reference implementation exists; the
+ * definition is this one.  For the resident spec s[t][h] of a channel (f32 dB, frame-major, the values th_tm_copy_spec returns,
+ * unclamped), frames [f0, f1), n = f1 - f0, column h:
+ *   TH_SPECTRUM_MEAN_AMP    20 log10((1 / n) sum_t 10^(s / 20))
+ *   TH_SPECTRUM_MEAN_POWER  10 log10((1 / n) sum_t 10^(s / 10))
+ *   TH_SPECTRUM_MAX         max_t s
+ * H = the spec's height f32 values, index 0 the lowest frequency.  A row value of -inf is amplitude 0 and still counts in n; a
+ * column that is all -inf gives -inf; a NaN anywhere in the column's range gives NaN under every kind; n = 0 gives a row of NaN.
+ * The sums are f64 in a fixed order, 10^x to f32 accuracy: a mean is within max(2e-5 dB, 2 f32 ulps) of the f64 evaluation, the
+ * maximum is exact (where a column's maximum is zero and the range holds both +0 and -0, which of the two is returned is not
+ * specified).
+ * Frames from seconds (tracks of one project differ in rate and hop): frame t is centred on sample t hop and is selected when
+ * its centre lies in [start_sec, end_sec): f0 = clamp(ceil(start_sec sr / hop), 0, T); f1 = T for end_sec = +inf, else
+ * max(f0, clamp(ceil(end_sec sr / hop), 0, T)); the arithmetic is C double, (sec * (double)sr) / (double)hop.
+ * th_spectrum_frame_range (host only) is that definition; TH_ERR_INVALID_ARG when start_sec is NaN, negative or infinite,
+ * end_sec is NaN or below start_sec, or sr or hop is zero.
+ * th_tm_get_spectra: rows packed dense, back to back, in request order; info[i] says where row i starts, its length, the frames
+ * it covers and the spectrogram revision it belongs to (a host caches by it).  *out_len = floats needed; TH_ERR_BUFFER_TOO_SMALL
+ * when cap_floats is less, with info and *out_len filled (out may then be NULL to query the size).  An unknown id or a channel
+ * without a resident spec: TH_ERR_NOT_FOUND; a channel the track does not have, an unknown kind or a bad time:
+ * TH_ERR_INVALID_ARG; the first faulty request in request order decides; on any error nothing is written to out.  These are
+ * readers, like the tile getters: they share the lock, run on a reader slot's own stream and wait for no other reader — except
+ * when a slot's scratch grows (the first call, or a batch larger than any before on that slot): the allocation waits for the
+ * device.  Scratch (partial sums, and a result buffer for results above the slot's pinned staging) is made on the first call and
+ * only grows; a manager that never calls them holds none.  A request's values
+ * depend on its rows, range and kind only — not on the rest of the batch, the slot, the call, or th_tm against th_tmg.
+ * th_tm_get_spectrum: one request; info may be NULL (info->height is the size needed on TH_ERR_BUFFER_TOO_SMALL). */
+#define TH_SPECTRUM_MEAN_AMP 0
+#define TH_SPECTRUM_MEAN_POWER 1
+#define TH_SPECTRUM_MAX 2
+typedef struct {
+    size_t id;
+    uint32_t ch;
+    uint32_t kind; /* TH_SPECTRUM_* */
+    double start_sec, end_sec;
+} th_spectrum_request;
+typedef struct {
+    uint64_t offset; /* floats into out */
+    uint64_t height; /* H of that channel's spec */
+    uint64_t frame_start, frame_end;
+    uint64_t spectrogram_revision;
+} th_spectrum_info;
+TH_API int th_spectrum_frame_range(uint32_t sr, size_t hop, size_t n_frames, double start_sec, double end_sec,
+                                   size_t *frame_start, size_t *frame_end);
+TH_API int th_tm_get_spectra(th_tm *tm, const th_spectrum_request *reqs, size_t n, float *out, size_t cap_floats,
+                             th_spectrum_info *info /* n */, size_t *out_len);
+TH_API int th_tm_get_spectrum(th_tm *tm, size_t id, uint32_t ch, int kind, double start_sec, double end_sec, float *out,
+                              size_t cap_floats, th_spectrum_info *info);
+
 /* ---------------------------------------------------------------- TrackManager over several devices (one process) */
 /* th_tmg: the th_tm_* calls above, call for call, with a th_tmg * in place of the th_tm *; a multi-GPU host swaps one for
  * the other.  Every result — updated ids, max_sr, db state, revisions, specs, images, tile bytes, batch offsets, render
@@ -636,6 +687,12 @@ TH_API int th_tmg_get_track_dynamics(th_tmg *tmg, size_t id, th_track_dynamics *
 TH_API int th_tmg_get_guard_clip_stats(th_tmg *tmg, size_t id, th_guard_clip_stats *out, size_t cap, size_t *n);
 TH_API int th_tmg_get_limiter_gain(th_tmg *tmg, size_t id, float *out, size_t cap, size_t *n);
 TH_API int th_tmg_copy_audio(th_tmg *tmg, size_t id, uint32_t ch, int which, float *out, size_t cap);
+/* spectra: the batch is split by owning slot and the slots are served side by side; the floats and infos are those of one th_tm
+ * (request order, packed dense), the revision stamped is the manager's own */
+TH_API int th_tmg_get_spectra(th_tmg *tmg, const th_spectrum_request *reqs, size_t n, float *out, size_t cap_floats,
+                              th_spectrum_info *info /* n */, size_t *out_len);
+TH_API int th_tmg_get_spectrum(th_tmg *tmg, size_t id, uint32_t ch, int kind, double start_sec, double end_sec, float *out,
+                               size_t cap_floats, th_spectrum_info *info);
 
 /* Test and measurement entry points (kernel selectors for A/B runs, per-launch kernel timing, replacing a resident image
  * with given pixels) are NOT part of this interface: include/thesia_amd_testing.h declares them; a thesia host binds none. */

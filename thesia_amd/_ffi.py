@@ -93,6 +93,15 @@ class GuardClipStats(C.Structure):  # th_guard_clip_stats
     _fields_ = [("max_reduction_gain_dB", C.c_float), ("reserved", C.c_uint32), ("reduction_cnt", C.c_uint64)]
 
 
+class SpectrumRequest(C.Structure):  # th_spectrum_request
+    _fields_ = [("id", C.c_size_t), ("ch", C.c_uint32), ("kind", C.c_uint32), ("start_sec", C.c_double), ("end_sec", C.c_double)]
+
+
+class SpectrumInfo(C.Structure):  # th_spectrum_info
+    _fields_ = [("offset", C.c_uint64), ("height", C.c_uint64), ("frame_start", C.c_uint64), ("frame_end", C.c_uint64),
+                ("spectrogram_revision", C.c_uint64)]
+
+
 class PyramidDesc(C.Structure):
     _fields_ = [("wav", C.c_void_p), ("out", C.c_void_p), ("n_samples", C.c_uint64), ("n_levels", C.c_uint32),
                 ("first_level", C.c_uint32)]
@@ -272,6 +281,11 @@ _SIGS = {
     "th_tmg_get_guard_clip_stats": [vp, C.c_size_t, C.POINTER(GuardClipStats), C.c_size_t, c_szp],
     "th_tmg_get_limiter_gain": [vp, C.c_size_t, c_f32p, C.c_size_t, c_szp],
     "th_tmg_copy_audio": [vp, C.c_size_t, C.c_uint32, C.c_int, c_f32p, C.c_size_t],
+    "th_spectrum_frame_range": [C.c_uint32, C.c_size_t, C.c_size_t, C.c_double, C.c_double, c_szp, c_szp],
+    "th_tm_get_spectra": [vp, C.POINTER(SpectrumRequest), C.c_size_t, c_f32p, C.c_size_t, C.POINTER(SpectrumInfo), c_szp],
+    "th_tm_get_spectrum": [vp, C.c_size_t, C.c_uint32, C.c_int, C.c_double, C.c_double, c_f32p, C.c_size_t, C.POINTER(SpectrumInfo)],
+    "th_tmg_get_spectra": [vp, C.POINTER(SpectrumRequest), C.c_size_t, c_f32p, C.c_size_t, C.POINTER(SpectrumInfo), c_szp],
+    "th_tmg_get_spectrum": [vp, C.c_size_t, C.c_uint32, C.c_int, C.c_double, C.c_double, c_f32p, C.c_size_t, C.POINTER(SpectrumInfo)],
     "th_tile_cache_create": [C.c_size_t, C.POINTER(vp)],
     "th_tile_cache_destroy": [vp],
     "th_tile_cache_lookup": [vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), c_u8p, C.c_size_t,

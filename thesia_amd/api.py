@@ -22,6 +22,7 @@ LINEAR, MEL = 0, 1
 NORM_OFF, NORM_LUFS, NORM_RMS_DB, NORM_PEAK_DB = 0, 1, 2, 3
 GUARD_CLIP, GUARD_REDUCE_GLOBAL_LEVEL, GUARD_LIMITER = 0, 1, 2
 GUARD_RESULT_GLOBAL_GAIN, GUARD_RESULT_BEFORE_CLIP, GUARD_RESULT_GAIN_SEQUENCE = 0, 1, 2
+SPECTRUM_MEAN_AMP, SPECTRUM_MEAN_POWER, SPECTRUM_MAX = 0, 1, 2
 WAVEFORM_TILE_MAX_BYTES = 24 + 1024 * 12
 SPECTROGRAM_TILE_MAX_BYTES = 40 + 520 * 520 * 4
 
@@ -153,6 +154,50 @@ def limiter_params(sr: int) -> dict:
     o = _ffi.LimiterDesc()
     check(lib.th_limiter_params(sr, C.byref(o)))
     return {"attack": o.attack, "hold_length": o.hold_length, "release_samples": o.release_samples, "box_len": list(o.box_len)}
+
+
+def spectrum_frame_range(sr: int, hop: int, n_frames: int, start_sec: float = 0.0, end_sec: float = float("inf")):
+    """-> (frame_start, frame_end): the frames of n_frames whose centre t * hop lies in [start_sec, end_sec) (host arithmetic)"""
+    f0, f1 = C.c_size_t(), C.c_size_t()
+    check(lib.th_spectrum_frame_range(sr, hop, n_frames, start_sec, end_sec, C.byref(f0), C.byref(f1)))
+    return f0.value, f1.value
+
+
+def _spectrum_info_dict(o) -> dict:
+    return {k: int(getattr(o, k)) for k, _ in o._fields_}
+
+
+class _SpectrumMethods:
+    """the spectrum of a time range of resident specs (th_tm_* and th_tmg_*: _PFX)"""
+
+    def spectra(self, requests):
+        """th_tm_get_spectra: requests = iterable of (track_id, ch, kind[, start_sec[, end_sec]]) -> list of (f32 row, info dict),
+        in request order.  kind: SPECTRUM_MEAN_AMP / SPECTRUM_MEAN_POWER / SPECTRUM_MAX; the range defaults to the whole track."""
+        reqs = [tuple(r) + (0.0, float("inf"))[len(r) - 3:] for r in requests]
+        n = len(reqs)
+        if n == 0:
+            return []
+        arr = (_ffi.SpectrumRequest * n)(*[_ffi.SpectrumRequest(*r) for r in reqs])
+        info = (_ffi.SpectrumInfo * n)()
+        need = C.c_size_t()
+        fn = getattr(lib, self._PFX + "get_spectra")
+        rc = fn(self.handle, arr, n, None, 0, info, C.byref(need))
+        if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+            check(rc)
+        out = np.empty(need.value, np.float32)
+        check(fn(self.handle, arr, n, _ptr(out, c_f32p), out.size, info, C.byref(need)))
+        return [(out[o.offset: o.offset + o.height], _spectrum_info_dict(o)) for o in info]
+
+    def spectrum(self, track_id: int, ch: int, kind: int, start_sec: float = 0.0, end_sec: float = float("inf")):
+        """th_tm_get_spectrum: the spectrum of one channel over [start_sec, end_sec) -> (f32 row of the spec's height, info dict)"""
+        info = _ffi.SpectrumInfo()
+        fn = getattr(lib, self._PFX + "get_spectrum")
+        rc = fn(self.handle, track_id, ch, kind, start_sec, end_sec, None, 0, C.byref(info))
+        if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+            check(rc)
+        out = np.empty(info.height, np.float32)
+        check(fn(self.handle, track_id, ch, kind, start_sec, end_sec, _ptr(out, c_f32p), out.size, C.byref(info)))
+        return out, _spectrum_info_dict(info)
 
 
 class _DynamicsMethods:
@@ -646,7 +691,7 @@ class TileCache:
                 "spectrogram_revision": sr.value, "hits": h.value, "misses": m.value}
 
 
-class TrackManager(_DynamicsMethods):
+class TrackManager(_DynamicsMethods, _SpectrumMethods):
     """th_tm: mirror of core/mod.rs TrackManager with HBM-resident audio / specs / images."""
     _PFX = "th_tm_"
 
@@ -846,7 +891,7 @@ class TrackManager(_DynamicsMethods):
         return out[: n.value].tobytes()
 
 
-class MultiTrackManager(_DynamicsMethods):
+class MultiTrackManager(_DynamicsMethods, _SpectrumMethods):
     """th_tmg: the TrackManager over several devices of one process (duplicates allowed: [0, 0] is two slots on one card).
     Same method names as TrackManager; results are bit-identical to one TrackManager holding every track."""
     _PFX = "th_tmg_"

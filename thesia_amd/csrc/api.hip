@@ -1598,6 +1598,16 @@ TH_API int th_limiter_params(uint32_t sr, th_limiter_desc *out) {
     TH_CATCH
 }
 
+TH_API int th_spectrum_frame_range(uint32_t sr, size_t hop, size_t n_frames, double start_sec, double end_sec, size_t *frame_start,
+                                   size_t *frame_end) {
+    TH_TRY
+    TH_REQUIRE(frame_start && frame_end, "NULL argument");
+    TH_REQUIRE(spectrum_frame_range(sr, hop, n_frames, start_sec, end_sec, frame_start, frame_end),
+               "bad time range [%g, %g) s at sr %u, hop %zu", start_sec, end_sec, sr, hop);
+    return TH_OK;
+    TH_CATCH
+}
+
 namespace th {
 
 LoudnessBatch::~LoudnessBatch() {

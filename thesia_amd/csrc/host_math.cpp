@@ -911,4 +911,15 @@ float db_from_amp(float x) {
     return x == 0.0f ? -INFINITY : (float)(20.0 * std::log10((double)x));
 }
 
+bool spectrum_frame_range(uint32_t sr, size_t hop, size_t n_frames, double start_sec, double end_sec, size_t *f0, size_t *f1) {
+    if (!(start_sec >= 0.0) || std::isinf(start_sec) || std::isnan(end_sec) || end_sec < start_sec || sr == 0 || hop == 0) return false;
+    auto first_at_or_after = [&](double sec) -> size_t {  // (sec >= 0)
+        const double x = std::ceil((sec * (double)sr) / (double)hop);
+        return x >= (double)n_frames ? n_frames : (size_t)x;
+    };
+    *f0 = first_at_or_after(start_sec);
+    *f1 = std::isinf(end_sec) ? n_frames : std::max(*f0, first_at_or_after(end_sec));
+    return true;
+}
+
 }  // namespace th

@@ -93,6 +93,11 @@ bool limiter_params(uint32_t sr, LimiterParams *out);
 // dB_from_amp_default of an f32 (decibel.rs:66-102, amin = 0): 20 log10 x, the logarithm in f64 and rounded once (as the AudioStats are)
 float db_from_amp(float x);
 
+// ---- spectrum of a time range (th_tm_get_spectra): the frames whose centre t hop lies in [start_sec, end_sec), as [f0, f1) of
+// n_frames: f0 = clamp(ceil(start_sec sr / hop), 0, T), f1 = T for end_sec = +inf, else max(f0, clamp(ceil(end_sec sr / hop), 0, T)),
+// in double.  false: start_sec NaN, negative or infinite, end_sec NaN or below start_sec, sr or hop zero.
+bool spectrum_frame_range(uint32_t sr, size_t hop, size_t n_frames, double start_sec, double end_sec, size_t *f0, size_t *f1);
+
 inline bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
 inline unsigned ilog2(size_t n) {
     unsigned l = 0;

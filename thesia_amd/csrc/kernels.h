@@ -329,4 +329,22 @@ struct LimJob {             // one track through PerfectLimiter::process_inplace
 };
 hipError_t launch_limiter(const LimJob *h_jobs, const LimJob *d_jobs, uint32_t n_jobs, hipStream_t s);
 
+// ---- kernels_spectrum.hip: per-column mean amplitude / mean power / maximum over a frame range of resident dB rows
+struct SpectrumShape {      // how one job is cut (spectrum_shape: from the job's own height and frame count alone)
+    uint32_t log_ct;        // a column tile is 2^log_ct quads of 4 columns (8 .. 64 quads)
+    uint32_t n_ctiles, n_slices, slice_len;  // frames [f0 + s slice_len, ...) are slice s; n_slices = 0 for an empty range
+};
+SpectrumShape spectrum_shape(uint32_t height, uint32_t n_frames);
+struct SpectrumJob {        // one (channel, frame range, kind)
+    const float *rows;      // T x pitch f32 dB, frame-major, 16-byte aligned
+    double *part;           // scratch: n_slices x (n_ctiles << (log_ct + 2)) partials
+    float *out;             // H results (device memory or mapped host memory)
+    uint64_t pitch;         // floats per row: a multiple of 4, >= H
+    uint32_t H, f0, f1, kind;  // frames [f0, f1), TH_SPECTRUM_*
+    uint32_t log_ct, n_ctiles, n_slices, slice_len;
+};
+static_assert(sizeof(SpectrumJob) == 64, "SpectrumJob must have no implicit padding");
+// max_blocks: the largest n_ctiles * n_slices of the jobs; max_height: the largest H
+hipError_t launch_spectrum(const SpectrumJob *d_jobs, uint32_t n_jobs, uint32_t max_blocks, uint32_t max_height, hipStream_t s);
+
 }  // namespace th

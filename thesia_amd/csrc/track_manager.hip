@@ -70,6 +70,9 @@ struct ReaderSlot {
     uint8_t *h_tile = nullptr;  // pinned, mapped into the device's address space
     uint8_t *h_tile_dev = nullptr;  // its device-side address
     bool busy = false;
+    // th_tm_get_spectra: job table, f64 partial sums, and the results of batches above h_tile (empty until the first such call;
+    // grow-only, freed with the slot)
+    th::DeviceTable spec_jobs, spec_part, spec_out;
 };
 constexpr size_t TILE_BYTES_MAX = 520 * 520 * 4;  // 512 core + 2 x 4 gutter (render_tiles.rs:15-16); >= 1024 * 12 waveform bins
 constexpr size_t MAX_READER_SLOTS = 16;
@@ -1389,6 +1392,129 @@ TH_API int th_tm_get_spectrogram_tiles(th_tm *tm, const th_tile_request *reqs, s
         put_u32(rec + 36, (uint32_t)it.g.origin_y);
     }
     return TH_OK;
+    TH_CATCH
+}
+
+// One request checked against the manager, in the order every caller reports: the id, the channel, the kind, the spec, the time
+// range, the shape.  i: the request's index (for the message).  The caller holds the lock.
+namespace {
+int check_spectrum_request(th_tm *tm, const Setting &st, const th_spectrum_request &r, size_t i, const Channel **ch, size_t *f0, size_t *f1) {
+    auto it = tm->tracks.find(r.id);
+    if (it == tm->tracks.end()) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", r.id);
+    const Track &tr = it->second;
+    TH_REQUIRE(r.ch < tr.ch.size(), "request %zu: track %zu has no channel %u", i, r.id, r.ch);
+    TH_REQUIRE(r.kind <= TH_SPECTRUM_MAX, "request %zu: unknown spectrum kind %u", i, r.kind);
+    const Channel &c = tr.ch[r.ch];
+    if (!c.has_spec) return fail(TH_ERR_NOT_FOUND, "Spectrogram %zu_%u does not exist", r.id, r.ch);
+    size_t hop, win, n_fft;
+    calc_framing_params(st.win_ms, st.t_overlap, st.f_overlap, tr.sr, &hop, &win, &n_fft);
+    TH_REQUIRE(spectrum_frame_range(tr.sr, hop, c.T, r.start_sec, r.end_sec, f0, f1), "request %zu: bad time range [%g, %g) s", i,
+               r.start_sec, r.end_sec);
+    if (c.T > INT32_MAX || c.H > INT32_MAX || (c.spec_pitch & 3) != 0)
+        return fail(TH_ERR_UNSUPPORTED, "Spectrogram %zu_%u: %zu x %zu rows of pitch %zu", r.id, r.ch, c.T, c.H, c.spec_pitch);
+    *ch = &c;
+    return TH_OK;
+}
+}  // namespace
+
+namespace th {
+namespace tmi {
+int spectrum_request_info(th_tm *tm, const th_spectrum_request &r, size_t i, th_spectrum_info *info) {
+    const Channel *c = nullptr;
+    size_t f0 = 0, f1 = 0;
+    TH_CHECK(check_spectrum_request(tm, setting_of(tm), r, i, &c, &f0, &f1));
+    *info = th_spectrum_info{0, c->H, f0, f1, tm->spectrogram_revision()};
+    return TH_OK;
+}
+}  // namespace tmi
+}  // namespace th
+
+// The spectrum of a time range of N (channel, range, kind) requests: a reader.  One job per request; the two launches of
+// kernels_spectrum.hip on the slot's stream; results of up to h_tile's size are written by the kernel into the slot's pinned
+// staging and copied out, larger ones go through the slot's device result buffer and one copy.
+TH_API int th_tm_get_spectra(th_tm *tm, const th_spectrum_request *reqs, size_t n, float *out, size_t cap, th_spectrum_info *info,
+                             size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(tm && out_len && (n == 0 || (reqs && info)), "NULL argument");
+    *out_len = 0;
+    if (n == 0) return TH_OK;
+    TH_REQUIRE(n <= UINT32_MAX, "too many requests");
+    std::shared_lock<std::shared_mutex> rl(tm->rw);
+    const uint64_t revision = tm->spectrogram_revision();
+    const Setting st = setting_of(tm);
+    std::vector<SpectrumJob> jobs(n);
+    std::vector<th_spectrum_info> infos(n);
+    std::vector<size_t> part0(n);  // first partial of job i, in doubles
+    size_t total = 0, part_total = 0;
+    uint32_t max_blocks = 0, max_h = 0;
+    for (size_t i = 0; i < n; i++) {
+        const th_spectrum_request &r = reqs[i];
+        const Channel *cp = nullptr;
+        size_t f0 = 0, f1 = 0;
+        TH_CHECK(check_spectrum_request(tm, st, r, i, &cp, &f0, &f1));
+        const Channel &c = *cp;
+        infos[i] = th_spectrum_info{total, c.H, f0, f1, revision};
+        const SpectrumShape sh = spectrum_shape((uint32_t)c.H, (uint32_t)(f1 - f0));
+        SpectrumJob &j = jobs[i];
+        j.rows = c.d_spec;
+        j.pitch = c.spec_pitch;
+        j.H = (uint32_t)c.H;
+        j.f0 = (uint32_t)f0;
+        j.f1 = (uint32_t)f1;
+        j.kind = r.kind;
+        j.log_ct = sh.log_ct;
+        j.n_ctiles = sh.n_ctiles;
+        j.n_slices = sh.n_slices;
+        j.slice_len = sh.slice_len;
+        part0[i] = part_total;
+        part_total += (size_t)sh.n_slices * ((size_t)sh.n_ctiles << (sh.log_ct + 2));
+        const uint64_t blocks = (uint64_t)sh.n_ctiles * sh.n_slices;
+        if (blocks > INT32_MAX) return fail(TH_ERR_UNSUPPORTED, "Spectrogram %zu_%u: too many blocks", r.id, r.ch);
+        max_blocks = std::max(max_blocks, (uint32_t)blocks);
+        max_h = std::max(max_h, j.H);
+        total += c.H;
+    }
+    std::memcpy(info, infos.data(), n * sizeof(th_spectrum_info));
+    *out_len = total;
+    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu floats", total);
+    TH_HIP(hipSetDevice(tm->ctx->device));
+    SlotLease lease{tm, nullptr};
+    int rc = acquire_slot(tm, &lease.slot);
+    if (rc != TH_OK) return rc;
+    ReaderSlot &sl = *lease.slot;
+    const size_t out_bytes = total * sizeof(float);
+    const bool pinned = out_bytes <= TILE_BYTES_MAX;
+    TH_CHECK(sl.spec_part.ensure(std::max<size_t>(part_total, 1) * sizeof(double)));
+    if (!pinned) TH_CHECK(sl.spec_out.ensure(out_bytes));
+    float *res = pinned ? reinterpret_cast<float *>(sl.h_tile_dev) : static_cast<float *>(sl.spec_out.dptr);
+    for (size_t i = 0; i < n; i++) {
+        jobs[i].part = static_cast<double *>(sl.spec_part.dptr) + part0[i];
+        jobs[i].out = res + infos[i].offset;
+    }
+    TH_CHECK(sl.spec_jobs.upload(sl.stream, jobs.data(), n * sizeof(SpectrumJob)));
+    TH_HIP(launch_spectrum(static_cast<const SpectrumJob *>(sl.spec_jobs.dptr), (uint32_t)n, max_blocks, max_h, sl.stream));
+    if (pinned) {
+        TH_HIP(hipStreamSynchronize(sl.stream));
+        std::memcpy(out, sl.h_tile, out_bytes);
+    } else {
+        TH_HIP(hipMemcpyAsync(out, res, out_bytes, hipMemcpyDeviceToHost, sl.stream));
+        TH_HIP(hipStreamSynchronize(sl.stream));
+    }
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_tm_get_spectrum(th_tm *tm, size_t id, uint32_t ch, int kind, double start_sec, double end_sec, float *out, size_t cap,
+                              th_spectrum_info *info) {
+    TH_TRY
+    TH_REQUIRE(tm, "tm is NULL");
+    TH_REQUIRE(kind >= 0, "unknown spectrum kind %d", kind);
+    const th_spectrum_request r{id, ch, (uint32_t)kind, start_sec, end_sec};
+    th_spectrum_info one{};
+    size_t len = 0;
+    const int rc = th_tm_get_spectra(tm, &r, 1, out, cap, &one, &len);
+    if (info && (rc == TH_OK || rc == TH_ERR_BUFFER_TOO_SMALL)) *info = one;
+    return rc;
     TH_CATCH
 }
 

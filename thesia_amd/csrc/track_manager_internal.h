@@ -50,6 +50,10 @@ int prepare_dynamics(th_tm *tm, int kind, float target, int mode, StagedPtr *out
 void get_common_dynamics(th_tm *tm, int *kind, float *target, int *mode);
 void commit(th_tm *tm, StagedPtr staged);
 
+// th_tm_get_spectra's check of ONE request (i: its index in the caller's batch, for the message), with the codes and in the order
+// th_tm_get_spectra reports them; *info: offset 0, the spec's height, the frame range and the slot's spectrogram revision
+int spectrum_request_info(th_tm *tm, const th_spectrum_request &r, size_t i, th_spectrum_info *info);
+
 // update_spec_imgs against `global` (NULL: the manager's own tracks, as th_tm_* does), then the writer's final wait:
 // for the images only (apply_track_list_changes, set_dB_range) or for everything (set_setting, set_colormap)
 int requantise(th_tm *tm, const DbRange *global, bool force_update_all, bool images_only, std::vector<size_t> *updated);

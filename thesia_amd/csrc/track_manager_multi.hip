@@ -524,6 +524,90 @@ TH_API int th_tmg_get_spectrogram_tiles(th_tmg *g, const th_tile_request *reqs, 
     TH_CATCH
 }
 
+// Spectra: the batch split by owner.  Every request is checked in request order against its owning slot (the codes and the order
+// of one th_tm: the first faulty request decides), which also gives the heights, so the packed offsets are known before any slot
+// runs; a batch owned by one slot goes to it whole, otherwise every slot fills a staging vector of its own, side by side, and the
+// rows are scattered to their places once all have succeeded.
+TH_API int th_tmg_get_spectra(th_tmg *g, const th_spectrum_request *reqs, size_t n, float *out, size_t cap, th_spectrum_info *info,
+                              size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(g && out_len && (n == 0 || (reqs && info)), "NULL argument");
+    *out_len = 0;
+    if (n == 0) return TH_OK;
+    std::shared_lock<std::shared_mutex> rl(g->rw);
+    std::vector<std::vector<size_t>> mine(g->slots.size());  // request indices per slot, in request order
+    std::vector<th_spectrum_info> infos(n);
+    for (size_t i = 0; i < n; i++) {
+        const th_tmg::Placement *p = find_track(g, reqs[i].id);
+        if (!p) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", reqs[i].id);
+        th_tm *tm = g->slots[p->slot].tm;
+        std::shared_lock<std::shared_mutex> sl(tmi::rw_of(tm));
+        TH_CHECK(tmi::spectrum_request_info(tm, reqs[i], i, &infos[i]));
+        mine[p->slot].push_back(i);
+    }
+    uint64_t revision;
+    {
+        std::lock_guard<std::mutex> lk(g->revs.mu);
+        revision = g->revs.spectrogram_revision;
+    }
+    std::vector<uint32_t> busy;
+    std::vector<std::vector<th_spectrum_request>> sub(g->slots.size());
+    for (uint32_t s = 0; s < g->slots.size(); s++) {
+        const std::vector<size_t> &idx = mine[s];
+        if (idx.empty()) continue;
+        busy.push_back(s);
+        sub[s].resize(idx.size());
+        for (size_t j = 0; j < idx.size(); j++) sub[s][j] = reqs[idx[j]];
+    }
+    size_t total = 0;
+    for (size_t i = 0; i < n; i++) {
+        infos[i].offset = total;
+        infos[i].spectrogram_revision = revision;
+        total += infos[i].height;
+    }
+    std::memcpy(info, infos.data(), n * sizeof(th_spectrum_info));
+    *out_len = total;
+    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu floats", total);
+    if (busy.size() == 1) {
+        std::vector<th_spectrum_info> si(n);
+        size_t len = 0;
+        return th_tm_get_spectra(g->slots[busy[0]].tm, reqs, n, out, cap, si.data(), &len);
+    }
+    std::vector<std::vector<float>> stage(g->slots.size());
+    const int rc = for_slots(g, busy, [&](uint32_t s) -> int {
+        size_t floats = 0;
+        for (size_t i : mine[s]) floats += infos[i].height;
+        stage[s].resize(floats);
+        std::vector<th_spectrum_info> si(mine[s].size());
+        size_t len = 0;
+        return th_tm_get_spectra(g->slots[s].tm, sub[s].data(), sub[s].size(), stage[s].data(), stage[s].size(), si.data(), &len);
+    });
+    if (rc != TH_OK) return rc;
+    for (uint32_t s : busy) {
+        size_t at = 0;
+        for (size_t i : mine[s]) {
+            std::memcpy(out + infos[i].offset, stage[s].data() + at, infos[i].height * sizeof(float));
+            at += infos[i].height;
+        }
+    }
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_tmg_get_spectrum(th_tmg *g, size_t id, uint32_t ch, int kind, double start_sec, double end_sec, float *out, size_t cap,
+                               th_spectrum_info *info) {
+    TH_TRY
+    TH_REQUIRE(g, "tmg is NULL");
+    TH_REQUIRE(kind >= 0, "unknown spectrum kind %d", kind);
+    const th_spectrum_request r{id, ch, (uint32_t)kind, start_sec, end_sec};
+    th_spectrum_info one{};
+    size_t len = 0;
+    const int rc = th_tmg_get_spectra(g, &r, 1, out, cap, &one, &len);
+    if (info && (rc == TH_OK || rc == TH_ERR_BUFFER_TOO_SMALL)) *info = one;
+    return rc;
+    TH_CATCH
+}
+
 // set_common_normalize / set_common_guard_clipping: every slot re-derives its tracks into staged buffers; all commit, or all discard
 namespace {
 int set_common_dynamics_all(th_tmg *g, int kind, float target, int mode) {
