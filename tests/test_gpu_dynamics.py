@@ -345,7 +345,34 @@ def test_defaults_round_trip(ctx, tracks, cmap):
         tm.close()
 
 
-def test_refusals_change_nothing(main, tracks):
+def _limiter_refusal_after_staging(mgr, cmap):
+    """A limiter refusal AFTER another track has staged its derived audio: track 1 (8 kHz) is derived first; track 2 runs at 99 Hz,
+    where the limiter's attack would be 0 samples.  (40 ms at 99 Hz: hop 1, win 4, n_fft 4.)  Under a two-slot manager track 2's
+    slot refuses while the other slot stages completely and is then discarded."""
+    two = {1: (8000, noise(101, 1, 5000)), 2: (99, noise(102, 2, 300))}
+    mgr.set_setting(40.0, 4, 1, ta.LINEAR)
+    _add(mgr, two, cmap)
+    mgr.set_common_normalize(ref.NORM_PEAK_DB, 6.0)  # every peak at 2: the limiter would have to run on both
+    assert all(mgr.track_dynamics(i)["global_gain"] < 1 for i in two)
+    before, dyn, rev = full_state(mgr, two), mgr.common_dynamics(), mgr.revisions()
+    assert dyn == (ref.NORM_PEAK_DB, 6.0, ref.GUARD_REDUCE_GLOBAL_LEVEL)
+    with pytest.raises(ta.ThError) as e:
+        mgr.set_common_guard_clipping(ref.GUARD_LIMITER)
+    assert e.value.code == _ffi.ERR_UNSUPPORTED
+    assert mgr.common_dynamics() == dyn and mgr.revisions() == rev
+    assert_same(before, full_state(mgr, two))
+    mgr.set_common_guard_clipping(ref.GUARD_CLIP)  # later calls still work
+    assert mgr.common_dynamics() == (ref.NORM_PEAK_DB, 6.0, ref.GUARD_CLIP) and mgr.revisions() == (rev[0] + 1, rev[1] + 1)
+    for i, (sr, x) in two.items():
+        assert mgr.track_dynamics(i)["guard_result"] == ref.RESULT_BEFORE_CLIP and np.abs(mgr.audio(i, 0)).max() == 1
+
+
+def test_refusals_change_nothing(ctx, main, tracks, cmap):
+    for mgr in (ta.TrackManager(ctx), ta.MultiTrackManager([0, 0])):
+        try:
+            _limiter_refusal_after_staging(mgr, cmap)
+        finally:
+            mgr.close()
     tm, _ = main
     set_case(tm, (ref.NORM_RMS_DB, -6.0, ref.GUARD_CLIP))
     before = (tm.common_dynamics(), tm.revisions(), tm.spec(QUIET_ID, 1), tm.audio(QUIET_ID, 1), tm.guard_clip_stats(QUIET_ID))

@@ -11,6 +11,7 @@ import pytest
 
 import thesia_amd as ta
 from thesia_amd import _ffi
+from tests import dynamics_ref as ref
 from tests.synth import synth_track
 
 pytestmark = pytest.mark.gpu
@@ -217,6 +218,34 @@ def test_failed_mutators_change_no_slot(ctx, cmap):
         assert [multi.device_of(i) for i in (10, 12)] == [where[10][0], where[12][0]]
         assert one.apply_track_list_changes() == multi.apply_track_list_changes()
         assert_same(snapshot(one, sorted(TRACKS_NOW)), snapshot(multi, sorted(TRACKS_NOW)))
+        # the same batch (as ids 20, 21, 22) while a normalise target is in force: every staged track's audio is derived from its
+        # stats before its specs are made, so the slots of 20 and 22 discard derived audio as well
+        for m in (one, multi):
+            m.set_common_normalize(ref.NORM_RMS_DB, -6.0)
+        before = snapshot(multi, sorted(TRACKS_NOW))
+        assert_same(snapshot(one, sorted(TRACKS_NOW)), before)
+        bad = [(i + 10, sr, x) for i, sr, x in bad]
+        resident = {i: (multi.device_of(i), x.size) for i, (_, x) in TRACKS_NOW.items()}
+        where = place(resident, [(i, x.size) for i, _, x in bad], 3)
+        assert where[21][0] not in (where[20][0], where[22][0])
+        for m in (one, multi):
+            with pytest.raises(ta.ThError) as e:
+                m.add_tracks(bad)
+            assert e.value.code == _ffi.ERR_UNSUPPORTED
+        assert f"slot {where[21][0]} (device 0)" in str(e.value)
+        for i in (20, 21, 22):
+            with pytest.raises(ta.ThError):
+                multi.device_of(i)
+        assert_same(before, snapshot(multi, sorted(TRACKS_NOW)))
+        assert_same(snapshot(one, sorted(TRACKS_NOW)), snapshot(multi, sorted(TRACKS_NOW)))
+        good = [b for b in bad if b[0] != 21]
+        for m in (one, multi):
+            m.add_tracks(good)
+        TRACKS_NOW.update({i: (sr, x) for i, sr, x in good})
+        assert [multi.device_of(i) for i in (20, 22)] == [where[20][0], where[22][0]]
+        assert one.apply_track_list_changes() == multi.apply_track_list_changes()
+        assert_same(snapshot(one, sorted(TRACKS_NOW)), snapshot(multi, sorted(TRACKS_NOW)))
+        assert all(one.track_dynamics(i)["normalize_gain"] > 1 and one.track_dynamics(i) == multi.track_dynamics(i) for i in (20, 22))
     finally:
         multi.close()
         one.close()

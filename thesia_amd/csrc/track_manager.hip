@@ -51,12 +51,12 @@ struct Channel {
     float *d_pyr = nullptr;      // resident waveform pyramid of d_draw: every level's (min, max, mean) bins, th_waveform_pyramid_offset
     float *d_orig = nullptr, *d_pyr_orig = nullptr;  // the samples as they were added and their pyramid (the track's pool)
     uint32_t pyr_levels = 0;     // levels 0 .. pyr_levels - 1 (the last one has a single bin)
-    float *d_spec = nullptr;
+    DeviceBuf<float> d_spec;
     size_t T = 0, H = 0, spec_pitch = 0;   // rows padded to 128 B (th_pitch_f32)
-    uint16_t *d_img = nullptr;
+    DeviceBuf<uint16_t> d_img;
     size_t img_h = 0, img_w = 0, img_pitch = 0;  // rows padded to 128 B (th_pitch_u16)
     std::map<std::pair<uint32_t, uint32_t>, MipLevel> mips;  // (level_x, level_y) != (0, 0): views into d_mips
-    uint16_t *d_mips = nullptr;                               // one allocation for every level
+    DeviceBuf<uint16_t> d_mips;                               // one allocation for every level
     size_t mips_elems = 0;                                    // its size (re-made images of the same shape reuse it)
     float mn = INFINITY, mx = -INFINITY;  // find_min_max of this spec (simd.rs:14-36)
     bool has_spec = false;
@@ -78,15 +78,8 @@ constexpr size_t TILE_BYTES_MAX = 520 * 520 * 4;  // 512 core + 2 x 4 gutter (re
 constexpr size_t MAX_READER_SLOTS = 16;
 
 // Lanczos tap table of one image axis at one LOD level, resident on the device (shared by every channel of that size)
-// a device allocation shared by the tap tables that were made together (freed when the last of them goes)
-struct DevBlock {
-    void *p = nullptr;
-    ~DevBlock() {
-        if (p) (void)hipFree(p);
-    }
-};
 struct AxisTable {
-    std::shared_ptr<DevBlock> owner;  // d_blob points into it
+    std::shared_ptr<DeviceBuf<unsigned char>> owner;  // the allocation shared by the tap tables that were made together (freed when the last of them goes): d_blob points into it
     void *d_blob = nullptr;
     uint32_t n_out = 0, max_taps = 0;
     uint32_t span[3] = {0, 0, 0};  // LodAxis::span
@@ -98,13 +91,13 @@ struct Track {
     std::vector<Channel> ch;
     // ONE device allocation for the samples and waveform pyramids of all channels (round 6: two hipMalloc per channel were 0.7 ms
     // of a 32-track add); Channel::d_wav / d_pyr are views into it and live exactly as long as the track
-    void *d_pool = nullptr;
+    DeviceBuf<float> d_pool;
     th_audio_stats stats{};       // AudioStats (StatCalculator::calc, dynamics/stats.rs:56-86) of the audio
     th_audio_stats orig_stats{};  // ... of the samples as they were added: what the normalise gain is computed from
     // The audio derived from the original under the common normalise target and clip guard (AudioTrack::apply_gain).  d_dyn == NULL:
     // the audio IS the original (gain 1 or not finite) and nothing below is held.  One allocation: per channel the audio, in Clip mode
     // the before-clip audio, and the pyramid of what is drawn; then the limiter's gain sequence.
-    void *d_dyn = nullptr;
+    DeviceBuf<float> d_dyn;
     float norm_gain = 1.0f;
     int guard_result = TH_GUARD_RESULT_GLOBAL_GAIN;
     float global_gain = 1.0f;
@@ -133,7 +126,7 @@ struct th_tm {
     std::map<PlanKey, th_plan *> plans;  // SpectrogramAnalyzer caches, spectrogram.rs:101-105
     // RenderTileCache state that the tile encoders need — render_tiles.rs:68-96
     std::vector<uint8_t> colormap_rgba{0, 0, 0, 255, 255, 255, 255, 255};
-    uint8_t *d_colormap = nullptr;  // device copy of colormap_rgba (uploaded when it changes, not per tile request)
+    DeviceBuf<uint8_t> d_colormap;  // device copy of colormap_rgba (uploaded when it changes, not per tile request)
     th_tile_cache cache{th_tile_cache::DEFAULT_BUDGET};  // revisions + waveform-tile LRU, render_tiles.rs:51-230
     // Writers (every mutator) take `rw` exclusively, tile readers share it — the reference's RwLock<TrackManager>.
     // A mutator leaves the context stream idle before it releases the lock, so readers never see half-made images.
@@ -184,27 +177,17 @@ struct th_tm {
 namespace {
 
 void free_mips(Channel &c) {
-    if (c.d_mips) (void)hipFree(c.d_mips);
-    c.d_mips = nullptr;
+    c.d_mips.reset();
     c.mips_elems = 0;
     c.mips.clear();
 }
 
-void free_channel(Channel &c) {  // (d_wav / d_pyr belong to the track's pool: free_track)
-    if (c.d_spec) (void)hipFree(c.d_spec);
-    if (c.d_img) (void)hipFree(c.d_img);
-    free_mips(c);
-    c = Channel();
-}
-
-void free_track(Track &t) {
-    for (Channel &ch : t.ch) free_channel(ch);
-    t.ch.clear();
-    if (t.d_pool) (void)hipFree(t.d_pool);
-    t.d_pool = nullptr;
-    if (t.d_dyn) (void)hipFree(t.d_dyn);
-    t.d_dyn = nullptr;
-    t.d_gain = nullptr;
+// DeviceBuf::reset() with the failure reported (update_spec_imgs, upload_colormap)
+template <class T>
+int free_checked(DeviceBuf<T> &b) {
+    TH_HIP(hipFree(b.ptr));
+    b.ptr = nullptr;
+    return TH_OK;
 }
 
 struct Setting {
@@ -256,113 +239,88 @@ void retain_plans(th_tm *tm) {
     }
 }
 
-// A freshly computed spec of one channel, not yet attached to it
+// A freshly computed spec, not yet attached to its channel: (track id, channel index) is looked up when it is attached
 struct NewSpec {
-    Channel *ch = nullptr;
-    float *d_spec = nullptr;
+    size_t id = 0;
+    uint32_t ch = 0;
+    DeviceBuf<float> d_spec;
     size_t T = 0, H = 0, pitch = 0;
     float mn = INFINITY, mx = -INFINITY;
 };
-void free_new_specs(std::vector<NewSpec> &v) {
-    for (NewSpec &n : v)
-        if (n.d_spec) (void)hipFree(n.d_spec);
-    v.clear();
-}
+// What a spec is computed from: n samples at d_wav, which need not be the audio of a resident channel (yet)
+struct SpecInput {
+    size_t id;
+    uint32_t ch, sr;
+    const float *d_wav;
+    size_t n;
+};
 
 // TrackManager::update_specs — core/mod.rs:137-164: one batched launch per plan, INTO FRESH BUFFERS.  Nothing the
-// manager owns is touched: the caller attaches the results (commit_specs) once every launch has succeeded, so a
+// manager owns is touched: the caller attaches the results (tmi::commit) once every launch has succeeded, so a
 // failure (unsupported n_fft, out of memory) leaves settings, specs and has_spec exactly as they were.
 // pending != NULL: the per-channel (min, max) pairs stay on the device (entries appended to *pending) and NOTHING here waits for
 // the launches — the caller synchronises once and calls finish_specs (th_tm_add_tracks launches group after group this way,
 // beside the next group's upload)
 struct PendingMinMax {
-    float *d_mm = nullptr;
+    DeviceBuf<float> d_mm;
     size_t first = 0, count = 0;
 };
-int finish_specs(th_tm *tm, std::vector<PendingMinMax> &pending, std::vector<NewSpec> *out, bool read) {
-    int rc = TH_OK;
+int finish_specs(std::vector<PendingMinMax> &pending, std::vector<NewSpec> *out) {
     for (PendingMinMax &pm : pending) {
-        if (read && rc == TH_OK) {
-            std::vector<float> mm(2 * pm.count);
-            const hipError_t e = hipMemcpy(mm.data(), pm.d_mm, mm.size() * sizeof(float), hipMemcpyDeviceToHost);
-            if (e != hipSuccess) rc = th::fail(TH_ERR_HIP, "%s", hipGetErrorString(e));
-            else
-                for (size_t i = 0; i < pm.count; i++) {
-                    (*out)[pm.first + i].mn = mm[2 * i];
-                    (*out)[pm.first + i].mx = mm[2 * i + 1];
-                }
+        std::vector<float> mm(2 * pm.count);
+        TH_HIP(hipMemcpy(mm.data(), pm.d_mm, mm.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < pm.count; i++) {
+            (*out)[pm.first + i].mn = mm[2 * i];
+            (*out)[pm.first + i].mx = mm[2 * i + 1];
         }
-        (void)hipFree(pm.d_mm);
     }
     pending.clear();
-    (void)tm;
-    return rc;
+    return TH_OK;
 }
-int compute_specs(th_tm *tm, const Setting &st, const std::vector<std::pair<uint32_t, Channel *>> &chans,
-                  std::map<PlanKey, th_plan *> &created, std::vector<NewSpec> *out, std::vector<PendingMinMax> *pending = nullptr) {
+int compute_specs(th_tm *tm, const Setting &st, const std::vector<SpecInput> &chans, std::map<PlanKey, th_plan *> &created,
+                  std::vector<NewSpec> *out, std::vector<PendingMinMax> *pending = nullptr) {
     th_ctx *c = tm->ctx;
-    std::map<th_plan *, std::vector<Channel *>> groups;
-    for (auto &sc : chans) {
+    std::map<th_plan *, std::vector<const SpecInput *>> groups;
+    for (const SpecInput &in : chans) {
         th_plan *p = nullptr;
-        int rc = get_plan(tm, st, sc.first, created, &p);
-        if (rc != TH_OK) return rc;
-        groups[p].push_back(sc.second);
+        TH_CHECK(get_plan(tm, st, in.sr, created, &p));
+        groups[p].push_back(&in);
     }
     for (auto &kv : groups) {
         th_plan *p = kv.first;
-        std::vector<Channel *> &chs = kv.second;
-        std::vector<th_chan_desc> descs(chs.size());
-        const size_t first = out->size();
-        for (size_t i = 0; i < chs.size(); i++) {
+        const std::vector<const SpecInput *> &ins = kv.second;
+        std::vector<th_chan_desc> descs(ins.size());
+        PendingMinMax pm;
+        pm.first = out->size();
+        pm.count = ins.size();
+        for (size_t i = 0; i < ins.size(); i++) {
             NewSpec ns;
-            ns.ch = chs[i];
-            ns.T = stft_n_frames(chs[i]->n, p->g.win, p->g.hop);
+            ns.id = ins[i]->id;
+            ns.ch = ins[i]->ch;
+            ns.T = stft_n_frames(ins[i]->n, p->g.win, p->g.hop);
             ns.H = p->g.height;
             ns.pitch = th_pitch_f32(ns.H);
-            out->push_back(ns);  // (recorded before the allocation: the caller frees whatever is in *out)
-            TH_HIP(hipMalloc((void **)&out->back().d_spec, std::max<size_t>(1, ns.T * ns.pitch) * sizeof(float)));
-            descs[i] = th_chan_desc{chs[i]->d_wav, out->back().d_spec, chs[i]->n, ns.T, ns.pitch};
+            TH_HIP(ns.d_spec.alloc(std::max<size_t>(1, ns.T * ns.pitch) * sizeof(float)));
+            descs[i] = th_chan_desc{ins[i]->d_wav, ns.d_spec, ins[i]->n, ns.T, ns.pitch};
+            out->push_back(std::move(ns));
         }
-        float *d_mm = nullptr;
-        TH_HIP(hipMalloc((void **)&d_mm, 2 * chs.size() * sizeof(float)));
+        TH_HIP(pm.d_mm.alloc(2 * ins.size() * sizeof(float)));
+        float *const d_mm = pm.d_mm;
         if (pending != nullptr) {
-            pending->push_back(PendingMinMax{d_mm, first, chs.size()});  // (recorded before the launch: the caller frees it on any outcome)
-            const int prc = th_calc_spec_batch_dev(p, descs.data(), descs.size(), d_mm);
-            if (prc != TH_OK) return prc;
+            pending->push_back(std::move(pm));  // (before the launch: it has to outlive it on any outcome)
+            TH_CHECK(th_calc_spec_batch_dev(p, descs.data(), descs.size(), d_mm));
             continue;
         }
-        int rc = th_calc_spec_batch_dev(p, descs.data(), descs.size(), d_mm);
-        std::vector<float> mm(2 * chs.size());
-        hipError_t e = hipSuccess;
-        if (rc == TH_OK) {
-            e = hipMemcpyAsync(mm.data(), d_mm, mm.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        }
-        (void)hipFree(d_mm);
-        if (rc != TH_OK) return rc;
-        TH_HIP(e);
-        for (size_t i = 0; i < chs.size(); i++) {
-            (*out)[first + i].mn = mm[2 * i];
-            (*out)[first + i].mx = mm[2 * i + 1];
+        TH_CHECK(th_calc_spec_batch_dev(p, descs.data(), descs.size(), d_mm));
+        std::vector<float> mm(2 * ins.size());
+        TH_HIP(hipMemcpyAsync(mm.data(), d_mm, mm.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        TH_HIP(hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i < ins.size(); i++) {
+            (*out)[pm.first + i].mn = mm[2 * i];
+            (*out)[pm.first + i].mx = mm[2 * i + 1];
         }
     }
     return TH_OK;
-}
-
-void commit_specs(std::vector<NewSpec> &v) {
-    for (NewSpec &n : v) {
-        Channel &ch = *n.ch;
-        if (ch.d_spec) (void)hipFree(ch.d_spec);
-        ch.d_spec = n.d_spec;
-        ch.T = n.T;
-        ch.H = n.H;
-        ch.spec_pitch = n.pitch;
-        ch.mn = n.mn;
-        ch.mx = n.mx;
-        ch.has_spec = true;
-        n.d_spec = nullptr;
-    }
-    v.clear();
 }
 
 // ---------------------------------------------------------------------------------------------- LOD mip pyramid
@@ -438,9 +396,9 @@ int make_axis_tables(th_tm *tm, const std::set<std::pair<uint32_t, uint32_t>> &k
     tm->axis_staging.emplace_back(total);
     std::vector<unsigned char> &stage = tm->axis_staging.back();
     for (size_t i = 0; i < todo.size(); i++) std::memcpy(stage.data() + at[i], host[i].blob.data(), host[i].blob.size());
-    std::shared_ptr<DevBlock> blk = std::make_shared<DevBlock>();
-    TH_HIP(hipMalloc(&blk->p, total));
-    const hipError_t e = hipMemcpyAsync(blk->p, stage.data(), total, hipMemcpyHostToDevice, tm->ctx->stream);
+    auto blk = std::make_shared<DeviceBuf<unsigned char>>();
+    TH_HIP(blk->alloc(total));
+    const hipError_t e = hipMemcpyAsync(blk->get(), stage.data(), total, hipMemcpyHostToDevice, tm->ctx->stream);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(tm->ctx->stream);
         TH_HIP(e);
@@ -448,7 +406,7 @@ int make_axis_tables(th_tm *tm, const std::set<std::pair<uint32_t, uint32_t>> &k
     for (size_t i = 0; i < todo.size(); i++) {
         AxisTable t;
         t.owner = blk;
-        t.d_blob = static_cast<unsigned char *>(blk->p) + at[i];
+        t.d_blob = blk->get() + at[i];
         t.n_out = host[i].n_out;
         t.max_taps = host[i].max_taps;
         t.bytes = host[i].blob.size();
@@ -551,12 +509,11 @@ int build_mips(th_tm *tm, const std::vector<Channel *> &chans) {
         if (!ch->d_mips || ch->mips_elems != total) {
             const std::map<std::pair<uint32_t, uint32_t>, MipLevel> views = ch->mips;
             free_mips(*ch);
-            hipError_t e = hipMalloc((void **)&ch->d_mips, total * sizeof(uint16_t));
-            if (e != hipSuccess) TH_HIP(e);
+            TH_HIP(ch->d_mips.alloc(total * sizeof(uint16_t)));
             ch->mips = views;
             ch->mips_elems = total;
         }
-        for (auto &kv : ch->mips) kv.second.d = ch->d_mips + reinterpret_cast<size_t>(kv.second.d);
+        for (auto &kv : ch->mips) kv.second.d = ch->d_mips.get() + reinterpret_cast<size_t>(kv.second.d);
         groups[Shape{W, Hh, (uint32_t)ch->img_pitch}].push_back(ch);
     }
     // One job table for all launches (uploaded once), then the launches in dependency order per shape.  The horizontal
@@ -713,8 +670,7 @@ int update_spec_imgs(th_tm *tm, bool force_update_all, std::vector<size_t> *upda
         for (auto &kv : tm->tracks)
             for (Channel &ch : kv.second.ch)
                 if (ch.d_img && !ids.count(kv.first)) {
-                    TH_HIP(hipFree(ch.d_img));
-                    ch.d_img = nullptr;
+                    TH_CHECK(free_checked(ch.d_img));
                     ch.img_h = ch.img_w = 0;
                     free_mips(ch);
                 }
@@ -731,12 +687,9 @@ int update_spec_imgs(th_tm *tm, bool force_update_all, std::vector<size_t> *upda
             size_t i0, i1;
             hz_range_to_idx(tm->freq_scale, 0.f, float(tm->max_sr) / 2.f, it->second.sr, ch.H, &i0, &i1);  // :210-214
             const size_t h = i1 - i0, w = ch.T;
-            if (ch.d_img && (ch.img_h != h || ch.img_w != w)) {
-                TH_HIP(hipFree(ch.d_img));
-                ch.d_img = nullptr;
-            }
+            if (ch.d_img && (ch.img_h != h || ch.img_w != w)) TH_CHECK(free_checked(ch.d_img));
             const size_t ipitch = th_pitch_u16(w);
-            if (!ch.d_img) TH_HIP(hipMalloc((void **)&ch.d_img, std::max<size_t>(1, h * ipitch) * sizeof(uint16_t)));
+            if (!ch.d_img) TH_HIP(ch.d_img.alloc(std::max<size_t>(1, h * ipitch) * sizeof(uint16_t)));
             ch.img_h = h;
             ch.img_w = w;
             ch.img_pitch = ipitch;
@@ -879,14 +832,13 @@ TH_API int th_tm_destroy(th_tm *tm) {
         (void)hipStreamDestroy(sp->stream);
         (void)hipHostFree(sp->h_tile);
     }
-    for (auto &kv : tm->tracks)
-        free_track(kv.second);
+    tm->tracks.clear();
     for (auto &kv : tm->plans) th_plan_destroy(kv.second);
     tm->axis_tabs.clear();
     if (tm->batch_stage) (void)hipHostFree(tm->batch_stage);
     tm->mip_jobs.release();
     tm->mip_scratch.release();
-    if (tm->d_colormap) (void)hipFree(tm->d_colormap);
+    tm->d_colormap.reset();
     if (tm->copy_ev) (void)hipEventDestroy(tm->copy_ev);
     if (tm->img_ev) (void)hipEventDestroy(tm->img_ev);
     if (tm->mips_ev) (void)hipEventDestroy(tm->mips_ev);
@@ -901,11 +853,8 @@ TH_API int th_tm_destroy(th_tm *tm) {
 
 namespace {
 int upload_colormap(th_tm *tm) {
-    if (tm->d_colormap) {
-        TH_HIP(hipFree(tm->d_colormap));
-        tm->d_colormap = nullptr;
-    }
-    TH_HIP(hipMalloc((void **)&tm->d_colormap, tm->colormap_rgba.size()));
+    if (tm->d_colormap) TH_CHECK(free_checked(tm->d_colormap));
+    TH_HIP(tm->d_colormap.alloc(tm->colormap_rgba.size()));
     TH_HIP(hipMemcpyAsync(tm->d_colormap, tm->colormap_rgba.data(), tm->colormap_rgba.size(), hipMemcpyHostToDevice,
                           tm->ctx->stream));
     TH_HIP(hipStreamSynchronize(tm->ctx->stream));
@@ -993,7 +942,6 @@ TH_API int th_tm_remove_track(th_tm *tm, size_t id) {
     auto it = tm->tracks.find(id);
     if (it == tm->tracks.end()) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", id);
     TH_HIP(hipStreamSynchronize(tm->ctx->stream));
-    free_track(it->second);
     tm->tracks.erase(it);
     prune_axis_tabs(tm);
     retain_plans(tm);      // core/mod.rs:96-99
@@ -1680,18 +1628,33 @@ TH_API int th_tm_mip_level(th_tm *tm, size_t id, uint32_t ch, uint32_t level_x, 
 // ---------------------------------------------------------------------------------------------- normalise + clip guard
 namespace {
 
-size_t wav_floats(size_t n) { return (n + 63) / 64 * 64; }  // (256-byte pieces: every view starts on a 256-byte boundary)
-size_t pyr_floats(size_t n, uint32_t lv) {
-    return (std::max<size_t>(1, th_waveform_pyramid_offset(n, std::max(lv, PYR_FIRST)) - th_waveform_pyramid_offset(n, PYR_FIRST)) + 63) / 64 * 64;
+// One channel's piece of a track's pool: `wav_copies` times the samples, then the materialised levels of its waveform pyramid
+// (256-byte pieces: every view starts on a 256-byte boundary).  The original pool holds the samples once; the derived one holds
+// the audio and, in Clip mode, the before-clip audio.
+// levels: up to the one whose single bin spans the channel (render_tiles.rs:232-259); PYR_FIRST .. levels - 1 are resident: level 0
+// would be (x, x, x) per sample — half of the pyramid's bytes — and level 1 a quarter; tiles of both are served from the resident
+// samples instead (th_pyramid_desc.first_level)
+struct PoolLayout {
+    uint32_t levels;
+    size_t wav_f, pyr_f, stride;  // in floats; stride: from one channel's piece to the next
+};
+PoolLayout pool_layout(size_t n, size_t wav_copies) {
+    PoolLayout p{};
+    p.levels = 1;
+    while (p.levels < PYR_MAX_LEVELS && ((uint64_t)1 << (p.levels - 1)) < n) p.levels++;
+    p.wav_f = (n + 63) / 64 * 64;
+    p.pyr_f = (std::max<size_t>(1, th_waveform_pyramid_offset(n, std::max(p.levels, PYR_FIRST)) - th_waveform_pyramid_offset(n, PYR_FIRST)) + 63) / 64 * 64;
+    p.stride = p.wav_f * wav_copies + p.pyr_f;
+    return p;
 }
 
 // One track's audio derived from its original under (kind, target, mode) — AudioTrack::apply_gain, track.rs:158-170 — staged beside
-// the track until install()
+// the track until install_derived()
 struct Derived {
     bool active = false;  // false: gain 1 or not finite, the audio is the original
-    void *d_pool = nullptr;
+    DeviceBuf<float> d_pool;
     float gain = 1.0f, global_gain = 1.0f;
-    int result = TH_GUARD_RESULT_GLOBAL_GAIN, mode = TH_GUARD_REDUCE_GLOBAL_LEVEL;
+    int result = TH_GUARD_RESULT_GLOBAL_GAIN;
     float *d_gain = nullptr;
     bool limiting = false, gain_below_one = false;
     std::vector<float *> aud, draw, pyr;
@@ -1699,26 +1662,20 @@ struct Derived {
     std::vector<th_guard_clip_stats> guard_stats;
     size_t red0 = 0, loud_index = 0;  // its first reduction slot; its place in the loudness batch
 };
+// The tracks of one mutator re-derived under the common settings (kind, target, mode), which it installs with them
 struct DeriveBatch {
-    th_ctx *ctx = nullptr;
+    int kind = TH_NORM_OFF, mode = TH_GUARD_REDUCE_GLOBAL_LEVEL;
+    float target = 0.0f;
     std::map<size_t, Derived> of;
     DeviceBuf<unsigned char> d_tab, d_scratch;  // job tables and reduction slots; the limiter's scratch
     std::unique_ptr<LoudnessBatch> loud;
     size_t n_red = 0, o_cnt = 0;
-    DeriveBatch() = default;
-    DeriveBatch(const DeriveBatch &) = delete;
-    DeriveBatch &operator=(const DeriveBatch &) = delete;
-    ~DeriveBatch() {  // (the caller has drained the stream; pools that were installed are NULL here)
-        if (ctx) (void)hipSetDevice(ctx->device);
-        for (auto &kv : of)
-            if (kv.second.d_pool) (void)hipFree(kv.second.d_pool);
-    }
 };
 
 // Enqueue, on the context stream, the derived audio of `tracks` with its waveform pyramids and loudness passes.  Nothing waits.
-int derive_enqueue(th_tm *tm, const std::vector<std::pair<size_t, Track *>> &tracks, int kind, float target, int mode, DeriveBatch *b) {
+int derive_enqueue(th_tm *tm, const std::vector<std::pair<size_t, Track *>> &tracks, DeriveBatch *b) {
     th_ctx *c = tm->ctx;
-    b->ctx = c;
+    const int kind = b->kind, mode = b->mode;
     std::vector<DynApplyJob> ajobs;
     std::vector<LimJob> ljobs;
     std::vector<size_t> l_scratch;  // bytes of scratch of every limiter job
@@ -1731,12 +1688,11 @@ int derive_enqueue(th_tm *tm, const std::vector<std::pair<size_t, Track *>> &tra
     for (auto &it : tracks) {
         Track &tr = *it.second;
         Derived &d = b->of[it.first];
-        d.mode = mode;
         float gain = 1.0f;
-        TH_REQUIRE(normalize_gain(kind, target, tr.orig_stats.global_lufs, tr.orig_stats.rms_dB, tr.orig_stats.max_peak_dB, &gain),
+        TH_REQUIRE(normalize_gain(kind, b->target, tr.orig_stats.global_lufs, tr.orig_stats.rms_dB, tr.orig_stats.max_peak_dB, &gain),
                    "unknown normalize kind %d", kind);
         if (!std::isfinite(gain) || gain == 1.0f) continue;  // the audio is the original
-        const size_t n = tr.ch[0].n, n_ch = tr.ch.size(), wav_f = wav_floats(n), pyr_f = pyr_floats(n, tr.ch[0].pyr_levels);
+        const size_t n = tr.ch[0].n, n_ch = tr.ch.size();
         // f32 multiplication by a positive gain is monotone: the peak of gain x is fl(gain max|x|) — no pass over the audio
         const float peak = gain * tr.orig_stats.max_peak;
         const bool clip = mode == TH_GUARD_CLIP;
@@ -1746,11 +1702,12 @@ int derive_enqueue(th_tm *tm, const std::vector<std::pair<size_t, Track *>> &tra
             if (!limiter_params(tr.sr, &lp)) return fail(TH_ERR_UNSUPPORTED, "track %zu: sample rate %u: the limiter's attack would be 0 samples", it.first, tr.sr);
             if ((uint64_t)n + lp.attack >= (1ull << 31)) return fail(TH_ERR_UNSUPPORTED, "track %zu: too long for the limiter (2^31 samples)", it.first);
         }
-        const size_t per_ch = wav_f * (clip ? 2 : 1) + pyr_f;
-        TH_HIP(hipMalloc(&d.d_pool, (per_ch * n_ch + (d.limiting ? wav_f : 0)) * sizeof(float)));
+        const PoolLayout pl = pool_layout(n, clip ? 2 : 1);
+        const size_t wav_f = pl.wav_f, per_ch = pl.stride;
+        TH_HIP(d.d_pool.alloc((per_ch * n_ch + (d.limiting ? wav_f : 0)) * sizeof(float)));
         d.active = true;
         d.gain = gain;
-        float *base = static_cast<float *>(d.d_pool);
+        float *base = d.d_pool;
         aptrs.emplace_back();
         for (size_t k = 0; k < n_ch; k++) {
             d.aud.push_back(base + k * per_ch);
@@ -1923,14 +1880,15 @@ int derive_collect(const std::vector<std::pair<size_t, Track *>> &tracks, Derive
             d.guard_stats.assign(1, st);
         }
     }
+    b->loud.reset();  // (read: only the pools are kept for install_derived)
+    b->d_scratch.reset();
+    b->d_tab.reset();
     return TH_OK;
 }
 
 // the track takes its derived audio (or goes back to its original); the stream is idle
 void install_derived(Track &tr, Derived &d) {
-    if (tr.d_dyn) (void)hipFree(tr.d_dyn);
-    tr.d_dyn = d.d_pool;
-    d.d_pool = nullptr;
+    tr.d_dyn = std::move(d.d_pool);
     for (size_t k = 0; k < tr.ch.size(); k++) {
         Channel &ch = tr.ch[k];
         ch.d_wav = d.active ? d.aud[k] : ch.d_orig;
@@ -1950,39 +1908,146 @@ void install_derived(Track &tr, Derived &d) {
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------- steps th_tmg drives per slot
+// What a mutator has made beside the manager.  Every part is present or empty in its own right; commit() applies what is there.
+// THE DISCARD RULE: a Staged that was not committed may still be read or written by work on either stream, so its destructor makes
+// the manager's device current and drains the copy stream, then the context stream; only then do the members below free what
+// they hold.  Nothing else in this file frees staged memory.  It runs on whatever thread drops the StagedPtr — under th_tmg the
+// caller's, with another slot's device current.
+struct th::tmi::Staged {
+    th_tm *tm;
+    bool committed = false;  // set by commit(): everything was moved out with both streams idle, nothing to wait for
+    std::map<PlanKey, th_plan *> created;
+    std::vector<NewSpec> fresh;
+    std::map<size_t, Track> tracks;  // add_tracks
+    std::set<size_t> added;          // ... and every id it was given
+    std::unique_ptr<DeriveBatch> derive;  // set_common_normalize / set_common_guard_clipping; add_tracks under a normalise target
+    std::unique_ptr<Setting> setting;     // set_setting
+    explicit Staged(th_tm *m) : tm(m) {}
+    ~Staged() {
+        if (committed) return;
+        (void)hipSetDevice(tm->ctx->device);
+        (void)hipStreamSynchronize(tm->copy_stream);
+        (void)hipStreamSynchronize(tm->ctx->stream);
+        for (auto &kv : created) th_plan_destroy(kv.second);
+    }
+};
+
+namespace {
+using th::tmi::Staged;
+
+// Derive `trs` (resident tracks, or the staged ones of an add) under stg.derive's settings and compute the spec of every channel
+// whose audio changes, from the staged audio; ONE synchronisation, between the launches and the stats
+int stage_derived(Staged &stg, const std::vector<std::pair<size_t, Track *>> &trs) {
+    th_tm *tm = stg.tm;
+    TH_CHECK(derive_enqueue(tm, trs, stg.derive.get()));
+    std::vector<SpecInput> chans;
+    for (auto &it : trs) {
+        const Track &tr = *it.second;
+        const Derived &d = stg.derive->of[it.first];
+        // (a track with specs that is and stays its original is left alone: they would come out the same bits)
+        if (!d.active && !tr.d_dyn && tr.ch[0].has_spec) continue;
+        for (size_t k = 0; k < tr.ch.size(); k++)
+            chans.push_back({it.first, (uint32_t)k, tr.sr, d.active ? d.aud[k] : tr.ch[k].d_orig, tr.ch[k].n});
+    }
+    TH_CHECK(compute_specs(tm, setting_of(tm), chans, stg.created, &stg.fresh));
+    TH_HIP(hipStreamSynchronize(tm->ctx->stream));
+    return derive_collect(trs, stg.derive.get());
+}
+
+// add_tracks arguments (th_tm_add_tracks), de-duplicated: of an id given twice the later one wins, as sequential adds would —
+// only its data is uploaded
+struct AddArgs {
+    size_t n_tracks;
+    const size_t *ids;
+    const uint32_t *srs, *n_channels;
+    const float *const *channels_flat;
+    const size_t *n_samples;
+    std::map<size_t, size_t> last_of;  // id -> the index that counts
+    std::vector<size_t> flat0;         // track index -> its first entry of channels_flat
+};
+// What add_tracks leaves in flight until its one drain
+struct AddInFlight {
+    std::vector<PendingMinMax> pending;                // (min, max) pairs of every spec launch
+    std::vector<std::unique_ptr<LoudnessBatch>> loud;  // one per group
+    std::vector<std::pair<size_t, size_t>> loud_ids;   // (id, its group), in the order of the groups' descriptors
+};
+
+// groups of about 96 MB of samples (at least one track each): a group's launches cost ~0.2 ms of host time (descriptor tables,
+// spec allocations: six groups of 32 MB were SLOWER than no pipeline, 6.0 against 5.1 ms for 32 tracks), the last group's
+// kernels are the only ones nothing hides.  (Round 6, tried: the uploads on a helper thread so that this thread's launches do
+// not hold up the copy engine — the launches then take 1.15 ms of host time instead of 0.67 and the call 5.2 instead of 4.9 ms:
+// the runtime serialises the pageable copy path and the launches of the two threads.)
+constexpr size_t GROUP_BYTES = (size_t)96 << 20;
+
+// One group of an add, from track *t on: the tracks staged in stg.tracks (one pool each, uploads on the copy stream); then, on the
+// context stream behind an event of the copy stream, their waveform pyramids, their loudness and, with normalise off, their specs
+int stage_group(Staged &stg, const AddArgs &a, size_t *t, AddInFlight *fl, double *t_launch) {
+    th_tm *tm = stg.tm;
+    th_ctx *c = tm->ctx;
+    std::vector<SpecInput> chans;
+    std::vector<th_pyramid_desc> pdescs;
+    std::vector<th_audio_desc> adescs;
+    std::vector<std::vector<const float *>> aptrs;
+    for (size_t bytes = 0; *t < a.n_tracks && (bytes == 0 || bytes < GROUP_BYTES); ++*t) {
+        const size_t i = *t, id = a.ids[i], n = a.n_samples[i];
+        if (a.last_of.at(id) != i) continue;
+        Track &tr = stg.tracks[id];
+        tr.sr = a.srs[i];
+        tr.ch.resize(a.n_channels[i]);
+        tr.guard_stats.assign(tr.ch.size(), th_guard_clip_stats{});
+        const PoolLayout pl = pool_layout(n, 1);
+        TH_HIP(tr.d_pool.alloc(pl.stride * tr.ch.size() * sizeof(float)));
+        aptrs.emplace_back();
+        for (uint32_t k = 0; k < a.n_channels[i]; k++) {
+            Channel &ch = tr.ch[k];
+            ch.n = n;
+            ch.pyr_levels = pl.levels;
+            ch.d_wav = ch.d_draw = ch.d_orig = tr.d_pool.get() + (size_t)k * pl.stride;
+            ch.d_pyr = ch.d_pyr_orig = ch.d_wav + pl.wav_f;
+            TH_HIP(hipMemcpyAsync(ch.d_wav, a.channels_flat[a.flat0[i] + k], n * sizeof(float), hipMemcpyHostToDevice, tm->copy_stream));
+            bytes += n * sizeof(float);
+            chans.push_back({id, k, tr.sr, ch.d_wav, n});
+            pdescs.push_back(th_pyramid_desc{ch.d_wav, ch.d_pyr, n, ch.pyr_levels, PYR_FIRST});
+            aptrs.back().push_back(ch.d_wav);
+        }
+        adescs.push_back(th_audio_desc{nullptr, (uint64_t)n, a.n_channels[i], a.srs[i], nullptr});
+        fl->loud_ids.emplace_back(id, fl->loud.size());
+    }
+    if (chans.empty()) return TH_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    TH_HIP(hipEventRecord(tm->copy_ev, tm->copy_stream));
+    TH_HIP(hipStreamWaitEvent(c->stream, tm->copy_ev, 0));
+    TH_CHECK(th_waveform_pyramid_dev(c, pdescs.data(), pdescs.size()));
+    // the group's loudness, behind its pyramid (read back after the one synchronisation)
+    for (size_t i = 0; i < adescs.size(); i++) adescs[i].channels = aptrs[i].data();
+    fl->loud.emplace_back(new LoudnessBatch);
+    TH_CHECK(loudness_enqueue(c, adescs.data(), adescs.size(), true, true, fl->loud.back().get()));
+    // (with a normalise target the specs come from the derived audio, which needs the stats first: stage_derived)
+    if (tm->norm_kind == TH_NORM_OFF) TH_CHECK(compute_specs(tm, setting_of(tm), chans, stg.created, &stg.fresh, &fl->pending));
+    *t_launch += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return TH_OK;
+}
+
+// after the drain: the (min, max) of every spec and the AudioStats of every staged track
+int collect_added(Staged &stg, AddInFlight *fl) {
+    TH_CHECK(finish_specs(fl->pending, &stg.fresh));
+    for (size_t g = 0, i = 0; g < fl->loud.size(); g++) {
+        TH_CHECK(loudness_collect(fl->loud[g].get(), false));
+        for (size_t k = 0; i < fl->loud_ids.size() && fl->loud_ids[i].second == g; i++, k++) {
+            Track &tr = stg.tracks[fl->loud_ids[i].first];
+            loudness_result(*fl->loud[g], k, &tr.stats);
+            tr.orig_stats = tr.stats;
+        }
+    }
+    return TH_OK;
+}
+
+}  // namespace
+
 namespace th {
 namespace tmi {
 
-struct Staged {
-    th_tm *tm = nullptr;
-    bool setting = false;  // set_setting: st + the specs of every resident channel; add_tracks: tracks (+ their specs), added
-    Setting st{};
-    std::map<PlanKey, th_plan *> created;
-    std::vector<NewSpec> fresh;
-    std::map<size_t, Track> tracks;
-    std::set<size_t> added;
-    // set_common_normalize / set_common_guard_clipping: the new settings, every track's derived audio, and the specs of the channels
-    // whose audio changes, computed from `views` (stand-ins that point at the staged audio)
-    bool dynamics = false;
-    int norm_kind = TH_NORM_OFF, guard_mode = TH_GUARD_REDUCE_GLOBAL_LEVEL;
-    float norm_target = 0.0f;
-    std::unique_ptr<DeriveBatch> derive;
-    std::list<Channel> views;
-    std::map<Channel *, Channel *> real_of;
-};
-
-void StagedDeleter::operator()(Staged *s) const {
-    if (!s) return;
-    if (!s->fresh.empty() || !s->tracks.empty() || !s->created.empty() || s->derive) {  // not committed: discard
-        (void)hipSetDevice(s->tm->ctx->device);
-        (void)hipStreamSynchronize(s->tm->copy_stream);
-        (void)hipStreamSynchronize(s->tm->ctx->stream);
-        free_new_specs(s->fresh);
-        for (auto &kv : s->tracks) free_track(kv.second);
-        for (auto &kv : s->created) th_plan_destroy(kv.second);
-    }
-    delete s;
-}
+void StagedDeleter::operator()(Staged *s) const { delete s; }
 
 std::shared_mutex &rw_of(th_tm *tm) { return tm->rw; }
 
@@ -1997,65 +2062,35 @@ void list_rates(th_tm *tm, std::vector<uint32_t> *out) {
 }
 
 // Transactional: plans and specs of the NEW setting are made first, into fresh buffers; the manager's own state changes only
-// in commit.  (The reference cannot fail here: realfft takes any even length.  This library plans n_fft = 2^a * odd with
-// a >= 1 and odd <= 63, up to TH_MAX_N_FFT (th_plan_create): f_overlap = 3, 5, 6, 7 run on the generic kernel; e.g.
-// f_overlap = 67 or an n_fft above 2^20 is refused and leaves everything as it was.)
+// in commit.  (The reference cannot fail here: realfft takes any even length.  This library plans every even n_fft up to
+// TH_MAX_N_FFT (th_plan_create): 2^a * odd with odd <= 63 on the FFT kernels, any other odd factor through the chirp-z route.
+// Only an n_fft above TH_MAX_N_FFT or a mel bank above 1 GiB is refused, and leaves everything as it was.)
 int prepare_setting(th_tm *tm, double win_ms, uint32_t t_overlap, uint32_t f_overlap, int freq_scale, StagedPtr *out) {
     TH_HIP(hipSetDevice(tm->ctx->device));
-    StagedPtr stg(new Staged);
-    stg->tm = tm;
-    stg->setting = true;
-    stg->st = Setting{win_ms, t_overlap, f_overlap, freq_scale};
-    std::vector<std::pair<uint32_t, Channel *>> chans;
+    StagedPtr stg(new Staged(tm));
+    stg->setting.reset(new Setting{win_ms, t_overlap, f_overlap, freq_scale});
+    std::vector<SpecInput> chans;
     for (auto &kv : tm->tracks)
-        for (Channel &ch : kv.second.ch) chans.push_back({kv.second.sr, &ch});
-    const int rc = compute_specs(tm, stg->st, chans, stg->created, &stg->fresh);
-    if (rc != TH_OK) return rc;  // (stg discards what was made)
+        for (size_t k = 0; k < kv.second.ch.size(); k++) chans.push_back({kv.first, (uint32_t)k, kv.second.sr, kv.second.ch[k].d_wav, kv.second.ch[k].n});
+    TH_CHECK(compute_specs(tm, *stg->setting, chans, stg->created, &stg->fresh));
     *out = std::move(stg);
     return TH_OK;
 }
 
 // set_common_normalize / set_common_guard_clipping (track.rs:329-337,432-436): every track re-derived from its resident original
-// into staged buffers, and the specs of every channel whose audio changes.  A track that is and stays its original is left alone
-// (its specs would come out the same bits).
+// into staged buffers, and the specs of every channel whose audio changes.
 int prepare_dynamics(th_tm *tm, int kind, float target, int mode, StagedPtr *out) {
     TH_REQUIRE(kind == TH_NORM_OFF || kind == TH_NORM_LUFS || kind == TH_NORM_RMS_DB || kind == TH_NORM_PEAK_DB, "unknown normalize kind %d", kind);
     TH_REQUIRE(mode == TH_GUARD_CLIP || mode == TH_GUARD_REDUCE_GLOBAL_LEVEL || mode == TH_GUARD_LIMITER, "unknown guard-clipping mode %d", mode);
-    th_ctx *c = tm->ctx;
-    TH_HIP(hipSetDevice(c->device));
-    StagedPtr stg(new Staged);
-    stg->tm = tm;
-    stg->dynamics = true;
-    stg->norm_kind = kind;
-    stg->norm_target = target;
-    stg->guard_mode = mode;
+    TH_HIP(hipSetDevice(tm->ctx->device));
+    StagedPtr stg(new Staged(tm));
     stg->derive.reset(new DeriveBatch);
-    stg->derive->ctx = c;
+    stg->derive->kind = kind;
+    stg->derive->target = target;
+    stg->derive->mode = mode;
     std::vector<std::pair<size_t, Track *>> trs;
     for (auto &kv : tm->tracks) trs.push_back({kv.first, &kv.second});
-    int rc = derive_enqueue(tm, trs, kind, target, mode, stg->derive.get());
-    if (rc == TH_OK) {
-        std::vector<std::pair<uint32_t, Channel *>> chans;
-        for (auto &kv : tm->tracks) {
-            const Derived &d = stg->derive->of[kv.first];
-            if (!d.active && !kv.second.d_dyn) continue;
-            for (size_t k = 0; k < kv.second.ch.size(); k++) {
-                Channel &real = kv.second.ch[k];
-                stg->views.emplace_back();
-                Channel &v = stg->views.back();
-                v.d_wav = d.active ? d.aud[k] : real.d_orig;
-                v.n = real.n;
-                stg->real_of[&v] = &real;
-                chans.push_back({kv.second.sr, &v});
-            }
-        }
-        rc = compute_specs(tm, setting_of(tm), chans, stg->created, &stg->fresh);
-    }
-    const hipError_t se = hipStreamSynchronize(c->stream);
-    if (rc != TH_OK) return rc;  // (stg discards what was made)
-    TH_HIP(se);
-    rc = derive_collect(trs, stg->derive.get());
-    if (rc != TH_OK) return rc;
+    TH_CHECK(stage_derived(*stg, trs));
     *out = std::move(stg);
     return TH_OK;
 }
@@ -2071,194 +2106,77 @@ int prepare_add(th_tm *tm, size_t n_tracks, const size_t *ids, const uint32_t *s
     th_ctx *c = tm->ctx;
     TH_HIP(hipSetDevice(c->device));
     // Transactional: the new tracks are staged (audio upload, waveform pyramid, spec) beside the resident ones and
-    // swapped in when everything has succeeded.  A failure frees the staging area and changes nothing.
+    // swapped in when everything has succeeded.  A failure drops the staging area (Staged's discard rule) and changes nothing.
     // Pipelined (round 6; the reference overlaps decode and calc_spec across rayon tasks, core/track.rs:211-239 -> core/mod.rs:
     // 153-163): the tracks go up in GROUPS on a copy stream of the manager's own; the waveform pyramids and the STFT of group g run
     // on the context stream (behind an event of the copy stream) while the host feeds group g + 1 to the copy engine — a pageable
     // source keeps the calling thread inside hipMemcpyAsync for the length of the transfer, so the kernels of the group before
     // cost nothing; nothing waits for the device until the end (one synchronisation, then the per-channel (min, max) read-back).
     // Inputs stay borrowed until the call returns.
-    StagedPtr stg(new Staged);
-    stg->tm = tm;
-    std::map<size_t, Track> &staged = stg->tracks;
-    std::map<PlanKey, th_plan *> &created = stg->created;
-    std::vector<NewSpec> &fresh = stg->fresh;
-    std::vector<PendingMinMax> pending;
     TH_REQUIRE(tm->copy_stream != nullptr && tm->copy_ev != nullptr, "manager without its copy stream");  // (th_tm_create)
-    auto abort_staging = [&]() {  // (the staged specs, tracks and plans go with stg)
-        (void)hipStreamSynchronize(tm->copy_stream);
-        (void)hipStreamSynchronize(c->stream);
-        (void)finish_specs(tm, pending, &fresh, false);
-        stg.reset();
-    };
-    int rc = TH_OK;
-    hipError_t e = hipSuccess;
-    std::vector<size_t> added;
-    std::vector<std::unique_ptr<LoudnessBatch>> loud;      // one per group (freed after the synchronisation below)
-    std::vector<std::pair<size_t, size_t>> loud_ids;       // (id, its group), in the order of the groups' descriptors
+    AddInFlight fl;  // (before stg: on an early return stg goes first, and drains both streams before these free anything)
+    StagedPtr stg(new Staged(tm));
     const bool prof = getenv("TH_TM_PROF") != nullptr;
     auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double tp0 = now();
-    // the same id twice in one call: the later one wins, as sequential adds would — only its data is uploaded
-    std::map<size_t, size_t> last_of;
-    std::vector<size_t> flat0(n_tracks, 0);
-    {
-        size_t flat = 0;
-        for (size_t t = 0; t < n_tracks; t++) {
-            last_of[ids[t]] = t;
-            flat0[t] = flat;
-            flat += n_channels[t];
-            added.push_back(ids[t]);
-        }
+    AddArgs a{n_tracks, ids, srs, n_channels, channels_flat, n_samples, {}, std::vector<size_t>(n_tracks, 0)};
+    for (size_t t = 0, flat = 0; t < n_tracks; t++) {
+        a.last_of[ids[t]] = t;
+        a.flat0[t] = flat;
+        flat += n_channels[t];
+        stg->added.insert(ids[t]);
     }
-    // groups of about 96 MB of samples (at least one track each): a group's launches cost ~0.2 ms of host time (descriptor tables,
-    // spec allocations: six groups of 32 MB were SLOWER than no pipeline, 6.0 against 5.1 ms for 32 tracks), the last group's
-    // kernels are the only ones nothing hides.  (Round 6, tried: the uploads on a helper thread so that this thread's launches do
-    // not hold up the copy engine — the launches then take 1.15 ms of host time instead of 0.67 and the call 5.2 instead of 4.9 ms:
-    // the runtime serialises the pageable copy path and the launches of the two threads.)
-    constexpr size_t GROUP_BYTES = (size_t)96 << 20;
-    const Setting st = setting_of(tm);
-    size_t t = 0;
     double t_launch = 0.0;
-    while (t < n_tracks && e == hipSuccess && rc == TH_OK) {
-        std::vector<std::pair<uint32_t, Channel *>> chans;
-        std::vector<th_pyramid_desc> pdescs;
-        std::vector<th_audio_desc> adescs;
-        std::vector<std::vector<const float *>> aptrs;
-        size_t bytes = 0;
-        for (; t < n_tracks && (bytes == 0 || bytes < GROUP_BYTES) && e == hipSuccess; t++) {
-            if (last_of[ids[t]] != t) continue;
-            Track &tr = staged[ids[t]];
-            tr.sr = srs[t];
-            tr.ch.assign(n_channels[t], Channel());
-            // resident waveform pyramid: levels up to the one whose single bin spans the channel (render_tiles.rs:232-259)
-            // (levels PYR_FIRST .. lv - 1: level 0 would be (x, x, x) per sample — half of the pyramid's bytes — and level 1 a
-            // quarter; tiles of both are served from the resident samples instead, th_pyramid_desc.first_level)
-            const size_t n = n_samples[t];
-            uint32_t lv = 1;
-            while (lv < PYR_MAX_LEVELS && ((uint64_t)1 << (lv - 1)) < n) lv++;
-            const size_t wav_f = (n + 63) / 64 * 64;  // (256-byte pieces: every view starts on a 256-byte boundary)
-            const size_t pyr_f = (std::max<size_t>(1, th_waveform_pyramid_offset(n, std::max(lv, PYR_FIRST)) - th_waveform_pyramid_offset(n, PYR_FIRST)) + 63) / 64 * 64;
-            e = hipMalloc(&tr.d_pool, (wav_f + pyr_f) * n_channels[t] * sizeof(float));
-            for (uint32_t k = 0; k < n_channels[t] && e == hipSuccess; k++) {
-                Channel &ch = tr.ch[k];
-                ch.n = n;
-                ch.pyr_levels = lv;
-                ch.d_wav = static_cast<float *>(tr.d_pool) + (size_t)k * (wav_f + pyr_f);
-                ch.d_pyr = ch.d_wav + wav_f;
-                ch.d_draw = ch.d_orig = ch.d_wav;
-                ch.d_pyr_orig = ch.d_pyr;
-                e = hipMemcpyAsync(ch.d_wav, channels_flat[flat0[t] + k], ch.n * sizeof(float), hipMemcpyHostToDevice, tm->copy_stream);
-                bytes += ch.n * sizeof(float);
-                // (std::map nodes and this vector do not move any more: the pointer stays valid while later groups are staged)
-                chans.push_back({tr.sr, &ch});
-                pdescs.push_back(th_pyramid_desc{ch.d_wav, ch.d_pyr, ch.n, ch.pyr_levels, PYR_FIRST});
-            }
-            if (e == hipSuccess) {
-                aptrs.emplace_back();
-                for (const Channel &ch : tr.ch) aptrs.back().push_back(ch.d_wav);
-                adescs.push_back(th_audio_desc{nullptr, (uint64_t)n, n_channels[t], srs[t], nullptr});
-                loud_ids.emplace_back(ids[t], loud.size());
-            }
-        }
-        if (e != hipSuccess) break;
-        if (chans.empty()) continue;
-        const double tl0 = now();
-        e = hipEventRecord(tm->copy_ev, tm->copy_stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, tm->copy_ev, 0);
-        if (e != hipSuccess) break;
-        rc = th_waveform_pyramid_dev(c, pdescs.data(), pdescs.size());
-        if (rc == TH_OK) {  // the group's loudness, behind its pyramid (read back at the one synchronisation below)
-            for (size_t i = 0; i < adescs.size(); i++) adescs[i].channels = aptrs[i].data();
-            loud.emplace_back(new LoudnessBatch);
-            rc = loudness_enqueue(c, adescs.data(), adescs.size(), true, true, loud.back().get());
-        }
-        // (with a normalise target the specs come from the derived audio, which needs the stats first: below)
-        if (rc == TH_OK && tm->norm_kind == TH_NORM_OFF) rc = compute_specs(tm, st, chans, created, &fresh, &pending);
-        t_launch += now() - tl0;
-    }
+    for (size_t t = 0; t < n_tracks;) TH_CHECK(stage_group(*stg, a, &t, &fl, &t_launch));
     const double tp1 = now();
-    if (e == hipSuccess && rc == TH_OK) e = hipStreamSynchronize(tm->copy_stream);  // inputs are borrowed for this call only
-    if (e == hipSuccess && rc == TH_OK) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess || rc != TH_OK) {
-        abort_staging();
-        if (rc != TH_OK) return rc;
-        TH_HIP(e);
-    }
-    rc = finish_specs(tm, pending, &fresh, true);
-    for (size_t g = 0, i = 0; rc == TH_OK && g < loud.size(); g++) {
-        rc = loudness_collect(loud[g].get(), false);
-        for (size_t k = 0; rc == TH_OK && i < loud_ids.size() && loud_ids[i].second == g; i++, k++)
-            loudness_result(*loud[g], k, &staged[loud_ids[i].first].stats);
-    }
-    for (auto &kv : staged) {
-        kv.second.orig_stats = kv.second.stats;
-        kv.second.guard_stats.assign(kv.second.ch.size(), th_guard_clip_stats{});
-    }
+    TH_HIP(hipStreamSynchronize(tm->copy_stream));  // inputs are borrowed for this call only
+    TH_HIP(hipStreamSynchronize(c->stream));
+    int rc = collect_added(*stg, &fl);
     if (rc == TH_OK && tm->norm_kind != TH_NORM_OFF) {
-        // track.normalize(common_normalize, common_guard_clipping) — track.rs:217: one synchronisation between the stats and the rest
+        // track.normalize(common_normalize, common_guard_clipping) — track.rs:217, under the settings in force
+        stg->derive.reset(new DeriveBatch);
+        get_common_dynamics(tm, &stg->derive->kind, &stg->derive->target, &stg->derive->mode);
         std::vector<std::pair<size_t, Track *>> trs;
-        for (auto &kv : staged) trs.push_back({kv.first, &kv.second});
-        DeriveBatch db;
-        rc = derive_enqueue(tm, trs, tm->norm_kind, tm->norm_target, tm->guard_mode, &db);
-        const hipError_t se = hipStreamSynchronize(c->stream);
-        if (rc == TH_OK && se != hipSuccess) rc = th::fail(TH_ERR_HIP, "%s", hipGetErrorString(se));
-        if (rc == TH_OK) rc = derive_collect(trs, &db);
-        if (rc == TH_OK) {
-            std::vector<std::pair<uint32_t, Channel *>> chans;
-            for (auto &kv : staged) {
-                install_derived(kv.second, db.of[kv.first]);
-                for (Channel &ch : kv.second.ch) chans.push_back({kv.second.sr, &ch});
-            }
-            rc = compute_specs(tm, st, chans, created, &fresh);
-        }
+        for (auto &kv : stg->tracks) trs.push_back({kv.first, &kv.second});
+        rc = stage_derived(*stg, trs);
     }
     if (prof) fprintf(stderr, "th_tm_add_tracks prof: staging + launches %.2f ms (of which pyramid / STFT launches %.2f), drain %.2f\n", tp1 - tp0, t_launch, now() - tp1);
-    if (rc != TH_OK) {
-        abort_staging();
-        return rc;
-    }
-    stg->added.insert(added.begin(), added.end());
+    if (rc != TH_OK) return rc;
     *out = std::move(stg);
     return TH_OK;
 }
 
+// Reached with the context stream and the copy stream idle; cannot fail.  One sequence: whatever part is present is applied.
 void commit(th_tm *tm, StagedPtr s) {
     (void)hipSetDevice(tm->ctx->device);
-    if (s->dynamics) {
-        tm->norm_kind = s->norm_kind;
-        tm->norm_target = s->norm_target;
-        tm->guard_mode = s->guard_mode;
-        for (auto &kv : s->derive->of) install_derived(tm->tracks.at(kv.first), kv.second);
-        for (NewSpec &n : s->fresh) n.ch = s->real_of.at(n.ch);
-        commit_specs(s->fresh);
-        for (auto &kv : s->created) tm->plans[kv.first] = kv.second;
-        s->created.clear();
-        s->derive.reset();
-        return;
+    // re-adding an id replaces it (reload_tracks, core/mod.rs:73-82): the old track's buffers go with the assignment
+    for (auto &kv : s->tracks) tm->tracks[kv.first] = std::move(kv.second);
+    if (s->derive) {
+        tm->norm_kind = s->derive->kind;
+        tm->norm_target = s->derive->target;
+        tm->guard_mode = s->derive->mode;
+        for (auto &kv : s->derive->of) install_derived(tm->tracks.find(kv.first)->second, kv.second);
+    }
+    for (auto &kv : s->created) tm->plans[kv.first] = kv.second;
+    for (NewSpec &n : s->fresh) {
+        Channel &ch = *find_channel(tm, n.id, n.ch);
+        ch.d_spec = std::move(n.d_spec);
+        ch.T = n.T;
+        ch.H = n.H;
+        ch.spec_pitch = n.pitch;
+        ch.mn = n.mn;
+        ch.mx = n.mx;
+        ch.has_spec = true;
     }
     if (s->setting) {
-        tm->win_ms = s->st.win_ms;
-        tm->t_overlap = s->st.t_overlap;
-        tm->f_overlap = s->st.f_overlap;
-        tm->freq_scale = s->st.freq_scale;
-        for (auto &kv : s->created) tm->plans[kv.first] = kv.second;
-        s->created.clear();
-        commit_specs(s->fresh);
-        retain_plans(tm);  // spec_analyzer.retain(...)  core/mod.rs:111-112
-        return;
+        tm->win_ms = s->setting->win_ms;
+        tm->t_overlap = s->setting->t_overlap;
+        tm->f_overlap = s->setting->f_overlap;
+        tm->freq_scale = s->setting->freq_scale;
+        retain_plans(tm);  // spec_analyzer.retain(...)  core/mod.rs:111-112; add_tracks does not prune (:62-71)
     }
-    commit_specs(s->fresh);  // (into the staged channels)
-    for (auto &kv : s->created) tm->plans[kv.first] = kv.second;
-    s->created.clear();
-    for (auto &kv : s->tracks) {
-        Track &dst = tm->tracks[kv.first];  // re-adding an id replaces it (reload_tracks, core/mod.rs:73-82)
-        free_track(dst);
-        dst = std::move(kv.second);
-        kv.second.d_pool = nullptr;
-    }
-    s->tracks.clear();
     tm->no_spec_img_ids.insert(tm->no_spec_img_ids.end(), s->added.begin(), s->added.end());  // core/mod.rs:70
+    s->committed = true;
 }
 
 int requantise(th_tm *tm, const DbRange *global, bool force_update_all, bool images_only, std::vector<size_t> *updated) {
