@@ -623,6 +623,59 @@ TH_API int th_tm_get_spectra(th_tm *tm, const th_spectrum_request *reqs, size_t 
 TH_API int th_tm_get_spectrum(th_tm *tm, size_t id, uint32_t ch, int kind, double start_sec, double end_sec, float *out,
                               size_t cap_floats, th_spectrum_info *info);
 
+/* ---------------------------------------------------------------- loudness meter of resident tracks */
+/* What an R128 loudness display shows beside the integrated value of th_tm_get_audio_stats, computed from a track's AUDIO (the
+ * derived audio while a normalise gain is in force, else the original): true peak, loudness range, maximum momentary and
+ * short-term loudness, and the two curves along the track.  No reference implementation exists (upstream reads loudness_global
+ * only); the arithmetic is libebur128's, restated, and these definitions are the contract:
+ *   s100 = (sr + 5) / 10, n_seg = n_samples / s100, q_c[k] = the K-weighted energy (sum of y^2) of segment k of channel c, w_c the
+ *   channel map of th_audio_stats.  Momentary M_k = sum_c w_c (q_c[k] + .. + q_c[k + 3]) / (4 s100), k <= n_seg - 4: the values and
+ *   bits of th_audio_desc.block_energy.  Short-term S_k = sum_c w_c (q_c[k] + .. + q_c[k + 29]) / (30 s100), k <= n_seg - 30.  f64,
+ *   segments summed in ascending order per channel, then the channels in ascending order.  A series is returned as LUFS,
+ *   10 log10(E) - 0.691 in f64 (E = 0: -inf; NaN stays NaN); max_*_lufs is the largest non-NaN value, -inf when there is none.
+ *   loudness_range (EBU Tech 3342) takes S_0, S_10, S_20, .. (one 3 s block per second) through the 1000 histogram bins of the
+ *   integrated loudness: blocks below -70 LUFS and NaN never count; the relative gate is 0.01 of the mean bin energy; of what passes,
+ *   lo = (size_t)((size - 1) 0.1 + 0.5) and hi = (size_t)((size - 1) 0.95 + 0.5) index the sorted blocks, and the range is
+ *   10 log10(E_hi) - 10 log10(E_lo) of their bins' centres; 0 when nothing passes.  th_loudness_range (host) is that definition.
+ *   true_peak: the oversampling factor F is 4 for sr < 96000, 2 for sr < 192000, else 1 (then true_peak = max_peak).  The
+ *   interpolator has 49 taps, c_j = sinc((j - 24) pi / F) 0.5 (1 - cos(2 pi j / 48)) in f64, kept when |c_j| > 1e-6; tap j belongs
+ *   to phase j mod F with delay j div F (th_true_peak_filter lists the kept taps in ascending j).  y_f[i] = sum_d c x[i - d] for
+ *   i in [0, n_samples), x[i < 0] = 0, nothing behind the last sample; on the device the coefficients are f32 and a phase is one
+ *   fmaf chain in ascending delay from 0.  true_peak = the largest |y| over channels, phases and i (NaN ignored; 0 for silence),
+ *   true_peak_dB = 20 log10 of it, taken in f64 and rounded once; true_peak_channel = the lowest channel that attains it.
+ * A track at a rate outside 16 .. 2 822 400 Hz (global_lufs = NaN) has no series: both counts are 0 and loudness_range and the two
+ * maxima are NaN; its true peak is still measured.
+ * th_tm_get_loudness_meters: meters[i] describes ids[i] (an id may repeat).  The series are f64 LUFS packed dense in request order,
+ * within a track the momentary series, then the short-term one; the offsets and counts are in the meter and *out_len is the number
+ * of doubles needed.  series == NULL: the series are not wanted, which is no error: the meters are filled, with counts and
+ * offsets.  A non-NULL series with cap_doubles < *out_len: TH_ERR_BUFFER_TOO_SMALL, nothing is written to series; the meters then
+ * carry the counts, offsets, oversampling and revision only.  An unknown id: TH_ERR_NOT_FOUND; a NULL handle, NULL ids with n > 0,
+ * NULL meters or NULL out_len: TH_ERR_INVALID_ARG; the first faulty request decides and nothing is written.  A reader like
+ * th_tm_get_spectra: shared lock, a reader slot's own stream, one batched launch sequence for all ids; its scratch on the slot is
+ * made on the first call and only grows.  Nothing is cached and nothing happens at add time: every call computes.  A track's
+ * values depend on its audio alone - not on the batch, the slot, or th_tm against th_tmg.  waveform_revision: the revision the
+ * values belong to (a host caches by it).
+ * th_tm_get_loudness_meter: one id; the doubles needed are meter->n_momentary + meter->n_short_term. */
+typedef struct {
+    double loudness_range; /* LU */
+    double max_momentary_lufs, max_short_term_lufs;
+    float true_peak, true_peak_dB;
+    uint32_t true_peak_channel, oversampling; /* 4, 2 or 1 */
+    uint64_t momentary_offset, n_momentary;   /* doubles into `series` */
+    uint64_t short_term_offset, n_short_term;
+    uint64_t waveform_revision;
+} th_loudness_meter;
+TH_API int th_tm_get_loudness_meters(th_tm *tm, const size_t *ids, size_t n, th_loudness_meter *meters /* n */, double *series,
+                                     size_t cap_doubles, size_t *out_len);
+TH_API int th_tm_get_loudness_meter(th_tm *tm, size_t id, th_loudness_meter *meter, double *series, size_t cap_doubles);
+/* The host arithmetic around it (no GPU).  th_true_peak_filter: the factor for sr and the kept taps in ascending j (coefficient,
+ * phase, delay; arrays of 49).  th_loudness_n_short_term: n_seg - 29 blocks, or 0 when n_seg < 30; TH_ERR_UNSUPPORTED outside
+ * 16 .. 2 822 400 Hz.  th_loudness_range: LU from the short-term ENERGIES taken once per second. */
+TH_API int th_true_peak_filter(uint32_t sr, uint32_t *factor, double coef[49], uint32_t phase[49], uint32_t delay[49],
+                               uint32_t *n_taps);
+TH_API int th_loudness_n_short_term(size_t n_samples, uint32_t sr, size_t *n_blocks);
+TH_API int th_loudness_range(const double *short_term_energies_1s, size_t n, double *lra);
+
 /* ---------------------------------------------------------------- TrackManager over several devices (one process) */
 /* th_tmg: the th_tm_* calls above, call for call, with a th_tmg * in place of the th_tm *; a multi-GPU host swaps one for
  * the other.  Every result — updated ids, max_sr, db state, revisions, specs, images, tile bytes, batch offsets, render
@@ -693,6 +746,12 @@ TH_API int th_tmg_get_spectra(th_tmg *tmg, const th_spectrum_request *reqs, size
                               th_spectrum_info *info /* n */, size_t *out_len);
 TH_API int th_tmg_get_spectrum(th_tmg *tmg, size_t id, uint32_t ch, int kind, double start_sec, double end_sec, float *out,
                                size_t cap_floats, th_spectrum_info *info);
+
+/* loudness meters: every id goes to its owning slot, the slots are served side by side; meters and series are those of one th_tm
+ * (request order, packed dense), the revision stamped is the manager's own */
+TH_API int th_tmg_get_loudness_meters(th_tmg *tmg, const size_t *ids, size_t n, th_loudness_meter *meters /* n */, double *series,
+                                      size_t cap_doubles, size_t *out_len);
+TH_API int th_tmg_get_loudness_meter(th_tmg *tmg, size_t id, th_loudness_meter *meter, double *series, size_t cap_doubles);
 
 /* Test and measurement entry points (kernel selectors for A/B runs, per-launch kernel timing, replacing a resident image
  * with given pixels) are NOT part of this interface: include/thesia_amd_testing.h declares them; a thesia host binds none. */

@@ -102,6 +102,13 @@ class SpectrumInfo(C.Structure):  # th_spectrum_info
                 ("spectrogram_revision", C.c_uint64)]
 
 
+class LoudnessMeter(C.Structure):  # th_loudness_meter
+    _fields_ = [("loudness_range", C.c_double), ("max_momentary_lufs", C.c_double), ("max_short_term_lufs", C.c_double),
+                ("true_peak", C.c_float), ("true_peak_dB", C.c_float), ("true_peak_channel", C.c_uint32), ("oversampling", C.c_uint32),
+                ("momentary_offset", C.c_uint64), ("n_momentary", C.c_uint64), ("short_term_offset", C.c_uint64),
+                ("n_short_term", C.c_uint64), ("waveform_revision", C.c_uint64)]
+
+
 class PyramidDesc(C.Structure):
     _fields_ = [("wav", C.c_void_p), ("out", C.c_void_p), ("n_samples", C.c_uint64), ("n_levels", C.c_uint32),
                 ("first_level", C.c_uint32)]
@@ -286,6 +293,14 @@ _SIGS = {
     "th_tm_get_spectrum": [vp, C.c_size_t, C.c_uint32, C.c_int, C.c_double, C.c_double, c_f32p, C.c_size_t, C.POINTER(SpectrumInfo)],
     "th_tmg_get_spectra": [vp, C.POINTER(SpectrumRequest), C.c_size_t, c_f32p, C.c_size_t, C.POINTER(SpectrumInfo), c_szp],
     "th_tmg_get_spectrum": [vp, C.c_size_t, C.c_uint32, C.c_int, C.c_double, C.c_double, c_f32p, C.c_size_t, C.POINTER(SpectrumInfo)],
+    "th_tm_get_loudness_meters": [vp, c_szp, C.c_size_t, C.POINTER(LoudnessMeter), C.POINTER(C.c_double), C.c_size_t, c_szp],
+    "th_tm_get_loudness_meter": [vp, C.c_size_t, C.POINTER(LoudnessMeter), C.POINTER(C.c_double), C.c_size_t],
+    "th_tmg_get_loudness_meters": [vp, c_szp, C.c_size_t, C.POINTER(LoudnessMeter), C.POINTER(C.c_double), C.c_size_t, c_szp],
+    "th_tmg_get_loudness_meter": [vp, C.c_size_t, C.POINTER(LoudnessMeter), C.POINTER(C.c_double), C.c_size_t],
+    "th_true_peak_filter": [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                            C.POINTER(C.c_uint32)],
+    "th_loudness_n_short_term": [C.c_size_t, C.c_uint32, c_szp],
+    "th_loudness_range": [C.POINTER(C.c_double), C.c_size_t, C.POINTER(C.c_double)],
     "th_tile_cache_create": [C.c_size_t, C.POINTER(vp)],
     "th_tile_cache_destroy": [vp],
     "th_tile_cache_lookup": [vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), c_u8p, C.c_size_t,

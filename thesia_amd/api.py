@@ -200,6 +200,68 @@ class _SpectrumMethods:
         return out, _spectrum_info_dict(info)
 
 
+def _meter_dict(o, series) -> dict:
+    d = {k: getattr(o, k) for k, _ in o._fields_}
+    for k in ("true_peak", "true_peak_dB"):
+        d[k] = np.float32(d[k])
+    if series is not None:
+        d["momentary"] = series[o.momentary_offset: o.momentary_offset + o.n_momentary]
+        d["short_term"] = series[o.short_term_offset: o.short_term_offset + o.n_short_term]
+    return d
+
+
+class _LoudnessMeterMethods:
+    """true peak, loudness range and the momentary / short-term curves of resident tracks (th_tm_* and th_tmg_*: _PFX)"""
+
+    def loudness_meters(self, track_ids, series: bool = True):
+        """th_tm_get_loudness_meters: -> one dict per id, in request order: the th_loudness_meter fields and, with series, the
+        f64 LUFS arrays "momentary" and "short_term" """
+        ids = [int(i) for i in track_ids]
+        n = len(ids)
+        if n == 0:
+            return []
+        arr = (C.c_size_t * n)(*ids)
+        ms = (_ffi.LoudnessMeter * n)()
+        need = C.c_size_t()
+        fn = getattr(lib, self._PFX + "get_loudness_meters")
+        if not series:
+            check(fn(self.handle, arr, n, ms, None, 0, C.byref(need)))
+            return [_meter_dict(m, None) for m in ms]
+        one = np.empty(1, np.float64)
+        rc = fn(self.handle, arr, n, ms, one.ctypes.data_as(C.POINTER(C.c_double)), 0, C.byref(need))  # (the size alone)
+        if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+            check(rc)
+        out = np.empty(max(need.value, 1), np.float64)
+        check(fn(self.handle, arr, n, ms, out.ctypes.data_as(C.POINTER(C.c_double)), need.value, C.byref(need)))
+        return [_meter_dict(m, out) for m in ms]
+
+    def loudness_meter(self, track_id: int, series: bool = True) -> dict:
+        """th_tm_get_loudness_meter: one track"""
+        return self.loudness_meters([track_id], series)[0]
+
+
+def true_peak_filter(sr: int):
+    """-> (factor, coef f64, phase, delay) of the kept taps of the true-peak interpolator at rate sr, ascending tap index (host)"""
+    f, n = C.c_uint32(), C.c_uint32()
+    c, p, d = (C.c_double * 49)(), (C.c_uint32 * 49)(), (C.c_uint32 * 49)()
+    check(lib.th_true_peak_filter(sr, C.byref(f), c, p, d, C.byref(n)))
+    return f.value, np.array(c[:n.value]), np.array(p[:n.value], np.uint32), np.array(d[:n.value], np.uint32)
+
+
+def loudness_n_short_term(n_samples: int, sr: int) -> int:
+    n = C.c_size_t()
+    check(lib.th_loudness_n_short_term(n_samples, sr, C.byref(n)))
+    return n.value
+
+
+def loudness_range(short_term_energies_1s) -> float:
+    """EBU Tech 3342 loudness range (LU) of the 3 s block energies taken once per second (host arithmetic)"""
+    e = np.ascontiguousarray(short_term_energies_1s, dtype=np.float64)
+    out = C.c_double()
+    check(lib.th_loudness_range(e.ctypes.data_as(C.POINTER(C.c_double)), e.size, C.byref(out)))
+    return out.value
+
+
 class _DynamicsMethods:
     """set_common_normalize / set_common_guard_clipping and what they leave to read (th_tm_* and th_tmg_*: _PFX)"""
 
@@ -691,7 +753,7 @@ class TileCache:
                 "spectrogram_revision": sr.value, "hits": h.value, "misses": m.value}
 
 
-class TrackManager(_DynamicsMethods, _SpectrumMethods):
+class TrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods):
     """th_tm: mirror of core/mod.rs TrackManager with HBM-resident audio / specs / images."""
     _PFX = "th_tm_"
 
@@ -891,7 +953,7 @@ class TrackManager(_DynamicsMethods, _SpectrumMethods):
         return out[: n.value].tobytes()
 
 
-class MultiTrackManager(_DynamicsMethods, _SpectrumMethods):
+class MultiTrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods):
     """th_tmg: the TrackManager over several devices of one process (duplicates allowed: [0, 0] is two slots on one card).
     Same method names as TrackManager; results are bit-identical to one TrackManager holding every track."""
     _PFX = "th_tmg_"

@@ -1576,6 +1576,32 @@ TH_API int th_gated_loudness(const double *block_energies, size_t n, double *luf
     TH_CATCH
 }
 
+TH_API int th_true_peak_filter(uint32_t sr, uint32_t *factor, double coef[49], uint32_t phase[49], uint32_t delay[49], uint32_t *n_taps) {
+    TH_TRY
+    TH_REQUIRE(factor && coef && phase && delay && n_taps, "NULL argument");
+    *factor = true_peak_factor(sr);
+    *n_taps = true_peak_filter(*factor, coef, phase, delay);
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_loudness_n_short_term(size_t n_samples, uint32_t sr, size_t *n_blocks) {
+    TH_TRY
+    TH_REQUIRE(n_blocks, "NULL argument");
+    if (!loudness_rate_ok(sr)) return fail(TH_ERR_UNSUPPORTED, "sample rate %u outside [16, 2822400]", sr);
+    *n_blocks = loudness_n_short_term(n_samples, sr);
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_loudness_range(const double *short_term_energies_1s, size_t n, double *lra) {
+    TH_TRY
+    TH_REQUIRE(lra && (n == 0 || short_term_energies_1s), "NULL argument");
+    *lra = loudness_range(short_term_energies_1s, n);
+    return TH_OK;
+    TH_CATCH
+}
+
 TH_API int th_normalize_gain(int kind, float target, const th_audio_stats *orig, float *gain) {
     TH_TRY
     TH_REQUIRE(orig && gain, "NULL argument");

@@ -442,6 +442,73 @@ double gated_loudness(const double *E, size_t n) {
     return 10.0 * std::log10(sum) - 0.691;
 }
 
+size_t loudness_n_short_term(size_t n, uint32_t sr) {
+    const size_t s100 = loudness_s100(sr);
+    const size_t n_seg = s100 ? n / s100 : 0;
+    return n_seg < 30 ? 0 : n_seg - 29;
+}
+
+double loudness_lufs(double e) { return 10.0 * std::log10(e) - 0.691; }
+
+double loudness_series_max(const double *lufs, size_t n) {
+    double m = -std::numeric_limits<double>::infinity();
+    for (size_t k = 0; k < n; k++)
+        if (lufs[k] > m) m = lufs[k];  // (NaN compares false)
+    return m;
+}
+
+// ebur128_loudness_range_multiple (histogram mode) for one state
+double loudness_range(const double *E, size_t n) {
+    const LoudnessHistogram &h = loudness_histogram();
+    std::vector<uint64_t> hist(1000, 0);
+    for (size_t k = 0; k < n; k++)
+        if (E[k] >= h.boundaries[0]) hist[h.index(E[k])]++;  // (NaN compares false: never counted)
+    uint64_t size = 0;
+    double power = 0.0;
+    for (size_t j = 0; j < 1000; j++) {
+        size += hist[j];
+        power += (double)hist[j] * h.energies[j];
+    }
+    if (!size) return 0.0;
+    power /= (double)size;
+    const double integ = 0.01 * power;  // the relative gate: -20 LU
+    size_t idx = 0;
+    if (!(integ < h.boundaries[0])) {
+        idx = h.index(integ);
+        if (integ > h.energies[idx]) idx++;
+    }
+    size = 0;
+    for (size_t j = idx; j < 1000; j++) size += hist[j];
+    if (!size) return 0.0;
+    const uint64_t lo = (uint64_t)((double)(size - 1) * 0.1 + 0.5), hi = (uint64_t)((double)(size - 1) * 0.95 + 0.5);
+    uint64_t cnt = 0;
+    size_t j = idx;
+    while (cnt <= lo) cnt += hist[j++];
+    const double l = h.energies[j - 1];
+    while (cnt <= hi) cnt += hist[j++];
+    const double hh = h.energies[j - 1];
+    return 10.0 * std::log10(hh) - 10.0 * std::log10(l);
+}
+
+uint32_t true_peak_factor(uint32_t sr) { return sr < 96000 ? 4 : sr < 192000 ? 2 : 1; }
+
+uint32_t true_peak_filter(uint32_t factor, double coef[TRUE_PEAK_TAPS], uint32_t phase[TRUE_PEAK_TAPS], uint32_t delay[TRUE_PEAK_TAPS]) {
+    const double pi = 3.14159265358979323846;
+    uint32_t n = 0;
+    for (uint32_t j = 0; j < TRUE_PEAK_TAPS; j++) {
+        const double m = (double)j - 24.0;
+        const double t = m * pi / (double)factor;
+        const double sinc = m == 0.0 ? 1.0 : std::sin(t) / t;
+        const double c = sinc * (0.5 * (1.0 - std::cos(2.0 * pi * (double)j / 48.0)));
+        if (!(std::fabs(c) > 1e-6)) continue;
+        coef[n] = c;
+        phase[n] = j % factor;
+        delay[n] = j / factor;
+        n++;
+    }
+    return n;
+}
+
 void kw_transition(const double a[5], double A[16]) {
     std::fill(A, A + 16, 0.0);
     for (int j = 0; j < 4; j++) A[j] = -a[j + 1];

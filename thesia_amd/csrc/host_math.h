@@ -81,6 +81,24 @@ struct LoudnessRate {
 };
 const LoudnessRate &loudness_rate(uint32_t sr);  // (cached per rate; sr must satisfy loudness_rate_ok)
 
+// ---- the loudness meter (th_tm_get_loudness_meters): EBU Tech 3342 loudness range, the momentary / short-term series as LUFS and
+// the true-peak interpolator, restated from libebur128 (PARITY UNPINNED like the block above)
+// 3 s blocks, one per 100 ms segment: n_seg - 29 of them, n_seg = n / s100, or 0 when n_seg < 30
+size_t loudness_n_short_term(size_t n_samples, uint32_t sr);
+// 10 log10(E) - 0.691 in f64: E = 0 gives -inf, NaN stays NaN
+double loudness_lufs(double energy);
+// the largest non-NaN value of a LUFS series, -inf when there is none
+double loudness_series_max(const double *lufs, size_t n);
+// ebur128_loudness_range in histogram mode over the short-term energies taken once per second: the 1000 bins of gated_loudness,
+// relative gate -20 LU, the 10th and 95th percentile of what passes -> LU (0 when nothing passes)
+double loudness_range(const double *short_term_energies, size_t n);
+// The true-peak interpolator: a 49-tap Hann-windowed sinc for an oversampling factor F (4 below 96 kHz, 2 below 192 kHz, else 1),
+// c_j = sinc((j - 24) pi / F) 0.5 (1 - cos(2 pi j / 48)); taps with |c_j| <= 1e-6 are dropped; tap j feeds phase j mod F with delay
+// j div F.  The kept taps in ascending j; returns their count.
+constexpr uint32_t TRUE_PEAK_TAPS = 49;
+uint32_t true_peak_factor(uint32_t sr);
+uint32_t true_peak_filter(uint32_t factor, double coef[TRUE_PEAK_TAPS], uint32_t phase[TRUE_PEAK_TAPS], uint32_t delay[TRUE_PEAK_TAPS]);
+
 // ---- normalisation and clip guarding (dynamics/normalize.rs, limiter.rs, envelope.rs, stats.rs)
 // 10f32.powf((target - stat) / 20) in f32 (normalize.rs:29-43); kind: TH_NORM_* (Off: 1); false for an unknown kind
 bool normalize_gain(int kind, float target, double global_lufs, float rms_dB, float max_peak_dB, float *gain);

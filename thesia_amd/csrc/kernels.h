@@ -296,6 +296,32 @@ struct LoudTrackJob {      // one track
 };
 hipError_t launch_loudness(const LoudJob *d_jobs, uint32_t n_jobs, uint32_t max_chunks, uint32_t max_fchunks, const LoudnessRate *d_rates,
                            uint32_t lds_floats, const LoudTrackJob *d_tjobs, uint32_t n_tracks, uint64_t max_blocks, hipStream_t s);
+// pass D alone over the q of an earlier launch_loudness: blocks of `span` segments (4: the momentary series, 30: the short-term one;
+// LoudTrackJob::L = span s100, n_blocks = n_seg - span + 1, n_fchunks >= n_seg n_sub), summed in the same order
+hipError_t launch_loudness_blocks(const LoudTrackJob *d_tjobs, uint32_t n_tracks, uint64_t max_blocks, uint32_t span, hipStream_t s);
+
+// ---- kernels_meter.hip: the true peak of a batch of channels (th_tm_get_loudness_meters): max |y| of the polyphase interpolator
+// of host_math.h true_peak_filter, F = 4 or 2, causal from zero history, nothing behind the last sample
+constexpr uint32_t TP_RUN = 33;                 // consecutive outputs of one thread (odd: the lanes' LDS reads hit different banks)
+constexpr uint32_t TP_THREADS = 256;
+constexpr uint32_t TP_CHUNK = TP_RUN * TP_THREADS;  // samples of one workgroup (a multiple of 4)
+struct TruePeakJob {       // one channel
+    const float *wav;
+    uint32_t *peak;        // max |y| as float bits (zeroed by the caller)
+    uint64_t n;
+    uint32_t n_chunks;     // ceil(n / TP_CHUNK)
+    uint32_t aligned16;
+};
+static_assert(sizeof(TruePeakJob) == 32, "TruePeakJob must have no implicit padding");
+struct TruePeakCoef {      // f32 taps: phase p = 1 .. F - 1, delay d at c[(p - 1) T + d] (T = 12 at F = 4, 24 at F = 2), then phase 0's one tap
+    float c[36];
+    float c0;
+    uint32_t d0;           // phase 0's delay (6 or 12)
+};
+void true_peak_coef(uint32_t factor, TruePeakCoef *out);  // host: from true_peak_filter, rounded to f32
+// factor 4 or 2 (K = true_peak_coef(factor)); every job of d_jobs is of that factor; max_chunks: the largest n_chunks
+hipError_t launch_true_peak(const TruePeakJob *d_jobs, uint32_t n_jobs, uint32_t max_chunks, uint32_t factor, const TruePeakCoef &K,
+                            hipStream_t s);
 
 // ---- kernels_dynamics.hip: normalise gain + clip guard (clip, global level, look-ahead limiter) of a batch of tracks
 struct DynApplyJob {        // one track: y = gain x in f32, then the clamp or a global gain

@@ -10,7 +10,8 @@
 //   pass B  one wave per channel: S_(i+1) = A^len_i S_i + e_i from chunk to chunk, serially; the start state of every chunk.
 //   pass C  pass A again, with the chunk's start state folded into its first non-empty lane, so the scan gives every lane its true
 //           start state; each lane re-runs its samples from it and sums y^2 (f64); one energy per chunk.
-//   pass D  one thread per 400 ms block: E_k = sum_c w_c (the energies of segments k .. k + 3) / L.
+//   pass D  one thread per 400 ms block: E_k = sum_c w_c (the energies of segments k .. k + 3) / L (the loudness meter runs it again
+//           over 30 segments: the short-term series, launch_loudness_blocks).
 // The lanes' runs and y^2 sums are plain f64, as the sequential filter's.  Everything that multiplies a state by a power of A is
 // double-double: A is far from normal (host_math.h), and those products in f64 put errors of 1e-9 .. 1e-5 into the energies of
 // DC-heavy audio at 44.1 .. 192 kHz where the sequential filter's own rounding stays near 1e-12.  (Built with -ffp-contract=off:
@@ -298,7 +299,8 @@ __global__ __launch_bounds__(64) void loudness_energy_kernel(const LoudJob *__re
     if (lane == 0) job.q[i] = acc;
 }
 
-__global__ __launch_bounds__(256) void loudness_blocks_kernel(const LoudTrackJob *__restrict__ tjobs) {
+// span: segments per block (4: momentary, 30: short-term); t.L = span s100
+__global__ __launch_bounds__(256) void loudness_blocks_kernel(const LoudTrackJob *__restrict__ tjobs, uint32_t span) {
     const LoudTrackJob t = tjobs[blockIdx.y];
     const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (k >= t.n_blocks) return;
@@ -308,7 +310,7 @@ __global__ __launch_bounds__(256) void loudness_blocks_kernel(const LoudTrackJob
         if (wc == 0.0) continue;
         const double *q = t.q + (uint64_t)c * t.n_fchunks + k * t.n_sub;
         double s = 0.0;
-        for (uint32_t i = 0; i < 4 * t.n_sub; i++) s += q[i];
+        for (uint32_t i = 0; i < span * t.n_sub; i++) s += q[i];
         e += wc * s;
     }
     t.out[k] = e / (double)t.L;
@@ -324,7 +326,13 @@ hipError_t launch_loudness(const LoudJob *d_jobs, uint32_t n_jobs, uint32_t max_
         hipLaunchKernelGGL(loudness_energy_kernel, dim3(max_fchunks, n_jobs), dim3(64), lds, s, d_jobs, d_rates);
     }
     if (max_blocks && n_tracks)
-        hipLaunchKernelGGL(loudness_blocks_kernel, dim3((uint32_t)((max_blocks + 255) / 256), n_tracks), dim3(256), 0, s, d_tjobs);
+        hipLaunchKernelGGL(loudness_blocks_kernel, dim3((uint32_t)((max_blocks + 255) / 256), n_tracks), dim3(256), 0, s, d_tjobs, 4u);
+    return hipGetLastError();
+}
+
+hipError_t launch_loudness_blocks(const LoudTrackJob *d_tjobs, uint32_t n_tracks, uint64_t max_blocks, uint32_t span, hipStream_t s) {
+    if (max_blocks && n_tracks)
+        hipLaunchKernelGGL(loudness_blocks_kernel, dim3((uint32_t)((max_blocks + 255) / 256), n_tracks), dim3(256), 0, s, d_tjobs, span);
     return hipGetLastError();
 }
 

@@ -73,6 +73,9 @@ struct ReaderSlot {
     // th_tm_get_spectra: job table, f64 partial sums, and the results of batches above h_tile (empty until the first such call;
     // grow-only, freed with the slot)
     th::DeviceTable spec_jobs, spec_part, spec_out;
+    // th_tm_get_loudness_meters: the job tables; the results (series energies, sums, peaks) and the filter states behind them
+    // (the same rule: empty until the first call, grow-only)
+    th::DeviceTable meter_tab, meter_mem;
 };
 constexpr size_t TILE_BYTES_MAX = 520 * 520 * 4;  // 512 core + 2 x 4 gutter (render_tiles.rs:15-16); >= 1024 * 12 waveform bins
 constexpr size_t MAX_READER_SLOTS = 16;
@@ -1543,6 +1546,242 @@ TH_API int th_tm_get_audio_stats(th_tm *tm, size_t id, th_audio_stats *out) {
     if (it == tm->tracks.end()) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", id);
     *out = it->second.stats;
     return TH_OK;
+    TH_CATCH
+}
+
+// ---------------------------------------------------------------------------------------------- loudness meter
+namespace {
+// what is known of a track's meter without the GPU: the factor and the lengths of the two series
+void meter_counts(const Track &tr, th_loudness_meter *m) {
+    *m = th_loudness_meter{};
+    const size_t n = tr.ch.empty() ? 0 : tr.ch[0].n;
+    m->oversampling = true_peak_factor(tr.sr);
+    if (loudness_rate_ok(tr.sr)) {
+        m->n_momentary = loudness_n_blocks(n, tr.sr);
+        m->n_short_term = loudness_n_short_term(n, tr.sr);
+    }
+}
+}  // namespace
+
+namespace th {
+namespace tmi {
+int loudness_meter_info(th_tm *tm, size_t id, th_loudness_meter *m) {
+    auto it = tm->tracks.find(id);
+    if (it == tm->tracks.end()) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", id);
+    meter_counts(it->second, m);
+    m->waveform_revision = tm->waveform_revision();
+    return TH_OK;
+}
+}  // namespace tmi
+}  // namespace th
+
+// The loudness meters of N tracks: a reader.  Per channel one LoudJob (passes A - C of kernels_loudness.hip, as at add time) and, at
+// F > 1, one TruePeakJob; per track two LoudTrackJobs (pass D over 4 and over 30 segments, writing the energies where the series go).
+// Everything runs on the slot's stream; the results come back in one copy (through the slot's pinned staging when they fit) and the
+// host turns them into LUFS, maxima and the loudness range.
+TH_API int th_tm_get_loudness_meters(th_tm *tm, const size_t *ids, size_t n, th_loudness_meter *meters, double *series, size_t cap,
+                                     size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(tm && meters && out_len && (n == 0 || ids), "NULL argument");
+    *out_len = 0;
+    if (n == 0) return TH_OK;
+    TH_REQUIRE(n <= 65535, "at most 65535 tracks per call");
+    std::shared_lock<std::shared_mutex> rl(tm->rw);
+    const uint64_t revision = tm->waveform_revision();
+    std::vector<th_loudness_meter> ms(n);
+    std::vector<const Track *> trs(n);
+    size_t total = 0, n_ch = 0;
+    for (size_t i = 0; i < n; i++) {
+        auto it = tm->tracks.find(ids[i]);
+        if (it == tm->tracks.end()) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", ids[i]);
+        trs[i] = &it->second;
+        meter_counts(it->second, &ms[i]);
+        ms[i].waveform_revision = revision;
+        ms[i].momentary_offset = total;
+        total += ms[i].n_momentary;
+        ms[i].short_term_offset = total;
+        total += ms[i].n_short_term;
+        n_ch += it->second.ch.size();
+    }
+    TH_REQUIRE(n_ch <= 65535, "at most 65535 channels per call");
+    if (series && cap < total) {
+        std::memcpy(meters, ms.data(), n * sizeof(th_loudness_meter));
+        *out_len = total;
+        return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu doubles", total);
+    }
+    // the job tables
+    std::vector<const LoudnessRate *> rates;
+    std::vector<LoudJob> jobs;
+    std::vector<LoudTrackJob> tj_m(n), tj_s(n);
+    std::vector<TruePeakJob> tp[2];  // F = 4, F = 2
+    std::vector<size_t> tp_ch[2];    // the channel (index into jobs) of every true-peak job
+    std::vector<size_t> ch0(n);
+    size_t n_states = 0;
+    uint32_t max_chunks = 0, max_fchunks = 0, lds_floats = 4, tp_chunks[2] = {0, 0};
+    uint64_t max_m = 0, max_s = 0;
+    for (size_t i = 0; i < n; i++) {
+        const Track &tr = *trs[i];
+        const bool ok = loudness_rate_ok(tr.sr);
+        const LoudnessRate &R = loudness_rate(ok ? tr.sr : 48000);  // (a refused rate: the peaks only, over chunks of a 48 kHz geometry)
+        size_t ri = 0;
+        while (ri < rates.size() && rates[ri] != &R) ri++;
+        if (ri == rates.size()) rates.push_back(&R);
+        const uint64_t ns = tr.ch.empty() ? 0 : tr.ch[0].n;
+        const uint64_t nseg_any = (ns + R.s100 - 1) / R.s100, nseg = ns / R.s100;
+        TH_REQUIRE(ns < (1ull << 40) && nseg_any * R.n_sub < (1ull << 31), "track %zu: too many samples", ids[i]);
+        const uint32_t nf = ok && nseg >= 4 ? (uint32_t)(nseg * R.n_sub) : 0u;
+        ch0[i] = jobs.size();
+        for (size_t k = 0; k < tr.ch.size(); k++) {
+            const float *wav = tr.ch[k].d_wav;
+            TH_REQUIRE(ns == 0 || wav, "track %zu channel %zu has no audio", ids[i], k);
+            LoudJob j{};
+            j.wav = wav;
+            j.n = ns;
+            j.rate = (uint32_t)ri;
+            j.n_chunks = (uint32_t)(nseg_any * R.n_sub);
+            j.n_fchunks = nf;
+            j.aligned16 = (reinterpret_cast<uintptr_t>(wav) & 15u) == 0;
+            if (ms[i].oversampling > 1 && ns) {
+                const int f = ms[i].oversampling == 4 ? 0 : 1;
+                TruePeakJob t{};
+                t.wav = wav;
+                t.n = ns;
+                t.n_chunks = (uint32_t)((ns + TP_CHUNK - 1) / TP_CHUNK);
+                t.aligned16 = j.aligned16;
+                tp[f].push_back(t);
+                tp_ch[f].push_back(jobs.size());
+                tp_chunks[f] = std::max(tp_chunks[f], t.n_chunks);
+            }
+            jobs.push_back(j);
+            n_states += nf;
+        }
+        for (int v = 0; v < 2; v++) {
+            LoudTrackJob &t = v ? tj_s[i] : tj_m[i];
+            t = LoudTrackJob{};
+            t.n_blocks = v ? ms[i].n_short_term : ms[i].n_momentary;
+            for (uint32_t k = 0; k < 8; k++) t.w[k] = loudness_channel_weight(k, (uint32_t)tr.ch.size());
+            t.n_ch = (uint32_t)tr.ch.size();
+            t.n_sub = R.n_sub;
+            t.n_fchunks = nf;
+            t.L = (v ? 30u : 4u) * R.s100;
+        }
+        max_chunks = std::max(max_chunks, (uint32_t)(nseg_any * R.n_sub));
+        max_fchunks = std::max(max_fchunks, nf);
+        max_m = std::max<uint64_t>(max_m, ms[i].n_momentary);
+        max_s = std::max<uint64_t>(max_s, ms[i].n_short_term);
+        lds_floats = std::max(lds_floats, R.cl + 4);
+    }
+    // device memory: results [energies: total][sums of squares: n_ch][pass A's peaks: n_ch u32][true peaks: n_ch u32] | states | q
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t pk_bytes = (n_ch * 4 + 7) / 8 * 8;
+    const size_t o_sums = total * 8, o_pka = o_sums + n_ch * 8, o_pkt = o_pka + pk_bytes, res_bytes = o_pkt + pk_bytes;
+    const size_t o_z = up(res_bytes), o_q = o_z + n_states * 64, mem_bytes = o_q + n_states * 8 + 8;
+    const size_t t_rates = up(jobs.size() * sizeof(LoudJob)), t_m = t_rates + up(rates.size() * sizeof(LoudnessRate));
+    const size_t t_s = t_m + up(n * sizeof(LoudTrackJob)), t_tp4 = t_s + up(n * sizeof(LoudTrackJob));
+    const size_t t_tp2 = t_tp4 + up(tp[0].size() * sizeof(TruePeakJob)), tab_bytes = t_tp2 + up(tp[1].size() * sizeof(TruePeakJob));
+    TH_HIP(hipSetDevice(tm->ctx->device));
+    SlotLease lease{tm, nullptr};
+    int rc = acquire_slot(tm, &lease.slot);
+    if (rc != TH_OK) return rc;
+    ReaderSlot &sl = *lease.slot;
+    TH_CHECK(sl.meter_mem.ensure(mem_bytes));
+    unsigned char *dm = static_cast<unsigned char *>(sl.meter_mem.dptr);
+    double *d_res = reinterpret_cast<double *>(dm), *d_sums = reinterpret_cast<double *>(dm + o_sums);
+    uint32_t *d_pka = reinterpret_cast<uint32_t *>(dm + o_pka), *d_pkt = reinterpret_cast<uint32_t *>(dm + o_pkt);
+    double *d_z = reinterpret_cast<double *>(dm + o_z), *d_q = reinterpret_cast<double *>(dm + o_q);
+    size_t si = 0;
+    for (size_t i = 0; i < n; i++) {
+        const size_t q0 = si;
+        for (size_t k = 0; k < trs[i]->ch.size(); k++) {
+            LoudJob &j = jobs[ch0[i] + k];
+            j.z = d_z + 8 * si;
+            j.q = d_q + si;
+            j.sumsq = d_sums + ch0[i] + k;
+            j.peak = d_pka + ch0[i] + k;
+            si += j.n_fchunks;
+        }
+        tj_m[i].q = tj_s[i].q = d_q + q0;
+        tj_m[i].out = d_res + ms[i].momentary_offset;
+        tj_s[i].out = d_res + ms[i].short_term_offset;
+    }
+    for (int f = 0; f < 2; f++)
+        for (size_t k = 0; k < tp[f].size(); k++) tp[f][k].peak = d_pkt + tp_ch[f][k];
+    std::vector<unsigned char> h(tab_bytes, 0);
+    std::memcpy(h.data(), jobs.data(), jobs.size() * sizeof(LoudJob));
+    for (size_t r = 0; r < rates.size(); r++) std::memcpy(h.data() + t_rates + r * sizeof(LoudnessRate), rates[r], sizeof(LoudnessRate));
+    std::memcpy(h.data() + t_m, tj_m.data(), n * sizeof(LoudTrackJob));
+    std::memcpy(h.data() + t_s, tj_s.data(), n * sizeof(LoudTrackJob));
+    if (!tp[0].empty()) std::memcpy(h.data() + t_tp4, tp[0].data(), tp[0].size() * sizeof(TruePeakJob));
+    if (!tp[1].empty()) std::memcpy(h.data() + t_tp2, tp[1].data(), tp[1].size() * sizeof(TruePeakJob));
+    TH_CHECK(sl.meter_tab.upload(sl.stream, h.data(), tab_bytes));
+    const unsigned char *dt = static_cast<const unsigned char *>(sl.meter_tab.dptr);
+    TH_HIP(hipMemsetAsync(dm + o_sums, 0, res_bytes - o_sums, sl.stream));  // sums = 0, peaks = +0.0
+    TH_HIP(launch_loudness(reinterpret_cast<const LoudJob *>(dt), (uint32_t)jobs.size(), max_chunks, max_fchunks,
+                           reinterpret_cast<const LoudnessRate *>(dt + t_rates), lds_floats, nullptr, 0, 0, sl.stream));
+    TH_HIP(launch_loudness_blocks(reinterpret_cast<const LoudTrackJob *>(dt + t_m), (uint32_t)n, max_m, 4, sl.stream));
+    TH_HIP(launch_loudness_blocks(reinterpret_cast<const LoudTrackJob *>(dt + t_s), (uint32_t)n, max_s, 30, sl.stream));
+    for (int f = 0; f < 2; f++) {
+        if (tp[f].empty()) continue;
+        TruePeakCoef K;
+        true_peak_coef(f ? 2 : 4, &K);
+        TH_HIP(launch_true_peak(reinterpret_cast<const TruePeakJob *>(dt + (f ? t_tp2 : t_tp4)), (uint32_t)tp[f].size(), tp_chunks[f], f ? 2 : 4, K,
+                                sl.stream));
+    }
+    std::vector<unsigned char> big;
+    const unsigned char *res = sl.h_tile;
+    if (res_bytes <= TILE_BYTES_MAX) {
+        TH_HIP(hipMemcpyAsync(sl.h_tile, dm, res_bytes, hipMemcpyDeviceToHost, sl.stream));
+    } else {
+        big.resize(res_bytes);
+        res = big.data();
+        TH_HIP(hipMemcpyAsync(big.data(), dm, res_bytes, hipMemcpyDeviceToHost, sl.stream));
+    }
+    TH_HIP(hipStreamSynchronize(sl.stream));
+    // the host's part: LUFS, maxima, the loudness range, the channel of the peak
+    const double *energies = reinterpret_cast<const double *>(res);
+    const uint32_t *pka = reinterpret_cast<const uint32_t *>(res + o_pka), *pkt = reinterpret_cast<const uint32_t *>(res + o_pkt);
+    std::vector<double> lufs, sub;
+    for (size_t i = 0; i < n; i++) {
+        th_loudness_meter &m = ms[i];
+        if (loudness_rate_ok(trs[i]->sr)) {
+            lufs.resize(m.n_momentary + m.n_short_term);
+            const double *e = energies + m.momentary_offset;  // (the short-term energies follow the momentary ones)
+            for (size_t k = 0; k < lufs.size(); k++) lufs[k] = loudness_lufs(e[k]);
+            if (series && !lufs.empty()) std::memcpy(series + m.momentary_offset, lufs.data(), lufs.size() * sizeof(double));
+            m.max_momentary_lufs = loudness_series_max(lufs.data(), m.n_momentary);
+            m.max_short_term_lufs = loudness_series_max(lufs.data() + m.n_momentary, m.n_short_term);
+            sub.clear();
+            for (size_t k = 0; k < m.n_short_term; k += 10) sub.push_back(energies[m.short_term_offset + k]);
+            m.loudness_range = loudness_range(sub.data(), sub.size());
+        } else {
+            m.loudness_range = m.max_momentary_lufs = m.max_short_term_lufs = NAN;
+        }
+        const uint32_t *pk = m.oversampling > 1 ? pkt : pka;
+        float peak = 0.0f;
+        uint32_t at = 0;
+        for (size_t k = 0; k < trs[i]->ch.size(); k++) {
+            float p;
+            std::memcpy(&p, &pk[ch0[i] + k], 4);
+            if (p > peak) {
+                peak = p;
+                at = (uint32_t)k;
+            }
+        }
+        m.true_peak = peak;
+        m.true_peak_dB = peak == 0.0f ? -INFINITY : (float)(20.0 * std::log10((double)peak));
+        m.true_peak_channel = at;
+    }
+    std::memcpy(meters, ms.data(), n * sizeof(th_loudness_meter));
+    *out_len = total;
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_tm_get_loudness_meter(th_tm *tm, size_t id, th_loudness_meter *meter, double *series, size_t cap) {
+    TH_TRY
+    TH_REQUIRE(tm && meter, "NULL argument");
+    size_t len = 0;
+    return th_tm_get_loudness_meters(tm, &id, 1, meter, series, cap, &len);
     TH_CATCH
 }
 

@@ -54,6 +54,10 @@ void commit(th_tm *tm, StagedPtr staged);
 // th_tm_get_spectra reports them; *info: offset 0, the spec's height, the frame range and the slot's spectrogram revision
 int spectrum_request_info(th_tm *tm, const th_spectrum_request &r, size_t i, th_spectrum_info *info);
 
+// th_tm_get_loudness_meters' check of ONE id: TH_ERR_NOT_FOUND, else the meter's oversampling, counts (offsets 0) and the slot's
+// waveform revision, everything else zero
+int loudness_meter_info(th_tm *tm, size_t id, th_loudness_meter *m);
+
 // update_spec_imgs against `global` (NULL: the manager's own tracks, as th_tm_* does), then the writer's final wait:
 // for the images only (apply_track_list_changes, set_dB_range) or for everything (set_setting, set_colormap)
 int requantise(th_tm *tm, const DbRange *global, bool force_update_all, bool images_only, std::vector<size_t> *updated);

@@ -608,6 +608,88 @@ TH_API int th_tmg_get_spectrum(th_tmg *g, size_t id, uint32_t ch, int kind, doub
     TH_CATCH
 }
 
+// Loudness meters: every id is checked in request order against its owning slot (which gives the counts, so the packed offsets are
+// known before any slot runs); a batch owned by one slot goes to it whole, otherwise every slot fills meters and a staging vector of
+// its own, side by side, and they are scattered to their places once all have succeeded.
+TH_API int th_tmg_get_loudness_meters(th_tmg *g, const size_t *ids, size_t n, th_loudness_meter *meters, double *series, size_t cap,
+                                      size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(g && meters && out_len && (n == 0 || ids), "NULL argument");
+    *out_len = 0;
+    if (n == 0) return TH_OK;
+    std::shared_lock<std::shared_mutex> rl(g->rw);
+    std::vector<std::vector<size_t>> mine(g->slots.size());  // request indices per slot, in request order
+    std::vector<th_loudness_meter> ms(n);
+    for (size_t i = 0; i < n; i++) {
+        const th_tmg::Placement *p = find_track(g, ids[i]);
+        if (!p) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", ids[i]);
+        th_tm *tm = g->slots[p->slot].tm;
+        std::shared_lock<std::shared_mutex> sl(tmi::rw_of(tm));
+        TH_CHECK(tmi::loudness_meter_info(tm, ids[i], &ms[i]));
+        mine[p->slot].push_back(i);
+    }
+    uint64_t revision;
+    {
+        std::lock_guard<std::mutex> lk(g->revs.mu);
+        revision = g->revs.waveform_revision;
+    }
+    size_t total = 0;
+    for (size_t i = 0; i < n; i++) {
+        ms[i].waveform_revision = revision;
+        ms[i].momentary_offset = total;
+        total += ms[i].n_momentary;
+        ms[i].short_term_offset = total;
+        total += ms[i].n_short_term;
+    }
+    if (series && cap < total) {
+        std::memcpy(meters, ms.data(), n * sizeof(th_loudness_meter));
+        *out_len = total;
+        return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu doubles", total);
+    }
+    std::vector<uint32_t> busy;
+    for (uint32_t s = 0; s < g->slots.size(); s++)
+        if (!mine[s].empty()) busy.push_back(s);
+    std::vector<std::vector<th_loudness_meter>> got(g->slots.size());
+    std::vector<std::vector<double>> stage(g->slots.size());
+    const int rc = for_slots(g, busy, [&](uint32_t s) -> int {
+        std::vector<size_t> sub(mine[s].size());
+        size_t doubles = 0;
+        for (size_t j = 0; j < sub.size(); j++) {
+            sub[j] = ids[mine[s][j]];
+            doubles += ms[mine[s][j]].n_momentary + ms[mine[s][j]].n_short_term;
+        }
+        got[s].resize(sub.size());
+        stage[s].resize(series ? std::max<size_t>(doubles, 1) : 0);
+        size_t len = 0;
+        return th_tm_get_loudness_meters(g->slots[s].tm, sub.data(), sub.size(), got[s].data(), series ? stage[s].data() : nullptr,
+                                         stage[s].size(), &len);
+    });
+    if (rc != TH_OK) return rc;
+    for (uint32_t s : busy)
+        for (size_t j = 0; j < mine[s].size(); j++) {
+            const size_t i = mine[s][j];
+            th_loudness_meter m = got[s][j];
+            if (series && m.n_momentary + m.n_short_term)
+                std::memcpy(series + ms[i].momentary_offset, stage[s].data() + m.momentary_offset, (m.n_momentary + m.n_short_term) * sizeof(double));
+            m.momentary_offset = ms[i].momentary_offset;
+            m.short_term_offset = ms[i].short_term_offset;
+            m.waveform_revision = revision;
+            ms[i] = m;
+        }
+    std::memcpy(meters, ms.data(), n * sizeof(th_loudness_meter));
+    *out_len = total;
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_tmg_get_loudness_meter(th_tmg *g, size_t id, th_loudness_meter *meter, double *series, size_t cap) {
+    TH_TRY
+    TH_REQUIRE(g && meter, "NULL argument");
+    size_t len = 0;
+    return th_tmg_get_loudness_meters(g, &id, 1, meter, series, cap, &len);
+    TH_CATCH
+}
+
 // set_common_normalize / set_common_guard_clipping: every slot re-derives its tracks into staged buffers; all commit, or all discard
 namespace {
 int set_common_dynamics_all(th_tmg *g, int kind, float target, int mode) {
