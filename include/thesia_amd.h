@@ -676,6 +676,78 @@ TH_API int th_true_peak_filter(uint32_t sr, uint32_t *factor, double coef[49], u
 TH_API int th_loudness_n_short_term(size_t n_samples, uint32_t sr, size_t *n_blocks);
 TH_API int th_loudness_range(const double *short_term_energies_1s, size_t n, double *lra);
 
+/* ---------------------------------------------------------------- PCM / WAV export of resident tracks */
+/* A time range of a track's resident audio as file-ready bytes, made on the device: the channels interleaved, quantised to 16- or
+ * 24-bit PCM (with or without TPDF dither) or copied as float32, and the WAV header around them: the last step of normalise ->
+ * guard -> save (upstream's planned "save normalized audio" and "region selection").  No reference implementation exists; these
+ * definitions are the contract.
+ *   Samples from seconds: s0 = clamp(ceil(start_sec sr), 0, n); s1 = n for end_sec = +inf, else max(s0, clamp(ceil(end_sec sr), 0,
+ *   n)); C double arithmetic; the argument rules are those of th_spectrum_frame_range (th_audio_sample_range is that definition:
+ *   TH_ERR_INVALID_ARG when start_sec is NaN, negative or infinite, end_sec is NaN or below start_sec, or sr is zero).
+ *   Dither generator (th_export_dither), counter-based: fmix32(h): h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35;
+ *   h ^= h >> 16 in uint32.  k0 = fmix32(seed + 0x9e3779b9 (ch + 1)) mod 2^32; k1 = fmix32(hi32(i) ^ k0); k = fmix32(lo32(i) ^ k1);
+ *   a = fmix32(k ^ 0x68bc21eb) >> 8; b = fmix32(k ^ 0x02e5be93) >> 8.  i is the ABSOLUTE sample index in the track, not the index
+ *   inside the range: the bytes of a range are the same bytes cut from the whole-track export, and a host may export a long track in
+ *   successive ranges and concatenate them.
+ *   Quantiser (th_export_quantize, one channel): S = 32768 (TH_PCM_S16) or 8388608 (TH_PCM_S24); v = (double)x S + d, d = 0 under
+ *   TH_DITHER_NONE and ((double)a - (double)b) 2^-24 under TH_DITHER_TPDF; q = rint(v), ties to even; a q outside [-S, S - 1] is
+ *   clamped and counted in n_clamped (so is +-inf); a NaN sample gives 0 and is counted in n_nan.  Little-endian, 2 or 3 bytes.
+ *   TH_PCM_F32 copies the sample's 4 bytes unchanged, NaN included: n_clamped = 0, n_nan is still counted, dither and seed are
+ *   ignored (th_export_quantize then returns the bit patterns in q).
+ *   Frames are interleaved: channel 0, 1, .. of sample s0, then of s0 + 1, and so on.
+ *   WAV header (th_wav_header): PCM formats the canonical 44 bytes ("fmt " of 16 bytes, tag 1); TH_PCM_F32 58 bytes ("fmt " of 18
+ *   bytes with tag 3 and cbSize 0, then a 12-byte "fact" chunk holding n_frames).  *pad_len is 1 when the data byte count is odd (24
+ *   bit, odd n_ch n_frames): one zero byte behind the data, which the RIFF size counts and the "data" size does not.  A file whose
+ *   RIFF size would exceed 2^32 - 1, more than 65535 channels, a block (n_ch x bytes per sample) above 65535 bytes or a byte rate
+ *   above 2^32 - 1: TH_ERR_UNSUPPORTED.  n_ch == 0, sr == 0 or an unknown format: TH_ERR_INVALID_ARG.
+ * th_tm_export_pcm: request i's bytes start at out + info[i].offset; the offsets are multiples of 16 in request order (offset[i + 1]
+ * = offset[i] + n_bytes[i] rounded up to 16) and the up to 15 bytes of padding between two requests are written as ZERO; nothing is
+ * written behind the last request's bytes, and *out_len = its offset + n_bytes.  The size query and the error rules are those of
+ * th_tm_get_spectra: out == NULL or cap_bytes < *out_len gives TH_ERR_BUFFER_TOO_SMALL with info (offsets, sizes, sample ranges,
+ * rate, channels, revision; the two counts zero) and *out_len filled; an unknown id: TH_ERR_NOT_FOUND; an unknown which, format or
+ * dither or a bad time: TH_ERR_INVALID_ARG; a track of more than TH_EXPORT_MAX_CHANNELS channels: TH_ERR_UNSUPPORTED; the first
+ * faulty request decides; on any of these errors nothing is written to out.  An empty range is valid: 0 bytes.
+ * th_tm_export_wav: one request as a complete file image, header + data + pad; info (may be NULL) then has offset = the header's
+ * length (44 or 58, not a multiple of 16) and n_bytes = the data bytes without the pad; an empty range gives a header-only file.
+ * A request's bytes and counts depend on the track's audio and the request alone - not on the batch, the reader slot, the pieces
+ * below, or th_tm against th_tmg.  waveform_revision: the revision the bytes belong to.
+ * Readers, like th_tm_get_spectra: shared lock, a reader slot's own stream.  The device staging is BOUNDED: a call is processed in
+ * pieces of at most TH_EXPORT_PIECE_BYTES output bytes, cut at frame boundaries, through two device buffers (piece p + 1 is computed
+ * while piece p is copied into the caller's buffer).  A slot's export scratch is made on its first export and never exceeds two
+ * pieces (each TH_EXPORT_PIECE_BYTES + 64 bytes) plus the job tables and counters of the largest call so far; a manager that never
+ * exports holds none. */
+#define TH_PCM_S16 0
+#define TH_PCM_S24 1
+#define TH_PCM_F32 2
+#define TH_DITHER_NONE 0
+#define TH_DITHER_TPDF 1
+#define TH_WAV_HEADER_MAX 64
+#define TH_EXPORT_PIECE_BYTES (32u << 20)
+#define TH_EXPORT_MAX_CHANNELS 1024
+typedef struct {
+    size_t id;
+    uint32_t which; /* as th_tm_copy_audio: 0 audio, 1 drawing, 2 original */
+    uint32_t format, dither, seed; /* TH_PCM_*, TH_DITHER_* */
+    double start_sec, end_sec;
+} th_export_request;
+typedef struct {
+    uint64_t offset, n_bytes; /* into out */
+    uint64_t sample_start, sample_end;
+    uint32_t sr, n_channels;
+    uint64_t n_clamped, n_nan, waveform_revision;
+} th_export_info;
+TH_API int th_audio_sample_range(uint32_t sr, size_t n_samples, double start_sec, double end_sec, size_t *sample_start,
+                                 size_t *sample_end);
+TH_API int th_export_dither(uint32_t seed, uint32_t ch, uint64_t i, uint32_t *a, uint32_t *b);
+TH_API int th_export_quantize(uint32_t format, uint32_t dither, uint32_t seed, uint32_t ch, uint64_t first_index, const float *x,
+                              size_t n, int32_t *q, uint64_t *n_clamped, uint64_t *n_nan);
+TH_API int th_wav_header(uint32_t format, uint32_t sr, uint32_t n_ch, uint64_t n_frames, uint8_t out[TH_WAV_HEADER_MAX],
+                         size_t *header_len, size_t *pad_len);
+TH_API int th_tm_export_pcm(th_tm *tm, const th_export_request *reqs, size_t n, uint8_t *out, size_t cap_bytes,
+                            th_export_info *info /* n */, size_t *out_len);
+TH_API int th_tm_export_wav(th_tm *tm, const th_export_request *req, uint8_t *out, size_t cap_bytes,
+                            th_export_info *info /* may be NULL */, size_t *out_len);
+
 /* ---------------------------------------------------------------- TrackManager over several devices (one process) */
 /* th_tmg: the th_tm_* calls above, call for call, with a th_tmg * in place of the th_tm *; a multi-GPU host swaps one for
  * the other.  Every result — updated ids, max_sr, db state, revisions, specs, images, tile bytes, batch offsets, render
@@ -752,6 +824,14 @@ TH_API int th_tmg_get_spectrum(th_tmg *tmg, size_t id, uint32_t ch, int kind, do
 TH_API int th_tmg_get_loudness_meters(th_tmg *tmg, const size_t *ids, size_t n, th_loudness_meter *meters /* n */, double *series,
                                       size_t cap_doubles, size_t *out_len);
 TH_API int th_tmg_get_loudness_meter(th_tmg *tmg, size_t id, th_loudness_meter *meter, double *series, size_t cap_doubles);
+
+/* export: every request goes to its owning slot and the slots are served side by side, each writing its requests' bytes straight
+ * into the caller's buffer; the bytes, offsets (zero padding included) and infos are those of one th_tm, the revision stamped is
+ * the manager's own */
+TH_API int th_tmg_export_pcm(th_tmg *tmg, const th_export_request *reqs, size_t n, uint8_t *out, size_t cap_bytes,
+                             th_export_info *info /* n */, size_t *out_len);
+TH_API int th_tmg_export_wav(th_tmg *tmg, const th_export_request *req, uint8_t *out, size_t cap_bytes,
+                             th_export_info *info /* may be NULL */, size_t *out_len);
 
 /* Test and measurement entry points (kernel selectors for A/B runs, per-launch kernel timing, replacing a resident image
  * with given pixels) are NOT part of this interface: include/thesia_amd_testing.h declares them; a thesia host binds none. */

@@ -109,6 +109,17 @@ class LoudnessMeter(C.Structure):  # th_loudness_meter
                 ("n_short_term", C.c_uint64), ("waveform_revision", C.c_uint64)]
 
 
+class ExportRequest(C.Structure):  # th_export_request
+    _fields_ = [("id", C.c_size_t), ("which", C.c_uint32), ("format", C.c_uint32), ("dither", C.c_uint32), ("seed", C.c_uint32),
+                ("start_sec", C.c_double), ("end_sec", C.c_double)]
+
+
+class ExportInfo(C.Structure):  # th_export_info
+    _fields_ = [("offset", C.c_uint64), ("n_bytes", C.c_uint64), ("sample_start", C.c_uint64), ("sample_end", C.c_uint64),
+                ("sr", C.c_uint32), ("n_channels", C.c_uint32), ("n_clamped", C.c_uint64), ("n_nan", C.c_uint64),
+                ("waveform_revision", C.c_uint64)]
+
+
 class PyramidDesc(C.Structure):
     _fields_ = [("wav", C.c_void_p), ("out", C.c_void_p), ("n_samples", C.c_uint64), ("n_levels", C.c_uint32),
                 ("first_level", C.c_uint32)]
@@ -301,6 +312,15 @@ _SIGS = {
                             C.POINTER(C.c_uint32)],
     "th_loudness_n_short_term": [C.c_size_t, C.c_uint32, c_szp],
     "th_loudness_range": [C.POINTER(C.c_double), C.c_size_t, C.POINTER(C.c_double)],
+    "th_audio_sample_range": [C.c_uint32, C.c_size_t, C.c_double, C.c_double, c_szp, c_szp],
+    "th_export_dither": [C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+    "th_export_quantize": [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, c_f32p, C.c_size_t, C.POINTER(C.c_int32),
+                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    "th_wav_header": [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, c_u8p, c_szp, c_szp],
+    "th_tm_export_pcm": [vp, C.POINTER(ExportRequest), C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(ExportInfo), c_szp],
+    "th_tm_export_wav": [vp, C.POINTER(ExportRequest), C.c_void_p, C.c_size_t, C.POINTER(ExportInfo), c_szp],
+    "th_tmg_export_pcm": [vp, C.POINTER(ExportRequest), C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(ExportInfo), c_szp],
+    "th_tmg_export_wav": [vp, C.POINTER(ExportRequest), C.c_void_p, C.c_size_t, C.POINTER(ExportInfo), c_szp],
     "th_tile_cache_create": [C.c_size_t, C.POINTER(vp)],
     "th_tile_cache_destroy": [vp],
     "th_tile_cache_lookup": [vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), c_u8p, C.c_size_t,

@@ -23,6 +23,12 @@ NORM_OFF, NORM_LUFS, NORM_RMS_DB, NORM_PEAK_DB = 0, 1, 2, 3
 GUARD_CLIP, GUARD_REDUCE_GLOBAL_LEVEL, GUARD_LIMITER = 0, 1, 2
 GUARD_RESULT_GLOBAL_GAIN, GUARD_RESULT_BEFORE_CLIP, GUARD_RESULT_GAIN_SEQUENCE = 0, 1, 2
 SPECTRUM_MEAN_AMP, SPECTRUM_MEAN_POWER, SPECTRUM_MAX = 0, 1, 2
+PCM_S16, PCM_S24, PCM_F32 = 0, 1, 2
+DITHER_NONE, DITHER_TPDF = 0, 1
+WAV_HEADER_MAX = 64
+EXPORT_PIECE_BYTES = 32 << 20      # TH_EXPORT_PIECE_BYTES
+EXPORT_MAX_CHANNELS = 1024         # TH_EXPORT_MAX_CHANNELS
+EXPORT_CHUNK_SAMPLES = 4096        # samples (frames x channels) of one workgroup of the export kernel, at most
 WAVEFORM_TILE_MAX_BYTES = 24 + 1024 * 12
 SPECTROGRAM_TILE_MAX_BYTES = 40 + 520 * 520 * 4
 
@@ -238,6 +244,95 @@ class _LoudnessMeterMethods:
     def loudness_meter(self, track_id: int, series: bool = True) -> dict:
         """th_tm_get_loudness_meter: one track"""
         return self.loudness_meters([track_id], series)[0]
+
+
+def export_chunk_frames(n_channels: int) -> int:
+    """frames of one chunk of the export kernel (chunks lie on the track's absolute frame grid): kernels.h export_chunk_frames"""
+    return max((EXPORT_CHUNK_SAMPLES // n_channels) & ~3, 4)
+
+
+def audio_sample_range(sr: int, n_samples: int, start_sec: float = 0.0, end_sec: float = float("inf")):
+    """-> (sample_start, sample_end): the samples of n_samples at or after start_sec and before end_sec (host arithmetic)"""
+    s0, s1 = C.c_size_t(), C.c_size_t()
+    check(lib.th_audio_sample_range(sr, n_samples, start_sec, end_sec, C.byref(s0), C.byref(s1)))
+    return s0.value, s1.value
+
+
+def export_dither(seed: int, ch: int, i: int):
+    """-> (a, b): the two 24-bit uniform integers of the export's TPDF dither for absolute sample index i of channel ch (host)"""
+    a, b = C.c_uint32(), C.c_uint32()
+    check(lib.th_export_dither(seed, ch, i, C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def export_quantize(fmt: int, dither: int, seed: int, ch: int, first_index: int, x):
+    """one channel through the export's quantiser on the host -> (int32 q, n_clamped, n_nan); PCM_F32: q holds the bit patterns"""
+    x = _f32(x).ravel()
+    q = np.empty(x.size, np.int32)
+    nc, nn = C.c_uint64(), C.c_uint64()
+    check(lib.th_export_quantize(fmt, dither, seed, ch, first_index, _ptr(x, c_f32p), x.size, q.ctypes.data_as(C.POINTER(C.c_int32)),
+                                 C.byref(nc), C.byref(nn)))
+    return q, nc.value, nn.value
+
+
+def wav_header(fmt: int, sr: int, n_channels: int, n_frames: int):
+    """-> (header bytes, pad_len): the RIFF / WAV header of n_frames frames and the zero bytes (0 or 1) that follow the data"""
+    out = (C.c_uint8 * WAV_HEADER_MAX)()
+    hl, pl = C.c_size_t(), C.c_size_t()
+    check(lib.th_wav_header(fmt, sr, n_channels, n_frames, out, C.byref(hl), C.byref(pl)))
+    return bytes(out[:hl.value]), pl.value
+
+
+def _export_info_dict(o) -> dict:
+    return {k: int(getattr(o, k)) for k, _ in o._fields_}
+
+
+def _export_request(r) -> "_ffi.ExportRequest":
+    """(track_id, fmt[, dither[, seed[, start_sec[, end_sec[, which]]]]]) or a dict with those names"""
+    if isinstance(r, dict):
+        r = (r["track_id"], r["fmt"], r.get("dither", DITHER_NONE), r.get("seed", 0), r.get("start_sec", 0.0),
+             r.get("end_sec", float("inf")), r.get("which", 0))
+    r = tuple(r) + (DITHER_NONE, 0, 0.0, float("inf"), 0)[len(r) - 2:]
+    track_id, fmt, dither, seed, start_sec, end_sec, which = r
+    return _ffi.ExportRequest(track_id, which, fmt, dither, seed, start_sec, end_sec)
+
+
+class _ExportMethods:
+    """a time range of resident audio as interleaved PCM / float bytes or a WAV file image (th_tm_* and th_tmg_*: _PFX)"""
+
+    def export_pcm(self, requests, out: Optional[np.ndarray] = None):
+        """th_tm_export_pcm: requests = iterable of (track_id, fmt[, dither[, seed[, start_sec[, end_sec[, which]]]]]) ->
+        (uint8 buffer, list of info dicts); request i's bytes are buffer[offset: offset + n_bytes].  out: a uint8 array to fill
+        (pinned memory, say) instead of a new one."""
+        reqs = [_export_request(r) for r in requests]
+        n = len(reqs)
+        if n == 0:
+            return np.empty(0, np.uint8), []
+        arr = (_ffi.ExportRequest * n)(*reqs)
+        info = (_ffi.ExportInfo * n)()
+        need = C.c_size_t()
+        fn = getattr(lib, self._PFX + "export_pcm")
+        if out is None:
+            rc = fn(self.handle, arr, n, None, 0, info, C.byref(need))
+            if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+                check(rc)
+            out = np.empty(max(need.value, 1), np.uint8)
+        check(fn(self.handle, arr, n, out.ctypes.data, out.size, info, C.byref(need)))
+        return out[:need.value], [_export_info_dict(o) for o in info]
+
+    def export_wav(self, track_id: int, fmt: int, dither: int = DITHER_NONE, seed: int = 0, start_sec: float = 0.0,
+                   end_sec: float = float("inf"), which: int = 0):
+        """th_tm_export_wav: -> (the complete file image as bytes, info dict)"""
+        req = _ffi.ExportRequest(track_id, which, fmt, dither, seed, start_sec, end_sec)
+        info = _ffi.ExportInfo()
+        need = C.c_size_t()
+        fn = getattr(lib, self._PFX + "export_wav")
+        rc = fn(self.handle, C.byref(req), None, 0, C.byref(info), C.byref(need))
+        if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+            check(rc)
+        out = np.empty(need.value, np.uint8)
+        check(fn(self.handle, C.byref(req), out.ctypes.data, out.size, C.byref(info), C.byref(need)))
+        return out.tobytes(), _export_info_dict(info)
 
 
 def true_peak_filter(sr: int):
@@ -753,7 +848,7 @@ class TileCache:
                 "spectrogram_revision": sr.value, "hits": h.value, "misses": m.value}
 
 
-class TrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods):
+class TrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods):
     """th_tm: mirror of core/mod.rs TrackManager with HBM-resident audio / specs / images."""
     _PFX = "th_tm_"
 
@@ -953,7 +1048,7 @@ class TrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods):
         return out[: n.value].tobytes()
 
 
-class MultiTrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods):
+class MultiTrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods):
     """th_tmg: the TrackManager over several devices of one process (duplicates allowed: [0, 0] is two slots on one card).
     Same method names as TrackManager; results are bit-identical to one TrackManager holding every track."""
     _PFX = "th_tmg_"

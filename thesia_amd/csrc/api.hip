@@ -11,9 +11,11 @@
 
 #include "common.h"
 #include "context.h"
+#include "export_core.h"
 #include "host_math.h"
 #include "kernels.h"
 #include "mel_fuse.h"
+#include "track_manager_internal.h"  // wav_header_checked
 #if !defined(TH_MEL_BAND_TAPS_2048)
 #define TH_MEL_BAND_TAPS_2048 64u  // (measured thresholds: th_plan_create)
 #define TH_MEL_BAND_TAPS_1024 80u
@@ -1631,6 +1633,62 @@ TH_API int th_spectrum_frame_range(uint32_t sr, size_t hop, size_t n_frames, dou
     TH_REQUIRE(spectrum_frame_range(sr, hop, n_frames, start_sec, end_sec, frame_start, frame_end),
                "bad time range [%g, %g) s at sr %u, hop %zu", start_sec, end_sec, sr, hop);
     return TH_OK;
+    TH_CATCH
+}
+
+// ---- the host arithmetic of the PCM / WAV export (export_core.h is what the kernel runs too)
+TH_API int th_audio_sample_range(uint32_t sr, size_t n_samples, double start_sec, double end_sec, size_t *sample_start,
+                                 size_t *sample_end) {
+    TH_TRY
+    TH_REQUIRE(sample_start && sample_end, "NULL argument");
+    TH_REQUIRE(spectrum_frame_range(sr, 1, n_samples, start_sec, end_sec, sample_start, sample_end),
+               "bad time range [%g, %g) s at sr %u", start_sec, end_sec, sr);
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_export_dither(uint32_t seed, uint32_t ch, uint64_t i, uint32_t *a, uint32_t *b) {
+    TH_TRY
+    TH_REQUIRE(a && b, "NULL argument");
+    export_dither_ab(export_dither_k1(export_dither_k0(seed, ch), i), i, a, b);
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_export_quantize(uint32_t format, uint32_t dither, uint32_t seed, uint32_t ch, uint64_t first_index, const float *x,
+                              size_t n, int32_t *q, uint64_t *n_clamped, uint64_t *n_nan) {
+    TH_TRY
+    TH_REQUIRE(n_clamped && n_nan && (n == 0 || (x && q)), "NULL argument");
+    TH_REQUIRE(format <= TH_PCM_F32, "unknown format %u", format);
+    TH_REQUIRE(dither <= TH_DITHER_TPDF, "unknown dither %u", dither);
+    uint64_t clamped = 0, nan = 0;
+    const uint32_t k0 = export_dither_k0(seed, ch);
+    const bool tpdf = dither == TH_DITHER_TPDF;
+    const double S = export_scale(format);
+    for (size_t j = 0; j < n; j++) {
+        if (format == TH_PCM_F32) {
+            std::memcpy(&q[j], &x[j], 4);
+            nan += x[j] != x[j];
+            continue;
+        }
+        const uint64_t i = first_index + j;
+        uint32_t a = 0, b = 0;
+        if (tpdf) export_dither_ab(export_dither_k1(k0, i), i, &a, &b);
+        ExportCounts c{0, 0};
+        q[j] = export_quantize_one(x[j], S, tpdf, a, b, &c);
+        clamped += c.clamped;
+        nan += c.nan;
+    }
+    *n_clamped = clamped;
+    *n_nan = nan;
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_wav_header(uint32_t format, uint32_t sr, uint32_t n_ch, uint64_t n_frames, uint8_t out[TH_WAV_HEADER_MAX],
+                         size_t *header_len, size_t *pad_len) {
+    TH_TRY
+    return tmi::wav_header_checked(format, sr, n_ch, n_frames, out, header_len, pad_len);
     TH_CATCH
 }
 

@@ -989,4 +989,47 @@ bool spectrum_frame_range(uint32_t sr, size_t hop, size_t n_frames, double start
     return true;
 }
 
+int wav_header(uint32_t bps, uint32_t sr, uint32_t n_ch, uint64_t n_frames, uint8_t out[64], size_t *header_len, size_t *pad_len) {
+    if (n_ch == 0 || sr == 0 || bps < 2 || bps > 4) return 1;
+    const bool flt = bps == 4;
+    const uint64_t block = (uint64_t)n_ch * bps, rate = block * sr;
+    if (n_ch > 65535 || block > 65535 || rate > UINT32_MAX) return 2;
+    if (n_frames > UINT32_MAX / block) return 2;  // (the data alone)
+    const uint64_t data = n_frames * block, pad = data & 1, hl = flt ? 58 : 44;
+    const uint64_t riff = hl - 8 + data + pad;
+    if (riff > UINT32_MAX) return 2;
+    auto u16 = [&](size_t at, uint32_t v) {
+        out[at] = (uint8_t)v;
+        out[at + 1] = (uint8_t)(v >> 8);
+    };
+    auto u32 = [&](size_t at, uint64_t v) {
+        u16(at, (uint32_t)v & 0xffff);
+        u16(at + 2, (uint32_t)(v >> 16) & 0xffff);
+    };
+    std::memset(out, 0, 64);
+    std::memcpy(out, "RIFF", 4);
+    u32(4, riff);
+    std::memcpy(out + 8, "WAVEfmt ", 8);
+    u32(16, flt ? 18 : 16);
+    u16(20, flt ? 3 : 1);
+    u16(22, n_ch);
+    u32(24, sr);
+    u32(28, rate);
+    u16(32, (uint32_t)block);
+    u16(34, bps * 8);
+    size_t at = 36;
+    if (flt) {
+        u16(36, 0);  // cbSize
+        std::memcpy(out + 38, "fact", 4);
+        u32(42, 4);
+        u32(46, n_frames);
+        at = 50;
+    }
+    std::memcpy(out + at, "data", 4);
+    u32(at + 4, data);
+    *header_len = (size_t)hl;
+    *pad_len = (size_t)pad;
+    return 0;
+}
+
 }  // namespace th

@@ -116,6 +116,13 @@ float db_from_amp(float x);
 // in double.  false: start_sec NaN, negative or infinite, end_sec NaN or below start_sec, sr or hop zero.
 bool spectrum_frame_range(uint32_t sr, size_t hop, size_t n_frames, double start_sec, double end_sec, size_t *f0, size_t *f1);
 
+// ---- PCM / WAV export (th_wav_header): the RIFF header around n_frames frames of n_ch channels; bytes_per_sample 2 or 3 (PCM, 44
+// bytes, tag 1) or 4 (float32, 58 bytes: an 18-byte "fmt " with tag 3 and a "fact" chunk).  *pad_len: the zero byte behind an odd
+// data size.  Returns 0, 1 for an invalid argument (no channels, no rate), 2 for a file RIFF cannot describe (a size above
+// 2^32 - 1, more than 65535 channels, a block above 65535 bytes, a byte rate above 2^32 - 1)
+int wav_header(uint32_t bytes_per_sample, uint32_t sr, uint32_t n_ch, uint64_t n_frames, uint8_t out[64], size_t *header_len,
+               size_t *pad_len);
+
 inline bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
 inline unsigned ilog2(size_t n) {
     unsigned l = 0;

@@ -373,4 +373,31 @@ static_assert(sizeof(SpectrumJob) == 64, "SpectrumJob must have no implicit padd
 // max_blocks: the largest n_ctiles * n_slices of the jobs; max_height: the largest H
 hipError_t launch_spectrum(const SpectrumJob *d_jobs, uint32_t n_jobs, uint32_t max_blocks, uint32_t max_height, hipStream_t s);
 
+// ---- kernels_export.hip: planar f32 channels to interleaved file bytes (16 / 24-bit PCM with optional TPDF dither, or float32)
+constexpr uint32_t EXPORT_THREADS = 256;
+constexpr uint32_t EXPORT_CHUNK_SAMPLES = 4096;  // samples (frames x channels) of one workgroup, at most
+// frames of one chunk: a multiple of 4, so that a chunk starts on a 16-byte boundary of every 16-byte aligned channel.  Chunks lie on
+// the ABSOLUTE grid k F .. (k + 1) F of the track: a range that starts or ends inside one gets a partial chunk
+constexpr uint32_t export_chunk_frames(uint32_t n_ch) {
+    return (EXPORT_CHUNK_SAMPLES / n_ch) & ~3u ? (EXPORT_CHUNK_SAMPLES / n_ch) & ~3u : 4u;
+}
+struct ExportJob {             // frames [f0, f1) of one request: a whole request, or the part of it that lies in one piece
+    const float *const *chan;  // n_ch channel pointers (device memory), each of n samples, 4-byte aligned
+    uint8_t *dst;              // where frame f0's first byte goes: ANY byte address
+    unsigned long long *cnt;   // [0] += clamped samples, [1] += NaN samples
+    uint64_t f0, f1, n;        // f0 <= f1 <= n
+    uint32_t n_ch;             // 1 .. TH_EXPORT_MAX_CHANNELS
+    uint32_t format, dither, seed;
+    uint32_t first_chunk;      // blocks [first_chunk, first_chunk of the next job) of the grid are this job's chunks
+    uint32_t pad;              // zero bytes behind frame f1 - 1's last byte (0 .. 15; written by the job's last chunk)
+};
+static_assert(sizeof(ExportJob) == 72, "ExportJob must have no implicit padding");
+// chunks of the absolute grid that [f0, f1) touches
+inline uint32_t export_n_chunks(uint64_t f0, uint64_t f1, uint32_t n_ch) {
+    const uint64_t F = export_chunk_frames(n_ch);
+    return f1 > f0 ? (uint32_t)((f1 - 1) / F - f0 / F + 1) : 0u;
+}
+// n_chunks: the sum over the jobs (the first_chunk a job behind the last would have)
+hipError_t launch_export(const ExportJob *d_jobs, uint32_t n_jobs, uint32_t n_chunks, hipStream_t s);
+
 }  // namespace th

@@ -28,6 +28,7 @@
 
 #include "common.h"
 #include "context.h"
+#include "export_core.h"
 #include "host_math.h"
 #include "kernels.h"
 #include "tile_cache.h"
@@ -76,6 +77,14 @@ struct ReaderSlot {
     // th_tm_get_loudness_meters: the job tables; the results (series energies, sums, peaks) and the filter states behind them
     // (the same rule: empty until the first call, grow-only)
     th::DeviceTable meter_tab, meter_mem;
+    // th_tm_export_pcm: two staging buffers (each at most EXPORT_STAGE_MAX bytes: a piece of TH_EXPORT_PIECE_BYTES and its
+    // alignment slack), the job table with the channel pointers, the counters, and a second stream with events so that piece p is
+    // copied out while piece p + 1 is computed.  Empty until the slot's first export; freed with the slot
+    th::DeviceBuf<uint8_t> exp_stage[2];
+    size_t exp_stage_cap[2] = {0, 0};
+    th::DeviceTable exp_tab, exp_cnt;
+    hipStream_t exp_copy = nullptr;
+    hipEvent_t exp_done[2] = {nullptr, nullptr}, exp_copied[2] = {nullptr, nullptr};
 };
 constexpr size_t TILE_BYTES_MAX = 520 * 520 * 4;  // 512 core + 2 x 4 gutter (render_tiles.rs:15-16); >= 1024 * 12 waveform bins
 constexpr size_t MAX_READER_SLOTS = 16;
@@ -834,6 +843,11 @@ TH_API int th_tm_destroy(th_tm *tm) {
         (void)hipStreamSynchronize(sp->stream);
         (void)hipStreamDestroy(sp->stream);
         (void)hipHostFree(sp->h_tile);
+        if (sp->exp_copy) (void)hipStreamDestroy(sp->exp_copy);
+        for (int b = 0; b < 2; b++) {
+            if (sp->exp_done[b]) (void)hipEventDestroy(sp->exp_done[b]);
+            if (sp->exp_copied[b]) (void)hipEventDestroy(sp->exp_copied[b]);
+        }
     }
     tm->tracks.clear();
     for (auto &kv : tm->plans) th_plan_destroy(kv.second);
@@ -2549,6 +2563,279 @@ TH_API int th_tm_copy_audio(th_tm *tm, size_t id, uint32_t ch, int which, float 
     const float *src = which == 0 ? c->d_wav : which == 1 ? c->d_draw : c->d_orig;
     TH_HIP(hipMemcpyAsync(out, src, c->n * sizeof(float), hipMemcpyDeviceToHost, tm->ctx->stream));
     TH_HIP(hipStreamSynchronize(tm->ctx->stream));
+    return TH_OK;
+    TH_CATCH
+}
+
+// ---------------------------------------------------------------------------------------------- PCM / WAV export
+// th_tm_export_pcm / th_tm_export_wav: a reader.  The requests are cut into PIECES of at most TH_EXPORT_PIECE_BYTES staged bytes (at
+// frame boundaries); a piece is one launch of kernels_export.hip into one of the slot's two staging buffers and one copy per
+// contiguous run of output bytes into the caller's buffer, on the slot's copy stream, while the next piece is computed.  The bytes in
+// staging sit at the same address modulo 16 as in the caller's image, so a run is one copy.
+namespace {
+constexpr size_t EXPORT_STAGE_MAX = (size_t)TH_EXPORT_PIECE_BYTES + 64;
+
+int check_export_request(th_tm *tm, const th_export_request &r, size_t i, const Track **trp, size_t *s0, size_t *s1) {
+    auto it = tm->tracks.find(r.id);
+    if (it == tm->tracks.end()) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", r.id);
+    const Track &tr = it->second;
+    TH_REQUIRE(r.which <= 2, "request %zu: which must be 0 (audio), 1 (drawn) or 2 (original)", i);
+    TH_REQUIRE(r.format <= TH_PCM_F32, "request %zu: unknown format %u", i, r.format);
+    TH_REQUIRE(r.dither <= TH_DITHER_TPDF, "request %zu: unknown dither %u", i, r.dither);
+    const size_t n = tr.ch.empty() ? 0 : tr.ch[0].n;
+    TH_REQUIRE(spectrum_frame_range(tr.sr, 1, n, r.start_sec, r.end_sec, s0, s1), "request %zu: bad time range [%g, %g) s", i,
+               r.start_sec, r.end_sec);
+    if (tr.ch.empty() || tr.ch.size() > TH_EXPORT_MAX_CHANNELS)
+        return fail(TH_ERR_UNSUPPORTED, "Track %zu: %zu channels (1 .. %d can be exported)", r.id, tr.ch.size(), TH_EXPORT_MAX_CHANNELS);
+    *trp = &tr;
+    return TH_OK;
+}
+
+// both streams of a slot idle before the call's host memory goes away (also on an error path)
+struct ExportDrain {
+    ReaderSlot *sl;
+    ~ExportDrain() {
+        (void)hipStreamSynchronize(sl->stream);
+        if (sl->exp_copy) (void)hipStreamSynchronize(sl->exp_copy);
+    }
+};
+
+int ensure_export_stage(ReaderSlot &sl, int b, size_t bytes) {
+    if (bytes <= sl.exp_stage_cap[b]) return TH_OK;
+    size_t want = 1 << 20;  // powers of two from 1 MiB, never above one piece
+    while (want < bytes) want <<= 1;
+    want = std::min(want, EXPORT_STAGE_MAX);
+    TH_HIP(hipStreamSynchronize(sl.stream));
+    if (sl.exp_copy) TH_HIP(hipStreamSynchronize(sl.exp_copy));
+    sl.exp_stage_cap[b] = 0;
+    TH_HIP(sl.exp_stage[b].alloc(want));
+    sl.exp_stage_cap[b] = want;
+    return TH_OK;
+}
+}  // namespace
+
+namespace th {
+namespace tmi {
+int wav_header_checked(uint32_t format, uint32_t sr, uint32_t n_ch, uint64_t n_frames, uint8_t out[TH_WAV_HEADER_MAX], size_t *header_len,
+                       size_t *pad_len) {
+    TH_REQUIRE(out && header_len && pad_len, "NULL argument");
+    TH_REQUIRE(format <= TH_PCM_F32, "unknown format %u", format);
+    const int rc = wav_header(export_bytes_per_sample(format), sr, n_ch, n_frames, out, header_len, pad_len);
+    TH_REQUIRE(rc != 1, "a WAV file needs at least one channel and a sample rate (%u channels at %u Hz)", n_ch, sr);
+    if (rc != 0) return fail(TH_ERR_UNSUPPORTED, "%llu frames of %u channels at %u Hz do not fit a RIFF / WAV header",
+                             (unsigned long long)n_frames, n_ch, sr);
+    return TH_OK;
+}
+
+int export_request_info(th_tm *tm, const th_export_request &r, size_t i, th_export_info *info) {
+    const Track *tr = nullptr;
+    size_t s0 = 0, s1 = 0;
+    TH_CHECK(check_export_request(tm, r, i, &tr, &s0, &s1));
+    *info = th_export_info{};
+    info->n_bytes = (uint64_t)(s1 - s0) * tr->ch.size() * export_bytes_per_sample(r.format);
+    info->sample_start = s0;
+    info->sample_end = s1;
+    info->sr = tr->sr;
+    info->n_channels = (uint32_t)tr->ch.size();
+    info->waveform_revision = tm->waveform_revision();
+    return TH_OK;
+}
+
+void export_layout(th_export_info *info, size_t n, uint32_t *pad, size_t *out_len) {
+    uint64_t at = 0;
+    for (size_t i = 0; i < n; i++) {
+        info[i].offset = at;
+        const uint64_t end = at + info[i].n_bytes;
+        at = (end + 15) & ~(uint64_t)15;
+        pad[i] = i + 1 < n ? (uint32_t)(at - end) : 0u;
+        if (i + 1 == n) at = end;
+    }
+    *out_len = (size_t)at;
+}
+
+int export_run(th_tm *tm, const th_export_request *reqs, size_t n, th_export_info *info, const uint32_t *pad, uint8_t *out) {
+    struct Run {
+        size_t stage_at;
+        uint64_t out_at;
+        size_t bytes;
+    };
+    struct Piece {
+        size_t job0 = 0, job1 = 0;
+        uint32_t n_chunks = 0;
+        size_t stage_bytes = 0;
+        std::vector<Run> runs;
+    };
+    struct Part {
+        size_t req, stage_at;
+    };
+    TH_REQUIRE(n <= UINT32_MAX, "too many requests");
+    std::vector<ExportJob> jobs;
+    std::vector<Part> parts;  // job j's request and place in its piece's staging buffer
+    std::vector<Piece> pieces;
+    std::vector<size_t> ptr0(n);  // request i's first channel pointer
+    std::vector<const float *> ptrs;
+    Piece cur;
+    uint64_t cur_out_end = 0;
+    auto close_piece = [&]() {
+        cur.job1 = jobs.size();
+        pieces.push_back(std::move(cur));
+        cur = Piece{};
+        cur.job0 = jobs.size();
+    };
+    for (size_t i = 0; i < n; i++) {
+        const th_export_request &r = reqs[i];
+        const Track &tr = tm->tracks.find(r.id)->second;  // (checked by the caller, under the same lock)
+        const uint32_t n_ch = (uint32_t)tr.ch.size();
+        const uint64_t fbytes = (uint64_t)n_ch * export_bytes_per_sample(r.format);
+        ptr0[i] = ptrs.size();
+        for (const Channel &c : tr.ch) ptrs.push_back(r.which == 0 ? c.d_wav : r.which == 1 ? c.d_draw : c.d_orig);
+        uint64_t f = info[i].sample_start;
+        const uint64_t s0 = info[i].sample_start, s1 = info[i].sample_end;
+        while (f < s1) {
+            const uint64_t out_at = info[i].offset + (f - s0) * fbytes;
+            const bool contiguous = !cur.runs.empty() && out_at == cur_out_end;
+            const size_t at = contiguous ? cur.stage_bytes : ((cur.stage_bytes + 15) & ~(size_t)15) + (size_t)(out_at & 15);
+            const uint64_t room = at < TH_EXPORT_PIECE_BYTES ? (TH_EXPORT_PIECE_BYTES - at) / fbytes : 0;
+            if (room == 0) {  // (a frame is at most 4 KiB: an empty piece always has room)
+                close_piece();
+                continue;
+            }
+            const uint64_t take = std::min<uint64_t>(room, s1 - f);
+            const uint32_t pd = f + take == s1 ? pad[i] : 0u;
+            const size_t bytes = (size_t)(take * fbytes) + pd;
+            ExportJob j{};
+            j.f0 = f;
+            j.f1 = f + take;
+            j.n = tr.ch[0].n;
+            j.n_ch = n_ch;
+            j.format = r.format;
+            j.dither = r.dither;
+            j.seed = r.seed;
+            j.first_chunk = cur.n_chunks;
+            j.pad = pd;
+            const uint64_t chunks = (uint64_t)cur.n_chunks + export_n_chunks(j.f0, j.f1, n_ch);
+            if (chunks > INT32_MAX) return fail(TH_ERR_UNSUPPORTED, "request %zu: too many chunks in one piece", i);
+            cur.n_chunks = (uint32_t)chunks;
+            jobs.push_back(j);
+            parts.push_back(Part{i, at});
+            if (contiguous)
+                cur.runs.back().bytes += bytes;
+            else
+                cur.runs.push_back(Run{at, out_at, bytes});
+            cur.stage_bytes = at + bytes;
+            cur_out_end = out_at + bytes;
+            f += take;
+        }
+    }
+    if (cur.n_chunks) close_piece();
+    for (size_t i = 0; i < n; i++) info[i].n_clamped = info[i].n_nan = 0;
+    if (pieces.empty()) return TH_OK;
+
+    TH_HIP(hipSetDevice(tm->ctx->device));
+    SlotLease lease{tm, nullptr};
+    int rc = acquire_slot(tm, &lease.slot);
+    if (rc != TH_OK) return rc;
+    ReaderSlot &sl = *lease.slot;
+    if (!sl.exp_copy) {
+        TH_HIP(hipStreamCreateWithFlags(&sl.exp_copy, hipStreamNonBlocking));
+        for (int b = 0; b < 2; b++) {
+            TH_HIP(hipEventCreateWithFlags(&sl.exp_done[b], hipEventDisableTiming));
+            TH_HIP(hipEventCreateWithFlags(&sl.exp_copied[b], hipEventDisableTiming));
+        }
+    }
+    ExportDrain drain{&sl};
+    size_t need[2] = {0, 0};
+    for (size_t p = 0; p < pieces.size(); p++) need[p & 1] = std::max(need[p & 1], pieces[p].stage_bytes);
+    for (int b = 0; b < 2; b++)
+        if (need[b]) TH_CHECK(ensure_export_stage(sl, b, need[b]));
+    // one table for the whole call: the jobs of every piece, then the channel pointers
+    const size_t jobs_bytes = jobs.size() * sizeof(ExportJob), tab_bytes = jobs_bytes + ptrs.size() * sizeof(const float *);
+    TH_CHECK(sl.exp_tab.ensure(tab_bytes));
+    TH_CHECK(sl.exp_cnt.ensure(n * 2 * sizeof(unsigned long long)));
+    unsigned char *d_tab = static_cast<unsigned char *>(sl.exp_tab.dptr);
+    const float *const *d_ptrs = reinterpret_cast<const float *const *>(d_tab + jobs_bytes);
+    unsigned long long *d_cnt = static_cast<unsigned long long *>(sl.exp_cnt.dptr);
+    for (size_t p = 0; p < pieces.size(); p++)
+        for (size_t j = pieces[p].job0; j < pieces[p].job1; j++) {
+            jobs[j].chan = d_ptrs + ptr0[parts[j].req];
+            jobs[j].dst = sl.exp_stage[p & 1].get() + parts[j].stage_at;
+            jobs[j].cnt = d_cnt + 2 * parts[j].req;
+        }
+    std::vector<unsigned char> tab(tab_bytes);
+    std::memcpy(tab.data(), jobs.data(), jobs_bytes);
+    std::memcpy(tab.data() + jobs_bytes, ptrs.data(), tab_bytes - jobs_bytes);
+    TH_CHECK(sl.exp_tab.upload(sl.stream, tab.data(), tab_bytes));
+    TH_HIP(hipMemsetAsync(d_cnt, 0, n * 2 * sizeof(unsigned long long), sl.stream));
+    const ExportJob *d_jobs = reinterpret_cast<const ExportJob *>(d_tab);
+    auto launch_piece = [&](size_t p) -> int {
+        const Piece &pc = pieces[p];
+        if (p >= 2) TH_HIP(hipStreamWaitEvent(sl.stream, sl.exp_copied[p & 1], 0));  // (the buffer's last piece has left it)
+        TH_HIP(launch_export(d_jobs + pc.job0, (uint32_t)(pc.job1 - pc.job0), pc.n_chunks, sl.stream));
+        TH_HIP(hipEventRecord(sl.exp_done[p & 1], sl.stream));
+        return TH_OK;
+    };
+    TH_CHECK(launch_piece(0));
+    for (size_t p = 0; p < pieces.size(); p++) {
+        if (p + 1 < pieces.size()) TH_CHECK(launch_piece(p + 1));  // (ahead of the copy: a copy into pageable memory holds the host)
+        TH_HIP(hipStreamWaitEvent(sl.exp_copy, sl.exp_done[p & 1], 0));
+        for (const Run &run : pieces[p].runs)
+            TH_HIP(hipMemcpyAsync(out + run.out_at, sl.exp_stage[p & 1].get() + run.stage_at, run.bytes, hipMemcpyDeviceToHost, sl.exp_copy));
+        TH_HIP(hipEventRecord(sl.exp_copied[p & 1], sl.exp_copy));
+    }
+    std::vector<unsigned long long> cnt(n * 2);
+    TH_HIP(hipMemcpyAsync(cnt.data(), d_cnt, cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, sl.stream));
+    TH_HIP(hipStreamSynchronize(sl.stream));
+    TH_HIP(hipStreamSynchronize(sl.exp_copy));
+    for (size_t i = 0; i < n; i++) {
+        info[i].n_clamped = cnt[2 * i];
+        info[i].n_nan = cnt[2 * i + 1];
+    }
+    return TH_OK;
+}
+}  // namespace tmi
+}  // namespace th
+
+TH_API int th_tm_export_pcm(th_tm *tm, const th_export_request *reqs, size_t n, uint8_t *out, size_t cap, th_export_info *info,
+                            size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(tm && out_len && (n == 0 || (reqs && info)), "NULL argument");
+    *out_len = 0;
+    if (n == 0) return TH_OK;
+    std::shared_lock<std::shared_mutex> rl(tm->rw);
+    std::vector<th_export_info> infos(n);
+    std::vector<uint32_t> pad(n);
+    for (size_t i = 0; i < n; i++) TH_CHECK(tmi::export_request_info(tm, reqs[i], i, &infos[i]));
+    size_t total = 0;
+    tmi::export_layout(infos.data(), n, pad.data(), &total);
+    std::memcpy(info, infos.data(), n * sizeof(th_export_info));
+    *out_len = total;
+    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
+    TH_CHECK(tmi::export_run(tm, reqs, n, infos.data(), pad.data(), out));
+    std::memcpy(info, infos.data(), n * sizeof(th_export_info));
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_tm_export_wav(th_tm *tm, const th_export_request *req, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(tm && req && out_len, "NULL argument");
+    *out_len = 0;
+    std::shared_lock<std::shared_mutex> rl(tm->rw);
+    th_export_info one{};
+    TH_CHECK(tmi::export_request_info(tm, *req, 0, &one));
+    uint8_t hdr[TH_WAV_HEADER_MAX];
+    size_t hl = 0, pl = 0;
+    TH_CHECK(tmi::wav_header_checked(req->format, one.sr, one.n_channels, one.sample_end - one.sample_start, hdr, &hl, &pl));
+    one.offset = hl;
+    const size_t total = hl + (size_t)one.n_bytes + pl;
+    if (info) *info = one;
+    *out_len = total;
+    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
+    const uint32_t pad = 0;
+    TH_CHECK(tmi::export_run(tm, req, 1, &one, &pad, out));
+    std::memcpy(out, hdr, hl);
+    if (pl) out[hl + one.n_bytes] = 0;
+    if (info) *info = one;
     return TH_OK;
     TH_CATCH
 }

@@ -58,6 +58,19 @@ int spectrum_request_info(th_tm *tm, const th_spectrum_request &r, size_t i, th_
 // waveform revision, everything else zero
 int loudness_meter_info(th_tm *tm, size_t id, th_loudness_meter *m);
 
+// th_tm_export_pcm in three steps (th_tmg runs them per owning slot).  export_request_info: the check of ONE request with the codes
+// and in the order th_tm_export_pcm reports them; *info: offset 0, the byte count, the sample range, rate, channels, counts 0 and the
+// slot's waveform revision.  export_layout: the offsets (multiples of 16 in request order), the zero bytes behind every request
+// (pad[i]: up to the next offset; 0 behind the last) and the bytes of the whole image.  export_run: the device work for requests
+// that were checked and laid out: request i's bytes, then pad[i] zero bytes, to out + info[i].offset (ascending in i; they need not
+// be adjacent), and its two counts into info[i].  Takes a reader slot; the caller holds the lock (shared)
+int export_request_info(th_tm *tm, const th_export_request &r, size_t i, th_export_info *info);
+void export_layout(th_export_info *info, size_t n, uint32_t *pad, size_t *out_len);
+int export_run(th_tm *tm, const th_export_request *reqs, size_t n, th_export_info *info, const uint32_t *pad, uint8_t *out);
+// th_wav_header with the status reported (host_math.h wav_header)
+int wav_header_checked(uint32_t format, uint32_t sr, uint32_t n_ch, uint64_t n_frames, uint8_t out[TH_WAV_HEADER_MAX], size_t *header_len,
+                       size_t *pad_len);
+
 // update_spec_imgs against `global` (NULL: the manager's own tracks, as th_tm_* does), then the writer's final wait:
 // for the images only (apply_track_list_changes, set_dB_range) or for everything (set_setting, set_colormap)
 int requantise(th_tm *tm, const DbRange *global, bool force_update_all, bool images_only, std::vector<size_t> *updated);

@@ -690,6 +690,101 @@ TH_API int th_tmg_get_loudness_meter(th_tmg *g, size_t id, th_loudness_meter *me
     TH_CATCH
 }
 
+// Export: every request is checked in request order against its owning slot (the codes and the order of one th_tm), which gives the
+// byte counts, so the offsets and the zero padding are known before any slot runs; the slots then run side by side, each writing
+// its own requests' bytes (and the padding behind them) straight into the caller's buffer.
+namespace {
+int export_on_slots(th_tmg *g, const th_export_request *reqs, size_t n, std::vector<th_export_info> &infos, const std::vector<uint32_t> &pad,
+                    uint8_t *out) {
+    std::vector<std::vector<size_t>> mine(g->slots.size());
+    for (size_t i = 0; i < n; i++) mine[find_track(g, reqs[i].id)->slot].push_back(i);
+    std::vector<uint32_t> busy;
+    for (uint32_t s = 0; s < g->slots.size(); s++)
+        if (!mine[s].empty()) busy.push_back(s);
+    return for_slots(g, busy, [&](uint32_t s) -> int {
+        const std::vector<size_t> &idx = mine[s];
+        std::vector<th_export_request> sub(idx.size());
+        std::vector<th_export_info> si(idx.size());
+        std::vector<uint32_t> sp(idx.size());
+        for (size_t j = 0; j < idx.size(); j++) {
+            sub[j] = reqs[idx[j]];
+            si[j] = infos[idx[j]];
+            sp[j] = pad[idx[j]];
+        }
+        th_tm *tm = g->slots[s].tm;
+        std::shared_lock<std::shared_mutex> sl(tmi::rw_of(tm));
+        const int rc = tmi::export_run(tm, sub.data(), sub.size(), si.data(), sp.data(), out);
+        if (rc != TH_OK) return rc;
+        for (size_t j = 0; j < idx.size(); j++) {
+            infos[idx[j]].n_clamped = si[j].n_clamped;
+            infos[idx[j]].n_nan = si[j].n_nan;
+        }
+        return TH_OK;
+    });
+}
+
+int export_check_all(th_tmg *g, const th_export_request *reqs, size_t n, std::vector<th_export_info> &infos) {
+    for (size_t i = 0; i < n; i++) {
+        const th_tmg::Placement *p = find_track(g, reqs[i].id);
+        if (!p) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", reqs[i].id);
+        th_tm *tm = g->slots[p->slot].tm;
+        std::shared_lock<std::shared_mutex> sl(tmi::rw_of(tm));
+        TH_CHECK(tmi::export_request_info(tm, reqs[i], i, &infos[i]));
+    }
+    uint64_t revision;
+    {
+        std::lock_guard<std::mutex> lk(g->revs.mu);
+        revision = g->revs.waveform_revision;
+    }
+    for (size_t i = 0; i < n; i++) infos[i].waveform_revision = revision;
+    return TH_OK;
+}
+}  // namespace
+
+TH_API int th_tmg_export_pcm(th_tmg *g, const th_export_request *reqs, size_t n, uint8_t *out, size_t cap, th_export_info *info,
+                             size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(g && out_len && (n == 0 || (reqs && info)), "NULL argument");
+    *out_len = 0;
+    if (n == 0) return TH_OK;
+    std::shared_lock<std::shared_mutex> rl(g->rw);
+    std::vector<th_export_info> infos(n);
+    std::vector<uint32_t> pad(n);
+    TH_CHECK(export_check_all(g, reqs, n, infos));
+    size_t total = 0;
+    tmi::export_layout(infos.data(), n, pad.data(), &total);
+    std::memcpy(info, infos.data(), n * sizeof(th_export_info));
+    *out_len = total;
+    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
+    TH_CHECK(export_on_slots(g, reqs, n, infos, pad, out));
+    std::memcpy(info, infos.data(), n * sizeof(th_export_info));
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_tmg_export_wav(th_tmg *g, const th_export_request *req, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(g && req && out_len, "NULL argument");
+    *out_len = 0;
+    std::shared_lock<std::shared_mutex> rl(g->rw);
+    std::vector<th_export_info> one(1);
+    TH_CHECK(export_check_all(g, req, 1, one));
+    uint8_t hdr[TH_WAV_HEADER_MAX];
+    size_t hl = 0, pl = 0;
+    TH_CHECK(tmi::wav_header_checked(req->format, one[0].sr, one[0].n_channels, one[0].sample_end - one[0].sample_start, hdr, &hl, &pl));
+    one[0].offset = hl;
+    const size_t total = hl + (size_t)one[0].n_bytes + pl;
+    if (info) *info = one[0];
+    *out_len = total;
+    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
+    TH_CHECK(export_on_slots(g, req, 1, one, std::vector<uint32_t>{0}, out));
+    std::memcpy(out, hdr, hl);
+    if (pl) out[hl + one[0].n_bytes] = 0;
+    if (info) *info = one[0];
+    return TH_OK;
+    TH_CATCH
+}
+
 // set_common_normalize / set_common_guard_clipping: every slot re-derives its tracks into staged buffers; all commit, or all discard
 namespace {
 int set_common_dynamics_all(th_tmg *g, int kind, float target, int mode) {
