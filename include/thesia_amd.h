@@ -748,6 +748,62 @@ TH_API int th_tm_export_pcm(th_tm *tm, const th_export_request *reqs, size_t n, 
 TH_API int th_tm_export_wav(th_tm *tm, const th_export_request *req, uint8_t *out, size_t cap_bytes,
                             th_export_info *info /* may be NULL */, size_t *out_len);
 
+/* ---------------------------------------------------------------- Export at a target sample rate (polyphase sinc resampler) */
+/* th_tm_export_pcm_at / th_tm_export_wav_at: th_tm_export_pcm / _wav with the audio converted to sr_out first, by a band-limited
+ * resampler on the device, an exact rational polyphase FIR of the kind the reference's player runs on the CPU (player/stream.rs: a
+ * rubato windowed-sinc resampler, sinc_len 256, BlackmanHarris2).  With TH_PCM_F32 the call is the player's interleaved float feed
+ * at the device rate.  No reference implementation can be pinned; these definitions are the contract.
+ *   Ratio and length.  g = gcd(sr_in, sr_out), L = sr_out / g, M = sr_in / g, rho = min(1, L / M), Z = 128, FC = 0.95,
+ *   K = Z when L >= M, else ceil(Z M / L); an output sample has 2K taps (th_resample_plan_for).
+ *   Prototype, in input samples, C double: h(t) = rho FC sinc(rho FC t) w(rho t / Z); sinc(x) = sin(pi x) / (pi x), sinc(0) = 1;
+ *   w(u) = b(u)^2 for |u| < 1, else 0; b(u) = 0.35875 + 0.48829 cos(pi u) + 0.14128 cos(2 pi u) + 0.01168 cos(3 pi u) (the 4-term
+ *   Blackman-Harris window, squared).  No per-phase normalisation: the DC gain of every phase is 1 within 1e-11.
+ *   Output sample j (the ABSOLUTE index on the output grid; its time is j / sr_out, no delay): j M = q L + r with 0 <= r < L in 64-bit
+ *   integers (TH_ERR_UNSUPPORTED for a track whose n_out M does not fit 64 bits);
+ *   y[j] = sum over k = 0 .. 2K - 1 of c[r][k] x[q - K + 1 + k], c[r][k] = (float)h(k - K + 1 - r / L) (th_resample_coefs),
+ *   x[n] = 0 outside [0, n_in).
+ *   Summation, in f32: tap k, in ascending k, goes into partial sum k mod 4 by one fmaf (a = fmaf(c, x, a), all four from +0, the
+ *   taps outside the track included, with x = 0); y = (a0 + a1) + (a2 + a3).  The order depends on nothing but k, and
+ *   th_resample_f32 (host, one channel, x = the whole channel) runs the very function the kernel runs: the same bits.
+ *   Length and ranges.  n_out = ceil(n_in L / M) (th_resample_n_out); th_audio_sample_range(sr_out, n_out, start_sec, end_sec) gives
+ *   [j0, j1) on the output grid; the dither index of the export is j.  The bytes of a range are therefore a slice of the whole-track
+ *   export at that rate: a sample depends on the track's audio, the two rates and j alone.
+ *   Same rate.  sr_out == 0 or sr_out == the track's rate applies no filter: bytes, counts and infos are exactly those of
+ *   th_tm_export_pcm / _wav for the same request (the filter at L = M = 1 is not an identity).
+ *   Limits.  TH_ERR_UNSUPPORTED when 2K > TH_RESAMPLE_MAX_TAPS (reduction by more than 64) or L 2K > TH_RESAMPLE_MAX_COEFS (a 64 MiB
+ *   table): 96000 -> 95999 and 192000 -> 2000 are refused; every pair of standard rates from 8 kHz to 192 kHz is far inside.
+ *   One deliberate difference from the reference: rubato interpolates cubically in a 128x oversampled table of the same kind of
+ *   kernel; here the kernel is evaluated at the exact rational phase, so there is no interpolation error and L table rows, not 128.
+ * Infos: th_export_info unchanged; sr = the output rate, sample_start/_end = [j0, j1) on the output grid, n_nan / n_clamped count
+ * OUTPUT samples; the WAV header carries sr_out.  Layout and errors are those of th_tm_export_pcm word for word (offsets multiples
+ * of 16, zero padding between requests, the first faulty request decides, nothing written on error, the size query, an empty range
+ * is valid), plus TH_ERR_UNSUPPORTED for an unsupported rate pair.
+ * A reader like th_tm_export_pcm, through the same pieces and staging buffers.  A slot that resamples also holds, from its first such
+ * call until it is destroyed, the planar f32 scratch of one piece (piece frames x channels x 4 bytes: at most
+ * 2 x TH_EXPORT_PIECE_BYTES + 64 KiB, reached with 16-bit output) and the coefficient table of the LAST rate pair it served (at most
+ * TH_RESAMPLE_MAX_COEFS floats); a manager that never resamples holds neither. */
+#define TH_RESAMPLE_MAX_TAPS 16384u
+#define TH_RESAMPLE_MAX_COEFS (1u << 24)
+typedef struct {
+    uint32_t L, M, half_taps; /* half_taps = K */
+    double rho, cutoff;       /* cutoff = rho FC */
+} th_resample_plan;
+/* host arithmetic.  th_resample_plan_for: TH_ERR_INVALID_ARG on a zero rate, TH_ERR_UNSUPPORTED per the limits.  th_resample_coefs:
+ * row r (< L) of the table, 2K taps, as f64 (h64, may be NULL) and rounded to f32 (c32, may be NULL).  th_resample_f32: outputs
+ * [j0, j0 + n) of one channel, j0 + n <= n_out */
+TH_API int th_resample_plan_for(uint32_t sr_in, uint32_t sr_out, th_resample_plan *out);
+TH_API int th_resample_n_out(size_t n_in, uint32_t sr_in, uint32_t sr_out, size_t *n_out);
+TH_API int th_resample_coefs(uint32_t sr_in, uint32_t sr_out, uint32_t r, double *h64, float *c32);
+TH_API int th_resample_f32(const float *x, size_t n_in, uint32_t sr_in, uint32_t sr_out, uint64_t j0, size_t n, float *y);
+typedef struct {
+    th_export_request base;
+    uint32_t sr_out; /* 0 = the track's own */
+} th_export_at_request;
+TH_API int th_tm_export_pcm_at(th_tm *tm, const th_export_at_request *reqs, size_t n, uint8_t *out, size_t cap_bytes,
+                               th_export_info *info /* n */, size_t *out_len);
+TH_API int th_tm_export_wav_at(th_tm *tm, const th_export_at_request *req, uint8_t *out, size_t cap_bytes,
+                               th_export_info *info /* may be NULL */, size_t *out_len);
+
 /* ---------------------------------------------------------------- TrackManager over several devices (one process) */
 /* th_tmg: the th_tm_* calls above, call for call, with a th_tmg * in place of the th_tm *; a multi-GPU host swaps one for
  * the other.  Every result — updated ids, max_sr, db state, revisions, specs, images, tile bytes, batch offsets, render
@@ -832,6 +888,11 @@ TH_API int th_tmg_export_pcm(th_tmg *tmg, const th_export_request *reqs, size_t 
                              th_export_info *info /* n */, size_t *out_len);
 TH_API int th_tmg_export_wav(th_tmg *tmg, const th_export_request *req, uint8_t *out, size_t cap_bytes,
                              th_export_info *info /* may be NULL */, size_t *out_len);
+/* export at a target sample rate: as above; every slot keeps its own scratch and coefficient table */
+TH_API int th_tmg_export_pcm_at(th_tmg *tmg, const th_export_at_request *reqs, size_t n, uint8_t *out, size_t cap_bytes,
+                                th_export_info *info /* n */, size_t *out_len);
+TH_API int th_tmg_export_wav_at(th_tmg *tmg, const th_export_at_request *req, uint8_t *out, size_t cap_bytes,
+                                th_export_info *info /* may be NULL */, size_t *out_len);
 
 /* Test and measurement entry points (kernel selectors for A/B runs, per-launch kernel timing, replacing a resident image
  * with given pixels) are NOT part of this interface: include/thesia_amd_testing.h declares them; a thesia host binds none. */

@@ -120,6 +120,14 @@ class ExportInfo(C.Structure):  # th_export_info
                 ("waveform_revision", C.c_uint64)]
 
 
+class ResamplePlan(C.Structure):  # th_resample_plan
+    _fields_ = [("L", C.c_uint32), ("M", C.c_uint32), ("half_taps", C.c_uint32), ("rho", C.c_double), ("cutoff", C.c_double)]
+
+
+class ExportAtRequest(C.Structure):  # th_export_at_request
+    _fields_ = [("base", ExportRequest), ("sr_out", C.c_uint32)]
+
+
 class PyramidDesc(C.Structure):
     _fields_ = [("wav", C.c_void_p), ("out", C.c_void_p), ("n_samples", C.c_uint64), ("n_levels", C.c_uint32),
                 ("first_level", C.c_uint32)]
@@ -321,6 +329,14 @@ _SIGS = {
     "th_tm_export_wav": [vp, C.POINTER(ExportRequest), C.c_void_p, C.c_size_t, C.POINTER(ExportInfo), c_szp],
     "th_tmg_export_pcm": [vp, C.POINTER(ExportRequest), C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(ExportInfo), c_szp],
     "th_tmg_export_wav": [vp, C.POINTER(ExportRequest), C.c_void_p, C.c_size_t, C.POINTER(ExportInfo), c_szp],
+    "th_resample_plan_for": [C.c_uint32, C.c_uint32, C.POINTER(ResamplePlan)],
+    "th_resample_n_out": [C.c_size_t, C.c_uint32, C.c_uint32, c_szp],
+    "th_resample_coefs": [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), c_f32p],
+    "th_resample_f32": [c_f32p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint64, C.c_size_t, c_f32p],
+    "th_tm_export_pcm_at": [vp, C.POINTER(ExportAtRequest), C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(ExportInfo), c_szp],
+    "th_tm_export_wav_at": [vp, C.POINTER(ExportAtRequest), C.c_void_p, C.c_size_t, C.POINTER(ExportInfo), c_szp],
+    "th_tmg_export_pcm_at": [vp, C.POINTER(ExportAtRequest), C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(ExportInfo), c_szp],
+    "th_tmg_export_wav_at": [vp, C.POINTER(ExportAtRequest), C.c_void_p, C.c_size_t, C.POINTER(ExportInfo), c_szp],
     "th_tile_cache_create": [C.c_size_t, C.POINTER(vp)],
     "th_tile_cache_destroy": [vp],
     "th_tile_cache_lookup": [vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), c_u8p, C.c_size_t,

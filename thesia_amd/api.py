@@ -29,6 +29,8 @@ WAV_HEADER_MAX = 64
 EXPORT_PIECE_BYTES = 32 << 20      # TH_EXPORT_PIECE_BYTES
 EXPORT_MAX_CHANNELS = 1024         # TH_EXPORT_MAX_CHANNELS
 EXPORT_CHUNK_SAMPLES = 4096        # samples (frames x channels) of one workgroup of the export kernel, at most
+RESAMPLE_MAX_TAPS = 16384          # TH_RESAMPLE_MAX_TAPS
+RESAMPLE_MAX_COEFS = 1 << 24       # TH_RESAMPLE_MAX_COEFS
 WAVEFORM_TILE_MAX_BYTES = 24 + 1024 * 12
 SPECTROGRAM_TILE_MAX_BYTES = 40 + 520 * 520 * 4
 
@@ -327,6 +329,108 @@ class _ExportMethods:
         info = _ffi.ExportInfo()
         need = C.c_size_t()
         fn = getattr(lib, self._PFX + "export_wav")
+        rc = fn(self.handle, C.byref(req), None, 0, C.byref(info), C.byref(need))
+        if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+            check(rc)
+        out = np.empty(need.value, np.uint8)
+        check(fn(self.handle, C.byref(req), out.ctypes.data, out.size, C.byref(info), C.byref(need)))
+        return out.tobytes(), _export_info_dict(info)
+
+
+def resample_plan(sr_in: int, sr_out: int) -> dict:
+    """th_resample_plan_for -> {L, M, half_taps, rho, cutoff} of the polyphase resampler sr_in -> sr_out (host)"""
+    p = _ffi.ResamplePlan()
+    check(lib.th_resample_plan_for(sr_in, sr_out, C.byref(p)))
+    return {"L": p.L, "M": p.M, "half_taps": p.half_taps, "rho": p.rho, "cutoff": p.cutoff}
+
+
+def resample_n_out(n_in: int, sr_in: int, sr_out: int) -> int:
+    """samples of a track of n_in samples at sr_in once it is resampled to sr_out: ceil(n_in L / M) (host)"""
+    n = C.c_size_t()
+    check(lib.th_resample_n_out(n_in, sr_in, sr_out, C.byref(n)))
+    return n.value
+
+
+def resample_coefs(sr_in: int, sr_out: int, r: int):
+    """-> (f64 row, f32 row): the 2K taps of phase r of the resampler's table (host)"""
+    taps = 2 * resample_plan(sr_in, sr_out)["half_taps"]
+    h64, c32 = np.empty(taps, np.float64), np.empty(taps, np.float32)
+    check(lib.th_resample_coefs(sr_in, sr_out, r, h64.ctypes.data_as(C.POINTER(C.c_double)), _ptr(c32, c_f32p)))
+    return h64, c32
+
+
+def resample_f32(x, sr_in: int, sr_out: int, j0: int = 0, n: Optional[int] = None) -> np.ndarray:
+    """outputs [j0, j0 + n) of one channel x (the whole channel) resampled sr_in -> sr_out on the host: what the kernel computes,
+    the same table, order and bits (n None: up to the end)"""
+    x = _f32(x).ravel()
+    if n is None:
+        n = resample_n_out(x.size, sr_in, sr_out) - j0
+    y = np.empty(max(n, 0), np.float32)
+    check(lib.th_resample_f32(_ptr(x, c_f32p), x.size, sr_in, sr_out, j0, y.size, _ptr(y, c_f32p)))
+    return y
+
+
+def resample_tile(sr_in: int, sr_out: int) -> dict:
+    """the resample kernel's tiling of the pair (kernels.h resample_tiling): a workgroup takes R consecutive outputs of one channel
+    in each of P periods, Lp outputs (Mp input samples) apart; a period of Lp outputs is S such sub-tiles"""
+    p = resample_plan(sr_in, sr_out)
+    L, M = p["L"], p["M"]
+    if L < 64:
+        Lp = L * (64 // L)
+        R, S = Lp, 1
+    else:
+        Lp, S = L, (L + 63) // 64
+        R = (L + S - 1) // S
+    Mp = M * (Lp // L)
+    lanes = ((R - 1) * M) // L + 1 + 64
+    for G, Pt in ((4, 8), (4, 4), (4, 2), (4, 1), (1, 2), (1, 1)):
+        span = (G * Pt - 1) * Mp + lanes
+        if span <= 5248:
+            break
+    return {"L": L, "M": M, "taps": 2 * p["half_taps"], "Lp": Lp, "Mp": Mp, "R": R, "S": S, "G": G, "Pt": Pt, "P": G * Pt, "span": span}
+
+
+def _export_at_request(r) -> "_ffi.ExportAtRequest":
+    """(track_id, sr_out, fmt[, dither[, seed[, start_sec[, end_sec[, which]]]]]) or a dict with those names"""
+    if isinstance(r, dict):
+        sr_out = r.get("sr_out", 0)
+        base = _export_request(r)
+    else:
+        r = tuple(r)
+        sr_out = r[1]
+        base = _export_request((r[0],) + r[2:])
+    return _ffi.ExportAtRequest(base, sr_out)
+
+
+class _ExportAtMethods:
+    """_ExportMethods at a caller-chosen sample rate: the polyphase sinc resampler in front of the same export (th_tm_* and th_tmg_*)"""
+
+    def export_pcm_at(self, requests, out: Optional[np.ndarray] = None):
+        """th_tm_export_pcm_at: requests = iterable of (track_id, sr_out, fmt[, dither[, seed[, start_sec[, end_sec[, which]]]]]) ->
+        (uint8 buffer, list of info dicts), as export_pcm; sr_out 0 = the track's own rate"""
+        reqs = [_export_at_request(r) for r in requests]
+        n = len(reqs)
+        if n == 0:
+            return np.empty(0, np.uint8), []
+        arr = (_ffi.ExportAtRequest * n)(*reqs)
+        info = (_ffi.ExportInfo * n)()
+        need = C.c_size_t()
+        fn = getattr(lib, self._PFX + "export_pcm_at")
+        if out is None:
+            rc = fn(self.handle, arr, n, None, 0, info, C.byref(need))
+            if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+                check(rc)
+            out = np.empty(max(need.value, 1), np.uint8)
+        check(fn(self.handle, arr, n, out.ctypes.data, out.size, info, C.byref(need)))
+        return out[:need.value], [_export_info_dict(o) for o in info]
+
+    def export_wav_at(self, track_id: int, sr_out: int, fmt: int, dither: int = DITHER_NONE, seed: int = 0, start_sec: float = 0.0,
+                      end_sec: float = float("inf"), which: int = 0):
+        """th_tm_export_wav_at: -> (the complete file image at sr_out as bytes, info dict)"""
+        req = _ffi.ExportAtRequest(_ffi.ExportRequest(track_id, which, fmt, dither, seed, start_sec, end_sec), sr_out)
+        info = _ffi.ExportInfo()
+        need = C.c_size_t()
+        fn = getattr(lib, self._PFX + "export_wav_at")
         rc = fn(self.handle, C.byref(req), None, 0, C.byref(info), C.byref(need))
         if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
             check(rc)
@@ -848,7 +952,7 @@ class TileCache:
                 "spectrogram_revision": sr.value, "hits": h.value, "misses": m.value}
 
 
-class TrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods):
+class TrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods, _ExportAtMethods):
     """th_tm: mirror of core/mod.rs TrackManager with HBM-resident audio / specs / images."""
     _PFX = "th_tm_"
 
@@ -1048,7 +1152,7 @@ class TrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _E
         return out[: n.value].tobytes()
 
 
-class MultiTrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods):
+class MultiTrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods, _ExportAtMethods):
     """th_tmg: the TrackManager over several devices of one process (duplicates allowed: [0, 0] is two slots on one card).
     Same method names as TrackManager; results are bit-identical to one TrackManager holding every track."""
     _PFX = "th_tmg_"

@@ -15,6 +15,7 @@
 #include "host_math.h"
 #include "kernels.h"
 #include "mel_fuse.h"
+#include "resample_core.h"
 #include "track_manager_internal.h"  // wav_header_checked
 #if !defined(TH_MEL_BAND_TAPS_2048)
 #define TH_MEL_BAND_TAPS_2048 64u  // (measured thresholds: th_plan_create)
@@ -1689,6 +1690,76 @@ TH_API int th_wav_header(uint32_t format, uint32_t sr, uint32_t n_ch, uint64_t n
                          size_t *header_len, size_t *pad_len) {
     TH_TRY
     return tmi::wav_header_checked(format, sr, n_ch, n_frames, out, header_len, pad_len);
+    TH_CATCH
+}
+
+// ---- the host arithmetic of the resampler (resample_core.h is what the kernel runs too)
+namespace {
+int resample_plan_checked(uint32_t sr_in, uint32_t sr_out, th_resample_plan *p) {
+    const int rc = th::resample_plan(sr_in, sr_out, p);
+    TH_REQUIRE(rc != 1, "a sample rate of zero (%u -> %u Hz)", sr_in, sr_out);
+    if (rc != 0) return th::fail(TH_ERR_UNSUPPORTED, "%u -> %u Hz needs more than %u taps or %u coefficients", sr_in, sr_out,
+                                 TH_RESAMPLE_MAX_TAPS, TH_RESAMPLE_MAX_COEFS);
+    return TH_OK;
+}
+}  // namespace
+
+TH_API int th_resample_plan_for(uint32_t sr_in, uint32_t sr_out, th_resample_plan *out) {
+    TH_TRY
+    TH_REQUIRE(out, "NULL argument");
+    return resample_plan_checked(sr_in, sr_out, out);
+    TH_CATCH
+}
+
+TH_API int th_resample_n_out(size_t n_in, uint32_t sr_in, uint32_t sr_out, size_t *n_out) {
+    TH_TRY
+    TH_REQUIRE(n_out, "NULL argument");
+    th_resample_plan p;
+    TH_CHECK(resample_plan_checked(sr_in, sr_out, &p));
+    if (!resample_n_out(n_in, p, n_out)) return fail(TH_ERR_UNSUPPORTED, "%zu samples at %u -> %u Hz: indices beyond 64 bits", n_in, sr_in, sr_out);
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_resample_coefs(uint32_t sr_in, uint32_t sr_out, uint32_t r, double *h64, float *c32) {
+    TH_TRY
+    th_resample_plan p;
+    TH_CHECK(resample_plan_checked(sr_in, sr_out, &p));
+    TH_REQUIRE(r < p.L, "phase %u of %u", r, p.L);
+    resample_row(p, r, h64, c32);
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_resample_f32(const float *x, size_t n_in, uint32_t sr_in, uint32_t sr_out, uint64_t j0, size_t n, float *y) {
+    TH_TRY
+    TH_REQUIRE(n == 0 || y, "NULL argument");
+    TH_REQUIRE(n_in == 0 || x, "NULL argument");
+    th_resample_plan p;
+    TH_CHECK(resample_plan_checked(sr_in, sr_out, &p));
+    size_t n_out = 0;
+    if (!resample_n_out(n_in, p, &n_out)) return fail(TH_ERR_UNSUPPORTED, "%zu samples at %u -> %u Hz: indices beyond 64 bits", n_in, sr_in, sr_out);
+    TH_REQUIRE(j0 <= n_out && n <= n_out - j0, "outputs [%llu, +%zu) of %zu", (unsigned long long)j0, n, n_out);
+    const uint32_t taps = 2 * p.half_taps;
+    const int64_t K = p.half_taps;
+    std::vector<float> win(taps);
+    std::vector<std::vector<float>> rows(p.L);  // (made when first met: outputs j and j + L share a row)
+    for (size_t i = 0; i < n; i++) {
+        uint64_t q;
+        uint32_t r;
+        resample_phase(j0 + i, p.L, p.M, &q, &r);
+        std::vector<float> &row = rows[r];
+        if (row.empty()) {
+            row.resize(taps);
+            resample_row(p, r, nullptr, row.data());
+        }
+        const int64_t first = (int64_t)q - K + 1;
+        for (int64_t k = 0; k < (int64_t)taps; k++) win[k] = first + k >= 0 && first + k < (int64_t)n_in ? x[first + k] : 0.0f;
+        ResampleAcc acc;
+        resample_taps(acc, row.data(), win.data(), taps);
+        y[i] = resample_fold(acc);
+    }
+    return TH_OK;
     TH_CATCH
 }
 

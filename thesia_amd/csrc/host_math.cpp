@@ -5,6 +5,7 @@
 #include "stft_plan.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -13,6 +14,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <thread>
 
 namespace th {
 
@@ -1030,6 +1032,70 @@ int wav_header(uint32_t bps, uint32_t sr, uint32_t n_ch, uint64_t n_frames, uint
     *header_len = (size_t)hl;
     *pad_len = (size_t)pad;
     return 0;
+}
+
+// ---- polyphase sinc resampler
+int resample_plan(uint32_t sr_in, uint32_t sr_out, th_resample_plan *out) {
+    if (sr_in == 0 || sr_out == 0) return 1;
+    uint32_t a = sr_in, b = sr_out;
+    while (b) {
+        const uint32_t t = a % b;
+        a = b;
+        b = t;
+    }
+    const uint32_t L = sr_out / a, M = sr_in / a;
+    const uint64_t Z = 128;
+    const uint64_t K = L >= M ? Z : (Z * M + L - 1) / L;
+    if (2 * K > TH_RESAMPLE_MAX_TAPS) return 2;
+    if ((uint64_t)L * 2 * K > TH_RESAMPLE_MAX_COEFS) return 2;
+    out->L = L;
+    out->M = M;
+    out->half_taps = (uint32_t)K;
+    out->rho = L >= M ? 1.0 : (double)L / (double)M;
+    out->cutoff = out->rho * 0.95;
+    return 0;
+}
+
+bool resample_n_out(size_t n_in, const th_resample_plan &p, size_t *n_out) {
+    const unsigned __int128 n = ((unsigned __int128)n_in * p.L + p.M - 1) / p.M;
+    if (n > (unsigned __int128)UINT64_MAX / p.M) return false;  // (every j M of the track, and n_out M, fit 64 bits)
+    *n_out = (size_t)n;
+    return true;
+}
+
+void resample_row(const th_resample_plan &p, uint32_t r, double *h64, float *c32) {
+    const double pi = 3.14159265358979323846, Z = 128.0;
+    const int64_t K = p.half_taps;
+    const double frac = (double)r / (double)p.L;
+    for (int64_t k = 0; k < 2 * K; k++) {
+        const double t = (double)(k - K + 1) - frac;
+        const double x = p.cutoff * t;
+        const double sinc = x == 0.0 ? 1.0 : std::sin(pi * x) / (pi * x);
+        const double u = p.rho * t / Z;
+        double h = 0.0;
+        if (std::fabs(u) < 1.0) {
+            const double bh = 0.35875 + 0.48829 * std::cos(pi * u) + 0.14128 * std::cos(2.0 * pi * u) + 0.01168 * std::cos(3.0 * pi * u);
+            h = p.cutoff * sinc * (bh * bh);
+        }
+        if (h64) h64[k] = h;
+        if (c32) c32[k] = (float)h;
+    }
+}
+
+void resample_table(const th_resample_plan &p, float *table) {
+    const size_t taps = 2 * (size_t)p.half_taps;
+    const size_t n_thr = std::min<size_t>(std::max<size_t>(1, (size_t)p.L * taps / 65536), std::max(1u, std::min(16u, std::thread::hardware_concurrency())));
+    std::atomic<uint32_t> next{0};
+    auto work = [&]() {
+        for (uint32_t r = next.fetch_add(1); r < p.L; r = next.fetch_add(1)) resample_row(p, r, nullptr, table + (size_t)r * taps);
+    };
+    std::vector<std::thread> thr;
+    try {
+        for (size_t i = 1; i < n_thr; i++) thr.emplace_back(work);
+    } catch (...) {  // (no more threads: the ones that started and this one do all of it)
+    }
+    work();
+    for (auto &t : thr) t.join();
 }
 
 }  // namespace th

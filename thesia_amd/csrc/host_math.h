@@ -6,6 +6,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "../../include/thesia_amd.h"  // th_resample_plan
+
 namespace th {
 
 void calc_framing_params(double win_ms, uint32_t t_overlap, uint32_t f_overlap, uint32_t sr, size_t *hop,
@@ -122,6 +124,15 @@ bool spectrum_frame_range(uint32_t sr, size_t hop, size_t n_frames, double start
 // 2^32 - 1, more than 65535 channels, a block above 65535 bytes, a byte rate above 2^32 - 1)
 int wav_header(uint32_t bytes_per_sample, uint32_t sr, uint32_t n_ch, uint64_t n_frames, uint8_t out[64], size_t *header_len,
                size_t *pad_len);
+
+// ---- polyphase sinc resampler (th_resample_plan_for; include/thesia_amd.h "Export at a target sample rate").  resample_plan: 0, 1 for a
+// zero rate, 2 for a pair beyond TH_RESAMPLE_MAX_TAPS / TH_RESAMPLE_MAX_COEFS.  resample_n_out: ceil(n_in L / M), false when
+// n_out M does not fit 64 bits (then no j M of the track overflows).  resample_row: row r of the table, 2K taps, in f64
+// and / or rounded to f32.  resample_table: rows [0, L) as L x 2K floats, built on up to 16 threads
+int resample_plan(uint32_t sr_in, uint32_t sr_out, th_resample_plan *out);
+bool resample_n_out(size_t n_in, const th_resample_plan &p, size_t *n_out);
+void resample_row(const th_resample_plan &p, uint32_t r, double *h64, float *c32);
+void resample_table(const th_resample_plan &p, float *table);
 
 inline bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
 inline unsigned ilog2(size_t n) {

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 
@@ -399,5 +400,68 @@ inline uint32_t export_n_chunks(uint64_t f0, uint64_t f1, uint32_t n_ch) {
 }
 // n_chunks: the sum over the jobs (the first_chunk a job behind the last would have)
 hipError_t launch_export(const ExportJob *d_jobs, uint32_t n_jobs, uint32_t n_chunks, hipStream_t s);
+
+// ---- kernels_resample.hip: polyphase sinc resampler, planar f32 channels at the track's rate to planar f32 at the output rate
+// (include/thesia_amd.h "Export at a target sample rate"; the summation is resample_core.h).  Outputs j and j + L share a coefficient
+// row and their windows lie M samples apart, so a workgroup takes ONE channel, R consecutive outputs (R <= 64 rows, one per lane) and
+// P = G Pt "periods" of them, Lp outputs apart (Lp a multiple of L): wave g of G takes periods g Pt .. g Pt + Pt - 1, a thread keeps
+// four coefficients in registers across its Pt periods.
+constexpr uint32_t RESAMPLE_LANES = 64;     // rows of a tile, at most
+constexpr uint32_t RESAMPLE_TAP_BLOCK = 64; // taps staged per step (a multiple of 4)
+constexpr uint32_t RESAMPLE_XS_MAX = 5248;  // input samples staged per step, at most (two copies of them, the second shifted by one)
+constexpr uint32_t RESAMPLE_MAX_PT = 8;
+struct ResampleTiling {
+    uint32_t L, M, taps;  // taps = 2K
+    uint32_t Lp;          // outputs between two periods: L (L >= 64) or the largest multiple of L that is at most 64
+    uint32_t R, S;        // a period of Lp outputs is cut into S sub-tiles of R outputs (the last one may be shorter); R <= 64
+    uint32_t G, Pt;       // waves of a workgroup, periods per thread: a tile is P = G Pt periods
+    uint32_t span;        // input samples a step stages: the largest offset of a window in the tile + RESAMPLE_TAP_BLOCK
+    uint64_t Mp;          // input samples between two periods: M Lp / L
+};
+inline ResampleTiling resample_tiling(const th_resample_plan &p) {
+    ResampleTiling t{};
+    t.L = p.L;
+    t.M = p.M;
+    t.taps = 2 * p.half_taps;
+    if (p.L < RESAMPLE_LANES) {  // (L = 1, 2, 6 ...: a row serves several lanes, no lane idles but the 64 mod L last ones)
+        t.Lp = p.L * (RESAMPLE_LANES / p.L);
+        t.R = t.Lp;
+        t.S = 1;
+    } else {
+        t.Lp = p.L;
+        t.S = (p.L + RESAMPLE_LANES - 1) / RESAMPLE_LANES;
+        t.R = (p.L + t.S - 1) / t.S;
+    }
+    t.Mp = (uint64_t)p.M * (t.Lp / p.L);
+    const uint64_t lanes = ((uint64_t)(t.R - 1) * p.M) / p.L + 1 + RESAMPLE_TAP_BLOCK;
+    static const uint32_t shapes[6][2] = {{4, 8}, {4, 4}, {4, 2}, {4, 1}, {1, 2}, {1, 1}};
+    for (const auto &sh : shapes) {
+        t.G = sh[0];
+        t.Pt = sh[1];
+        const uint64_t span = (uint64_t)(t.G * t.Pt - 1) * t.Mp + lanes;
+        t.span = (uint32_t)std::min<uint64_t>(span, UINT32_MAX);
+        if (span <= RESAMPLE_XS_MAX) break;
+    }
+    return t;  // ({1, 1} fits every plan: M / L <= 64 under TH_RESAMPLE_MAX_TAPS, so lanes <= 63 x 64 + 65)
+}
+struct ResampleJob {           // outputs [ja, jb) of every channel of one request
+    const float *const *chan;  // n_ch channel pointers (device memory), each of n_in samples
+    float *dst;                // output ja of channel 0; channel c's run starts ch_stride floats further per channel
+    uint64_t ja, jb;           // ja <= jb <= n_out
+    uint64_t n_in;
+    uint64_t ch_stride;
+    uint32_t n_ch;
+    uint32_t n_sb;             // tiles of P Lp outputs that [ja, jb) takes, counted from ja
+    uint32_t first_block;      // blocks [first_block, first_block of the next job) of the grid are this job's: n_ch x n_sb x S
+    uint32_t pad;
+};
+static_assert(sizeof(ResampleJob) == 64, "ResampleJob must have no implicit padding");
+inline uint64_t resample_n_sb(uint64_t ja, uint64_t jb, const ResampleTiling &t) {
+    const uint64_t per = (uint64_t)t.G * t.Pt * t.Lp;
+    return (jb - ja + per - 1) / per;
+}
+// table: L rows of `taps` floats (host_math.h resample_table); n_blocks: the sum over the jobs
+hipError_t launch_resample(const ResampleJob *d_jobs, uint32_t n_jobs, uint32_t n_blocks, const float *d_table, const ResampleTiling &t,
+                           hipStream_t s);
 
 }  // namespace th

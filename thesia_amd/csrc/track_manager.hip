@@ -31,6 +31,7 @@
 #include "export_core.h"
 #include "host_math.h"
 #include "kernels.h"
+#include "resample_core.h"
 #include "tile_cache.h"
 #include "track_manager_internal.h"
 
@@ -85,6 +86,11 @@ struct ReaderSlot {
     th::DeviceTable exp_tab, exp_cnt;
     hipStream_t exp_copy = nullptr;
     hipEvent_t exp_done[2] = {nullptr, nullptr}, exp_copied[2] = {nullptr, nullptr};
+    // th_tm_export_pcm_at: the planar f32 scratch of one piece (the resampler writes it, the export kernel reads it; at most
+    // RESAMPLE_SCRATCH_MAX bytes) and the coefficient table of the last rate pair served.  Empty until the slot first resamples
+    th::DeviceBuf<float> rs_scratch, rs_table;
+    size_t rs_scratch_cap = 0, rs_table_cap = 0;  // floats
+    uint32_t rs_sr_in = 0, rs_sr_out = 0;         // the pair rs_table holds (0: none)
 };
 constexpr size_t TILE_BYTES_MAX = 520 * 520 * 4;  // 512 core + 2 x 4 gutter (render_tiles.rs:15-16); >= 1024 * 12 waveform bins
 constexpr size_t MAX_READER_SLOTS = 16;
@@ -2575,15 +2581,35 @@ TH_API int th_tm_copy_audio(th_tm *tm, size_t id, uint32_t ch, int which, float 
 namespace {
 constexpr size_t EXPORT_STAGE_MAX = (size_t)TH_EXPORT_PIECE_BYTES + 64;
 
-int check_export_request(th_tm *tm, const th_export_request &r, size_t i, const Track **trp, size_t *s0, size_t *s1) {
+// the resampler of a request: on == false when the request keeps the track's rate
+struct RatePlan {
+    bool on = false;
+    th_resample_plan plan{};
+    size_t n_out = 0;
+};
+
+int check_export_request(th_tm *tm, const th_export_at_request &ar, size_t i, const Track **trp, RatePlan *rp, size_t *s0, size_t *s1) {
+    const th_export_request &r = ar.base;
     auto it = tm->tracks.find(r.id);
     if (it == tm->tracks.end()) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", r.id);
     const Track &tr = it->second;
     TH_REQUIRE(r.which <= 2, "request %zu: which must be 0 (audio), 1 (drawn) or 2 (original)", i);
     TH_REQUIRE(r.format <= TH_PCM_F32, "request %zu: unknown format %u", i, r.format);
     TH_REQUIRE(r.dither <= TH_DITHER_TPDF, "request %zu: unknown dither %u", i, r.dither);
-    const size_t n = tr.ch.empty() ? 0 : tr.ch[0].n;
-    TH_REQUIRE(spectrum_frame_range(tr.sr, 1, n, r.start_sec, r.end_sec, s0, s1), "request %zu: bad time range [%g, %g) s", i,
+    size_t n = tr.ch.empty() ? 0 : tr.ch[0].n;
+    uint32_t sr = tr.sr;
+    *rp = RatePlan{};
+    if (ar.sr_out != 0 && ar.sr_out != tr.sr) {
+        const int rc = resample_plan(tr.sr, ar.sr_out, &rp->plan);
+        TH_REQUIRE(rc != 1, "request %zu: Track %zu has no sample rate", i, r.id);
+        if (rc != 0 || !resample_n_out(n, rp->plan, &rp->n_out))
+            return fail(TH_ERR_UNSUPPORTED, "request %zu: %u -> %u Hz is beyond the resampler's limits (%u taps, %u coefficients, 64-bit indices)",
+                        i, tr.sr, ar.sr_out, TH_RESAMPLE_MAX_TAPS, TH_RESAMPLE_MAX_COEFS);
+        rp->on = true;
+        n = rp->n_out;
+        sr = ar.sr_out;
+    }
+    TH_REQUIRE(spectrum_frame_range(sr, 1, n, r.start_sec, r.end_sec, s0, s1), "request %zu: bad time range [%g, %g) s", i,
                r.start_sec, r.end_sec);
     if (tr.ch.empty() || tr.ch.size() > TH_EXPORT_MAX_CHANNELS)
         return fail(TH_ERR_UNSUPPORTED, "Track %zu: %zu channels (1 .. %d can be exported)", r.id, tr.ch.size(), TH_EXPORT_MAX_CHANNELS);
@@ -2612,6 +2638,42 @@ int ensure_export_stage(ReaderSlot &sl, int b, size_t bytes) {
     sl.exp_stage_cap[b] = want;
     return TH_OK;
 }
+
+// the planar scratch of a piece: frames x channels x 4 bytes, and per job up to 7 frames more (the hull on the grid of 4 frames and
+// the channel pitch), so 2 x TH_EXPORT_PIECE_BYTES (16-bit output) + 64 KiB bounds it; a piece is closed before it would need more
+constexpr size_t RESAMPLE_SCRATCH_MAX = 2 * (size_t)TH_EXPORT_PIECE_BYTES + (64u << 10);
+
+int ensure_resample_scratch(ReaderSlot &sl, size_t floats) {
+    if (floats <= sl.rs_scratch_cap) return TH_OK;
+    size_t want = 1 << 18;  // powers of two from 1 MiB, never above the bound
+    while (want < floats) want <<= 1;
+    want = std::min(want, RESAMPLE_SCRATCH_MAX / sizeof(float));
+    TH_HIP(hipStreamSynchronize(sl.stream));
+    sl.rs_scratch_cap = 0;
+    TH_HIP(sl.rs_scratch.alloc(want * sizeof(float)));
+    sl.rs_scratch_cap = want;
+    return TH_OK;
+}
+
+// the slot's coefficient table becomes that of (sr_in, sr_out): built on the host (host_math.h resample_table, the rows
+// th_resample_coefs returns) into *host, which must outlive the upload, and sent on the slot's stream
+int ensure_resample_table(ReaderSlot &sl, uint32_t sr_in, uint32_t sr_out, const th_resample_plan &plan, std::vector<float> *host) {
+    if (sl.rs_sr_in == sr_in && sl.rs_sr_out == sr_out) return TH_OK;
+    const size_t floats = (size_t)plan.L * 2 * plan.half_taps;
+    host->resize(floats);
+    resample_table(plan, host->data());
+    sl.rs_sr_in = sl.rs_sr_out = 0;
+    if (floats > sl.rs_table_cap) {
+        TH_HIP(hipStreamSynchronize(sl.stream));
+        sl.rs_table_cap = 0;
+        TH_HIP(sl.rs_table.alloc(floats * sizeof(float)));
+        sl.rs_table_cap = floats;
+    }
+    TH_HIP(hipMemcpyAsync(sl.rs_table.get(), host->data(), floats * sizeof(float), hipMemcpyHostToDevice, sl.stream));
+    sl.rs_sr_in = sr_in;
+    sl.rs_sr_out = sr_out;
+    return TH_OK;
+}
 }  // namespace
 
 namespace th {
@@ -2627,18 +2689,25 @@ int wav_header_checked(uint32_t format, uint32_t sr, uint32_t n_ch, uint64_t n_f
     return TH_OK;
 }
 
-int export_request_info(th_tm *tm, const th_export_request &r, size_t i, th_export_info *info) {
+int export_request_info(th_tm *tm, const th_export_at_request &r, size_t i, th_export_info *info) {
     const Track *tr = nullptr;
+    RatePlan rp;
     size_t s0 = 0, s1 = 0;
-    TH_CHECK(check_export_request(tm, r, i, &tr, &s0, &s1));
+    TH_CHECK(check_export_request(tm, r, i, &tr, &rp, &s0, &s1));
     *info = th_export_info{};
-    info->n_bytes = (uint64_t)(s1 - s0) * tr->ch.size() * export_bytes_per_sample(r.format);
+    info->n_bytes = (uint64_t)(s1 - s0) * tr->ch.size() * export_bytes_per_sample(r.base.format);
     info->sample_start = s0;
     info->sample_end = s1;
-    info->sr = tr->sr;
+    info->sr = rp.on ? r.sr_out : tr->sr;
     info->n_channels = (uint32_t)tr->ch.size();
     info->waveform_revision = tm->waveform_revision();
     return TH_OK;
+}
+
+std::vector<th_export_at_request> export_at_requests(const th_export_request *reqs, size_t n) {
+    std::vector<th_export_at_request> out(n);
+    for (size_t i = 0; i < n; i++) out[i] = th_export_at_request{reqs[i], 0u};
+    return out;
 }
 
 void export_layout(th_export_info *info, size_t n, uint32_t *pad, size_t *out_len) {
@@ -2653,7 +2722,7 @@ void export_layout(th_export_info *info, size_t n, uint32_t *pad, size_t *out_le
     *out_len = (size_t)at;
 }
 
-int export_run(th_tm *tm, const th_export_request *reqs, size_t n, th_export_info *info, const uint32_t *pad, uint8_t *out) {
+int export_run(th_tm *tm, const th_export_at_request *reqs, size_t n, th_export_info *info, const uint32_t *pad, uint8_t *out) {
     struct Run {
         size_t stage_at;
         uint64_t out_at;
@@ -2664,12 +2733,21 @@ int export_run(th_tm *tm, const th_export_request *reqs, size_t n, th_export_inf
         uint32_t n_chunks = 0;
         size_t stage_bytes = 0;
         std::vector<Run> runs;
+        // the resampler's launch in front of the export's: every resampled request of a piece has the piece's rate pair
+        size_t rjob0 = 0, rjob1 = 0;
+        uint32_t n_rblocks = 0, sr_in = 0, sr_out = 0;
+        size_t scratch_floats = 0;
+        th_resample_plan plan{};
     };
     struct Part {
         size_t req, stage_at;
+        size_t scratch_at, ptr_at;  // resampled jobs: the job's runs in the scratch, its (biased) channel pointers
+        uint64_t hull0, stride;
+        bool resampled;
     };
     TH_REQUIRE(n <= UINT32_MAX, "too many requests");
     std::vector<ExportJob> jobs;
+    std::vector<ResampleJob> rjobs;
     std::vector<Part> parts;  // job j's request and place in its piece's staging buffer
     std::vector<Piece> pieces;
     std::vector<size_t> ptr0(n);  // request i's first channel pointer
@@ -2678,20 +2756,33 @@ int export_run(th_tm *tm, const th_export_request *reqs, size_t n, th_export_inf
     uint64_t cur_out_end = 0;
     auto close_piece = [&]() {
         cur.job1 = jobs.size();
+        cur.rjob1 = rjobs.size();
         pieces.push_back(std::move(cur));
         cur = Piece{};
         cur.job0 = jobs.size();
+        cur.rjob0 = rjobs.size();
     };
     for (size_t i = 0; i < n; i++) {
-        const th_export_request &r = reqs[i];
+        const th_export_request &r = reqs[i].base;
         const Track &tr = tm->tracks.find(r.id)->second;  // (checked by the caller, under the same lock)
         const uint32_t n_ch = (uint32_t)tr.ch.size();
         const uint64_t fbytes = (uint64_t)n_ch * export_bytes_per_sample(r.format);
+        RatePlan rp;
+        if (info[i].sr != tr.sr) {  // (export_request_info has accepted the pair)
+            rp.on = resample_plan(tr.sr, info[i].sr, &rp.plan) == 0 && resample_n_out(tr.ch[0].n, rp.plan, &rp.n_out);
+            if (!rp.on) return fail(TH_ERR_INTERNAL, "request %zu: no resampler for %u -> %u Hz", i, tr.sr, info[i].sr);
+        }
+        const ResampleTiling tiling = rp.on ? resample_tiling(rp.plan) : ResampleTiling{};
+        const uint64_t F = export_chunk_frames(n_ch);
         ptr0[i] = ptrs.size();
         for (const Channel &c : tr.ch) ptrs.push_back(r.which == 0 ? c.d_wav : r.which == 1 ? c.d_draw : c.d_orig);
         uint64_t f = info[i].sample_start;
         const uint64_t s0 = info[i].sample_start, s1 = info[i].sample_end;
         while (f < s1) {
+            if (rp.on && cur.sr_out != 0 && (cur.sr_in != tr.sr || cur.sr_out != info[i].sr)) {  // (one table per launch)
+                close_piece();
+                continue;
+            }
             const uint64_t out_at = info[i].offset + (f - s0) * fbytes;
             const bool contiguous = !cur.runs.empty() && out_at == cur_out_end;
             const size_t at = contiguous ? cur.stage_bytes : ((cur.stage_bytes + 15) & ~(size_t)15) + (size_t)(out_at & 15);
@@ -2700,13 +2791,35 @@ int export_run(th_tm *tm, const th_export_request *reqs, size_t n, th_export_inf
                 close_piece();
                 continue;
             }
-            const uint64_t take = std::min<uint64_t>(room, s1 - f);
+            uint64_t take = std::min<uint64_t>(room, s1 - f);
+            // a resampled request is cut on the export kernel's chunk grid, and its hull on the grid of 4 frames is what the
+            // resampler makes: the export kernel's 16-byte loads then stay aligned and inside what was written
+            uint64_t hull0 = 0, stride = 0;
+            if (rp.on) {
+                if (f + take < s1) {
+                    const uint64_t cut = (f + take) / F * F;
+                    if (cut <= f) {  // (an empty piece has room for a whole chunk: at most 16 KiB)
+                        close_piece();
+                        continue;
+                    }
+                    take = cut - f;
+                }
+                hull0 = f & ~(uint64_t)3;
+                const uint64_t hull1 = std::min<uint64_t>((f + take + 3) & ~(uint64_t)3, rp.n_out);
+                stride = (hull1 - hull0 + 3) & ~(uint64_t)3;
+                if ((cur.scratch_floats + stride * n_ch) * sizeof(float) > RESAMPLE_SCRATCH_MAX) {
+                    if (jobs.size() == cur.job0)
+                        return fail(TH_ERR_INTERNAL, "request %zu: a piece of %llu frames exceeds the resampler's scratch", i, (unsigned long long)take);
+                    close_piece();
+                    continue;
+                }
+            }
             const uint32_t pd = f + take == s1 ? pad[i] : 0u;
             const size_t bytes = (size_t)(take * fbytes) + pd;
             ExportJob j{};
             j.f0 = f;
             j.f1 = f + take;
-            j.n = tr.ch[0].n;
+            j.n = rp.on ? rp.n_out : tr.ch[0].n;
             j.n_ch = n_ch;
             j.format = r.format;
             j.dither = r.dither;
@@ -2715,9 +2828,33 @@ int export_run(th_tm *tm, const th_export_request *reqs, size_t n, th_export_inf
             j.pad = pd;
             const uint64_t chunks = (uint64_t)cur.n_chunks + export_n_chunks(j.f0, j.f1, n_ch);
             if (chunks > INT32_MAX) return fail(TH_ERR_UNSUPPORTED, "request %zu: too many chunks in one piece", i);
+            Part part{i, at, 0, 0, hull0, stride, rp.on};
+            if (rp.on) {
+                const uint64_t hull1 = std::min<uint64_t>(hull0 + stride, rp.n_out);
+                ResampleJob rj{};
+                rj.ja = hull0;
+                rj.jb = hull1;
+                rj.n_in = tr.ch[0].n;
+                rj.ch_stride = stride;
+                rj.n_ch = n_ch;
+                const uint64_t n_sb = resample_n_sb(rj.ja, rj.jb, tiling);
+                const uint64_t blocks = (uint64_t)cur.n_rblocks + n_sb * n_ch * tiling.S;
+                if (n_sb > UINT32_MAX || blocks > INT32_MAX) return fail(TH_ERR_UNSUPPORTED, "request %zu: too many resampler tiles in one piece", i);
+                rj.n_sb = (uint32_t)n_sb;
+                rj.first_block = cur.n_rblocks;
+                cur.n_rblocks = (uint32_t)blocks;
+                part.scratch_at = cur.scratch_floats;
+                part.ptr_at = ptrs.size();
+                ptrs.resize(ptrs.size() + n_ch, nullptr);  // (filled once the scratch has its address)
+                cur.scratch_floats += stride * n_ch;
+                cur.sr_in = tr.sr;
+                cur.sr_out = info[i].sr;
+                cur.plan = rp.plan;
+                rjobs.push_back(rj);
+            }
             cur.n_chunks = (uint32_t)chunks;
             jobs.push_back(j);
-            parts.push_back(Part{i, at});
+            parts.push_back(part);
             if (contiguous)
                 cur.runs.back().bytes += bytes;
             else
@@ -2743,32 +2880,57 @@ int export_run(th_tm *tm, const th_export_request *reqs, size_t n, th_export_inf
             TH_HIP(hipEventCreateWithFlags(&sl.exp_copied[b], hipEventDisableTiming));
         }
     }
+    std::vector<std::vector<float>> host_tables(pieces.size());  // (behind the drain: alive until the uploads are done)
     ExportDrain drain{&sl};
-    size_t need[2] = {0, 0};
-    for (size_t p = 0; p < pieces.size(); p++) need[p & 1] = std::max(need[p & 1], pieces[p].stage_bytes);
+    size_t need[2] = {0, 0}, need_scratch = 0;
+    for (size_t p = 0; p < pieces.size(); p++) {
+        need[p & 1] = std::max(need[p & 1], pieces[p].stage_bytes);
+        need_scratch = std::max(need_scratch, pieces[p].scratch_floats);
+    }
     for (int b = 0; b < 2; b++)
         if (need[b]) TH_CHECK(ensure_export_stage(sl, b, need[b]));
-    // one table for the whole call: the jobs of every piece, then the channel pointers
-    const size_t jobs_bytes = jobs.size() * sizeof(ExportJob), tab_bytes = jobs_bytes + ptrs.size() * sizeof(const float *);
+    if (need_scratch) TH_CHECK(ensure_resample_scratch(sl, need_scratch));
+    // one table for the whole call: the export jobs of every piece, the resampler's jobs, then the channel pointers
+    const size_t jobs_bytes = jobs.size() * sizeof(ExportJob), rjobs_bytes = rjobs.size() * sizeof(ResampleJob);
+    const size_t tab_bytes = jobs_bytes + rjobs_bytes + ptrs.size() * sizeof(const float *);
     TH_CHECK(sl.exp_tab.ensure(tab_bytes));
     TH_CHECK(sl.exp_cnt.ensure(n * 2 * sizeof(unsigned long long)));
     unsigned char *d_tab = static_cast<unsigned char *>(sl.exp_tab.dptr);
-    const float *const *d_ptrs = reinterpret_cast<const float *const *>(d_tab + jobs_bytes);
+    const float *const *d_ptrs = reinterpret_cast<const float *const *>(d_tab + jobs_bytes + rjobs_bytes);
     unsigned long long *d_cnt = static_cast<unsigned long long *>(sl.exp_cnt.dptr);
-    for (size_t p = 0; p < pieces.size(); p++)
+    for (size_t p = 0; p < pieces.size(); p++) {
+        size_t rj = pieces[p].rjob0;
         for (size_t j = pieces[p].job0; j < pieces[p].job1; j++) {
-            jobs[j].chan = d_ptrs + ptr0[parts[j].req];
-            jobs[j].dst = sl.exp_stage[p & 1].get() + parts[j].stage_at;
-            jobs[j].cnt = d_cnt + 2 * parts[j].req;
+            const Part &pt = parts[j];
+            jobs[j].chan = d_ptrs + ptr0[pt.req];
+            jobs[j].dst = sl.exp_stage[p & 1].get() + pt.stage_at;
+            jobs[j].cnt = d_cnt + 2 * pt.req;
+            if (!pt.resampled) continue;
+            // the export kernel indexes a channel by the absolute output frame: bias the run's address by the hull's first frame
+            // (the run and the hull start on 16-byte boundaries, so the biased pointer is 16-byte aligned as well)
+            float *run = sl.rs_scratch.get() + pt.scratch_at;
+            for (uint32_t c = 0; c < jobs[j].n_ch; c++)
+                ptrs[pt.ptr_at + c] = reinterpret_cast<const float *>(reinterpret_cast<uintptr_t>(run + (size_t)c * pt.stride) - (uintptr_t)pt.hull0 * sizeof(float));
+            jobs[j].chan = d_ptrs + pt.ptr_at;
+            rjobs[rj].chan = d_ptrs + ptr0[pt.req];
+            rjobs[rj].dst = run;
+            rj++;
         }
+    }
     std::vector<unsigned char> tab(tab_bytes);
     std::memcpy(tab.data(), jobs.data(), jobs_bytes);
-    std::memcpy(tab.data() + jobs_bytes, ptrs.data(), tab_bytes - jobs_bytes);
+    if (rjobs_bytes) std::memcpy(tab.data() + jobs_bytes, rjobs.data(), rjobs_bytes);
+    std::memcpy(tab.data() + jobs_bytes + rjobs_bytes, ptrs.data(), tab_bytes - jobs_bytes - rjobs_bytes);
     TH_CHECK(sl.exp_tab.upload(sl.stream, tab.data(), tab_bytes));
     TH_HIP(hipMemsetAsync(d_cnt, 0, n * 2 * sizeof(unsigned long long), sl.stream));
     const ExportJob *d_jobs = reinterpret_cast<const ExportJob *>(d_tab);
+    const ResampleJob *d_rjobs = reinterpret_cast<const ResampleJob *>(d_tab + jobs_bytes);
     auto launch_piece = [&](size_t p) -> int {
         const Piece &pc = pieces[p];
+        if (pc.n_rblocks) {  // (the stream's order keeps the scratch and the table from the last piece's readers)
+            TH_CHECK(ensure_resample_table(sl, pc.sr_in, pc.sr_out, pc.plan, &host_tables[p]));
+            TH_HIP(launch_resample(d_rjobs + pc.rjob0, (uint32_t)(pc.rjob1 - pc.rjob0), pc.n_rblocks, sl.rs_table.get(), resample_tiling(pc.plan), sl.stream));
+        }
         if (p >= 2) TH_HIP(hipStreamWaitEvent(sl.stream, sl.exp_copied[p & 1], 0));  // (the buffer's last piece has left it)
         TH_HIP(launch_export(d_jobs + pc.job0, (uint32_t)(pc.job1 - pc.job0), pc.n_chunks, sl.stream));
         TH_HIP(hipEventRecord(sl.exp_done[p & 1], sl.stream));
@@ -2795,9 +2957,8 @@ int export_run(th_tm *tm, const th_export_request *reqs, size_t n, th_export_inf
 }  // namespace tmi
 }  // namespace th
 
-TH_API int th_tm_export_pcm(th_tm *tm, const th_export_request *reqs, size_t n, uint8_t *out, size_t cap, th_export_info *info,
-                            size_t *out_len) {
-    TH_TRY
+namespace {
+int export_pcm_at(th_tm *tm, const th_export_at_request *reqs, size_t n, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
     TH_REQUIRE(tm && out_len && (n == 0 || (reqs && info)), "NULL argument");
     *out_len = 0;
     if (n == 0) return TH_OK;
@@ -2813,11 +2974,9 @@ TH_API int th_tm_export_pcm(th_tm *tm, const th_export_request *reqs, size_t n, 
     TH_CHECK(tmi::export_run(tm, reqs, n, infos.data(), pad.data(), out));
     std::memcpy(info, infos.data(), n * sizeof(th_export_info));
     return TH_OK;
-    TH_CATCH
 }
 
-TH_API int th_tm_export_wav(th_tm *tm, const th_export_request *req, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
-    TH_TRY
+int export_wav_at(th_tm *tm, const th_export_at_request *req, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
     TH_REQUIRE(tm && req && out_len, "NULL argument");
     *out_len = 0;
     std::shared_lock<std::shared_mutex> rl(tm->rw);
@@ -2825,7 +2984,7 @@ TH_API int th_tm_export_wav(th_tm *tm, const th_export_request *req, uint8_t *ou
     TH_CHECK(tmi::export_request_info(tm, *req, 0, &one));
     uint8_t hdr[TH_WAV_HEADER_MAX];
     size_t hl = 0, pl = 0;
-    TH_CHECK(tmi::wav_header_checked(req->format, one.sr, one.n_channels, one.sample_end - one.sample_start, hdr, &hl, &pl));
+    TH_CHECK(tmi::wav_header_checked(req->base.format, one.sr, one.n_channels, one.sample_end - one.sample_start, hdr, &hl, &pl));
     one.offset = hl;
     const size_t total = hl + (size_t)one.n_bytes + pl;
     if (info) *info = one;
@@ -2837,5 +2996,34 @@ TH_API int th_tm_export_wav(th_tm *tm, const th_export_request *req, uint8_t *ou
     if (pl) out[hl + one.n_bytes] = 0;
     if (info) *info = one;
     return TH_OK;
+}
+}  // namespace
+
+TH_API int th_tm_export_pcm(th_tm *tm, const th_export_request *reqs, size_t n, uint8_t *out, size_t cap, th_export_info *info,
+                            size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(n == 0 || reqs, "NULL argument");
+    return export_pcm_at(tm, tmi::export_at_requests(reqs, n).data(), n, out, cap, info, out_len);
+    TH_CATCH
+}
+
+TH_API int th_tm_export_wav(th_tm *tm, const th_export_request *req, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(req, "NULL argument");
+    const th_export_at_request at{*req, 0u};
+    return export_wav_at(tm, &at, out, cap, info, out_len);
+    TH_CATCH
+}
+
+TH_API int th_tm_export_pcm_at(th_tm *tm, const th_export_at_request *reqs, size_t n, uint8_t *out, size_t cap, th_export_info *info,
+                               size_t *out_len) {
+    TH_TRY
+    return export_pcm_at(tm, reqs, n, out, cap, info, out_len);
+    TH_CATCH
+}
+
+TH_API int th_tm_export_wav_at(th_tm *tm, const th_export_at_request *req, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
+    TH_TRY
+    return export_wav_at(tm, req, out, cap, info, out_len);
     TH_CATCH
 }

@@ -64,9 +64,13 @@ int loudness_meter_info(th_tm *tm, size_t id, th_loudness_meter *m);
 // (pad[i]: up to the next offset; 0 behind the last) and the bytes of the whole image.  export_run: the device work for requests
 // that were checked and laid out: request i's bytes, then pad[i] zero bytes, to out + info[i].offset (ascending in i; they need not
 // be adjacent), and its two counts into info[i].  Takes a reader slot; the caller holds the lock (shared)
-int export_request_info(th_tm *tm, const th_export_request &r, size_t i, th_export_info *info);
+// Every request carries its output rate (th_export_at_request; sr_out 0: the track's own, which is all th_tm_export_pcm asks for:
+// export_at_requests); info->sr is the rate the request comes out at, and a request whose info->sr is not the track's is resampled
+// by export_run (kernels_resample.hip into the slot's planar scratch, then the same export kernel)
+int export_request_info(th_tm *tm, const th_export_at_request &r, size_t i, th_export_info *info);
 void export_layout(th_export_info *info, size_t n, uint32_t *pad, size_t *out_len);
-int export_run(th_tm *tm, const th_export_request *reqs, size_t n, th_export_info *info, const uint32_t *pad, uint8_t *out);
+int export_run(th_tm *tm, const th_export_at_request *reqs, size_t n, th_export_info *info, const uint32_t *pad, uint8_t *out);
+std::vector<th_export_at_request> export_at_requests(const th_export_request *reqs, size_t n);
 // th_wav_header with the status reported (host_math.h wav_header)
 int wav_header_checked(uint32_t format, uint32_t sr, uint32_t n_ch, uint64_t n_frames, uint8_t out[TH_WAV_HEADER_MAX], size_t *header_len,
                        size_t *pad_len);

@@ -694,16 +694,16 @@ TH_API int th_tmg_get_loudness_meter(th_tmg *g, size_t id, th_loudness_meter *me
 // byte counts, so the offsets and the zero padding are known before any slot runs; the slots then run side by side, each writing
 // its own requests' bytes (and the padding behind them) straight into the caller's buffer.
 namespace {
-int export_on_slots(th_tmg *g, const th_export_request *reqs, size_t n, std::vector<th_export_info> &infos, const std::vector<uint32_t> &pad,
+int export_on_slots(th_tmg *g, const th_export_at_request *reqs, size_t n, std::vector<th_export_info> &infos, const std::vector<uint32_t> &pad,
                     uint8_t *out) {
     std::vector<std::vector<size_t>> mine(g->slots.size());
-    for (size_t i = 0; i < n; i++) mine[find_track(g, reqs[i].id)->slot].push_back(i);
+    for (size_t i = 0; i < n; i++) mine[find_track(g, reqs[i].base.id)->slot].push_back(i);
     std::vector<uint32_t> busy;
     for (uint32_t s = 0; s < g->slots.size(); s++)
         if (!mine[s].empty()) busy.push_back(s);
     return for_slots(g, busy, [&](uint32_t s) -> int {
         const std::vector<size_t> &idx = mine[s];
-        std::vector<th_export_request> sub(idx.size());
+        std::vector<th_export_at_request> sub(idx.size());
         std::vector<th_export_info> si(idx.size());
         std::vector<uint32_t> sp(idx.size());
         for (size_t j = 0; j < idx.size(); j++) {
@@ -723,10 +723,10 @@ int export_on_slots(th_tmg *g, const th_export_request *reqs, size_t n, std::vec
     });
 }
 
-int export_check_all(th_tmg *g, const th_export_request *reqs, size_t n, std::vector<th_export_info> &infos) {
+int export_check_all(th_tmg *g, const th_export_at_request *reqs, size_t n, std::vector<th_export_info> &infos) {
     for (size_t i = 0; i < n; i++) {
-        const th_tmg::Placement *p = find_track(g, reqs[i].id);
-        if (!p) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", reqs[i].id);
+        const th_tmg::Placement *p = find_track(g, reqs[i].base.id);
+        if (!p) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", reqs[i].base.id);
         th_tm *tm = g->slots[p->slot].tm;
         std::shared_lock<std::shared_mutex> sl(tmi::rw_of(tm));
         TH_CHECK(tmi::export_request_info(tm, reqs[i], i, &infos[i]));
@@ -741,9 +741,8 @@ int export_check_all(th_tmg *g, const th_export_request *reqs, size_t n, std::ve
 }
 }  // namespace
 
-TH_API int th_tmg_export_pcm(th_tmg *g, const th_export_request *reqs, size_t n, uint8_t *out, size_t cap, th_export_info *info,
-                             size_t *out_len) {
-    TH_TRY
+namespace {
+int tmg_export_pcm_at(th_tmg *g, const th_export_at_request *reqs, size_t n, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
     TH_REQUIRE(g && out_len && (n == 0 || (reqs && info)), "NULL argument");
     *out_len = 0;
     if (n == 0) return TH_OK;
@@ -759,11 +758,9 @@ TH_API int th_tmg_export_pcm(th_tmg *g, const th_export_request *reqs, size_t n,
     TH_CHECK(export_on_slots(g, reqs, n, infos, pad, out));
     std::memcpy(info, infos.data(), n * sizeof(th_export_info));
     return TH_OK;
-    TH_CATCH
 }
 
-TH_API int th_tmg_export_wav(th_tmg *g, const th_export_request *req, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
-    TH_TRY
+int tmg_export_wav_at(th_tmg *g, const th_export_at_request *req, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
     TH_REQUIRE(g && req && out_len, "NULL argument");
     *out_len = 0;
     std::shared_lock<std::shared_mutex> rl(g->rw);
@@ -771,7 +768,7 @@ TH_API int th_tmg_export_wav(th_tmg *g, const th_export_request *req, uint8_t *o
     TH_CHECK(export_check_all(g, req, 1, one));
     uint8_t hdr[TH_WAV_HEADER_MAX];
     size_t hl = 0, pl = 0;
-    TH_CHECK(tmi::wav_header_checked(req->format, one[0].sr, one[0].n_channels, one[0].sample_end - one[0].sample_start, hdr, &hl, &pl));
+    TH_CHECK(tmi::wav_header_checked(req->base.format, one[0].sr, one[0].n_channels, one[0].sample_end - one[0].sample_start, hdr, &hl, &pl));
     one[0].offset = hl;
     const size_t total = hl + (size_t)one[0].n_bytes + pl;
     if (info) *info = one[0];
@@ -782,6 +779,35 @@ TH_API int th_tmg_export_wav(th_tmg *g, const th_export_request *req, uint8_t *o
     if (pl) out[hl + one[0].n_bytes] = 0;
     if (info) *info = one[0];
     return TH_OK;
+}
+}  // namespace
+
+TH_API int th_tmg_export_pcm(th_tmg *g, const th_export_request *reqs, size_t n, uint8_t *out, size_t cap, th_export_info *info,
+                             size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(n == 0 || reqs, "NULL argument");
+    return tmg_export_pcm_at(g, tmi::export_at_requests(reqs, n).data(), n, out, cap, info, out_len);
+    TH_CATCH
+}
+
+TH_API int th_tmg_export_wav(th_tmg *g, const th_export_request *req, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(req, "NULL argument");
+    const th_export_at_request at{*req, 0u};
+    return tmg_export_wav_at(g, &at, out, cap, info, out_len);
+    TH_CATCH
+}
+
+TH_API int th_tmg_export_pcm_at(th_tmg *g, const th_export_at_request *reqs, size_t n, uint8_t *out, size_t cap, th_export_info *info,
+                                size_t *out_len) {
+    TH_TRY
+    return tmg_export_pcm_at(g, reqs, n, out, cap, info, out_len);
+    TH_CATCH
+}
+
+TH_API int th_tmg_export_wav_at(th_tmg *g, const th_export_at_request *req, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
+    TH_TRY
+    return tmg_export_wav_at(g, req, out, cap, info, out_len);
     TH_CATCH
 }
 
