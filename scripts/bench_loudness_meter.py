@@ -2,7 +2,8 @@
 the getter's wall time (median of --reps after warm-up), beside it th_audio_stats_dev and th_dev_copy of the same bytes.  The
 per-kernel times come from a run of this script under `rocprofv3 --kernel-trace --stats -- python scripts/bench_loudness_meter.py`
 (true_peak_kernel against loudness_zero_state_kernel, pass A, on the same audio in the same run).
-Usage: python scripts/bench_loudness_meter.py [--tracks 128] [--seconds 30] [--reps 20]"""
+--devices 0,0 runs the getter's loop through a MultiTrackManager over those slots (th_tmg_get_loudness_meters: the batch split by owner).
+Usage: python scripts/bench_loudness_meter.py [--tracks 128] [--seconds 30] [--reps 20] [--devices 0,0]"""
 import argparse
 import json
 import os
@@ -21,6 +22,7 @@ def main():
     ap.add_argument("--seconds", type=float, default=30.0)
     ap.add_argument("--sr", type=int, default=48000)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--devices", type=lambda s: [int(d) for d in s.split(",")], default=None)
     a = ap.parse_args()
     n = int(a.seconds * a.sr)
     rng = np.random.default_rng(0)
@@ -28,7 +30,7 @@ def main():
     nbytes = n * 4 * a.tracks
     ids = list(range(a.tracks))
     with ta.Context(0) as ctx:
-        tm = ta.TrackManager(ctx)
+        tm = ta.MultiTrackManager(a.devices) if a.devices else ta.TrackManager(ctx)
         tm.set_setting(40.0, 2, 1, ta.LINEAR)  # (the specs are not what is measured: a cheap framing)
         tm.add_tracks([(i, a.sr, x) for i in ids])
         for _ in range(3):
@@ -65,7 +67,7 @@ def main():
             b.free()
         tm.close()
     med = lambda v: round(float(np.median(v)), 4)  # noqa: E731
-    print(json.dumps({"tracks": a.tracks, "samples": n * a.tracks, "bytes": nbytes, "meters_ms_median": med(ts), "meters_ms_min": round(min(ts), 4),
+    print(json.dumps({"devices": a.devices, "tracks": a.tracks, "samples": n * a.tracks, "bytes": nbytes, "meters_ms_median": med(ts), "meters_ms_min": round(min(ts), 4),
                       "meters_with_series_ms_median": med(ts_series), "series_doubles": int(sum(d["n_momentary"] + d["n_short_term"] for d in m)),
                       "true_peak_dB": float(m[0]["true_peak_dB"]), "loudness_range": m[0]["loudness_range"],
                       "audio_stats_ms_median": med(ss), "copy_ms": med(cs), "copy_TBps": round(2 * nbytes / float(np.median(cs)) / 1e9, 3),

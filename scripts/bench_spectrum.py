@@ -2,7 +2,8 @@
 linear: T = 2813, H = 1025, row pitch 1056) against th_dev_copy of the bytes the kernel reads (tracks x T x pitch x 4), the two
 alternating in one process.  Host clock: both calls end in a synchronise.  The kernels' own times come from a separate run under
 rocprofv3 --kernel-trace --stats (spectrum_partial_kernel + spectrum_finish_kernel against copy_f4_kernel).
-Usage: python scripts/bench_spectrum.py [--tracks 128] [--seconds 30] [--reps 20] [--kind 0]"""
+--devices 0,0 runs the same loop through a MultiTrackManager over those slots (th_tmg_get_spectra: the batch split by owner).
+Usage: python scripts/bench_spectrum.py [--tracks 128] [--seconds 30] [--reps 20] [--kind 0] [--devices 0,0]"""
 import argparse
 import json
 import os
@@ -33,12 +34,13 @@ def main():
     ap.add_argument("--sr", type=int, default=48000)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--kind", type=int, default=ta.SPECTRUM_MEAN_AMP)
+    ap.add_argument("--devices", type=lambda s: [int(d) for d in s.split(",")], default=None)
     a = ap.parse_args()
     n = int(a.seconds * a.sr)
     rng = np.random.default_rng(0)
     x = rng.uniform(-0.5, 0.5, n).astype(np.float32)
     with ta.Context(0) as ctx:
-        tm = ta.TrackManager(ctx)
+        tm = ta.MultiTrackManager(a.devices) if a.devices else ta.TrackManager(ctx)
         tm.set_setting(2048 / 48, 4, 1, ta.LINEAR)
         tm.add_tracks([(i, a.sr, x) for i in range(a.tracks)])
         T, H = tm.spec(0, 0).shape
@@ -64,7 +66,7 @@ def main():
         dst.free()
         tm.close()
     ms, cms = float(np.median(ts)), float(np.median(cs))
-    print(json.dumps({"tracks": a.tracks, "n_frames": T, "height": H, "kind": a.kind, "bytes_read": nbytes,
+    print(json.dumps({"devices": a.devices, "tracks": a.tracks, "n_frames": T, "height": H, "kind": a.kind, "bytes_read": nbytes,
                       "get_spectra_ms_median": round(ms, 4), "get_spectra_ms_min": round(min(ts), 4),
                       "read_TBps": round(nbytes / ms / 1e9, 3), "copy_ms_median": round(cms, 4), "copy_ms_min": round(min(cs), 4),
                       "copy_TBps_read_plus_write": round(2 * nbytes / cms / 1e9, 3),

@@ -362,6 +362,7 @@ def test_independence_and_refusals(ctx, ragged):
             mg.add_tracks([(i, sr, x) for i, (sr, x) in sorted(RAGGED.items())])
             rc, mbg, sg, tg = _raw(mg, ids)
             assert rc == 0 and tg == total and sg[:total].tobytes() == series[:total].tobytes(), devices
+            assert np.all(sg[total:] == -777.0)
             a = (_ffi.LoudnessMeter * len(ids)).from_buffer_copy(mbg)
             b = (_ffi.LoudnessMeter * len(ids)).from_buffer_copy(mbytes)
             wrev = mg.revisions()[0]
@@ -371,3 +372,19 @@ def test_independence_and_refusals(ctx, ragged):
             assert bytes(a) == bytes(b), devices
             rc, _, s5, _ = _raw(mg, [ids[0], 999])
             assert rc == _ffi.ERR_NOT_FOUND and np.all(s5 == -777.0)
+            if len(devices) == 1:
+                continue
+            # both slots own tracks and take turns in the id list: each writes its tracks' values between the other's.  The list
+            # reversed: every track's meter and values again, at other places
+            owners = [mg.device_of(i) for i in ids]
+            assert set(owners) == {0, 1} and any(p != q for p, q in zip(owners, owners[1:]))
+            rc, mbr, sr_, tr_ = _raw(mg, ids[::-1])
+            assert rc == 0 and tr_ == total and np.all(sr_[total:] == -777.0)
+            r = (_ffi.LoudnessMeter * len(ids)).from_buffer_copy(mbr)[::-1]
+            a = (_ffi.LoudnessMeter * len(ids)).from_buffer_copy(mbg)
+            for x, y in zip(a, r):
+                k = x.n_momentary + x.n_short_term
+                assert y.short_term_offset == y.momentary_offset + y.n_momentary
+                assert sr_[y.momentary_offset: y.momentary_offset + k].tobytes() == sg[x.momentary_offset: x.momentary_offset + k].tobytes()
+                y.momentary_offset, y.short_term_offset = x.momentary_offset, x.short_term_offset
+                assert bytes(y) == bytes(x)

@@ -67,8 +67,9 @@ def place(resident, batch, n_slots):
     return out
 
 
-def raw_batch(mgr, reqs):
-    """th_*_get_spectrogram_tiles into a ZEROED pageable buffer: the whole buffer (padding included) and the offsets."""
+def raw_batch(mgr, reqs, fill=0, extra=0):
+    """th_*_get_spectrogram_tiles into a pageable buffer of `extra` bytes more than needed, every byte `fill` before the call: the
+    whole buffer (padding included) and the offsets."""
     multi = isinstance(mgr, ta.MultiTrackManager)
     fn = _ffi.lib.th_tmg_get_spectrogram_tiles if multi else _ffi.lib.th_tm_get_spectrogram_tiles
     n = len(reqs)
@@ -76,8 +77,9 @@ def raw_batch(mgr, reqs):
     offs = (C.c_size_t * (n + 1))()
     need = C.c_size_t()
     assert fn(mgr.handle, arr, n, None, 0, offs, C.byref(need)) == _ffi.ERR_BUFFER_TOO_SMALL
-    buf = np.zeros(need.value, np.uint8)
+    buf = np.full(need.value + extra, fill, np.uint8)
     _ffi.check(fn(mgr.handle, arr, n, buf.ctypes.data_as(C.c_void_p), buf.size, offs, C.byref(need)))
+    assert need.value == buf.size - extra == offs[n]
     return buf.tobytes(), list(offs)
 
 
@@ -249,6 +251,29 @@ def test_failed_mutators_change_no_slot(ctx, cmap):
     finally:
         multi.close()
         one.close()
+
+
+def test_batched_tiles_of_two_slots_write_their_records_only():
+    """A pageable buffer, so every slot stages its own records; slot 0's requests first, so slot 1's first record lies behind all of
+    slot 0's in the caller's buffer but first in slot 1's staging.  Every record is the single-tile path's; the padding between
+    records and the bytes behind the last keep what they held.  No colormap is set: the batch makes each slot upload the default."""
+    with ta.MultiTrackManager([0, 0]) as multi:
+        multi.add_tracks([(i, sr, x) for i, (sr, x) in TRACKS.items()])
+        multi.apply_track_list_changes()
+        reqs = [(i, ch, lx, ly, tx, 0) for i, (_, x) in TRACKS.items() for ch in range(x.shape[0])
+                for lx, ly, tx in [(0, 0, 0), (0, 0, 1), (1, 1, 0), (3, 4, 0)]]
+        reqs.sort(key=lambda r: multi.device_of(r[0]))  # (stable)
+        owners = [multi.device_of(r[0]) for r in reqs]
+        assert set(owners) == {0, 1} and owners == sorted(owners)
+        buf, offs = raw_batch(multi, reqs, fill=0xA5, extra=64)
+        padding = 0
+        for k, r in enumerate(reqs):
+            rec = multi.get_spectrogram_tile(*r)
+            assert len(rec) >= 40 and offs[k] + len(rec) <= offs[k + 1] and offs[k] % 64 == 0
+            assert buf[offs[k]: offs[k] + len(rec)] == rec, r
+            assert set(buf[offs[k] + len(rec): offs[k + 1]]) <= {0xA5}, r
+            padding += offs[k + 1] - offs[k] - len(rec)
+        assert padding > 0 and set(buf[offs[-1]:]) == {0xA5}
 
 
 def test_tile_readers_against_a_writer(ctx, cmap):

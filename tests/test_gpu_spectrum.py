@@ -18,6 +18,7 @@ twice (under `lin`, T = 7501, H = 257: the body once, the tail once).  cut() res
 which path a case takes."""
 import ctypes as C
 import functools
+import itertools
 import math
 import threading
 
@@ -320,17 +321,18 @@ def every_request(name):
 
 
 def packed(mgr, reqs):
-    """th_*_get_spectra through the raw ABI into a sentinel-filled buffer -> (floats as bytes, infos as tuples)"""
+    """th_*_get_spectra through the raw ABI into a sentinel-filled buffer a few floats longer than the result, which stay as they
+    were -> (floats as bytes, infos as tuples)"""
     fn = getattr(_ffi.lib, mgr._PFX + "get_spectra")
     n = len(reqs)
     arr = (_ffi.SpectrumRequest * n)(*[_ffi.SpectrumRequest(*r) for r in reqs])
     info = (_ffi.SpectrumInfo * n)()
     need = C.c_size_t()
     assert fn(mgr.handle, arr, n, None, 0, info, C.byref(need)) == _ffi.ERR_BUFFER_TOO_SMALL
-    out = np.full(need.value, 12345.0, np.float32)
+    out = np.full(need.value + 5, 12345.0, np.float32)
     _ffi.check(fn(mgr.handle, arr, n, out.ctypes.data_as(_ffi.c_f32p), out.size, info, C.byref(need)))
-    assert need.value == out.size
-    return out, [tuple(getattr(o, k) for k, _ in o._fields_) for o in info]
+    assert need.value == out.size - 5 and (out[need.value:] == 12345.0).all()
+    return out[: need.value], [tuple(getattr(o, k) for k, _ in o._fields_) for o in info]
 
 
 @pytest.mark.parametrize("name", ["mel", "lin", "tall", "wide"])
@@ -356,14 +358,26 @@ def test_batch_equals_single_calls_bit_for_bit(managers, name):
         assert out.size * 4 > 520 * 520 * 4  # (this batch took the route for results above the readers' pinned staging)
 
 
-@pytest.mark.parametrize("name", ["lin", "tall"])
+def taking_turns(reqs, owner):
+    """the same requests, the two slots' by turns while both have some left: every slot's rows go to places that are not adjacent"""
+    mine = [[r for r in reqs if owner(r[0]) == s] for s in (0, 1)]
+    return [r for pair in itertools.zip_longest(*mine) for r in pair if r is not None]
+
+
+@pytest.mark.parametrize("name", ["lin", "tall", "wide"])
 def test_multi_manager_returns_the_same_bytes_and_infos(managers, name):
     reqs = every_request(name)
-    want, winfos = packed(managers(name), reqs)  # (made by the same calls as the two-slot manager below: the revisions agree too)
     with ta.MultiTrackManager([0, 0]) as mg:
         mg.set_setting(*SETTINGS[name])
         mg.add_tracks([(i, sr, x) for i, (sr, x) in sorted(TRACKS.items())])
         assert len({mg.device_of(i) for i in TRACKS}) == 2
+        if name == "wide":  # one slot's share alone is above the readers' pinned staging: copies out of its device result buffer
+            reqs = taking_turns(reqs, mg.device_of)
+            share = [sum(spec_of(managers, name, r[0], r[1]).shape[1] for r in reqs if mg.device_of(r[0]) == s) for s in (0, 1)]
+            assert max(share) * 4 > 520 * 520 * 4
+        owners = [mg.device_of(r[0]) for r in reqs]
+        assert any(a != b for a, b in zip(owners, owners[1:]))
+        want, winfos = packed(managers(name), reqs)  # (made by the same calls as the two-slot manager: the revisions agree too)
         got, ginfos = packed(mg, reqs)
         assert np.array_equal(got.view(np.uint32), want.view(np.uint32)) and ginfos == winfos
         assert ginfos[0][4] == mg.revisions()[1]

@@ -1217,68 +1217,52 @@ TH_API int th_host_free(th_ctx *c, void *ptr) {
 // N tiles, one raster launch (th_raster_tiles_dev on the context stream), one wait.  Level (0, 0) tiles are crops of the
 // u16 image, LOD > 0 tiles crops of their mip level; requests for levels the pyramid does not hold (or with the per-request
 // route selected) go through the single-tile path one by one.
-TH_API int th_tm_get_spectrogram_tiles(th_tm *tm, const th_tile_request *reqs, size_t n, uint8_t *out, size_t cap,
-                                       size_t *offsets, size_t *out_len) {
-    TH_TRY
-    TH_REQUIRE(tm && out_len && (n == 0 || (reqs && offsets)), "NULL argument");
-    *out_len = 0;
-    if (n == 0) {
-        if (offsets) offsets[0] = 0;
-        return TH_OK;
+namespace th {
+namespace tmi {
+int ensure_colormap(th_tm *tm) {
+    {
+        std::shared_lock<std::shared_mutex> rl(tm->rw);
+        if (tm->d_colormap) return TH_OK;
     }
-    std::shared_lock<std::shared_mutex> rl(tm->rw);
-    if (!tm->d_colormap) {  // no th_tm_set_colormap yet: upload the default map (as the single-tile path does)
-        rl.unlock();
-        {
-            std::unique_lock<std::shared_mutex> wl(tm->rw);
-            TH_HIP(hipSetDevice(tm->ctx->device));
-            if (!tm->d_colormap) {
-                int rc = upload_colormap(tm);
-                if (rc != TH_OK) return rc;
-            }
+    std::unique_lock<std::shared_mutex> wl(tm->rw);  // no th_tm_set_colormap yet: the default two-colour map
+    TH_HIP(hipSetDevice(tm->ctx->device));
+    return tm->d_colormap ? TH_OK : upload_colormap(tm);
+}
+
+int tile_request_info(th_tm *tm, const th_tile_request &r, TileInfo *info) {
+    Channel *c = find_channel(tm, r.id, r.ch);
+    if (!c || !c->d_img) return fail(TH_ERR_NOT_FOUND, "Spectrogram %zu_%u does not exist", r.id, r.ch);
+    TileInfo &it = *info;
+    it = TileInfo{spectrogram_tile_geometry(c->img_w, c->img_h, r.level_x, r.level_y, r.tile_x, r.tile_y), c->d_img,
+                  (uint32_t)c->img_w, (uint32_t)c->img_h, (uint32_t)c->img_pitch, false, 0};
+    if (r.level_x != 0 || r.level_y != 0) {
+        auto im = c->mips.find({r.level_x, r.level_y});
+        if (tm->lod_source != 0 || im == c->mips.end()) {
+            it.single = true;  // (src: the level-0 image the single-tile path resamples)
+        } else {
+            it.src = im->second.d;
+            it.src_w = im->second.w;
+            it.src_h = im->second.h;
+            it.src_pitch = im->second.pitch;
+            if (it.g.width && it.g.height && (it.g.lod_w != it.src_w || it.g.lod_h != it.src_h))
+                return fail(TH_ERR_INTERNAL, "mip level (%u, %u) has the wrong shape", r.level_x, r.level_y);
         }
-        rl.lock();
     }
-    const uint64_t revision = tm->spectrogram_revision();
-    struct Item {
-        TileGeom g;
-        const uint16_t *src;
-        uint32_t src_w, src_h, src_pitch;
-        bool single;  // served by th_tm_get_spectrogram_tile
-    };
-    std::vector<Item> items(n);
+    return TH_OK;
+}
+
+size_t tiles_layout(TileInfo *info, size_t n, size_t *offsets) {
     size_t total = 0;
     for (size_t i = 0; i < n; i++) {
-        const th_tile_request &r = reqs[i];
-        Channel *c = find_channel(tm, r.id, r.ch);
-        if (!c || !c->d_img) return fail(TH_ERR_NOT_FOUND, "Spectrogram %zu_%u does not exist", r.id, r.ch);
-        Item &it = items[i];
-        it.g = spectrogram_tile_geometry(c->img_w, c->img_h, r.level_x, r.level_y, r.tile_x, r.tile_y);
-        it.src = c->d_img;
-        it.src_w = (uint32_t)c->img_w;
-        it.src_h = (uint32_t)c->img_h;
-        it.src_pitch = (uint32_t)c->img_pitch;
-        it.single = false;
-        if (r.level_x != 0 || r.level_y != 0) {
-            auto im = c->mips.find({r.level_x, r.level_y});
-            if (tm->lod_source != 0 || im == c->mips.end()) {
-                it.single = true;
-            } else {
-                it.src = im->second.d;
-                it.src_w = im->second.w;
-                it.src_h = im->second.h;
-                it.src_pitch = im->second.pitch;
-                if (it.g.width && it.g.height && (it.g.lod_w != it.src_w || it.g.lod_h != it.src_h))
-                    return fail(TH_ERR_INTERNAL, "mip level (%u, %u) has the wrong shape", r.level_x, r.level_y);
-            }
-        }
-        offsets[i] = total;
-        total += (40 + it.g.width * it.g.height * 4 + 63) / 64 * 64;
+        offsets[i] = info[i].offset = total;
+        total += tile_record_bytes(info[i].g);
     }
-    offsets[n] = total;
-    *out_len = total;
-    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
+    return offsets[n] = total;
+}
+
+int tiles_run(th_tm *tm, const th_tile_request *reqs, size_t n, const TileInfo *info, uint8_t *out) {
     TH_HIP(hipSetDevice(tm->ctx->device));
+    const uint64_t revision = tm->spectrogram_revision();
     // where the kernel writes: the caller's buffer when the GPU can reach it, else the manager's pinned staging buffer
     uint8_t *dev_base = nullptr;
     {
@@ -1294,26 +1278,33 @@ TH_API int th_tm_get_spectrogram_tiles(th_tm *tm, const th_tile_request *reqs, s
     }
     std::unique_lock<std::mutex> bl(tm->batch_mu, std::defer_lock);
     const bool staged = dev_base == nullptr;
+    // request i's record under dev_base: at the caller's offset, or, staged, packed with this run's own records
+    std::vector<size_t> at(n);
+    size_t own = 0;
+    for (size_t i = 0; i < n; i++) {
+        at[i] = staged ? own : info[i].offset;
+        own += tile_record_bytes(info[i].g);
+    }
     if (staged) {
         bl.lock();
-        if (tm->batch_stage_cap < total) {
+        if (tm->batch_stage_cap < own) {
             if (tm->batch_stage) (void)hipHostFree(tm->batch_stage);
             tm->batch_stage = tm->batch_stage_dev = nullptr;
             tm->batch_stage_cap = 0;
-            TH_HIP(hipHostMalloc(&tm->batch_stage, total, hipHostMallocMapped));
+            TH_HIP(hipHostMalloc(&tm->batch_stage, own, hipHostMallocMapped));
             TH_HIP(hipHostGetDevicePointer(&tm->batch_stage_dev, tm->batch_stage, 0));
-            tm->batch_stage_cap = total;
+            tm->batch_stage_cap = own;
         }
         dev_base = static_cast<uint8_t *>(tm->batch_stage_dev);
     }
     std::vector<th_raster_desc> descs;
     descs.reserve(n);
     for (size_t i = 0; i < n; i++) {
-        const Item &it = items[i];
+        const TileInfo &it = info[i];
         if (it.single || !it.g.width || !it.g.height) continue;
         th_raster_desc d{};
         d.img = it.src;
-        d.rgba = dev_base + offsets[i] + 40;
+        d.rgba = dev_base + at[i] + 40;
         d.img_width = it.src_w;
         d.img_height = it.src_h;
         d.origin_x = (uint32_t)it.g.origin_x;
@@ -1333,22 +1324,20 @@ TH_API int th_tm_get_spectrogram_tiles(th_tm *tm, const th_tile_request *reqs, s
         // the staging buffer is held only until its pixels are copied out: the per-request fallbacks and the
         // headers below no longer keep other pageable-buffer callers waiting
         for (size_t i = 0; i < n; i++) {
-            const Item &it = items[i];
-            const size_t px = it.g.width * it.g.height * 4;
-            if (!it.single && px) std::memcpy(out + offsets[i] + 40, static_cast<uint8_t *>(tm->batch_stage) + offsets[i] + 40, px);
+            const size_t px = info[i].g.width * info[i].g.height * 4;
+            if (!info[i].single && px) std::memcpy(out + info[i].offset + 40, static_cast<uint8_t *>(tm->batch_stage) + at[i] + 40, px);
         }
         bl.unlock();
     }
     for (size_t i = 0; i < n; i++) {
         const th_tile_request &r = reqs[i];
-        const Item &it = items[i];
-        uint8_t *rec = out + offsets[i];
+        const TileInfo &it = info[i];
+        uint8_t *rec = out + it.offset;
         if (it.single) {
             size_t len = 0;
-            const Channel *c = find_channel(tm, r.id, r.ch);  // (checked in the first pass; the shared lock is still held)
-            int rc = th_encode_spectrogram_tile_dev(tm->ctx, c->d_img, c->img_h, c->img_w, c->img_pitch, tm->colormap_rgba.data(),
+            int rc = th_encode_spectrogram_tile_dev(tm->ctx, it.src, it.src_h, it.src_w, it.src_pitch, tm->colormap_rgba.data(),
                                                     tm->colormap_rgba.size(), revision, r.level_x, r.level_y, r.tile_x, r.tile_y,
-                                                    rec, offsets[i + 1] - offsets[i], &len);
+                                                    rec, tile_record_bytes(it.g), &len);
             if (rc != TH_OK) return rc;
             continue;
         }
@@ -1363,13 +1352,37 @@ TH_API int th_tm_get_spectrogram_tiles(th_tm *tm, const th_tile_request *reqs, s
         put_u32(rec + 36, (uint32_t)it.g.origin_y);
     }
     return TH_OK;
+}
+}  // namespace tmi
+}  // namespace th
+
+TH_API int th_tm_get_spectrogram_tiles(th_tm *tm, const th_tile_request *reqs, size_t n, uint8_t *out, size_t cap,
+                                       size_t *offsets, size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(tm && out_len && (n == 0 || (reqs && offsets)), "NULL argument");
+    *out_len = 0;
+    if (n == 0) {
+        if (offsets) offsets[0] = 0;
+        return TH_OK;
+    }
+    TH_CHECK(tmi::ensure_colormap(tm));
+    std::shared_lock<std::shared_mutex> rl(tm->rw);
+    std::vector<tmi::TileInfo> infos(n);
+    for (size_t i = 0; i < n; i++) TH_CHECK(tmi::tile_request_info(tm, reqs[i], &infos[i]));
+    const size_t total = tmi::tiles_layout(infos.data(), n, offsets);
+    *out_len = total;
+    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
+    return tmi::tiles_run(tm, reqs, n, infos.data(), out);
     TH_CATCH
 }
 
-// One request checked against the manager, in the order every caller reports: the id, the channel, the kind, the spec, the time
-// range, the shape.  i: the request's index (for the message).  The caller holds the lock.
-namespace {
-int check_spectrum_request(th_tm *tm, const Setting &st, const th_spectrum_request &r, size_t i, const Channel **ch, size_t *f0, size_t *f1) {
+// The spectrum of a time range of N (channel, range, kind) requests: a reader.  One job per request; the two launches of
+// kernels_spectrum.hip on the slot's stream; results of up to h_tile's size are written by the kernel into the slot's pinned
+// staging and copied out, larger ones go through the slot's device result buffer.
+namespace th {
+namespace tmi {
+// in the order every caller reports: the id, the channel, the kind, the spec, the time range, the shape
+int spectrum_request_info(th_tm *tm, const th_spectrum_request &r, size_t i, SpectrumInfo *info) {
     auto it = tm->tracks.find(r.id);
     if (it == tm->tracks.end()) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", r.id);
     const Track &tr = it->second;
@@ -1377,32 +1390,91 @@ int check_spectrum_request(th_tm *tm, const Setting &st, const th_spectrum_reque
     TH_REQUIRE(r.kind <= TH_SPECTRUM_MAX, "request %zu: unknown spectrum kind %u", i, r.kind);
     const Channel &c = tr.ch[r.ch];
     if (!c.has_spec) return fail(TH_ERR_NOT_FOUND, "Spectrogram %zu_%u does not exist", r.id, r.ch);
-    size_t hop, win, n_fft;
-    calc_framing_params(st.win_ms, st.t_overlap, st.f_overlap, tr.sr, &hop, &win, &n_fft);
-    TH_REQUIRE(spectrum_frame_range(tr.sr, hop, c.T, r.start_sec, r.end_sec, f0, f1), "request %zu: bad time range [%g, %g) s", i,
+    size_t hop, win, n_fft, f0 = 0, f1 = 0;
+    calc_framing_params(tm->win_ms, tm->t_overlap, tm->f_overlap, tr.sr, &hop, &win, &n_fft);
+    TH_REQUIRE(spectrum_frame_range(tr.sr, hop, c.T, r.start_sec, r.end_sec, &f0, &f1), "request %zu: bad time range [%g, %g) s", i,
                r.start_sec, r.end_sec);
     if (c.T > INT32_MAX || c.H > INT32_MAX || (c.spec_pitch & 3) != 0)
         return fail(TH_ERR_UNSUPPORTED, "Spectrogram %zu_%u: %zu x %zu rows of pitch %zu", r.id, r.ch, c.T, c.H, c.spec_pitch);
-    *ch = &c;
+    const SpectrumShape sh = spectrum_shape((uint32_t)c.H, (uint32_t)(f1 - f0));
+    if ((uint64_t)sh.n_ctiles * sh.n_slices > INT32_MAX) return fail(TH_ERR_UNSUPPORTED, "Spectrogram %zu_%u: too many blocks", r.id, r.ch);
+    *info = SpectrumInfo{{0, c.H, f0, f1, 0}, c.d_spec, c.spec_pitch};
     return TH_OK;
 }
-}  // namespace
 
-namespace th {
-namespace tmi {
-int spectrum_request_info(th_tm *tm, const th_spectrum_request &r, size_t i, th_spectrum_info *info) {
-    const Channel *c = nullptr;
-    size_t f0 = 0, f1 = 0;
-    TH_CHECK(check_spectrum_request(tm, setting_of(tm), r, i, &c, &f0, &f1));
-    *info = th_spectrum_info{0, c->H, f0, f1, tm->spectrogram_revision()};
+size_t spectra_layout(SpectrumInfo *info, size_t n) {
+    size_t total = 0;
+    for (size_t i = 0; i < n; i++) {
+        info[i].offset = total;
+        total += info[i].height;
+    }
+    return total;
+}
+
+int spectra_run(th_tm *tm, const th_spectrum_request *reqs, size_t n, const SpectrumInfo *info, float *out) {
+    TH_REQUIRE(n <= UINT32_MAX, "too many requests");
+    std::vector<SpectrumJob> jobs(n);
+    std::vector<size_t> part0(n), res0(n);  // job i in the slot's areas: its first partial, in doubles, and its first result, in floats
+    size_t total = 0, part_total = 0;
+    uint32_t max_blocks = 0, max_h = 0;
+    for (size_t i = 0; i < n; i++) {
+        const SpectrumShape sh = spectrum_shape((uint32_t)info[i].height, (uint32_t)(info[i].frame_end - info[i].frame_start));
+        SpectrumJob &j = jobs[i];
+        j.rows = info[i].rows;
+        j.pitch = info[i].pitch;
+        j.H = (uint32_t)info[i].height;
+        j.f0 = (uint32_t)info[i].frame_start;
+        j.f1 = (uint32_t)info[i].frame_end;
+        j.kind = reqs[i].kind;
+        j.log_ct = sh.log_ct;
+        j.n_ctiles = sh.n_ctiles;
+        j.n_slices = sh.n_slices;
+        j.slice_len = sh.slice_len;
+        part0[i] = part_total;
+        part_total += (size_t)sh.n_slices * ((size_t)sh.n_ctiles << (sh.log_ct + 2));
+        max_blocks = std::max(max_blocks, sh.n_ctiles * sh.n_slices);
+        max_h = std::max(max_h, j.H);
+        res0[i] = total;
+        total += info[i].height;
+    }
+    TH_HIP(hipSetDevice(tm->ctx->device));
+    SlotLease lease{tm, nullptr};
+    int rc = acquire_slot(tm, &lease.slot);
+    if (rc != TH_OK) return rc;
+    ReaderSlot &sl = *lease.slot;
+    const bool pinned = total * sizeof(float) <= TILE_BYTES_MAX;
+    TH_CHECK(sl.spec_part.ensure(std::max<size_t>(part_total, 1) * sizeof(double)));
+    if (!pinned) TH_CHECK(sl.spec_out.ensure(total * sizeof(float)));
+    float *res = pinned ? reinterpret_cast<float *>(sl.h_tile_dev) : static_cast<float *>(sl.spec_out.dptr);
+    for (size_t i = 0; i < n; i++) {
+        jobs[i].part = static_cast<double *>(sl.spec_part.dptr) + part0[i];
+        jobs[i].out = res + res0[i];
+    }
+    TH_CHECK(sl.spec_jobs.upload(sl.stream, jobs.data(), n * sizeof(SpectrumJob)));
+    TH_HIP(launch_spectrum(static_cast<const SpectrumJob *>(sl.spec_jobs.dptr), (uint32_t)n, max_blocks, max_h, sl.stream));
+    if (pinned) TH_HIP(hipStreamSynchronize(sl.stream));
+    // one copy per maximal run of adjacent destinations (a batch this manager owns whole: one copy); a failed enqueue still waits
+    // for the copies in front of it, which write the caller's memory
+    hipError_t e = hipSuccess;
+    for (size_t i = 0, k; i < n; i = k) {
+        k = i + 1;
+        while (k < n && info[k].offset == info[k - 1].offset + info[k - 1].height) k++;
+        const size_t bytes = (res0[k - 1] + info[k - 1].height - res0[i]) * sizeof(float);
+        if (pinned)
+            std::memcpy(out + info[i].offset, reinterpret_cast<const float *>(sl.h_tile) + res0[i], bytes);
+        else if (e == hipSuccess)
+            e = hipMemcpyAsync(out + info[i].offset, res + res0[i], bytes, hipMemcpyDeviceToHost, sl.stream);
+    }
+    if (!pinned) {
+        const hipError_t waited = hipStreamSynchronize(sl.stream);
+        TH_HIP(e);
+        TH_HIP(waited);
+    }
     return TH_OK;
 }
 }  // namespace tmi
 }  // namespace th
 
-// The spectrum of a time range of N (channel, range, kind) requests: a reader.  One job per request; the two launches of
-// kernels_spectrum.hip on the slot's stream; results of up to h_tile's size are written by the kernel into the slot's pinned
-// staging and copied out, larger ones go through the slot's device result buffer and one copy.
 TH_API int th_tm_get_spectra(th_tm *tm, const th_spectrum_request *reqs, size_t n, float *out, size_t cap, th_spectrum_info *info,
                              size_t *out_len) {
     TH_TRY
@@ -1411,67 +1483,17 @@ TH_API int th_tm_get_spectra(th_tm *tm, const th_spectrum_request *reqs, size_t 
     if (n == 0) return TH_OK;
     TH_REQUIRE(n <= UINT32_MAX, "too many requests");
     std::shared_lock<std::shared_mutex> rl(tm->rw);
+    std::vector<tmi::SpectrumInfo> infos(n);
+    for (size_t i = 0; i < n; i++) TH_CHECK(tmi::spectrum_request_info(tm, reqs[i], i, &infos[i]));
+    const size_t total = tmi::spectra_layout(infos.data(), n);
     const uint64_t revision = tm->spectrogram_revision();
-    const Setting st = setting_of(tm);
-    std::vector<SpectrumJob> jobs(n);
-    std::vector<th_spectrum_info> infos(n);
-    std::vector<size_t> part0(n);  // first partial of job i, in doubles
-    size_t total = 0, part_total = 0;
-    uint32_t max_blocks = 0, max_h = 0;
     for (size_t i = 0; i < n; i++) {
-        const th_spectrum_request &r = reqs[i];
-        const Channel *cp = nullptr;
-        size_t f0 = 0, f1 = 0;
-        TH_CHECK(check_spectrum_request(tm, st, r, i, &cp, &f0, &f1));
-        const Channel &c = *cp;
-        infos[i] = th_spectrum_info{total, c.H, f0, f1, revision};
-        const SpectrumShape sh = spectrum_shape((uint32_t)c.H, (uint32_t)(f1 - f0));
-        SpectrumJob &j = jobs[i];
-        j.rows = c.d_spec;
-        j.pitch = c.spec_pitch;
-        j.H = (uint32_t)c.H;
-        j.f0 = (uint32_t)f0;
-        j.f1 = (uint32_t)f1;
-        j.kind = r.kind;
-        j.log_ct = sh.log_ct;
-        j.n_ctiles = sh.n_ctiles;
-        j.n_slices = sh.n_slices;
-        j.slice_len = sh.slice_len;
-        part0[i] = part_total;
-        part_total += (size_t)sh.n_slices * ((size_t)sh.n_ctiles << (sh.log_ct + 2));
-        const uint64_t blocks = (uint64_t)sh.n_ctiles * sh.n_slices;
-        if (blocks > INT32_MAX) return fail(TH_ERR_UNSUPPORTED, "Spectrogram %zu_%u: too many blocks", r.id, r.ch);
-        max_blocks = std::max(max_blocks, (uint32_t)blocks);
-        max_h = std::max(max_h, j.H);
-        total += c.H;
+        infos[i].spectrogram_revision = revision;
+        info[i] = infos[i];
     }
-    std::memcpy(info, infos.data(), n * sizeof(th_spectrum_info));
     *out_len = total;
     if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu floats", total);
-    TH_HIP(hipSetDevice(tm->ctx->device));
-    SlotLease lease{tm, nullptr};
-    int rc = acquire_slot(tm, &lease.slot);
-    if (rc != TH_OK) return rc;
-    ReaderSlot &sl = *lease.slot;
-    const size_t out_bytes = total * sizeof(float);
-    const bool pinned = out_bytes <= TILE_BYTES_MAX;
-    TH_CHECK(sl.spec_part.ensure(std::max<size_t>(part_total, 1) * sizeof(double)));
-    if (!pinned) TH_CHECK(sl.spec_out.ensure(out_bytes));
-    float *res = pinned ? reinterpret_cast<float *>(sl.h_tile_dev) : static_cast<float *>(sl.spec_out.dptr);
-    for (size_t i = 0; i < n; i++) {
-        jobs[i].part = static_cast<double *>(sl.spec_part.dptr) + part0[i];
-        jobs[i].out = res + infos[i].offset;
-    }
-    TH_CHECK(sl.spec_jobs.upload(sl.stream, jobs.data(), n * sizeof(SpectrumJob)));
-    TH_HIP(launch_spectrum(static_cast<const SpectrumJob *>(sl.spec_jobs.dptr), (uint32_t)n, max_blocks, max_h, sl.stream));
-    if (pinned) {
-        TH_HIP(hipStreamSynchronize(sl.stream));
-        std::memcpy(out, sl.h_tile, out_bytes);
-    } else {
-        TH_HIP(hipMemcpyAsync(out, res, out_bytes, hipMemcpyDeviceToHost, sl.stream));
-        TH_HIP(hipStreamSynchronize(sl.stream));
-    }
-    return TH_OK;
+    return tmi::spectra_run(tm, reqs, n, infos.data(), out);
     TH_CATCH
 }
 
@@ -1581,16 +1603,37 @@ void meter_counts(const Track &tr, th_loudness_meter *m) {
         m->n_short_term = loudness_n_short_term(n, tr.sr);
     }
 }
+
+// the limits of one launch (its grid), and the channels of its tracks
+int meters_fit_one_launch(const tmi::MeterInfo *ms, size_t n, size_t *n_ch) {
+    TH_REQUIRE(n <= 65535, "at most 65535 tracks per call");
+    *n_ch = 0;
+    for (size_t i = 0; i < n; i++) *n_ch += ms[i].n_channels;
+    TH_REQUIRE(*n_ch <= 65535, "at most 65535 channels per call");
+    return TH_OK;
+}
 }  // namespace
 
 namespace th {
 namespace tmi {
-int loudness_meter_info(th_tm *tm, size_t id, th_loudness_meter *m) {
+int loudness_meter_info(th_tm *tm, size_t id, MeterInfo *m) {
     auto it = tm->tracks.find(id);
     if (it == tm->tracks.end()) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", id);
     meter_counts(it->second, m);
-    m->waveform_revision = tm->waveform_revision();
+    m->track = &it->second;
+    m->n_channels = it->second.ch.size();
     return TH_OK;
+}
+
+size_t meters_layout(MeterInfo *m, size_t n) {
+    size_t total = 0;
+    for (size_t i = 0; i < n; i++) {
+        m[i].momentary_offset = total;
+        total += m[i].n_momentary;
+        m[i].short_term_offset = total;
+        total += m[i].n_short_term;
+    }
+    return total;
 }
 }  // namespace tmi
 }  // namespace th
@@ -1599,35 +1642,17 @@ int loudness_meter_info(th_tm *tm, size_t id, th_loudness_meter *m) {
 // F > 1, one TruePeakJob; per track two LoudTrackJobs (pass D over 4 and over 30 segments, writing the energies where the series go).
 // Everything runs on the slot's stream; the results come back in one copy (through the slot's pinned staging when they fit) and the
 // host turns them into LUFS, maxima and the loudness range.
-TH_API int th_tm_get_loudness_meters(th_tm *tm, const size_t *ids, size_t n, th_loudness_meter *meters, double *series, size_t cap,
-                                     size_t *out_len) {
-    TH_TRY
-    TH_REQUIRE(tm && meters && out_len && (n == 0 || ids), "NULL argument");
-    *out_len = 0;
-    if (n == 0) return TH_OK;
-    TH_REQUIRE(n <= 65535, "at most 65535 tracks per call");
-    std::shared_lock<std::shared_mutex> rl(tm->rw);
-    const uint64_t revision = tm->waveform_revision();
-    std::vector<th_loudness_meter> ms(n);
-    std::vector<const Track *> trs(n);
+namespace th {
+namespace tmi {
+int meters_run(th_tm *tm, const size_t *ids, size_t n, MeterInfo *ms, double *series) {
     size_t total = 0, n_ch = 0;
+    TH_CHECK(meters_fit_one_launch(ms, n, &n_ch));
+    std::vector<const Track *> trs(n);
+    std::vector<size_t> e0(n);  // track i's first energy in the slot's result area: the momentary ones, then the short-term ones
     for (size_t i = 0; i < n; i++) {
-        auto it = tm->tracks.find(ids[i]);
-        if (it == tm->tracks.end()) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", ids[i]);
-        trs[i] = &it->second;
-        meter_counts(it->second, &ms[i]);
-        ms[i].waveform_revision = revision;
-        ms[i].momentary_offset = total;
-        total += ms[i].n_momentary;
-        ms[i].short_term_offset = total;
-        total += ms[i].n_short_term;
-        n_ch += it->second.ch.size();
-    }
-    TH_REQUIRE(n_ch <= 65535, "at most 65535 channels per call");
-    if (series && cap < total) {
-        std::memcpy(meters, ms.data(), n * sizeof(th_loudness_meter));
-        *out_len = total;
-        return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu doubles", total);
+        trs[i] = static_cast<const Track *>(ms[i].track);
+        e0[i] = total;
+        total += ms[i].n_momentary + ms[i].n_short_term;
     }
     // the job tables
     std::vector<const LoudnessRate *> rates;
@@ -1721,8 +1746,8 @@ TH_API int th_tm_get_loudness_meters(th_tm *tm, const size_t *ids, size_t n, th_
             si += j.n_fchunks;
         }
         tj_m[i].q = tj_s[i].q = d_q + q0;
-        tj_m[i].out = d_res + ms[i].momentary_offset;
-        tj_s[i].out = d_res + ms[i].short_term_offset;
+        tj_m[i].out = d_res + e0[i];
+        tj_s[i].out = d_res + e0[i] + ms[i].n_momentary;
     }
     for (int f = 0; f < 2; f++)
         for (size_t k = 0; k < tp[f].size(); k++) tp[f][k].peak = d_pkt + tp_ch[f][k];
@@ -1765,13 +1790,14 @@ TH_API int th_tm_get_loudness_meters(th_tm *tm, const size_t *ids, size_t n, th_
         th_loudness_meter &m = ms[i];
         if (loudness_rate_ok(trs[i]->sr)) {
             lufs.resize(m.n_momentary + m.n_short_term);
-            const double *e = energies + m.momentary_offset;  // (the short-term energies follow the momentary ones)
+            const double *e = energies + e0[i];
             for (size_t k = 0; k < lufs.size(); k++) lufs[k] = loudness_lufs(e[k]);
+            // (meters_layout: the short-term values follow the momentary ones)
             if (series && !lufs.empty()) std::memcpy(series + m.momentary_offset, lufs.data(), lufs.size() * sizeof(double));
             m.max_momentary_lufs = loudness_series_max(lufs.data(), m.n_momentary);
             m.max_short_term_lufs = loudness_series_max(lufs.data() + m.n_momentary, m.n_short_term);
             sub.clear();
-            for (size_t k = 0; k < m.n_short_term; k += 10) sub.push_back(energies[m.short_term_offset + k]);
+            for (size_t k = 0; k < m.n_short_term; k += 10) sub.push_back(e[m.n_momentary + k]);
             m.loudness_range = loudness_range(sub.data(), sub.size());
         } else {
             m.loudness_range = m.max_momentary_lufs = m.max_short_term_lufs = NAN;
@@ -1791,8 +1817,33 @@ TH_API int th_tm_get_loudness_meters(th_tm *tm, const size_t *ids, size_t n, th_
         m.true_peak_dB = peak == 0.0f ? -INFINITY : (float)(20.0 * std::log10((double)peak));
         m.true_peak_channel = at;
     }
-    std::memcpy(meters, ms.data(), n * sizeof(th_loudness_meter));
+    return TH_OK;
+}
+}  // namespace tmi
+}  // namespace th
+
+TH_API int th_tm_get_loudness_meters(th_tm *tm, const size_t *ids, size_t n, th_loudness_meter *meters, double *series, size_t cap,
+                                     size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(tm && meters && out_len && (n == 0 || ids), "NULL argument");
+    *out_len = 0;
+    if (n == 0) return TH_OK;
+    TH_REQUIRE(n <= 65535, "at most 65535 tracks per call");  // (before 65536 infos are made)
+    std::shared_lock<std::shared_mutex> rl(tm->rw);
+    std::vector<tmi::MeterInfo> ms(n);
+    for (size_t i = 0; i < n; i++) TH_CHECK(tmi::loudness_meter_info(tm, ids[i], &ms[i]));
+    size_t n_ch = 0;
+    TH_CHECK(meters_fit_one_launch(ms.data(), n, &n_ch));  // (reported before a short buffer)
+    const size_t total = tmi::meters_layout(ms.data(), n);
+    const uint64_t revision = tm->waveform_revision();
+    for (size_t i = 0; i < n; i++) {
+        ms[i].waveform_revision = revision;
+        meters[i] = ms[i];
+    }
     *out_len = total;
+    if (series && cap < total) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu doubles", total);
+    TH_CHECK(tmi::meters_run(tm, ids, n, ms.data(), series));
+    for (size_t i = 0; i < n; i++) meters[i] = ms[i];
     return TH_OK;
     TH_CATCH
 }

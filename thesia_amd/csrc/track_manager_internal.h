@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "common.h"
+#include "host_math.h"
 
 namespace th {
 namespace tmi {
@@ -50,20 +51,60 @@ int prepare_dynamics(th_tm *tm, int kind, float target, int mode, StagedPtr *out
 void get_common_dynamics(th_tm *tm, int *kind, float *target, int *mode);
 void commit(th_tm *tm, StagedPtr staged);
 
-// th_tm_get_spectra's check of ONE request (i: its index in the caller's batch, for the message), with the codes and in the order
-// th_tm_get_spectra reports them; *info: offset 0, the spec's height, the frame range and the slot's spectrogram revision
-int spectrum_request_info(th_tm *tm, const th_spectrum_request &r, size_t i, th_spectrum_info *info);
+// The batched readers (spectra, loudness meters, spectrogram tiles, export) in three steps each, so that th_tm's entry point and
+// th_tmg's are the same lines: check every request in request order, lay the output out, publish the infos and the length, report
+// a short buffer, run.  th_tmg checks each request against its owning slot and hands every slot its subset for the run.
+//   Locks: none of these takes rw; the caller holds rw_of(tm) shared around each call (ensure_colormap is the exception).
+//   *_info: the check of ONE request, with the codes and in the order the th_tm entry reports them (i: the request's index in the
+//     caller's batch, for the message).  *info then holds everything that is known without the GPU, with its offset(s) 0, and what
+//     the run needs of the manager for this request, so that the run looks nothing up again (valid until a writer gets in: th_tm
+//     holds rw from the check to the run, th_tmg its own rw, which every writer of its slots takes first).  The revision is the
+//     entry point's to stamp, its own manager's (export_request_info stamps the slot's, which th_tmg overwrites).
+//   *_layout: the offset of every info, in request order; returns the length of the whole output.
+//   *_run: the device work for n requests that were checked and laid out.  It takes a reader slot, packs its own n results in the
+//     slot's areas and writes request i's to out + info[i].offset and nowhere else: the destinations ascend with i and need not be
+//     adjacent (the caller may hold a subset of a larger batch), so whatever lies between them is left alone.  The limits of one
+//     launch are checked here.
+struct SpectrumInfo : th_spectrum_info {  // + the channel's resident rows
+    const float *rows;
+    size_t pitch;
+};
+int spectrum_request_info(th_tm *tm, const th_spectrum_request &r, size_t i, SpectrumInfo *info);
+size_t spectra_layout(SpectrumInfo *info, size_t n);
+int spectra_run(th_tm *tm, const th_spectrum_request *reqs, size_t n, const SpectrumInfo *info, float *out);
 
-// th_tm_get_loudness_meters' check of ONE id: TH_ERR_NOT_FOUND, else the meter's oversampling, counts (offsets 0) and the slot's
-// waveform revision, everything else zero
-int loudness_meter_info(th_tm *tm, size_t id, th_loudness_meter *m);
+// *m: the oversampling and the two counts, everything else zero.  meters_run fills meters[i] in place (it keeps the oversampling,
+// the counts, the offsets and the revision as the caller set them) and, with series, writes track i's LUFS to
+// series + meters[i].momentary_offset (the short-term values follow the momentary ones, as meters_layout places them)
+struct MeterInfo : th_loudness_meter {  // + the track (a Track of track_manager.hip) and its channel count
+    const void *track;
+    size_t n_channels;
+};
+int loudness_meter_info(th_tm *tm, size_t id, MeterInfo *m);
+size_t meters_layout(MeterInfo *m, size_t n);
+int meters_run(th_tm *tm, const size_t *ids, size_t n, MeterInfo *meters, double *series);
 
-// th_tm_export_pcm in three steps (th_tmg runs them per owning slot).  export_request_info: the check of ONE request with the codes
-// and in the order th_tm_export_pcm reports them; *info: offset 0, the byte count, the sample range, rate, channels, counts 0 and the
-// slot's waveform revision.  export_layout: the offsets (multiples of 16 in request order), the zero bytes behind every request
-// (pad[i]: up to the next offset; 0 behind the last) and the bytes of the whole image.  export_run: the device work for requests
-// that were checked and laid out: request i's bytes, then pad[i] zero bytes, to out + info[i].offset (ascending in i; they need not
-// be adjacent), and its two counts into info[i].  Takes a reader slot; the caller holds the lock (shared)
+// Spectrogram tiles: what the run needs of one request (the crop box, the image or mip level it is cut from; single: no such level
+// is held, the request goes through the single-tile path) and where its record starts.  Records are 40-byte header + RGBA, padded
+// to 64 bytes (tile_record_bytes); tiles_layout also writes the n + 1 offsets the ABI returns.  tiles_run writes headers and
+// pixels, never the padding.  It needs the device colormap: ensure_colormap uploads the default one if none was set, taking the
+// WRITE lock for that, so callers invoke it before they take the shared lock
+struct TileInfo {
+    TileGeom g;
+    const uint16_t *src;
+    uint32_t src_w, src_h, src_pitch;
+    bool single;
+    size_t offset;
+};
+inline size_t tile_record_bytes(const TileGeom &g) { return (40 + g.width * g.height * 4 + 63) / 64 * 64; }
+int ensure_colormap(th_tm *tm);
+int tile_request_info(th_tm *tm, const th_tile_request &r, TileInfo *info);
+size_t tiles_layout(TileInfo *info, size_t n, size_t *offsets);
+int tiles_run(th_tm *tm, const th_tile_request *reqs, size_t n, const TileInfo *info, uint8_t *out);
+
+// Export.  *info: the byte count, the sample range, rate, channels, counts 0.  export_layout: offsets that are multiples of 16, the
+// zero bytes behind every request (pad[i]: up to the next offset; 0 behind the last).  export_run: request i's bytes, then pad[i] zero
+// bytes, and its two counts into info[i].
 // Every request carries its output rate (th_export_at_request; sr_out 0: the track's own, which is all th_tm_export_pcm asks for:
 // export_at_requests); info->sr is the rate the request comes out at, and a request whose info->sr is not the track's is resampled
 // by export_run (kernels_resample.hip into the slot's planar scratch, then the same export kernel)

@@ -51,13 +51,14 @@ struct th_tmg {
 
 namespace {
 
+// the manager's (waveform, spectrogram) revisions
+std::pair<uint64_t, uint64_t> revisions(const th_tmg *g) {
+    std::lock_guard<std::mutex> lk(g->revs.mu);
+    return {g->revs.waveform_revision, g->revs.spectrogram_revision};
+}
+
 void sync_revisions(th_tmg *g) {
-    uint64_t w, s;
-    {
-        std::lock_guard<std::mutex> lk(g->revs.mu);
-        w = g->revs.waveform_revision;
-        s = g->revs.spectrogram_revision;
-    }
+    const auto [w, s] = revisions(g);
     for (auto &sl : g->slots) {
         th_tile_cache *c = nullptr;
         if (th_tm_tile_cache(sl.tm, &c) == TH_OK) c->set_revisions(w, s);
@@ -145,6 +146,47 @@ int requantise_all(th_tmg *g, bool force_update_all, bool images_only, std::vect
 const th_tmg::Placement *find_track(const th_tmg *g, size_t id) {
     auto it = g->where.find(id);
     return it == g->where.end() ? nullptr : &it->second;
+}
+
+// A batch of n requests split by owner (id_of(i): request i's track).  Every request is checked in request order against its
+// owning slot, under that slot's shared lock (check(tm, i): the codes and the order of one th_tm, the first faulty request
+// decides).  mine[s]: the requests of slot s in request order; busy: the slots that have any.  The caller holds g->rw.
+struct Split {
+    std::vector<std::vector<size_t>> mine;
+    std::vector<uint32_t> busy;
+};
+template <class IdOf, class Check>
+int check_and_split(th_tmg *g, size_t n, IdOf id_of, Check check, Split *sp) {
+    sp->mine.assign(g->slots.size(), {});
+    for (size_t i = 0; i < n; i++) {
+        const th_tmg::Placement *p = find_track(g, id_of(i));
+        if (!p) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", (size_t)id_of(i));
+        th_tm *tm = g->slots[p->slot].tm;
+        std::shared_lock<std::shared_mutex> sl(tmi::rw_of(tm));
+        TH_CHECK(check(tm, i));
+        sp->mine[p->slot].push_back(i);
+    }
+    for (uint32_t s = 0; s < g->slots.size(); s++)
+        if (!sp->mine[s].empty()) sp->busy.push_back(s);
+    return TH_OK;
+}
+
+// run(tm, idx) on every busy slot side by side (one slot: on the caller's thread), under the slot's shared lock; idx = mine[slot]
+template <class Run>
+int run_on_owners(th_tmg *g, const Split &sp, Run run) {
+    return for_slots(g, sp.busy, [&](uint32_t s) -> int {
+        th_tm *tm = g->slots[s].tm;
+        std::shared_lock<std::shared_mutex> sl(tmi::rw_of(tm));
+        return run(tm, sp.mine[s]);
+    });
+}
+
+// a slot's subset of the batch's requests or infos
+template <class T>
+std::vector<T> gather(const T *all, const std::vector<size_t> &idx) {
+    std::vector<T> sub(idx.size());
+    for (size_t j = 0; j < idx.size(); j++) sub[j] = all[idx[j]];
+    return sub;
 }
 
 }  // namespace
@@ -425,9 +467,9 @@ TH_API int th_tmg_copy_img(th_tmg *g, size_t id, uint32_t ch, uint16_t *out, siz
 TH_API int th_tmg_revisions(const th_tmg *g, uint64_t *waveform_revision, uint64_t *spectrogram_revision) {
     TH_TRY
     TH_REQUIRE(g, "tmg is NULL");
-    std::lock_guard<std::mutex> lk(g->revs.mu);
-    if (waveform_revision) *waveform_revision = g->revs.waveform_revision;
-    if (spectrogram_revision) *spectrogram_revision = g->revs.spectrogram_revision;
+    const auto [w, s] = revisions(g);
+    if (waveform_revision) *waveform_revision = w;
+    if (spectrogram_revision) *spectrogram_revision = s;
     return TH_OK;
     TH_CATCH
 }
@@ -463,10 +505,9 @@ TH_API int th_tmg_get_audio_render_metadata(th_tmg *g, size_t id, uint32_t ch, d
     TH_CATCH
 }
 
-// The batch split by owner, the slots served side by side.  Record sizes follow from the images' shapes
-// (spectrogram_tile_geometry), so the offsets are known before any slot runs: a batch owned by one slot goes to it whole
-// (its th_tm writes the caller's buffer directly when its device can reach it, else stages); otherwise each slot writes its
-// records into a staging buffer of its own and they are scattered to their places.
+// The batched readers: check_and_split, one layout, the manager's own revision, the infos and the length published, a short buffer
+// reported; then every owning slot runs its subset side by side and writes its results straight to their places in the caller's
+// buffer (track_manager_internal.h).
 TH_API int th_tmg_get_spectrogram_tiles(th_tmg *g, const th_tile_request *reqs, size_t n, uint8_t *out, size_t out_capacity,
                                         size_t *offsets, size_t *out_len) {
     TH_TRY
@@ -477,57 +518,20 @@ TH_API int th_tmg_get_spectrogram_tiles(th_tmg *g, const th_tile_request *reqs, 
         return TH_OK;
     }
     std::shared_lock<std::shared_mutex> rl(g->rw);
-    std::vector<uint32_t> owner(n);
-    size_t total = 0;
-    for (size_t i = 0; i < n; i++) {
-        const th_tile_request &r = reqs[i];
-        const th_tmg::Placement *p = find_track(g, r.id);
-        if (!p) return fail(TH_ERR_NOT_FOUND, "Spectrogram %zu_%u does not exist", r.id, r.ch);
-        owner[i] = p->slot;
-        size_t h = 0, w = 0;
-        int rc = th_tm_img_shape(g->slots[p->slot].tm, r.id, r.ch, &h, &w);
-        if (rc != TH_OK) return rc;
-        const TileGeom tg = spectrogram_tile_geometry(w, h, r.level_x, r.level_y, r.tile_x, r.tile_y);
-        offsets[i] = total;
-        total += (40 + tg.width * tg.height * 4 + 63) / 64 * 64;
-    }
-    offsets[n] = total;
+    std::vector<tmi::TileInfo> infos(n);
+    Split sp;
+    TH_CHECK(check_and_split(g, n, [&](size_t i) { return reqs[i].id; },
+                             [&](th_tm *tm, size_t i) { return tmi::tile_request_info(tm, reqs[i], &infos[i]); }, &sp));
+    const size_t total = tmi::tiles_layout(infos.data(), n, offsets);  // (the headers' revision: every slot carries the manager's)
     *out_len = total;
     if (out_capacity < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
-    std::vector<std::vector<size_t>> mine(g->slots.size());  // request indices per slot, in request order
-    for (size_t i = 0; i < n; i++) mine[owner[i]].push_back(i);
-    std::vector<uint32_t> busy;
-    for (uint32_t s = 0; s < g->slots.size(); s++)
-        if (!mine[s].empty()) busy.push_back(s);
-    if (busy.size() == 1) return th_tm_get_spectrogram_tiles(g->slots[busy[0]].tm, reqs, n, out, out_capacity, offsets, out_len);
-    return for_slots(g, busy, [&](uint32_t s) -> int {
-        const std::vector<size_t> &idx = mine[s];
-        std::vector<th_tile_request> sub(idx.size());
-        size_t bytes = 0;
-        for (size_t j = 0; j < idx.size(); j++) {
-            sub[j] = reqs[idx[j]];
-            bytes += offsets[idx[j] + 1] - offsets[idx[j]];
-        }
-        std::vector<uint8_t> stage(bytes);
-        std::vector<size_t> soff(idx.size() + 1);
-        size_t len = 0;
-        int rc = th_tm_get_spectrogram_tiles(g->slots[s].tm, sub.data(), sub.size(), stage.data(), stage.size(), soff.data(), &len);
-        if (rc != TH_OK) return rc;
-        for (size_t j = 0; j < idx.size(); j++) {  // (the record itself: 40-byte header + RGBA, not the padding after it)
-            uint32_t w, h;
-            std::memcpy(&w, stage.data() + soff[j] + 8, 4);
-            std::memcpy(&h, stage.data() + soff[j] + 12, 4);
-            std::memcpy(out + offsets[idx[j]], stage.data() + soff[j], 40 + (size_t)w * h * 4);
-        }
-        return TH_OK;
+    for (uint32_t s : sp.busy) TH_CHECK(tmi::ensure_colormap(g->slots[s].tm));
+    return run_on_owners(g, sp, [&](th_tm *tm, const std::vector<size_t> &idx) -> int {
+        return tmi::tiles_run(tm, gather(reqs, idx).data(), idx.size(), gather(infos.data(), idx).data(), out);
     });
     TH_CATCH
 }
 
-// Spectra: the batch split by owner.  Every request is checked in request order against its owning slot (the codes and the order
-// of one th_tm: the first faulty request decides), which also gives the heights, so the packed offsets are known before any slot
-// runs; a batch owned by one slot goes to it whole, otherwise every slot fills a staging vector of its own, side by side, and the
-// rows are scattered to their places once all have succeeded.
 TH_API int th_tmg_get_spectra(th_tmg *g, const th_spectrum_request *reqs, size_t n, float *out, size_t cap, th_spectrum_info *info,
                               size_t *out_len) {
     TH_TRY
@@ -535,62 +539,21 @@ TH_API int th_tmg_get_spectra(th_tmg *g, const th_spectrum_request *reqs, size_t
     *out_len = 0;
     if (n == 0) return TH_OK;
     std::shared_lock<std::shared_mutex> rl(g->rw);
-    std::vector<std::vector<size_t>> mine(g->slots.size());  // request indices per slot, in request order
-    std::vector<th_spectrum_info> infos(n);
+    std::vector<tmi::SpectrumInfo> infos(n);
+    Split sp;
+    TH_CHECK(check_and_split(g, n, [&](size_t i) { return reqs[i].id; },
+                             [&](th_tm *tm, size_t i) { return tmi::spectrum_request_info(tm, reqs[i], i, &infos[i]); }, &sp));
+    const size_t total = tmi::spectra_layout(infos.data(), n);
+    const uint64_t revision = revisions(g).second;
     for (size_t i = 0; i < n; i++) {
-        const th_tmg::Placement *p = find_track(g, reqs[i].id);
-        if (!p) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", reqs[i].id);
-        th_tm *tm = g->slots[p->slot].tm;
-        std::shared_lock<std::shared_mutex> sl(tmi::rw_of(tm));
-        TH_CHECK(tmi::spectrum_request_info(tm, reqs[i], i, &infos[i]));
-        mine[p->slot].push_back(i);
-    }
-    uint64_t revision;
-    {
-        std::lock_guard<std::mutex> lk(g->revs.mu);
-        revision = g->revs.spectrogram_revision;
-    }
-    std::vector<uint32_t> busy;
-    std::vector<std::vector<th_spectrum_request>> sub(g->slots.size());
-    for (uint32_t s = 0; s < g->slots.size(); s++) {
-        const std::vector<size_t> &idx = mine[s];
-        if (idx.empty()) continue;
-        busy.push_back(s);
-        sub[s].resize(idx.size());
-        for (size_t j = 0; j < idx.size(); j++) sub[s][j] = reqs[idx[j]];
-    }
-    size_t total = 0;
-    for (size_t i = 0; i < n; i++) {
-        infos[i].offset = total;
         infos[i].spectrogram_revision = revision;
-        total += infos[i].height;
+        info[i] = infos[i];
     }
-    std::memcpy(info, infos.data(), n * sizeof(th_spectrum_info));
     *out_len = total;
     if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu floats", total);
-    if (busy.size() == 1) {
-        std::vector<th_spectrum_info> si(n);
-        size_t len = 0;
-        return th_tm_get_spectra(g->slots[busy[0]].tm, reqs, n, out, cap, si.data(), &len);
-    }
-    std::vector<std::vector<float>> stage(g->slots.size());
-    const int rc = for_slots(g, busy, [&](uint32_t s) -> int {
-        size_t floats = 0;
-        for (size_t i : mine[s]) floats += infos[i].height;
-        stage[s].resize(floats);
-        std::vector<th_spectrum_info> si(mine[s].size());
-        size_t len = 0;
-        return th_tm_get_spectra(g->slots[s].tm, sub[s].data(), sub[s].size(), stage[s].data(), stage[s].size(), si.data(), &len);
+    return run_on_owners(g, sp, [&](th_tm *tm, const std::vector<size_t> &idx) -> int {
+        return tmi::spectra_run(tm, gather(reqs, idx).data(), idx.size(), gather(infos.data(), idx).data(), out);
     });
-    if (rc != TH_OK) return rc;
-    for (uint32_t s : busy) {
-        size_t at = 0;
-        for (size_t i : mine[s]) {
-            std::memcpy(out + infos[i].offset, stage[s].data() + at, infos[i].height * sizeof(float));
-            at += infos[i].height;
-        }
-    }
-    return TH_OK;
     TH_CATCH
 }
 
@@ -608,9 +571,6 @@ TH_API int th_tmg_get_spectrum(th_tmg *g, size_t id, uint32_t ch, int kind, doub
     TH_CATCH
 }
 
-// Loudness meters: every id is checked in request order against its owning slot (which gives the counts, so the packed offsets are
-// known before any slot runs); a batch owned by one slot goes to it whole, otherwise every slot fills meters and a staging vector of
-// its own, side by side, and they are scattered to their places once all have succeeded.
 TH_API int th_tmg_get_loudness_meters(th_tmg *g, const size_t *ids, size_t n, th_loudness_meter *meters, double *series, size_t cap,
                                       size_t *out_len) {
     TH_TRY
@@ -618,66 +578,25 @@ TH_API int th_tmg_get_loudness_meters(th_tmg *g, const size_t *ids, size_t n, th
     *out_len = 0;
     if (n == 0) return TH_OK;
     std::shared_lock<std::shared_mutex> rl(g->rw);
-    std::vector<std::vector<size_t>> mine(g->slots.size());  // request indices per slot, in request order
-    std::vector<th_loudness_meter> ms(n);
-    for (size_t i = 0; i < n; i++) {
-        const th_tmg::Placement *p = find_track(g, ids[i]);
-        if (!p) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", ids[i]);
-        th_tm *tm = g->slots[p->slot].tm;
-        std::shared_lock<std::shared_mutex> sl(tmi::rw_of(tm));
-        TH_CHECK(tmi::loudness_meter_info(tm, ids[i], &ms[i]));
-        mine[p->slot].push_back(i);
-    }
-    uint64_t revision;
-    {
-        std::lock_guard<std::mutex> lk(g->revs.mu);
-        revision = g->revs.waveform_revision;
-    }
-    size_t total = 0;
+    std::vector<tmi::MeterInfo> ms(n);
+    Split sp;
+    TH_CHECK(check_and_split(g, n, [&](size_t i) { return ids[i]; },
+                             [&](th_tm *tm, size_t i) { return tmi::loudness_meter_info(tm, ids[i], &ms[i]); }, &sp));
+    const size_t total = tmi::meters_layout(ms.data(), n);
+    const uint64_t revision = revisions(g).first;
     for (size_t i = 0; i < n; i++) {
         ms[i].waveform_revision = revision;
-        ms[i].momentary_offset = total;
-        total += ms[i].n_momentary;
-        ms[i].short_term_offset = total;
-        total += ms[i].n_short_term;
+        meters[i] = ms[i];
     }
-    if (series && cap < total) {
-        std::memcpy(meters, ms.data(), n * sizeof(th_loudness_meter));
-        *out_len = total;
-        return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu doubles", total);
-    }
-    std::vector<uint32_t> busy;
-    for (uint32_t s = 0; s < g->slots.size(); s++)
-        if (!mine[s].empty()) busy.push_back(s);
-    std::vector<std::vector<th_loudness_meter>> got(g->slots.size());
-    std::vector<std::vector<double>> stage(g->slots.size());
-    const int rc = for_slots(g, busy, [&](uint32_t s) -> int {
-        std::vector<size_t> sub(mine[s].size());
-        size_t doubles = 0;
-        for (size_t j = 0; j < sub.size(); j++) {
-            sub[j] = ids[mine[s][j]];
-            doubles += ms[mine[s][j]].n_momentary + ms[mine[s][j]].n_short_term;
-        }
-        got[s].resize(sub.size());
-        stage[s].resize(series ? std::max<size_t>(doubles, 1) : 0);
-        size_t len = 0;
-        return th_tm_get_loudness_meters(g->slots[s].tm, sub.data(), sub.size(), got[s].data(), series ? stage[s].data() : nullptr,
-                                         stage[s].size(), &len);
-    });
-    if (rc != TH_OK) return rc;
-    for (uint32_t s : busy)
-        for (size_t j = 0; j < mine[s].size(); j++) {
-            const size_t i = mine[s][j];
-            th_loudness_meter m = got[s][j];
-            if (series && m.n_momentary + m.n_short_term)
-                std::memcpy(series + ms[i].momentary_offset, stage[s].data() + m.momentary_offset, (m.n_momentary + m.n_short_term) * sizeof(double));
-            m.momentary_offset = ms[i].momentary_offset;
-            m.short_term_offset = ms[i].short_term_offset;
-            m.waveform_revision = revision;
-            ms[i] = m;
-        }
-    std::memcpy(meters, ms.data(), n * sizeof(th_loudness_meter));
     *out_len = total;
+    if (series && cap < total) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu doubles", total);
+    TH_CHECK(run_on_owners(g, sp, [&](th_tm *tm, const std::vector<size_t> &idx) -> int {
+        std::vector<tmi::MeterInfo> sub = gather(ms.data(), idx);
+        TH_CHECK(tmi::meters_run(tm, gather(ids, idx).data(), idx.size(), sub.data(), series));
+        for (size_t j = 0; j < idx.size(); j++) ms[idx[j]] = sub[j];
+        return TH_OK;
+    }));
+    for (size_t i = 0; i < n; i++) meters[i] = ms[i];
     return TH_OK;
     TH_CATCH
 }
@@ -690,31 +609,13 @@ TH_API int th_tmg_get_loudness_meter(th_tmg *g, size_t id, th_loudness_meter *me
     TH_CATCH
 }
 
-// Export: every request is checked in request order against its owning slot (the codes and the order of one th_tm), which gives the
-// byte counts, so the offsets and the zero padding are known before any slot runs; the slots then run side by side, each writing
-// its own requests' bytes (and the padding behind them) straight into the caller's buffer.
+// Export: the same shape; a slot also writes the zero padding behind each of its requests, and its two counts come back into infos
 namespace {
-int export_on_slots(th_tmg *g, const th_export_at_request *reqs, size_t n, std::vector<th_export_info> &infos, const std::vector<uint32_t> &pad,
+int export_on_slots(th_tmg *g, const Split &sp, const th_export_at_request *reqs, std::vector<th_export_info> &infos, const std::vector<uint32_t> &pad,
                     uint8_t *out) {
-    std::vector<std::vector<size_t>> mine(g->slots.size());
-    for (size_t i = 0; i < n; i++) mine[find_track(g, reqs[i].base.id)->slot].push_back(i);
-    std::vector<uint32_t> busy;
-    for (uint32_t s = 0; s < g->slots.size(); s++)
-        if (!mine[s].empty()) busy.push_back(s);
-    return for_slots(g, busy, [&](uint32_t s) -> int {
-        const std::vector<size_t> &idx = mine[s];
-        std::vector<th_export_at_request> sub(idx.size());
-        std::vector<th_export_info> si(idx.size());
-        std::vector<uint32_t> sp(idx.size());
-        for (size_t j = 0; j < idx.size(); j++) {
-            sub[j] = reqs[idx[j]];
-            si[j] = infos[idx[j]];
-            sp[j] = pad[idx[j]];
-        }
-        th_tm *tm = g->slots[s].tm;
-        std::shared_lock<std::shared_mutex> sl(tmi::rw_of(tm));
-        const int rc = tmi::export_run(tm, sub.data(), sub.size(), si.data(), sp.data(), out);
-        if (rc != TH_OK) return rc;
+    return run_on_owners(g, sp, [&](th_tm *tm, const std::vector<size_t> &idx) -> int {
+        std::vector<th_export_info> si = gather(infos.data(), idx);
+        TH_CHECK(tmi::export_run(tm, gather(reqs, idx).data(), idx.size(), si.data(), gather(pad.data(), idx).data(), out));
         for (size_t j = 0; j < idx.size(); j++) {
             infos[idx[j]].n_clamped = si[j].n_clamped;
             infos[idx[j]].n_nan = si[j].n_nan;
@@ -723,20 +624,11 @@ int export_on_slots(th_tmg *g, const th_export_at_request *reqs, size_t n, std::
     });
 }
 
-int export_check_all(th_tmg *g, const th_export_at_request *reqs, size_t n, std::vector<th_export_info> &infos) {
-    for (size_t i = 0; i < n; i++) {
-        const th_tmg::Placement *p = find_track(g, reqs[i].base.id);
-        if (!p) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", reqs[i].base.id);
-        th_tm *tm = g->slots[p->slot].tm;
-        std::shared_lock<std::shared_mutex> sl(tmi::rw_of(tm));
-        TH_CHECK(tmi::export_request_info(tm, reqs[i], i, &infos[i]));
-    }
-    uint64_t revision;
-    {
-        std::lock_guard<std::mutex> lk(g->revs.mu);
-        revision = g->revs.waveform_revision;
-    }
-    for (size_t i = 0; i < n; i++) infos[i].waveform_revision = revision;
+int export_check_all(th_tmg *g, const th_export_at_request *reqs, size_t n, std::vector<th_export_info> &infos, Split *sp) {
+    TH_CHECK(check_and_split(g, n, [&](size_t i) { return reqs[i].base.id; },
+                             [&](th_tm *tm, size_t i) { return tmi::export_request_info(tm, reqs[i], i, &infos[i]); }, sp));
+    const uint64_t revision = revisions(g).first;
+    for (th_export_info &f : infos) f.waveform_revision = revision;
     return TH_OK;
 }
 }  // namespace
@@ -749,13 +641,14 @@ int tmg_export_pcm_at(th_tmg *g, const th_export_at_request *reqs, size_t n, uin
     std::shared_lock<std::shared_mutex> rl(g->rw);
     std::vector<th_export_info> infos(n);
     std::vector<uint32_t> pad(n);
-    TH_CHECK(export_check_all(g, reqs, n, infos));
+    Split sp;
+    TH_CHECK(export_check_all(g, reqs, n, infos, &sp));
     size_t total = 0;
     tmi::export_layout(infos.data(), n, pad.data(), &total);
     std::memcpy(info, infos.data(), n * sizeof(th_export_info));
     *out_len = total;
     if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
-    TH_CHECK(export_on_slots(g, reqs, n, infos, pad, out));
+    TH_CHECK(export_on_slots(g, sp, reqs, infos, pad, out));
     std::memcpy(info, infos.data(), n * sizeof(th_export_info));
     return TH_OK;
 }
@@ -765,7 +658,8 @@ int tmg_export_wav_at(th_tmg *g, const th_export_at_request *req, uint8_t *out, 
     *out_len = 0;
     std::shared_lock<std::shared_mutex> rl(g->rw);
     std::vector<th_export_info> one(1);
-    TH_CHECK(export_check_all(g, req, 1, one));
+    Split sp;
+    TH_CHECK(export_check_all(g, req, 1, one, &sp));
     uint8_t hdr[TH_WAV_HEADER_MAX];
     size_t hl = 0, pl = 0;
     TH_CHECK(tmi::wav_header_checked(req->base.format, one[0].sr, one[0].n_channels, one[0].sample_end - one[0].sample_start, hdr, &hl, &pl));
@@ -774,7 +668,7 @@ int tmg_export_wav_at(th_tmg *g, const th_export_at_request *req, uint8_t *out, 
     if (info) *info = one[0];
     *out_len = total;
     if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
-    TH_CHECK(export_on_slots(g, req, 1, one, std::vector<uint32_t>{0}, out));
+    TH_CHECK(export_on_slots(g, sp, req, one, std::vector<uint32_t>{0}, out));
     std::memcpy(out, hdr, hl);
     if (pl) out[hl + one[0].n_bytes] = 0;
     if (info) *info = one[0];
