@@ -35,7 +35,7 @@ CSRC = os.path.join(ROOT, "thesia_amd", "csrc")
 
 
 def build_ab():
-    deps = [AB_SRC] + [os.path.join(CSRC, f) for f in ("kernels_resample.hip", "resample_block.h", "resample_core.h", "kernels.h")]
+    deps = [AB_SRC] + [os.path.join(CSRC, f) for f in ("kernels_resample.hip", "resample_block.h", "resample_core.h", "kernels.h", "reader_plan.h")]
     if os.path.exists(AB_EXE) and all(os.path.getmtime(d) <= os.path.getmtime(AB_EXE) for d in deps):
         return
     lib_dir = os.path.join(ROOT, "thesia_amd")

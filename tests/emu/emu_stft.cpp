@@ -15,6 +15,7 @@
 #include "../../thesia_amd/csrc/mel_fuse.h"
 #include "../../thesia_amd/csrc/host_math.h"  // bluestein_tables (host_math.cpp is compiled into the emulator)
 #include "../../thesia_amd/csrc/stft_plan.h"  // the plan tables and the launch planner, as th_plan_create / th_calc_spec_batch_dev call them
+#include "../../thesia_amd/csrc/reader_plan.h"  // the export and meter readers' planners, as export_run / meters_run call them (reader_plan.cpp is compiled in)
 
 using namespace th;
 
@@ -692,5 +693,196 @@ extern "C" __attribute__((visibility("default"))) void *emu_wave_window(const fl
     EmuBlobs *e = new EmuBlobs;
     e->add(ww.wtab);
     e->add(ww.phased);
+    return e;
+}
+
+// ---- the export and loudness-meter readers' plans (reader_plan.h), for tests/test_reader_plan_host.py
+#define EMU_API extern "C" __attribute__((visibility("default")))
+// rows of 11: {n_ch, n_in, sr_in, sr_out, format, dither, seed, s0, s1, offset, pad}; the resampler's plan and n_out as the check makes them
+static bool emu_export_requests(const uint64_t *rows, uint64_t n, std::vector<ExportPlanRequest> *out) {
+    out->assign(n, ExportPlanRequest{});
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t *r = rows + 11 * i;
+        ExportPlanRequest &q = (*out)[i];
+        q.n_ch = (uint32_t)r[0];
+        q.n_in = r[1];
+        q.sr_in = (uint32_t)r[2];
+        q.sr_out = (uint32_t)r[3];
+        q.format = (uint32_t)r[4];
+        q.dither = (uint32_t)r[5];
+        q.seed = (uint32_t)r[6];
+        q.s0 = r[7];
+        q.s1 = r[8];
+        q.offset = r[9];
+        q.pad = (uint32_t)r[10];
+        if (q.sr_out == q.sr_in) continue;
+        size_t n_out = 0;
+        if (resample_plan(q.sr_in, q.sr_out, &q.plan) != 0 || !resample_n_out(q.n_in, q.plan, &n_out)) return false;
+        q.n_out = n_out;
+    }
+    return true;
+}
+// Blobs (u64 unless said): 0 {err, n_ptrs, o_rjobs, o_ptrs, tab_bytes, stage_need[0], stage_need[1], scratch_need}; 1 the error text
+// (bytes); 2 jobs, rows of {request, f0, f1, n, n_ch, format, dither, seed, first_chunk, pad, stage_at, resampled, hull0, stride,
+// scratch_at, ptr_at}; 3 resample jobs, rows of {ja, jb, n_in, ch_stride, n_ch, n_sb, first_block}; 4 pieces, rows of {job0, job1,
+// n_chunks, stage_bytes, run0, run1, rjob0, rjob1, n_rblocks, sr_in, sr_out, scratch_floats}; 5 runs, rows of {stage_at, out_at,
+// bytes}; 6 ptr0; 7 per request {n_out, S, outputs per tile (G Pt Lp)} of its resampler (zeros: not resampled)
+EMU_API void *emu_plan_export(const uint64_t *rows, uint64_t n) {
+    std::vector<ExportPlanRequest> reqs;
+    if (!emu_export_requests(rows, n, &reqs)) return nullptr;
+    const ExportPlan p = plan_export(reqs.data(), reqs.size());
+    EmuBlobs *e = new EmuBlobs;
+    e->add(std::vector<uint64_t>{(uint64_t)p.err, p.n_ptrs, p.o_rjobs, p.o_ptrs, p.tab_bytes, p.stage_need[0], p.stage_need[1], p.scratch_need});
+    e->add(std::vector<char>(p.err_text.begin(), p.err_text.end()));
+    std::vector<uint64_t> jobs, rjobs, pieces, runs, per_req;
+    for (size_t j = 0; j < p.jobs.size(); j++) {
+        const ExportJob &x = p.jobs[j];
+        const ExportPlace &pl = p.places[j];
+        jobs.insert(jobs.end(), {pl.req, x.f0, x.f1, x.n, x.n_ch, x.format, x.dither, x.seed, x.first_chunk, x.pad, pl.stage_at, pl.resampled,
+                                 pl.hull0, pl.stride, pl.scratch_at, pl.ptr_at});
+    }
+    for (const ResampleJob &x : p.rjobs) rjobs.insert(rjobs.end(), {x.ja, x.jb, x.n_in, x.ch_stride, x.n_ch, x.n_sb, x.first_block});
+    for (const ExportPiece &x : p.pieces) {
+        const uint64_t run0 = runs.size() / 3;
+        for (const ExportRun &r : x.runs) runs.insert(runs.end(), {r.stage_at, r.out_at, r.bytes});
+        pieces.insert(pieces.end(), {x.job0, x.job1, x.n_chunks, x.stage_bytes, run0, runs.size() / 3, x.rjob0, x.rjob1, x.n_rblocks, x.sr_in,
+                                     x.sr_out, x.scratch_floats});
+    }
+    for (const ExportPlanRequest &q : reqs) {
+        const ResampleTiling t = q.sr_out != q.sr_in ? resample_tiling(q.plan) : ResampleTiling{};
+        per_req.insert(per_req.end(), {q.n_out, t.S, (uint64_t)t.G * t.Pt * t.Lp});
+    }
+    e->add(jobs);
+    e->add(rjobs);
+    e->add(pieces);
+    e->add(runs);
+    e->add(std::vector<uint64_t>(p.ptr0.begin(), p.ptr0.end()));
+    e->add(per_req);
+    return e;
+}
+// bind_export on the plan of the same rows.  bases: {stage 0, stage 1, scratch, table, counters} as addresses; chan: every
+// request's channel addresses in request order.  Blobs (u64): 0 jobs, rows of {chan, dst, cnt}; 1 resample jobs, rows of {chan, dst};
+// 2 the table as it would be uploaded (bytes)
+EMU_API void *emu_bind_export(const uint64_t *rows, uint64_t n, const uint64_t *bases, const uint64_t *chan, uint64_t n_chan) {
+    std::vector<ExportPlanRequest> reqs;
+    if (!emu_export_requests(rows, n, &reqs)) return nullptr;
+    ExportPlan p = plan_export(reqs.data(), reqs.size());
+    if (p.err != TH_OK) return nullptr;
+    std::vector<const float *> ch(n_chan);
+    for (uint64_t i = 0; i < n_chan; i++) ch[i] = reinterpret_cast<const float *>((uintptr_t)chan[i]);
+    const ExportBases b{{reinterpret_cast<uint8_t *>((uintptr_t)bases[0]), reinterpret_cast<uint8_t *>((uintptr_t)bases[1])},
+                        reinterpret_cast<float *>((uintptr_t)bases[2]), reinterpret_cast<unsigned char *>((uintptr_t)bases[3]),
+                        reinterpret_cast<unsigned long long *>((uintptr_t)bases[4])};
+    const std::vector<unsigned char> tab = bind_export(p, b, ch.data());
+    EmuBlobs *e = new EmuBlobs;
+    std::vector<uint64_t> jobs, rjobs;
+    for (const ExportJob &x : p.jobs) jobs.insert(jobs.end(), {(uint64_t)(uintptr_t)x.chan, (uint64_t)(uintptr_t)x.dst, (uint64_t)(uintptr_t)x.cnt});
+    for (const ResampleJob &x : p.rjobs) rjobs.insert(rjobs.end(), {(uint64_t)(uintptr_t)x.chan, (uint64_t)(uintptr_t)x.dst});
+    e->add(jobs);
+    e->add(rjobs);
+    e->add(tab);
+    return e;
+}
+
+// rows of 4: {id, sr, n_ch, n_samples}; the oversampling and the two counts as loudness_meter_info makes them
+static std::vector<MeterPlanTrack> emu_meter_tracks(const uint64_t *rows, uint64_t n) {
+    std::vector<MeterPlanTrack> out(n);
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t *r = rows + 4 * i;
+        const uint32_t sr = (uint32_t)r[1];
+        const bool ok = loudness_rate_ok(sr);
+        out[i] = MeterPlanTrack{(size_t)r[0], sr, (uint32_t)r[2], true_peak_factor(sr), r[3], ok ? loudness_n_blocks(r[3], sr) : 0,
+                                ok ? loudness_n_short_term(r[3], sr) : 0};
+    }
+    return out;
+}
+// Blobs (u64 unless said): 0 {err, n_ch, n_energies, n_states, max_chunks, max_fchunks, lds_floats, tp_chunks[0], tp_chunks[1], max_m,
+// max_s, o_sums, o_pka, o_pkt, res_bytes, o_z, o_q, mem_bytes, t_rates, t_m, t_s, t_tp4, t_tp2, tab_bytes, sizeof LoudJob, LoudnessRate,
+// LoudTrackJob, TruePeakJob}; 1 the error text (bytes); 2 rates, rows of {sr, s100, n_sub, cl}; 3 jobs, rows of {n, rate, n_chunks,
+// n_fchunks}; 4 momentary and 5 short-term track jobs, rows of {n_blocks, n_ch, n_sub, n_fchunks, L}; 6 the track jobs' weights (f64,
+// 8 per track); 7 F = 4 and 8 F = 2 true-peak jobs, rows of {n, n_chunks, channel}; 9 per track {ch0, e0, rate_ok, oversampling,
+// n_momentary, n_short_term}
+EMU_API void *emu_plan_meters(const uint64_t *rows, uint64_t n) {
+    const std::vector<MeterPlanTrack> trs = emu_meter_tracks(rows, n);
+    const MeterPlan p = plan_meters(trs.data(), trs.size());
+    EmuBlobs *e = new EmuBlobs;
+    e->add(std::vector<uint64_t>{(uint64_t)p.err, p.n_ch, p.n_energies, p.n_states, p.max_chunks, p.max_fchunks, p.lds_floats, p.tp_chunks[0],
+                                 p.tp_chunks[1], p.max_m, p.max_s, p.o_sums, p.o_pka, p.o_pkt, p.res_bytes, p.o_z, p.o_q, p.mem_bytes, p.t_rates,
+                                 p.t_m, p.t_s, p.t_tp4, p.t_tp2, p.tab_bytes, sizeof(LoudJob), sizeof(LoudnessRate), sizeof(LoudTrackJob),
+                                 sizeof(TruePeakJob)});
+    e->add(std::vector<char>(p.err_text.begin(), p.err_text.end()));
+    std::vector<uint64_t> rates, jobs, tj[2], tp[2], per;
+    std::vector<double> w;
+    for (const LoudnessRate *r : p.rates) rates.insert(rates.end(), {r->sr, r->s100, r->n_sub, r->cl});
+    for (const LoudJob &j : p.jobs) jobs.insert(jobs.end(), {j.n, j.rate, j.n_chunks, j.n_fchunks});
+    for (int v = 0; v < 2; v++)
+        for (const LoudTrackJob &t : v ? p.tj_s : p.tj_m) tj[v].insert(tj[v].end(), {t.n_blocks, t.n_ch, t.n_sub, t.n_fchunks, t.L});
+    for (const LoudTrackJob &t : p.tj_m) w.insert(w.end(), t.w, t.w + 8);
+    for (int f = 0; f < 2; f++)
+        for (size_t k = 0; k < p.tp[f].size(); k++) tp[f].insert(tp[f].end(), {p.tp[f][k].n, p.tp[f][k].n_chunks, p.tp_ch[f][k]});
+    for (size_t i = 0; i < p.tracks.size(); i++)
+        per.insert(per.end(), {p.ch0[i], p.e0[i], p.rate_ok[i], trs[i].oversampling, trs[i].n_momentary, trs[i].n_short_term});
+    e->add(rates);
+    e->add(jobs);
+    e->add(tj[0]);
+    e->add(tj[1]);
+    e->add(w);
+    e->add(tp[0]);
+    e->add(tp[1]);
+    e->add(per);
+    return e;
+}
+// bind_meters on the plan of the same rows (mem: the memory's address; wav: every channel's address).  Blobs (u64): 0 jobs, rows of
+// {wav, z, q, sumsq, peak, aligned16}; 1 momentary and 2 short-term track jobs, rows of {q, out}; 3 F = 4 and 4 F = 2 true-peak
+// jobs, rows of {wav, peak, aligned16}; 5 the table as it would be uploaded (bytes)
+EMU_API void *emu_bind_meters(const uint64_t *rows, uint64_t n, uint64_t mem, const uint64_t *wav, uint64_t n_wav) {
+    const std::vector<MeterPlanTrack> trs = emu_meter_tracks(rows, n);
+    MeterPlan p = plan_meters(trs.data(), trs.size());
+    if (p.err != TH_OK || n_wav != p.n_ch) return nullptr;
+    std::vector<const float *> w(n_wav);
+    for (uint64_t i = 0; i < n_wav; i++) w[i] = reinterpret_cast<const float *>((uintptr_t)wav[i]);
+    const std::vector<unsigned char> tab = bind_meters(p, reinterpret_cast<unsigned char *>((uintptr_t)mem), w.data());
+    auto a = [](const void *q) { return (uint64_t)(uintptr_t)q; };
+    std::vector<uint64_t> jobs, tj[2], tp[2];
+    for (const LoudJob &j : p.jobs) jobs.insert(jobs.end(), {a(j.wav), a(j.z), a(j.q), a(j.sumsq), a(j.peak), j.aligned16});
+    for (int v = 0; v < 2; v++)
+        for (const LoudTrackJob &t : v ? p.tj_s : p.tj_m) tj[v].insert(tj[v].end(), {a(t.q), a(t.out)});
+    for (int f = 0; f < 2; f++)
+        for (const TruePeakJob &t : p.tp[f]) tp[f].insert(tp[f].end(), {a(t.wav), a(t.peak), t.aligned16});
+    EmuBlobs *e = new EmuBlobs;
+    e->add(jobs);
+    e->add(tj[0]);
+    e->add(tj[1]);
+    e->add(tp[0]);
+    e->add(tp[1]);
+    e->add(tab);
+    return e;
+}
+// meter_results from a result area of res_bytes (the series laid out as meters_layout does: track by track, the momentary values,
+// then the short-term ones).  Blobs (f64): 0 rows of {max_momentary_lufs, max_short_term_lufs, loudness_range, true_peak,
+// true_peak_dB, true_peak_channel}; 1 the series
+EMU_API void *emu_meter_results(const uint64_t *rows, uint64_t n, const unsigned char *res, uint64_t res_bytes) {
+    const std::vector<MeterPlanTrack> trs = emu_meter_tracks(rows, n);
+    const MeterPlan p = plan_meters(trs.data(), trs.size());
+    if (p.err != TH_OK || res_bytes != p.res_bytes) return nullptr;
+    std::vector<th_loudness_meter> ms(trs.size());
+    std::vector<th_loudness_meter *> mp(trs.size());
+    for (size_t i = 0; i < trs.size(); i++) {
+        ms[i] = th_loudness_meter{};
+        ms[i].oversampling = trs[i].oversampling;
+        ms[i].n_momentary = trs[i].n_momentary;
+        ms[i].n_short_term = trs[i].n_short_term;
+        ms[i].momentary_offset = p.e0[i];
+        ms[i].short_term_offset = p.e0[i] + trs[i].n_momentary;
+        mp[i] = &ms[i];
+    }
+    std::vector<double> out, series(p.n_energies, -1.0);
+    meter_results(res, p, mp.data(), series.data());
+    for (const th_loudness_meter &m : ms)
+        out.insert(out.end(), {m.max_momentary_lufs, m.max_short_term_lufs, m.loudness_range, (double)m.true_peak, (double)m.true_peak_dB,
+                               (double)m.true_peak_channel});
+    EmuBlobs *e = new EmuBlobs;
+    e->add(out);
+    e->add(series);
     return e;
 }

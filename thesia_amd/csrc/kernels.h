@@ -10,6 +10,7 @@
 #include "../../include/thesia_amd.h"
 #include "host_math.h"
 #include "stft_core.h"
+#include "reader_plan.h"  // LoudJob, LoudTrackJob, TruePeakJob, ExportJob, ResampleJob, ResampleTiling and their constants
 #include "stft_plan.h"  // WavePostJob, MelJob, MEL_TILE_FRAMES, MEL_ROWS_*
 
 // Measured-and-dropped kernel variants: the packed-f32 pipeline (selector 9), the sweep chunk schedule (11), the
@@ -275,45 +276,15 @@ hipError_t launch_pyramid_up(const PyrJob *d_jobs, uint32_t n_jobs, uint64_t max
 uint32_t waveform_blocks_for(uint32_t level, uint32_t bin_count);
 
 
-// ---- kernels_loudness.hip: K-weighted chunk energies, per-channel sum of squares and peak, 400 ms block energies
-struct LoudJob {           // one channel
-    const float *wav;
-    double *z;             // n_fchunks x 8: double-double states (4 hi, 4 lo), the chunks' zero-state end states, then their start states
-    double *q;             // n_fchunks chunk energies (sum of y^2)
-    double *sumsq;         // += sum of x^2 over all samples (zeroed by the caller)
-    uint32_t *peak;        // max |x| as float bits (zeroed by the caller)
-    uint64_t n;
-    uint32_t rate;         // index into the LoudnessRate table
-    uint32_t n_chunks;     // chunks that hold samples (the sums)
-    uint32_t n_fchunks;    // chunks the 400 ms blocks cover: (n_blocks + 3) n_sub, or 0
-    uint32_t aligned16;
-};
-struct LoudTrackJob {      // one track
-    const double *q;       // channel c's chunk energies at q + c n_fchunks
-    double *out;           // n_blocks block energies
-    uint64_t n_blocks;
-    double w[8];           // channel weights (channel c >= 7: w[7])
-    uint32_t n_ch, n_sub, n_fchunks, L;
-};
+// ---- kernels_loudness.hip: K-weighted chunk energies, per-channel sum of squares and peak, 400 ms block energies (LoudJob,
+// LoudTrackJob: reader_plan.h)
 hipError_t launch_loudness(const LoudJob *d_jobs, uint32_t n_jobs, uint32_t max_chunks, uint32_t max_fchunks, const LoudnessRate *d_rates,
                            uint32_t lds_floats, const LoudTrackJob *d_tjobs, uint32_t n_tracks, uint64_t max_blocks, hipStream_t s);
 // pass D alone over the q of an earlier launch_loudness: blocks of `span` segments (4: the momentary series, 30: the short-term one;
 // LoudTrackJob::L = span s100, n_blocks = n_seg - span + 1, n_fchunks >= n_seg n_sub), summed in the same order
 hipError_t launch_loudness_blocks(const LoudTrackJob *d_tjobs, uint32_t n_tracks, uint64_t max_blocks, uint32_t span, hipStream_t s);
 
-// ---- kernels_meter.hip: the true peak of a batch of channels (th_tm_get_loudness_meters): max |y| of the polyphase interpolator
-// of host_math.h true_peak_filter, F = 4 or 2, causal from zero history, nothing behind the last sample
-constexpr uint32_t TP_RUN = 33;                 // consecutive outputs of one thread (odd: the lanes' LDS reads hit different banks)
-constexpr uint32_t TP_THREADS = 256;
-constexpr uint32_t TP_CHUNK = TP_RUN * TP_THREADS;  // samples of one workgroup (a multiple of 4)
-struct TruePeakJob {       // one channel
-    const float *wav;
-    uint32_t *peak;        // max |y| as float bits (zeroed by the caller)
-    uint64_t n;
-    uint32_t n_chunks;     // ceil(n / TP_CHUNK)
-    uint32_t aligned16;
-};
-static_assert(sizeof(TruePeakJob) == 32, "TruePeakJob must have no implicit padding");
+// ---- kernels_meter.hip: the true peak of a batch of channels (TruePeakJob, TP_*: reader_plan.h)
 struct TruePeakCoef {      // f32 taps: phase p = 1 .. F - 1, delay d at c[(p - 1) T + d] (T = 12 at F = 4, 24 at F = 2), then phase 0's one tap
     float c[36];
     float c0;
@@ -374,92 +345,12 @@ static_assert(sizeof(SpectrumJob) == 64, "SpectrumJob must have no implicit padd
 // max_blocks: the largest n_ctiles * n_slices of the jobs; max_height: the largest H
 hipError_t launch_spectrum(const SpectrumJob *d_jobs, uint32_t n_jobs, uint32_t max_blocks, uint32_t max_height, hipStream_t s);
 
-// ---- kernels_export.hip: planar f32 channels to interleaved file bytes (16 / 24-bit PCM with optional TPDF dither, or float32)
+// ---- kernels_export.hip: planar f32 channels to interleaved file bytes (ExportJob, export_chunk_frames: reader_plan.h)
 constexpr uint32_t EXPORT_THREADS = 256;
-constexpr uint32_t EXPORT_CHUNK_SAMPLES = 4096;  // samples (frames x channels) of one workgroup, at most
-// frames of one chunk: a multiple of 4, so that a chunk starts on a 16-byte boundary of every 16-byte aligned channel.  Chunks lie on
-// the ABSOLUTE grid k F .. (k + 1) F of the track: a range that starts or ends inside one gets a partial chunk
-constexpr uint32_t export_chunk_frames(uint32_t n_ch) {
-    return (EXPORT_CHUNK_SAMPLES / n_ch) & ~3u ? (EXPORT_CHUNK_SAMPLES / n_ch) & ~3u : 4u;
-}
-struct ExportJob {             // frames [f0, f1) of one request: a whole request, or the part of it that lies in one piece
-    const float *const *chan;  // n_ch channel pointers (device memory), each of n samples, 4-byte aligned
-    uint8_t *dst;              // where frame f0's first byte goes: ANY byte address
-    unsigned long long *cnt;   // [0] += clamped samples, [1] += NaN samples
-    uint64_t f0, f1, n;        // f0 <= f1 <= n
-    uint32_t n_ch;             // 1 .. TH_EXPORT_MAX_CHANNELS
-    uint32_t format, dither, seed;
-    uint32_t first_chunk;      // blocks [first_chunk, first_chunk of the next job) of the grid are this job's chunks
-    uint32_t pad;              // zero bytes behind frame f1 - 1's last byte (0 .. 15; written by the job's last chunk)
-};
-static_assert(sizeof(ExportJob) == 72, "ExportJob must have no implicit padding");
-// chunks of the absolute grid that [f0, f1) touches
-inline uint32_t export_n_chunks(uint64_t f0, uint64_t f1, uint32_t n_ch) {
-    const uint64_t F = export_chunk_frames(n_ch);
-    return f1 > f0 ? (uint32_t)((f1 - 1) / F - f0 / F + 1) : 0u;
-}
 // n_chunks: the sum over the jobs (the first_chunk a job behind the last would have)
 hipError_t launch_export(const ExportJob *d_jobs, uint32_t n_jobs, uint32_t n_chunks, hipStream_t s);
 
-// ---- kernels_resample.hip: polyphase sinc resampler, planar f32 channels at the track's rate to planar f32 at the output rate
-// (include/thesia_amd.h "Export at a target sample rate"; the summation is resample_core.h).  Outputs j and j + L share a coefficient
-// row and their windows lie M samples apart, so a workgroup takes ONE channel, R consecutive outputs (R <= 64 rows, one per lane) and
-// P = G Pt "periods" of them, Lp outputs apart (Lp a multiple of L): wave g of G takes periods g Pt .. g Pt + Pt - 1, a thread keeps
-// four coefficients in registers across its Pt periods.
-constexpr uint32_t RESAMPLE_LANES = 64;     // rows of a tile, at most
-constexpr uint32_t RESAMPLE_TAP_BLOCK = 64; // taps staged per step (a multiple of 4)
-constexpr uint32_t RESAMPLE_XS_MAX = 5248;  // input samples staged per step, at most (two copies of them, the second shifted by one)
-constexpr uint32_t RESAMPLE_MAX_PT = 8;
-struct ResampleTiling {
-    uint32_t L, M, taps;  // taps = 2K
-    uint32_t Lp;          // outputs between two periods: L (L >= 64) or the largest multiple of L that is at most 64
-    uint32_t R, S;        // a period of Lp outputs is cut into S sub-tiles of R outputs (the last one may be shorter); R <= 64
-    uint32_t G, Pt;       // waves of a workgroup, periods per thread: a tile is P = G Pt periods
-    uint32_t span;        // input samples a step stages: the largest offset of a window in the tile + RESAMPLE_TAP_BLOCK
-    uint64_t Mp;          // input samples between two periods: M Lp / L
-};
-inline ResampleTiling resample_tiling(const th_resample_plan &p) {
-    ResampleTiling t{};
-    t.L = p.L;
-    t.M = p.M;
-    t.taps = 2 * p.half_taps;
-    if (p.L < RESAMPLE_LANES) {  // (L = 1, 2, 6 ...: a row serves several lanes, no lane idles but the 64 mod L last ones)
-        t.Lp = p.L * (RESAMPLE_LANES / p.L);
-        t.R = t.Lp;
-        t.S = 1;
-    } else {
-        t.Lp = p.L;
-        t.S = (p.L + RESAMPLE_LANES - 1) / RESAMPLE_LANES;
-        t.R = (p.L + t.S - 1) / t.S;
-    }
-    t.Mp = (uint64_t)p.M * (t.Lp / p.L);
-    const uint64_t lanes = ((uint64_t)(t.R - 1) * p.M) / p.L + 1 + RESAMPLE_TAP_BLOCK;
-    static const uint32_t shapes[6][2] = {{4, 8}, {4, 4}, {4, 2}, {4, 1}, {1, 2}, {1, 1}};
-    for (const auto &sh : shapes) {
-        t.G = sh[0];
-        t.Pt = sh[1];
-        const uint64_t span = (uint64_t)(t.G * t.Pt - 1) * t.Mp + lanes;
-        t.span = (uint32_t)std::min<uint64_t>(span, UINT32_MAX);
-        if (span <= RESAMPLE_XS_MAX) break;
-    }
-    return t;  // ({1, 1} fits every plan: M / L <= 64 under TH_RESAMPLE_MAX_TAPS, so lanes <= 63 x 64 + 65)
-}
-struct ResampleJob {           // outputs [ja, jb) of every channel of one request
-    const float *const *chan;  // n_ch channel pointers (device memory), each of n_in samples
-    float *dst;                // output ja of channel 0; channel c's run starts ch_stride floats further per channel
-    uint64_t ja, jb;           // ja <= jb <= n_out
-    uint64_t n_in;
-    uint64_t ch_stride;
-    uint32_t n_ch;
-    uint32_t n_sb;             // tiles of P Lp outputs that [ja, jb) takes, counted from ja
-    uint32_t first_block;      // blocks [first_block, first_block of the next job) of the grid are this job's: n_ch x n_sb x S
-    uint32_t pad;
-};
-static_assert(sizeof(ResampleJob) == 64, "ResampleJob must have no implicit padding");
-inline uint64_t resample_n_sb(uint64_t ja, uint64_t jb, const ResampleTiling &t) {
-    const uint64_t per = (uint64_t)t.G * t.Pt * t.Lp;
-    return (jb - ja + per - 1) / per;
-}
+// ---- kernels_resample.hip: polyphase sinc resampler (ResampleJob, ResampleTiling: reader_plan.h)
 // table: L rows of `taps` floats (host_math.h resample_table); n_blocks: the sum over the jobs
 hipError_t launch_resample(const ResampleJob *d_jobs, uint32_t n_jobs, uint32_t n_blocks, const float *d_table, const ResampleTiling &t,
                            hipStream_t s);

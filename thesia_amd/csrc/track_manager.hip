@@ -1604,12 +1604,11 @@ void meter_counts(const Track &tr, th_loudness_meter *m) {
     }
 }
 
-// the limits of one launch (its grid), and the channels of its tracks
-int meters_fit_one_launch(const tmi::MeterInfo *ms, size_t n, size_t *n_ch) {
-    TH_REQUIRE(n <= 65535, "at most 65535 tracks per call");
-    *n_ch = 0;
-    for (size_t i = 0; i < n; i++) *n_ch += ms[i].n_channels;
-    TH_REQUIRE(*n_ch <= 65535, "at most 65535 channels per call");
+// the limits of one launch (its grid: reader_plan.h), as the entry point reports them before a short buffer
+int meters_fit_one_launch(const tmi::MeterInfo *ms, size_t n) {
+    size_t n_ch = 0;
+    for (size_t i = 0; i < n; i++) n_ch += ms[i].n_channels;
+    if (const char *text = meter_limits_text(n, n_ch)) return fail(TH_ERR_INVALID_ARG, "%s", text);
     return TH_OK;
 }
 }  // namespace
@@ -1638,185 +1637,61 @@ size_t meters_layout(MeterInfo *m, size_t n) {
 }  // namespace tmi
 }  // namespace th
 
-// The loudness meters of N tracks: a reader.  Per channel one LoudJob (passes A - C of kernels_loudness.hip, as at add time) and, at
-// F > 1, one TruePeakJob; per track two LoudTrackJobs (pass D over 4 and over 30 segments, writing the energies where the series go).
-// Everything runs on the slot's stream; the results come back in one copy (through the slot's pinned staging when they fit) and the
-// host turns them into LUFS, maxima and the loudness range.
+// The loudness meters of N tracks: a reader.  plan_meters (reader_plan.h) makes the job tables and lays the slot's memory out,
+// bind_meters gives them their addresses.  Everything runs on the slot's stream; the results come back in one copy (through the slot's
+// pinned staging when they fit) and meter_results turns them into LUFS, maxima and the loudness range.
 namespace th {
 namespace tmi {
 int meters_run(th_tm *tm, const size_t *ids, size_t n, MeterInfo *ms, double *series) {
-    size_t total = 0, n_ch = 0;
-    TH_CHECK(meters_fit_one_launch(ms, n, &n_ch));
-    std::vector<const Track *> trs(n);
-    std::vector<size_t> e0(n);  // track i's first energy in the slot's result area: the momentary ones, then the short-term ones
+    TH_CHECK(meters_fit_one_launch(ms, n));  // (before n tracks are gathered)
+    std::vector<MeterPlanTrack> trs(n);
+    std::vector<const float *> wav;
     for (size_t i = 0; i < n; i++) {
-        trs[i] = static_cast<const Track *>(ms[i].track);
-        e0[i] = total;
-        total += ms[i].n_momentary + ms[i].n_short_term;
-    }
-    // the job tables
-    std::vector<const LoudnessRate *> rates;
-    std::vector<LoudJob> jobs;
-    std::vector<LoudTrackJob> tj_m(n), tj_s(n);
-    std::vector<TruePeakJob> tp[2];  // F = 4, F = 2
-    std::vector<size_t> tp_ch[2];    // the channel (index into jobs) of every true-peak job
-    std::vector<size_t> ch0(n);
-    size_t n_states = 0;
-    uint32_t max_chunks = 0, max_fchunks = 0, lds_floats = 4, tp_chunks[2] = {0, 0};
-    uint64_t max_m = 0, max_s = 0;
-    for (size_t i = 0; i < n; i++) {
-        const Track &tr = *trs[i];
-        const bool ok = loudness_rate_ok(tr.sr);
-        const LoudnessRate &R = loudness_rate(ok ? tr.sr : 48000);  // (a refused rate: the peaks only, over chunks of a 48 kHz geometry)
-        size_t ri = 0;
-        while (ri < rates.size() && rates[ri] != &R) ri++;
-        if (ri == rates.size()) rates.push_back(&R);
+        const Track &tr = *static_cast<const Track *>(ms[i].track);
         const uint64_t ns = tr.ch.empty() ? 0 : tr.ch[0].n;
-        const uint64_t nseg_any = (ns + R.s100 - 1) / R.s100, nseg = ns / R.s100;
-        TH_REQUIRE(ns < (1ull << 40) && nseg_any * R.n_sub < (1ull << 31), "track %zu: too many samples", ids[i]);
-        const uint32_t nf = ok && nseg >= 4 ? (uint32_t)(nseg * R.n_sub) : 0u;
-        ch0[i] = jobs.size();
+        trs[i] = MeterPlanTrack{ids[i], tr.sr, (uint32_t)tr.ch.size(), ms[i].oversampling, ns, ms[i].n_momentary, ms[i].n_short_term};
         for (size_t k = 0; k < tr.ch.size(); k++) {
-            const float *wav = tr.ch[k].d_wav;
-            TH_REQUIRE(ns == 0 || wav, "track %zu channel %zu has no audio", ids[i], k);
-            LoudJob j{};
-            j.wav = wav;
-            j.n = ns;
-            j.rate = (uint32_t)ri;
-            j.n_chunks = (uint32_t)(nseg_any * R.n_sub);
-            j.n_fchunks = nf;
-            j.aligned16 = (reinterpret_cast<uintptr_t>(wav) & 15u) == 0;
-            if (ms[i].oversampling > 1 && ns) {
-                const int f = ms[i].oversampling == 4 ? 0 : 1;
-                TruePeakJob t{};
-                t.wav = wav;
-                t.n = ns;
-                t.n_chunks = (uint32_t)((ns + TP_CHUNK - 1) / TP_CHUNK);
-                t.aligned16 = j.aligned16;
-                tp[f].push_back(t);
-                tp_ch[f].push_back(jobs.size());
-                tp_chunks[f] = std::max(tp_chunks[f], t.n_chunks);
-            }
-            jobs.push_back(j);
-            n_states += nf;
+            TH_REQUIRE(ns == 0 || tr.ch[k].d_wav, "track %zu channel %zu has no audio", ids[i], k);
+            wav.push_back(tr.ch[k].d_wav);
         }
-        for (int v = 0; v < 2; v++) {
-            LoudTrackJob &t = v ? tj_s[i] : tj_m[i];
-            t = LoudTrackJob{};
-            t.n_blocks = v ? ms[i].n_short_term : ms[i].n_momentary;
-            for (uint32_t k = 0; k < 8; k++) t.w[k] = loudness_channel_weight(k, (uint32_t)tr.ch.size());
-            t.n_ch = (uint32_t)tr.ch.size();
-            t.n_sub = R.n_sub;
-            t.n_fchunks = nf;
-            t.L = (v ? 30u : 4u) * R.s100;
-        }
-        max_chunks = std::max(max_chunks, (uint32_t)(nseg_any * R.n_sub));
-        max_fchunks = std::max(max_fchunks, nf);
-        max_m = std::max<uint64_t>(max_m, ms[i].n_momentary);
-        max_s = std::max<uint64_t>(max_s, ms[i].n_short_term);
-        lds_floats = std::max(lds_floats, R.cl + 4);
     }
-    // device memory: results [energies: total][sums of squares: n_ch][pass A's peaks: n_ch u32][true peaks: n_ch u32] | states | q
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t pk_bytes = (n_ch * 4 + 7) / 8 * 8;
-    const size_t o_sums = total * 8, o_pka = o_sums + n_ch * 8, o_pkt = o_pka + pk_bytes, res_bytes = o_pkt + pk_bytes;
-    const size_t o_z = up(res_bytes), o_q = o_z + n_states * 64, mem_bytes = o_q + n_states * 8 + 8;
-    const size_t t_rates = up(jobs.size() * sizeof(LoudJob)), t_m = t_rates + up(rates.size() * sizeof(LoudnessRate));
-    const size_t t_s = t_m + up(n * sizeof(LoudTrackJob)), t_tp4 = t_s + up(n * sizeof(LoudTrackJob));
-    const size_t t_tp2 = t_tp4 + up(tp[0].size() * sizeof(TruePeakJob)), tab_bytes = t_tp2 + up(tp[1].size() * sizeof(TruePeakJob));
+    MeterPlan pl = plan_meters(trs.data(), n);
+    if (pl.err != TH_OK) return fail(pl.err, "%s", pl.err_text.c_str());
     TH_HIP(hipSetDevice(tm->ctx->device));
     SlotLease lease{tm, nullptr};
     int rc = acquire_slot(tm, &lease.slot);
     if (rc != TH_OK) return rc;
     ReaderSlot &sl = *lease.slot;
-    TH_CHECK(sl.meter_mem.ensure(mem_bytes));
+    TH_CHECK(sl.meter_mem.ensure(pl.mem_bytes));
     unsigned char *dm = static_cast<unsigned char *>(sl.meter_mem.dptr);
-    double *d_res = reinterpret_cast<double *>(dm), *d_sums = reinterpret_cast<double *>(dm + o_sums);
-    uint32_t *d_pka = reinterpret_cast<uint32_t *>(dm + o_pka), *d_pkt = reinterpret_cast<uint32_t *>(dm + o_pkt);
-    double *d_z = reinterpret_cast<double *>(dm + o_z), *d_q = reinterpret_cast<double *>(dm + o_q);
-    size_t si = 0;
-    for (size_t i = 0; i < n; i++) {
-        const size_t q0 = si;
-        for (size_t k = 0; k < trs[i]->ch.size(); k++) {
-            LoudJob &j = jobs[ch0[i] + k];
-            j.z = d_z + 8 * si;
-            j.q = d_q + si;
-            j.sumsq = d_sums + ch0[i] + k;
-            j.peak = d_pka + ch0[i] + k;
-            si += j.n_fchunks;
-        }
-        tj_m[i].q = tj_s[i].q = d_q + q0;
-        tj_m[i].out = d_res + e0[i];
-        tj_s[i].out = d_res + e0[i] + ms[i].n_momentary;
-    }
-    for (int f = 0; f < 2; f++)
-        for (size_t k = 0; k < tp[f].size(); k++) tp[f][k].peak = d_pkt + tp_ch[f][k];
-    std::vector<unsigned char> h(tab_bytes, 0);
-    std::memcpy(h.data(), jobs.data(), jobs.size() * sizeof(LoudJob));
-    for (size_t r = 0; r < rates.size(); r++) std::memcpy(h.data() + t_rates + r * sizeof(LoudnessRate), rates[r], sizeof(LoudnessRate));
-    std::memcpy(h.data() + t_m, tj_m.data(), n * sizeof(LoudTrackJob));
-    std::memcpy(h.data() + t_s, tj_s.data(), n * sizeof(LoudTrackJob));
-    if (!tp[0].empty()) std::memcpy(h.data() + t_tp4, tp[0].data(), tp[0].size() * sizeof(TruePeakJob));
-    if (!tp[1].empty()) std::memcpy(h.data() + t_tp2, tp[1].data(), tp[1].size() * sizeof(TruePeakJob));
-    TH_CHECK(sl.meter_tab.upload(sl.stream, h.data(), tab_bytes));
+    const std::vector<unsigned char> h = bind_meters(pl, dm, wav.data());
+    TH_CHECK(sl.meter_tab.upload(sl.stream, h.data(), h.size()));
     const unsigned char *dt = static_cast<const unsigned char *>(sl.meter_tab.dptr);
-    TH_HIP(hipMemsetAsync(dm + o_sums, 0, res_bytes - o_sums, sl.stream));  // sums = 0, peaks = +0.0
-    TH_HIP(launch_loudness(reinterpret_cast<const LoudJob *>(dt), (uint32_t)jobs.size(), max_chunks, max_fchunks,
-                           reinterpret_cast<const LoudnessRate *>(dt + t_rates), lds_floats, nullptr, 0, 0, sl.stream));
-    TH_HIP(launch_loudness_blocks(reinterpret_cast<const LoudTrackJob *>(dt + t_m), (uint32_t)n, max_m, 4, sl.stream));
-    TH_HIP(launch_loudness_blocks(reinterpret_cast<const LoudTrackJob *>(dt + t_s), (uint32_t)n, max_s, 30, sl.stream));
+    TH_HIP(hipMemsetAsync(dm + pl.o_sums, 0, pl.res_bytes - pl.o_sums, sl.stream));  // sums = 0, peaks = +0.0
+    TH_HIP(launch_loudness(reinterpret_cast<const LoudJob *>(dt), (uint32_t)pl.jobs.size(), pl.max_chunks, pl.max_fchunks,
+                           reinterpret_cast<const LoudnessRate *>(dt + pl.t_rates), pl.lds_floats, nullptr, 0, 0, sl.stream));
+    TH_HIP(launch_loudness_blocks(reinterpret_cast<const LoudTrackJob *>(dt + pl.t_m), (uint32_t)n, pl.max_m, 4, sl.stream));
+    TH_HIP(launch_loudness_blocks(reinterpret_cast<const LoudTrackJob *>(dt + pl.t_s), (uint32_t)n, pl.max_s, 30, sl.stream));
     for (int f = 0; f < 2; f++) {
-        if (tp[f].empty()) continue;
+        if (pl.tp[f].empty()) continue;
         TruePeakCoef K;
         true_peak_coef(f ? 2 : 4, &K);
-        TH_HIP(launch_true_peak(reinterpret_cast<const TruePeakJob *>(dt + (f ? t_tp2 : t_tp4)), (uint32_t)tp[f].size(), tp_chunks[f], f ? 2 : 4, K,
-                                sl.stream));
+        TH_HIP(launch_true_peak(reinterpret_cast<const TruePeakJob *>(dt + (f ? pl.t_tp2 : pl.t_tp4)), (uint32_t)pl.tp[f].size(), pl.tp_chunks[f],
+                                f ? 2 : 4, K, sl.stream));
     }
     std::vector<unsigned char> big;
     const unsigned char *res = sl.h_tile;
-    if (res_bytes <= TILE_BYTES_MAX) {
-        TH_HIP(hipMemcpyAsync(sl.h_tile, dm, res_bytes, hipMemcpyDeviceToHost, sl.stream));
+    if (pl.res_bytes <= TILE_BYTES_MAX) {
+        TH_HIP(hipMemcpyAsync(sl.h_tile, dm, pl.res_bytes, hipMemcpyDeviceToHost, sl.stream));
     } else {
-        big.resize(res_bytes);
+        big.resize(pl.res_bytes);
         res = big.data();
-        TH_HIP(hipMemcpyAsync(big.data(), dm, res_bytes, hipMemcpyDeviceToHost, sl.stream));
+        TH_HIP(hipMemcpyAsync(big.data(), dm, pl.res_bytes, hipMemcpyDeviceToHost, sl.stream));
     }
     TH_HIP(hipStreamSynchronize(sl.stream));
-    // the host's part: LUFS, maxima, the loudness range, the channel of the peak
-    const double *energies = reinterpret_cast<const double *>(res);
-    const uint32_t *pka = reinterpret_cast<const uint32_t *>(res + o_pka), *pkt = reinterpret_cast<const uint32_t *>(res + o_pkt);
-    std::vector<double> lufs, sub;
-    for (size_t i = 0; i < n; i++) {
-        th_loudness_meter &m = ms[i];
-        if (loudness_rate_ok(trs[i]->sr)) {
-            lufs.resize(m.n_momentary + m.n_short_term);
-            const double *e = energies + e0[i];
-            for (size_t k = 0; k < lufs.size(); k++) lufs[k] = loudness_lufs(e[k]);
-            // (meters_layout: the short-term values follow the momentary ones)
-            if (series && !lufs.empty()) std::memcpy(series + m.momentary_offset, lufs.data(), lufs.size() * sizeof(double));
-            m.max_momentary_lufs = loudness_series_max(lufs.data(), m.n_momentary);
-            m.max_short_term_lufs = loudness_series_max(lufs.data() + m.n_momentary, m.n_short_term);
-            sub.clear();
-            for (size_t k = 0; k < m.n_short_term; k += 10) sub.push_back(e[m.n_momentary + k]);
-            m.loudness_range = loudness_range(sub.data(), sub.size());
-        } else {
-            m.loudness_range = m.max_momentary_lufs = m.max_short_term_lufs = NAN;
-        }
-        const uint32_t *pk = m.oversampling > 1 ? pkt : pka;
-        float peak = 0.0f;
-        uint32_t at = 0;
-        for (size_t k = 0; k < trs[i]->ch.size(); k++) {
-            float p;
-            std::memcpy(&p, &pk[ch0[i] + k], 4);
-            if (p > peak) {
-                peak = p;
-                at = (uint32_t)k;
-            }
-        }
-        m.true_peak = peak;
-        m.true_peak_dB = peak == 0.0f ? -INFINITY : (float)(20.0 * std::log10((double)peak));
-        m.true_peak_channel = at;
-    }
+    std::vector<th_loudness_meter *> meters(n);
+    for (size_t i = 0; i < n; i++) meters[i] = &ms[i];
+    meter_results(res, pl, meters.data(), series);
     return TH_OK;
 }
 }  // namespace tmi
@@ -1832,8 +1707,7 @@ TH_API int th_tm_get_loudness_meters(th_tm *tm, const size_t *ids, size_t n, th_
     std::shared_lock<std::shared_mutex> rl(tm->rw);
     std::vector<tmi::MeterInfo> ms(n);
     for (size_t i = 0; i < n; i++) TH_CHECK(tmi::loudness_meter_info(tm, ids[i], &ms[i]));
-    size_t n_ch = 0;
-    TH_CHECK(meters_fit_one_launch(ms.data(), n, &n_ch));  // (reported before a short buffer)
+    TH_CHECK(meters_fit_one_launch(ms.data(), n));  // (reported before a short buffer)
     const size_t total = tmi::meters_layout(ms.data(), n);
     const uint64_t revision = tm->waveform_revision();
     for (size_t i = 0; i < n; i++) {
@@ -2630,16 +2504,8 @@ TH_API int th_tm_copy_audio(th_tm *tm, size_t id, uint32_t ch, int which, float 
 // contiguous run of output bytes into the caller's buffer, on the slot's copy stream, while the next piece is computed.  The bytes in
 // staging sit at the same address modulo 16 as in the caller's image, so a run is one copy.
 namespace {
-constexpr size_t EXPORT_STAGE_MAX = (size_t)TH_EXPORT_PIECE_BYTES + 64;
-
-// the resampler of a request: on == false when the request keeps the track's rate
-struct RatePlan {
-    bool on = false;
-    th_resample_plan plan{};
-    size_t n_out = 0;
-};
-
-int check_export_request(th_tm *tm, const th_export_at_request &ar, size_t i, const Track **trp, RatePlan *rp, size_t *s0, size_t *s1) {
+// the check of one request; *info: the track, the resampler of a request that leaves the track's rate, the sample range at info->sr
+int check_export_request(th_tm *tm, const th_export_at_request &ar, size_t i, tmi::ExportInfo *info) {
     const th_export_request &r = ar.base;
     auto it = tm->tracks.find(r.id);
     if (it == tm->tracks.end()) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", r.id);
@@ -2648,23 +2514,25 @@ int check_export_request(th_tm *tm, const th_export_at_request &ar, size_t i, co
     TH_REQUIRE(r.format <= TH_PCM_F32, "request %zu: unknown format %u", i, r.format);
     TH_REQUIRE(r.dither <= TH_DITHER_TPDF, "request %zu: unknown dither %u", i, r.dither);
     size_t n = tr.ch.empty() ? 0 : tr.ch[0].n;
-    uint32_t sr = tr.sr;
-    *rp = RatePlan{};
+    *info = tmi::ExportInfo{};
+    info->sr = tr.sr;
     if (ar.sr_out != 0 && ar.sr_out != tr.sr) {
-        const int rc = resample_plan(tr.sr, ar.sr_out, &rp->plan);
+        const int rc = resample_plan(tr.sr, ar.sr_out, &info->plan);
         TH_REQUIRE(rc != 1, "request %zu: Track %zu has no sample rate", i, r.id);
-        if (rc != 0 || !resample_n_out(n, rp->plan, &rp->n_out))
+        if (rc != 0 || !resample_n_out(n, info->plan, &info->n_out))
             return fail(TH_ERR_UNSUPPORTED, "request %zu: %u -> %u Hz is beyond the resampler's limits (%u taps, %u coefficients, 64-bit indices)",
                         i, tr.sr, ar.sr_out, TH_RESAMPLE_MAX_TAPS, TH_RESAMPLE_MAX_COEFS);
-        rp->on = true;
-        n = rp->n_out;
-        sr = ar.sr_out;
+        n = info->n_out;
+        info->sr = ar.sr_out;
     }
-    TH_REQUIRE(spectrum_frame_range(sr, 1, n, r.start_sec, r.end_sec, s0, s1), "request %zu: bad time range [%g, %g) s", i,
+    size_t s0 = 0, s1 = 0;
+    TH_REQUIRE(spectrum_frame_range(info->sr, 1, n, r.start_sec, r.end_sec, &s0, &s1), "request %zu: bad time range [%g, %g) s", i,
                r.start_sec, r.end_sec);
     if (tr.ch.empty() || tr.ch.size() > TH_EXPORT_MAX_CHANNELS)
         return fail(TH_ERR_UNSUPPORTED, "Track %zu: %zu channels (1 .. %d can be exported)", r.id, tr.ch.size(), TH_EXPORT_MAX_CHANNELS);
-    *trp = &tr;
+    info->sample_start = s0;
+    info->sample_end = s1;
+    info->track = &tr;
     return TH_OK;
 }
 
@@ -2677,32 +2545,19 @@ struct ExportDrain {
     }
 };
 
-int ensure_export_stage(ReaderSlot &sl, int b, size_t bytes) {
-    if (bytes <= sl.exp_stage_cap[b]) return TH_OK;
-    size_t want = 1 << 20;  // powers of two from 1 MiB, never above one piece
-    while (want < bytes) want <<= 1;
-    want = std::min(want, EXPORT_STAGE_MAX);
+// One of the slot's export buffers grows to hold `need` elements: `floor` doubled until it does, at most `ceil`.  The stream that
+// uses it (and `also`, when a second one does) is idle before the old buffer goes; the capacity is 0 while the allocation is pending
+template <class T>
+int grow_export_buf(ReaderSlot &sl, DeviceBuf<T> &buf, size_t &cap, size_t need, size_t floor, size_t ceil, hipStream_t also) {
+    if (need <= cap) return TH_OK;
+    size_t want = floor;
+    while (want < need) want <<= 1;
+    want = std::min(want, ceil);
     TH_HIP(hipStreamSynchronize(sl.stream));
-    if (sl.exp_copy) TH_HIP(hipStreamSynchronize(sl.exp_copy));
-    sl.exp_stage_cap[b] = 0;
-    TH_HIP(sl.exp_stage[b].alloc(want));
-    sl.exp_stage_cap[b] = want;
-    return TH_OK;
-}
-
-// the planar scratch of a piece: frames x channels x 4 bytes, and per job up to 7 frames more (the hull on the grid of 4 frames and
-// the channel pitch), so 2 x TH_EXPORT_PIECE_BYTES (16-bit output) + 64 KiB bounds it; a piece is closed before it would need more
-constexpr size_t RESAMPLE_SCRATCH_MAX = 2 * (size_t)TH_EXPORT_PIECE_BYTES + (64u << 10);
-
-int ensure_resample_scratch(ReaderSlot &sl, size_t floats) {
-    if (floats <= sl.rs_scratch_cap) return TH_OK;
-    size_t want = 1 << 18;  // powers of two from 1 MiB, never above the bound
-    while (want < floats) want <<= 1;
-    want = std::min(want, RESAMPLE_SCRATCH_MAX / sizeof(float));
-    TH_HIP(hipStreamSynchronize(sl.stream));
-    sl.rs_scratch_cap = 0;
-    TH_HIP(sl.rs_scratch.alloc(want * sizeof(float)));
-    sl.rs_scratch_cap = want;
+    if (also) TH_HIP(hipStreamSynchronize(also));
+    cap = 0;
+    TH_HIP(buf.alloc(want * sizeof(T)));
+    cap = want;
     return TH_OK;
 }
 
@@ -2714,12 +2569,7 @@ int ensure_resample_table(ReaderSlot &sl, uint32_t sr_in, uint32_t sr_out, const
     host->resize(floats);
     resample_table(plan, host->data());
     sl.rs_sr_in = sl.rs_sr_out = 0;
-    if (floats > sl.rs_table_cap) {
-        TH_HIP(hipStreamSynchronize(sl.stream));
-        sl.rs_table_cap = 0;
-        TH_HIP(sl.rs_table.alloc(floats * sizeof(float)));
-        sl.rs_table_cap = floats;
-    }
+    TH_CHECK(grow_export_buf(sl, sl.rs_table, sl.rs_table_cap, floats, floats, floats, nullptr));  // (exactly the table)
     TH_HIP(hipMemcpyAsync(sl.rs_table.get(), host->data(), floats * sizeof(float), hipMemcpyHostToDevice, sl.stream));
     sl.rs_sr_in = sr_in;
     sl.rs_sr_out = sr_out;
@@ -2740,17 +2590,10 @@ int wav_header_checked(uint32_t format, uint32_t sr, uint32_t n_ch, uint64_t n_f
     return TH_OK;
 }
 
-int export_request_info(th_tm *tm, const th_export_at_request &r, size_t i, th_export_info *info) {
-    const Track *tr = nullptr;
-    RatePlan rp;
-    size_t s0 = 0, s1 = 0;
-    TH_CHECK(check_export_request(tm, r, i, &tr, &rp, &s0, &s1));
-    *info = th_export_info{};
-    info->n_bytes = (uint64_t)(s1 - s0) * tr->ch.size() * export_bytes_per_sample(r.base.format);
-    info->sample_start = s0;
-    info->sample_end = s1;
-    info->sr = rp.on ? r.sr_out : tr->sr;
-    info->n_channels = (uint32_t)tr->ch.size();
+int export_request_info(th_tm *tm, const th_export_at_request &r, size_t i, ExportInfo *info) {
+    TH_CHECK(check_export_request(tm, r, i, info));
+    info->n_channels = (uint32_t)static_cast<const Track *>(info->track)->ch.size();
+    info->n_bytes = (uint64_t)(info->sample_end - info->sample_start) * info->n_channels * export_bytes_per_sample(r.base.format);
     info->waveform_revision = tm->waveform_revision();
     return TH_OK;
 }
@@ -2761,162 +2604,46 @@ std::vector<th_export_at_request> export_at_requests(const th_export_request *re
     return out;
 }
 
-void export_layout(th_export_info *info, size_t n, uint32_t *pad, size_t *out_len) {
+void export_layout(ExportInfo *info, size_t n, size_t *out_len) {
     uint64_t at = 0;
     for (size_t i = 0; i < n; i++) {
         info[i].offset = at;
         const uint64_t end = at + info[i].n_bytes;
         at = (end + 15) & ~(uint64_t)15;
-        pad[i] = i + 1 < n ? (uint32_t)(at - end) : 0u;
+        info[i].pad = i + 1 < n ? (uint32_t)(at - end) : 0u;
         if (i + 1 == n) at = end;
     }
     *out_len = (size_t)at;
 }
 
-int export_run(th_tm *tm, const th_export_at_request *reqs, size_t n, th_export_info *info, const uint32_t *pad, uint8_t *out) {
-    struct Run {
-        size_t stage_at;
-        uint64_t out_at;
-        size_t bytes;
-    };
-    struct Piece {
-        size_t job0 = 0, job1 = 0;
-        uint32_t n_chunks = 0;
-        size_t stage_bytes = 0;
-        std::vector<Run> runs;
-        // the resampler's launch in front of the export's: every resampled request of a piece has the piece's rate pair
-        size_t rjob0 = 0, rjob1 = 0;
-        uint32_t n_rblocks = 0, sr_in = 0, sr_out = 0;
-        size_t scratch_floats = 0;
-        th_resample_plan plan{};
-    };
-    struct Part {
-        size_t req, stage_at;
-        size_t scratch_at, ptr_at;  // resampled jobs: the job's runs in the scratch, its (biased) channel pointers
-        uint64_t hull0, stride;
-        bool resampled;
-    };
-    TH_REQUIRE(n <= UINT32_MAX, "too many requests");
-    std::vector<ExportJob> jobs;
-    std::vector<ResampleJob> rjobs;
-    std::vector<Part> parts;  // job j's request and place in its piece's staging buffer
-    std::vector<Piece> pieces;
-    std::vector<size_t> ptr0(n);  // request i's first channel pointer
-    std::vector<const float *> ptrs;
-    Piece cur;
-    uint64_t cur_out_end = 0;
-    auto close_piece = [&]() {
-        cur.job1 = jobs.size();
-        cur.rjob1 = rjobs.size();
-        pieces.push_back(std::move(cur));
-        cur = Piece{};
-        cur.job0 = jobs.size();
-        cur.rjob0 = rjobs.size();
-    };
+// plan_export (reader_plan.h) cuts the requests into pieces and bind_export gives the jobs their addresses; what is left here is the
+// slot, its buffers, the upload and the pipeline of the two streams
+int export_run(th_tm *tm, const th_export_at_request *reqs, size_t n, ExportInfo *info, uint8_t *out) {
+    std::vector<ExportPlanRequest> prs(n);
+    std::vector<const float *> chan;
     for (size_t i = 0; i < n; i++) {
         const th_export_request &r = reqs[i].base;
-        const Track &tr = tm->tracks.find(r.id)->second;  // (checked by the caller, under the same lock)
-        const uint32_t n_ch = (uint32_t)tr.ch.size();
-        const uint64_t fbytes = (uint64_t)n_ch * export_bytes_per_sample(r.format);
-        RatePlan rp;
-        if (info[i].sr != tr.sr) {  // (export_request_info has accepted the pair)
-            rp.on = resample_plan(tr.sr, info[i].sr, &rp.plan) == 0 && resample_n_out(tr.ch[0].n, rp.plan, &rp.n_out);
-            if (!rp.on) return fail(TH_ERR_INTERNAL, "request %zu: no resampler for %u -> %u Hz", i, tr.sr, info[i].sr);
-        }
-        const ResampleTiling tiling = rp.on ? resample_tiling(rp.plan) : ResampleTiling{};
-        const uint64_t F = export_chunk_frames(n_ch);
-        ptr0[i] = ptrs.size();
-        for (const Channel &c : tr.ch) ptrs.push_back(r.which == 0 ? c.d_wav : r.which == 1 ? c.d_draw : c.d_orig);
-        uint64_t f = info[i].sample_start;
-        const uint64_t s0 = info[i].sample_start, s1 = info[i].sample_end;
-        while (f < s1) {
-            if (rp.on && cur.sr_out != 0 && (cur.sr_in != tr.sr || cur.sr_out != info[i].sr)) {  // (one table per launch)
-                close_piece();
-                continue;
-            }
-            const uint64_t out_at = info[i].offset + (f - s0) * fbytes;
-            const bool contiguous = !cur.runs.empty() && out_at == cur_out_end;
-            const size_t at = contiguous ? cur.stage_bytes : ((cur.stage_bytes + 15) & ~(size_t)15) + (size_t)(out_at & 15);
-            const uint64_t room = at < TH_EXPORT_PIECE_BYTES ? (TH_EXPORT_PIECE_BYTES - at) / fbytes : 0;
-            if (room == 0) {  // (a frame is at most 4 KiB: an empty piece always has room)
-                close_piece();
-                continue;
-            }
-            uint64_t take = std::min<uint64_t>(room, s1 - f);
-            // a resampled request is cut on the export kernel's chunk grid, and its hull on the grid of 4 frames is what the
-            // resampler makes: the export kernel's 16-byte loads then stay aligned and inside what was written
-            uint64_t hull0 = 0, stride = 0;
-            if (rp.on) {
-                if (f + take < s1) {
-                    const uint64_t cut = (f + take) / F * F;
-                    if (cut <= f) {  // (an empty piece has room for a whole chunk: at most 16 KiB)
-                        close_piece();
-                        continue;
-                    }
-                    take = cut - f;
-                }
-                hull0 = f & ~(uint64_t)3;
-                const uint64_t hull1 = std::min<uint64_t>((f + take + 3) & ~(uint64_t)3, rp.n_out);
-                stride = (hull1 - hull0 + 3) & ~(uint64_t)3;
-                if ((cur.scratch_floats + stride * n_ch) * sizeof(float) > RESAMPLE_SCRATCH_MAX) {
-                    if (jobs.size() == cur.job0)
-                        return fail(TH_ERR_INTERNAL, "request %zu: a piece of %llu frames exceeds the resampler's scratch", i, (unsigned long long)take);
-                    close_piece();
-                    continue;
-                }
-            }
-            const uint32_t pd = f + take == s1 ? pad[i] : 0u;
-            const size_t bytes = (size_t)(take * fbytes) + pd;
-            ExportJob j{};
-            j.f0 = f;
-            j.f1 = f + take;
-            j.n = rp.on ? rp.n_out : tr.ch[0].n;
-            j.n_ch = n_ch;
-            j.format = r.format;
-            j.dither = r.dither;
-            j.seed = r.seed;
-            j.first_chunk = cur.n_chunks;
-            j.pad = pd;
-            const uint64_t chunks = (uint64_t)cur.n_chunks + export_n_chunks(j.f0, j.f1, n_ch);
-            if (chunks > INT32_MAX) return fail(TH_ERR_UNSUPPORTED, "request %zu: too many chunks in one piece", i);
-            Part part{i, at, 0, 0, hull0, stride, rp.on};
-            if (rp.on) {
-                const uint64_t hull1 = std::min<uint64_t>(hull0 + stride, rp.n_out);
-                ResampleJob rj{};
-                rj.ja = hull0;
-                rj.jb = hull1;
-                rj.n_in = tr.ch[0].n;
-                rj.ch_stride = stride;
-                rj.n_ch = n_ch;
-                const uint64_t n_sb = resample_n_sb(rj.ja, rj.jb, tiling);
-                const uint64_t blocks = (uint64_t)cur.n_rblocks + n_sb * n_ch * tiling.S;
-                if (n_sb > UINT32_MAX || blocks > INT32_MAX) return fail(TH_ERR_UNSUPPORTED, "request %zu: too many resampler tiles in one piece", i);
-                rj.n_sb = (uint32_t)n_sb;
-                rj.first_block = cur.n_rblocks;
-                cur.n_rblocks = (uint32_t)blocks;
-                part.scratch_at = cur.scratch_floats;
-                part.ptr_at = ptrs.size();
-                ptrs.resize(ptrs.size() + n_ch, nullptr);  // (filled once the scratch has its address)
-                cur.scratch_floats += stride * n_ch;
-                cur.sr_in = tr.sr;
-                cur.sr_out = info[i].sr;
-                cur.plan = rp.plan;
-                rjobs.push_back(rj);
-            }
-            cur.n_chunks = (uint32_t)chunks;
-            jobs.push_back(j);
-            parts.push_back(part);
-            if (contiguous)
-                cur.runs.back().bytes += bytes;
-            else
-                cur.runs.push_back(Run{at, out_at, bytes});
-            cur.stage_bytes = at + bytes;
-            cur_out_end = out_at + bytes;
-            f += take;
-        }
+        const Track &tr = *static_cast<const Track *>(info[i].track);
+        ExportPlanRequest &pr = prs[i];
+        pr.n_ch = info[i].n_channels;
+        pr.sr_in = tr.sr;
+        pr.sr_out = info[i].sr;
+        pr.n_in = tr.ch[0].n;
+        pr.plan = info[i].plan;
+        pr.n_out = info[i].n_out;
+        pr.format = r.format;
+        pr.dither = r.dither;
+        pr.seed = r.seed;
+        pr.s0 = info[i].sample_start;
+        pr.s1 = info[i].sample_end;
+        pr.offset = info[i].offset;
+        pr.pad = info[i].pad;
+        for (const Channel &c : tr.ch) chan.push_back(r.which == 0 ? c.d_wav : r.which == 1 ? c.d_draw : c.d_orig);
+        info[i].n_clamped = info[i].n_nan = 0;
     }
-    if (cur.n_chunks) close_piece();
-    for (size_t i = 0; i < n; i++) info[i].n_clamped = info[i].n_nan = 0;
+    ExportPlan pl = plan_export(prs.data(), n);
+    if (pl.err != TH_OK) return fail(pl.err, "%s", pl.err_text.c_str());
+    const std::vector<ExportPiece> &pieces = pl.pieces;
     if (pieces.empty()) return TH_OK;
 
     TH_HIP(hipSetDevice(tm->ctx->device));
@@ -2933,51 +2660,23 @@ int export_run(th_tm *tm, const th_export_at_request *reqs, size_t n, th_export_
     }
     std::vector<std::vector<float>> host_tables(pieces.size());  // (behind the drain: alive until the uploads are done)
     ExportDrain drain{&sl};
-    size_t need[2] = {0, 0}, need_scratch = 0;
-    for (size_t p = 0; p < pieces.size(); p++) {
-        need[p & 1] = std::max(need[p & 1], pieces[p].stage_bytes);
-        need_scratch = std::max(need_scratch, pieces[p].scratch_floats);
-    }
-    for (int b = 0; b < 2; b++)
-        if (need[b]) TH_CHECK(ensure_export_stage(sl, b, need[b]));
-    if (need_scratch) TH_CHECK(ensure_resample_scratch(sl, need_scratch));
+    for (int b = 0; b < 2; b++)  // powers of two from 1 MiB, never above one piece; the copy stream reads them too
+        TH_CHECK(grow_export_buf(sl, sl.exp_stage[b], sl.exp_stage_cap[b], pl.stage_need[b], 1 << 20, EXPORT_STAGE_MAX, sl.exp_copy));
+    // (floats) powers of two from 1 MiB, never above the bound
+    TH_CHECK(grow_export_buf(sl, sl.rs_scratch, sl.rs_scratch_cap, pl.scratch_need, 1 << 18, RESAMPLE_SCRATCH_MAX / sizeof(float), nullptr));
     // one table for the whole call: the export jobs of every piece, the resampler's jobs, then the channel pointers
-    const size_t jobs_bytes = jobs.size() * sizeof(ExportJob), rjobs_bytes = rjobs.size() * sizeof(ResampleJob);
-    const size_t tab_bytes = jobs_bytes + rjobs_bytes + ptrs.size() * sizeof(const float *);
-    TH_CHECK(sl.exp_tab.ensure(tab_bytes));
+    TH_CHECK(sl.exp_tab.ensure(pl.tab_bytes));
     TH_CHECK(sl.exp_cnt.ensure(n * 2 * sizeof(unsigned long long)));
     unsigned char *d_tab = static_cast<unsigned char *>(sl.exp_tab.dptr);
-    const float *const *d_ptrs = reinterpret_cast<const float *const *>(d_tab + jobs_bytes + rjobs_bytes);
     unsigned long long *d_cnt = static_cast<unsigned long long *>(sl.exp_cnt.dptr);
-    for (size_t p = 0; p < pieces.size(); p++) {
-        size_t rj = pieces[p].rjob0;
-        for (size_t j = pieces[p].job0; j < pieces[p].job1; j++) {
-            const Part &pt = parts[j];
-            jobs[j].chan = d_ptrs + ptr0[pt.req];
-            jobs[j].dst = sl.exp_stage[p & 1].get() + pt.stage_at;
-            jobs[j].cnt = d_cnt + 2 * pt.req;
-            if (!pt.resampled) continue;
-            // the export kernel indexes a channel by the absolute output frame: bias the run's address by the hull's first frame
-            // (the run and the hull start on 16-byte boundaries, so the biased pointer is 16-byte aligned as well)
-            float *run = sl.rs_scratch.get() + pt.scratch_at;
-            for (uint32_t c = 0; c < jobs[j].n_ch; c++)
-                ptrs[pt.ptr_at + c] = reinterpret_cast<const float *>(reinterpret_cast<uintptr_t>(run + (size_t)c * pt.stride) - (uintptr_t)pt.hull0 * sizeof(float));
-            jobs[j].chan = d_ptrs + pt.ptr_at;
-            rjobs[rj].chan = d_ptrs + ptr0[pt.req];
-            rjobs[rj].dst = run;
-            rj++;
-        }
-    }
-    std::vector<unsigned char> tab(tab_bytes);
-    std::memcpy(tab.data(), jobs.data(), jobs_bytes);
-    if (rjobs_bytes) std::memcpy(tab.data() + jobs_bytes, rjobs.data(), rjobs_bytes);
-    std::memcpy(tab.data() + jobs_bytes + rjobs_bytes, ptrs.data(), tab_bytes - jobs_bytes - rjobs_bytes);
-    TH_CHECK(sl.exp_tab.upload(sl.stream, tab.data(), tab_bytes));
+    const std::vector<unsigned char> tab =
+        bind_export(pl, ExportBases{{sl.exp_stage[0].get(), sl.exp_stage[1].get()}, sl.rs_scratch.get(), d_tab, d_cnt}, chan.data());
+    TH_CHECK(sl.exp_tab.upload(sl.stream, tab.data(), tab.size()));
     TH_HIP(hipMemsetAsync(d_cnt, 0, n * 2 * sizeof(unsigned long long), sl.stream));
     const ExportJob *d_jobs = reinterpret_cast<const ExportJob *>(d_tab);
-    const ResampleJob *d_rjobs = reinterpret_cast<const ResampleJob *>(d_tab + jobs_bytes);
+    const ResampleJob *d_rjobs = reinterpret_cast<const ResampleJob *>(d_tab + pl.o_rjobs);
     auto launch_piece = [&](size_t p) -> int {
-        const Piece &pc = pieces[p];
+        const ExportPiece &pc = pieces[p];
         if (pc.n_rblocks) {  // (the stream's order keeps the scratch and the table from the last piece's readers)
             TH_CHECK(ensure_resample_table(sl, pc.sr_in, pc.sr_out, pc.plan, &host_tables[p]));
             TH_HIP(launch_resample(d_rjobs + pc.rjob0, (uint32_t)(pc.rjob1 - pc.rjob0), pc.n_rblocks, sl.rs_table.get(), resample_tiling(pc.plan), sl.stream));
@@ -2991,7 +2690,7 @@ int export_run(th_tm *tm, const th_export_at_request *reqs, size_t n, th_export_
     for (size_t p = 0; p < pieces.size(); p++) {
         if (p + 1 < pieces.size()) TH_CHECK(launch_piece(p + 1));  // (ahead of the copy: a copy into pageable memory holds the host)
         TH_HIP(hipStreamWaitEvent(sl.exp_copy, sl.exp_done[p & 1], 0));
-        for (const Run &run : pieces[p].runs)
+        for (const ExportRun &run : pieces[p].runs)
             TH_HIP(hipMemcpyAsync(out + run.out_at, sl.exp_stage[p & 1].get() + run.stage_at, run.bytes, hipMemcpyDeviceToHost, sl.exp_copy));
         TH_HIP(hipEventRecord(sl.exp_copied[p & 1], sl.exp_copy));
     }
@@ -3014,16 +2713,15 @@ int export_pcm_at(th_tm *tm, const th_export_at_request *reqs, size_t n, uint8_t
     *out_len = 0;
     if (n == 0) return TH_OK;
     std::shared_lock<std::shared_mutex> rl(tm->rw);
-    std::vector<th_export_info> infos(n);
-    std::vector<uint32_t> pad(n);
+    std::vector<tmi::ExportInfo> infos(n);
     for (size_t i = 0; i < n; i++) TH_CHECK(tmi::export_request_info(tm, reqs[i], i, &infos[i]));
     size_t total = 0;
-    tmi::export_layout(infos.data(), n, pad.data(), &total);
-    std::memcpy(info, infos.data(), n * sizeof(th_export_info));
+    tmi::export_layout(infos.data(), n, &total);
+    for (size_t i = 0; i < n; i++) info[i] = infos[i];
     *out_len = total;
     if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
-    TH_CHECK(tmi::export_run(tm, reqs, n, infos.data(), pad.data(), out));
-    std::memcpy(info, infos.data(), n * sizeof(th_export_info));
+    TH_CHECK(tmi::export_run(tm, reqs, n, infos.data(), out));
+    for (size_t i = 0; i < n; i++) info[i] = infos[i];
     return TH_OK;
 }
 
@@ -3031,7 +2729,7 @@ int export_wav_at(th_tm *tm, const th_export_at_request *req, uint8_t *out, size
     TH_REQUIRE(tm && req && out_len, "NULL argument");
     *out_len = 0;
     std::shared_lock<std::shared_mutex> rl(tm->rw);
-    th_export_info one{};
+    tmi::ExportInfo one{};
     TH_CHECK(tmi::export_request_info(tm, *req, 0, &one));
     uint8_t hdr[TH_WAV_HEADER_MAX];
     size_t hl = 0, pl = 0;
@@ -3041,8 +2739,7 @@ int export_wav_at(th_tm *tm, const th_export_at_request *req, uint8_t *out, size
     if (info) *info = one;
     *out_len = total;
     if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
-    const uint32_t pad = 0;
-    TH_CHECK(tmi::export_run(tm, req, 1, &one, &pad, out));
+    TH_CHECK(tmi::export_run(tm, req, 1, &one, out));
     std::memcpy(out, hdr, hl);
     if (pl) out[hl + one.n_bytes] = 0;
     if (info) *info = one;

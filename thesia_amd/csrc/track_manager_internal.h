@@ -64,7 +64,7 @@ void commit(th_tm *tm, StagedPtr staged);
 //   *_run: the device work for n requests that were checked and laid out.  It takes a reader slot, packs its own n results in the
 //     slot's areas and writes request i's to out + info[i].offset and nowhere else: the destinations ascend with i and need not be
 //     adjacent (the caller may hold a subset of a larger batch), so whatever lies between them is left alone.  The limits of one
-//     launch are checked here.
+//     launch are checked here (for the meters and the export: by their planners, reader_plan.h, which the run calls).
 struct SpectrumInfo : th_spectrum_info {  // + the channel's resident rows
     const float *rows;
     size_t pitch;
@@ -102,15 +102,19 @@ int tile_request_info(th_tm *tm, const th_tile_request &r, TileInfo *info);
 size_t tiles_layout(TileInfo *info, size_t n, size_t *offsets);
 int tiles_run(th_tm *tm, const th_tile_request *reqs, size_t n, const TileInfo *info, uint8_t *out);
 
-// Export.  *info: the byte count, the sample range, rate, channels, counts 0.  export_layout: offsets that are multiples of 16, the
-// zero bytes behind every request (pad[i]: up to the next offset; 0 behind the last).  export_run: request i's bytes, then pad[i] zero
-// bytes, and its two counts into info[i].
-// Every request carries its output rate (th_export_at_request; sr_out 0: the track's own, which is all th_tm_export_pcm asks for:
-// export_at_requests); info->sr is the rate the request comes out at, and a request whose info->sr is not the track's is resampled
-// by export_run (kernels_resample.hip into the slot's planar scratch, then the same export kernel)
-int export_request_info(th_tm *tm, const th_export_at_request &r, size_t i, th_export_info *info);
-void export_layout(th_export_info *info, size_t n, uint32_t *pad, size_t *out_len);
-int export_run(th_tm *tm, const th_export_at_request *reqs, size_t n, th_export_info *info, const uint32_t *pad, uint8_t *out);
+// Export.  Every request carries its output rate (th_export_at_request; sr_out 0: the track's own, which is all th_tm_export_pcm asks
+// for: export_at_requests); info->sr is the rate the request comes out at, and a request whose info->sr is not the track's is resampled.
+// export_layout: offsets that are multiples of 16, and in info[i].pad the zero bytes up to the next one (0 behind the last).
+// export_run: request i's bytes, then info[i].pad zero bytes, and its two counts into info[i]
+struct ExportInfo : th_export_info {  // + the track (a Track of track_manager.hip), its resampler, the zero bytes behind the request
+    const void *track;
+    th_resample_plan plan;  // of (the track's rate, sr) when they differ, and the track's length at sr
+    size_t n_out;
+    uint32_t pad;
+};
+int export_request_info(th_tm *tm, const th_export_at_request &r, size_t i, ExportInfo *info);
+void export_layout(ExportInfo *info, size_t n, size_t *out_len);
+int export_run(th_tm *tm, const th_export_at_request *reqs, size_t n, ExportInfo *info, uint8_t *out);
 std::vector<th_export_at_request> export_at_requests(const th_export_request *reqs, size_t n);
 // th_wav_header with the status reported (host_math.h wav_header)
 int wav_header_checked(uint32_t format, uint32_t sr, uint32_t n_ch, uint64_t n_frames, uint8_t out[TH_WAV_HEADER_MAX], size_t *header_len,

@@ -611,11 +611,10 @@ TH_API int th_tmg_get_loudness_meter(th_tmg *g, size_t id, th_loudness_meter *me
 
 // Export: the same shape; a slot also writes the zero padding behind each of its requests, and its two counts come back into infos
 namespace {
-int export_on_slots(th_tmg *g, const Split &sp, const th_export_at_request *reqs, std::vector<th_export_info> &infos, const std::vector<uint32_t> &pad,
-                    uint8_t *out) {
+int export_on_slots(th_tmg *g, const Split &sp, const th_export_at_request *reqs, std::vector<tmi::ExportInfo> &infos, uint8_t *out) {
     return run_on_owners(g, sp, [&](th_tm *tm, const std::vector<size_t> &idx) -> int {
-        std::vector<th_export_info> si = gather(infos.data(), idx);
-        TH_CHECK(tmi::export_run(tm, gather(reqs, idx).data(), idx.size(), si.data(), gather(pad.data(), idx).data(), out));
+        std::vector<tmi::ExportInfo> si = gather(infos.data(), idx);
+        TH_CHECK(tmi::export_run(tm, gather(reqs, idx).data(), idx.size(), si.data(), out));
         for (size_t j = 0; j < idx.size(); j++) {
             infos[idx[j]].n_clamped = si[j].n_clamped;
             infos[idx[j]].n_nan = si[j].n_nan;
@@ -624,11 +623,11 @@ int export_on_slots(th_tmg *g, const Split &sp, const th_export_at_request *reqs
     });
 }
 
-int export_check_all(th_tmg *g, const th_export_at_request *reqs, size_t n, std::vector<th_export_info> &infos, Split *sp) {
+int export_check_all(th_tmg *g, const th_export_at_request *reqs, size_t n, std::vector<tmi::ExportInfo> &infos, Split *sp) {
     TH_CHECK(check_and_split(g, n, [&](size_t i) { return reqs[i].base.id; },
                              [&](th_tm *tm, size_t i) { return tmi::export_request_info(tm, reqs[i], i, &infos[i]); }, sp));
     const uint64_t revision = revisions(g).first;
-    for (th_export_info &f : infos) f.waveform_revision = revision;
+    for (tmi::ExportInfo &f : infos) f.waveform_revision = revision;
     return TH_OK;
 }
 }  // namespace
@@ -639,17 +638,16 @@ int tmg_export_pcm_at(th_tmg *g, const th_export_at_request *reqs, size_t n, uin
     *out_len = 0;
     if (n == 0) return TH_OK;
     std::shared_lock<std::shared_mutex> rl(g->rw);
-    std::vector<th_export_info> infos(n);
-    std::vector<uint32_t> pad(n);
+    std::vector<tmi::ExportInfo> infos(n);
     Split sp;
     TH_CHECK(export_check_all(g, reqs, n, infos, &sp));
     size_t total = 0;
-    tmi::export_layout(infos.data(), n, pad.data(), &total);
-    std::memcpy(info, infos.data(), n * sizeof(th_export_info));
+    tmi::export_layout(infos.data(), n, &total);
+    for (size_t i = 0; i < n; i++) info[i] = infos[i];
     *out_len = total;
     if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
-    TH_CHECK(export_on_slots(g, sp, reqs, infos, pad, out));
-    std::memcpy(info, infos.data(), n * sizeof(th_export_info));
+    TH_CHECK(export_on_slots(g, sp, reqs, infos, out));
+    for (size_t i = 0; i < n; i++) info[i] = infos[i];
     return TH_OK;
 }
 
@@ -657,7 +655,7 @@ int tmg_export_wav_at(th_tmg *g, const th_export_at_request *req, uint8_t *out, 
     TH_REQUIRE(g && req && out_len, "NULL argument");
     *out_len = 0;
     std::shared_lock<std::shared_mutex> rl(g->rw);
-    std::vector<th_export_info> one(1);
+    std::vector<tmi::ExportInfo> one(1);
     Split sp;
     TH_CHECK(export_check_all(g, req, 1, one, &sp));
     uint8_t hdr[TH_WAV_HEADER_MAX];
@@ -668,7 +666,7 @@ int tmg_export_wav_at(th_tmg *g, const th_export_at_request *req, uint8_t *out, 
     if (info) *info = one[0];
     *out_len = total;
     if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
-    TH_CHECK(export_on_slots(g, sp, req, one, std::vector<uint32_t>{0}, out));
+    TH_CHECK(export_on_slots(g, sp, req, one, out));
     std::memcpy(out, hdr, hl);
     if (pl) out[hl + one[0].n_bytes] = 0;
     if (info) *info = one[0];
