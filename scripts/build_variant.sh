@@ -3,6 +3,8 @@
 # THESIA_AMD_LIB=scripts/variants/libthesia_amd_<tag>.so python scripts/bench_stft.py).
 # usage: scripts/build_variant.sh <tag> [flags...]     (run after __graft_entry__.build())
 # By default only kernels_stft.hip is recompiled; VARIANT_SOURCES="kernels_image.hip api.hip" picks others.
+# Only the named sources see the flags: an image-stage variant that changes how jobs are cut (-DTH_FUSED_FB, -DTH_RASTER_QPB, ...) must
+# name batch_plan.cpp as well, where the planners count blocks with the same constants: VARIANT_SOURCES="kernels_image.hip batch_plan.cpp".
 # The link list and each source's own flags come from __graft_entry__ (SOURCES, EXTRA_FLAGS): the variant links what the product does.
 set -e
 tag=$1; shift

@@ -886,3 +886,162 @@ EMU_API void *emu_meter_results(const uint64_t *rows, uint64_t n, const unsigned
     e->add(series);
     return e;
 }
+
+// ---- the image, raster and waveform batch entries' plans (batch_plan.h), for tests/test_batch_plan_host.py.  Descriptors come as rows
+// of u64 in the order of their struct's fields, pointers as addresses (a planner never reads through them).  Blob 0 of every plan
+// starts with the error code, blob 1 is the error text (bytes).
+#include "../../thesia_amd/csrc/batch_plan.h"  // (batch_plan.cpp is compiled in)
+template <class T>
+static T *emu_ptr(uint64_t a) { return reinterpret_cast<T *>((uintptr_t)a); }
+static uint64_t emu_addr(const void *p) { return (uint64_t)(uintptr_t)p; }
+static EmuBlobs *emu_status(const PlanStatus &p, std::initializer_list<uint64_t> more) {
+    EmuBlobs *e = new EmuBlobs;
+    std::vector<uint64_t> head{(uint64_t)(int64_t)p.err};
+    head.insert(head.end(), more.begin(), more.end());
+    e->add(head);
+    e->add(std::vector<char>(p.err_text.begin(), p.err_text.end()));
+    return e;
+}
+static th_img_desc emu_img_desc(const uint64_t *r) {
+    return th_img_desc{emu_ptr<const float>(r[0]), emu_ptr<uint16_t>(r[1]), r[2], r[3], r[4], r[5], r[6], r[7]};
+}
+static float emu_f32(uint32_t bits) {
+    float f;
+    std::memcpy(&f, &bits, 4);
+    return f;
+}
+// check_img.  rows of 8: th_img_desc; the range as float bits.  Blobs: 0 {err, all_neg_inf}
+EMU_API void *emu_check_img(const uint64_t *rows, uint64_t n, uint32_t min_bits, uint32_t max_bits, uint64_t d_range) {
+    std::vector<th_img_desc> d(n);
+    for (uint64_t i = 0; i < n; i++) d[i] = emu_img_desc(rows + 8 * i);
+    const float lo = emu_f32(min_bits), hi = emu_f32(max_bits);
+    return emu_status(check_img(d.data(), n, lo, hi, emu_ptr<const float>(d_range)), {db_range_all_neg_inf(lo, hi, emu_ptr<const float>(d_range))});
+}
+// plan_img.  Blobs: 0 {err, n_blocks}; 2 jobs, rows of {spec, img, n_frames, height, i_start, i_end, spec_pitch, img_pitch, first_tile,
+// n_tiles}; 3 the block -> job table (u32)
+EMU_API void *emu_plan_img(const uint64_t *rows, uint64_t n) {
+    std::vector<th_img_desc> d(n);
+    for (uint64_t i = 0; i < n; i++) d[i] = emu_img_desc(rows + 8 * i);
+    const ImgPlan p = plan_img(d.data(), n);
+    EmuBlobs *e = emu_status(p, {p.n_blocks});
+    std::vector<uint64_t> jobs;
+    for (const ImgJob &j : p.jobs)
+        jobs.insert(jobs.end(), {emu_addr(j.spec), emu_addr(j.img), j.n_frames, j.height, j.i_start, j.i_end, j.spec_pitch, j.img_pitch, j.first_tile, j.n_tiles});
+    e->add(jobs);
+    e->add(p.block_job);
+    return e;
+}
+// check_fused, then plan_fused.  rows of 11: th_img_desc, then {index of the image's first tile pointer in `tiles` (~0: tiles is NULL),
+// n_tiles_x, n_tiles_y}.  Blobs: 0 {err of the first of the two that failed, n_blocks, sizeof(th_img_tiles_desc)}; 2 the key
+// (bytes); 3 jobs, rows of {spec, img, n_frames, height, i_start, i_end, spec_pitch, img_pitch, first_block, n_bands, n_tx, n_ty,
+// tile0}; 4 the block -> job table (u32); 5 the pointer table
+EMU_API void *emu_plan_fused(const uint64_t *rows, uint64_t n, const uint64_t *tiles, uint32_t min_bits, uint32_t max_bits, uint64_t d_range) {
+    std::vector<th_img_tiles_desc> d(n);
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t *r = rows + 11 * i;
+        d[i] = th_img_tiles_desc{emu_img_desc(r), r[8] == ~0ull ? nullptr : reinterpret_cast<uint8_t *const *>(tiles + r[8]), (uint32_t)r[9], (uint32_t)r[10]};
+    }
+    std::vector<unsigned char> key;
+    const PlanStatus ok = check_fused(d.data(), n, emu_f32(min_bits), emu_f32(max_bits), emu_ptr<const float>(d_range), &key);
+    const FusedPlan p = ok.err == TH_OK ? plan_fused(d.data(), n) : FusedPlan{};
+    EmuBlobs *e = emu_status(ok.err != TH_OK ? ok : p, {p.n_blocks, sizeof(th_img_tiles_desc)});
+    e->add(key);
+    std::vector<uint64_t> jobs, ptrs;
+    for (const FusedJob &j : p.jobs)
+        jobs.insert(jobs.end(), {emu_addr(j.spec), emu_addr(j.img), j.n_frames, j.height, j.i_start, j.i_end, j.spec_pitch, j.img_pitch, j.first_block,
+                                 j.n_bands, j.n_tx, j.n_ty, j.tile0});
+    for (const uint8_t *t : p.ptrs) ptrs.push_back(emu_addr(t));
+    e->add(jobs);
+    e->add(p.block_job);
+    e->add(ptrs);
+    return e;
+}
+// plan_raster.  rows of 10: th_raster_desc.  Blobs: 0 {err, n_blocks}; 2 jobs, rows of {img, rgba, img_width, img_height, origin_x,
+// origin_y, width, height, img_pitch, quads_per_row, inv_qpr, inv_width, first_block}; 3 the block -> job table (u32)
+EMU_API void *emu_plan_raster(const uint64_t *rows, uint64_t n) {
+    std::vector<th_raster_desc> d(n);
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t *r = rows + 10 * i;
+        d[i] = th_raster_desc{emu_ptr<const uint16_t>(r[0]), emu_ptr<uint8_t>(r[1]), (uint32_t)r[2], (uint32_t)r[3], (uint32_t)r[4], (uint32_t)r[5],
+                              (uint32_t)r[6], (uint32_t)r[7], (uint32_t)r[8], (uint32_t)r[9]};
+    }
+    const RasterPlan p = plan_raster(d.data(), n);
+    EmuBlobs *e = emu_status(p, {p.n_blocks});
+    std::vector<uint64_t> jobs;
+    for (const RasterJob &j : p.jobs)
+        jobs.insert(jobs.end(), {emu_addr(j.img), emu_addr(j.rgba), j.img_width, j.img_height, j.origin_x, j.origin_y, j.width, j.height, j.img_pitch,
+                                 j.quads_per_row, j.inv_qpr, j.inv_width, j.first_block});
+    e->add(jobs);
+    e->add(p.block_job);
+    return e;
+}
+// plan_wave_tiles.  rows of 6: th_wave_desc.  Blobs: 0 {err, n_blocks}; 2 jobs, rows of 6 as the descriptor; 3 the n + 1 starts (u32)
+EMU_API void *emu_plan_wave_tiles(const uint64_t *rows, uint64_t n) {
+    std::vector<th_wave_desc> d(n);
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t *r = rows + 6 * i;
+        d[i] = th_wave_desc{emu_ptr<const float>(r[0]), emu_ptr<float>(r[1]), r[2], r[3], (uint32_t)r[4], (uint32_t)r[5]};
+    }
+    const WavePlan p = plan_wave_tiles(d.data(), n);
+    EmuBlobs *e = emu_status(p, {p.n_blocks});
+    std::vector<uint64_t> jobs;
+    for (const WaveJob &j : p.jobs) jobs.insert(jobs.end(), {emu_addr(j.wav), emu_addr(j.bins), j.n_samples, j.start, j.level, j.bin_count});
+    e->add(jobs);
+    e->add(p.start);
+    return e;
+}
+// plan_stats.  rows of 2: th_stats_desc.  Blobs: 0 {err, max_samples}; 2 jobs, rows of {wav, n_samples, aligned16}
+EMU_API void *emu_plan_stats(const uint64_t *rows, uint64_t n) {
+    std::vector<th_stats_desc> d(n);
+    for (uint64_t i = 0; i < n; i++) d[i] = th_stats_desc{emu_ptr<const float>(rows[2 * i]), rows[2 * i + 1]};
+    const StatsPlan p = plan_stats(d.data(), n);
+    EmuBlobs *e = emu_status(p, {p.max_samples});
+    std::vector<uint64_t> jobs;
+    for (const StatsJob &j : p.jobs) jobs.insert(jobs.end(), {emu_addr(j.wav), j.n_samples, j.aligned16});
+    e->add(jobs);
+    return e;
+}
+// plan_pyramid, then bind_pyramid(sums).  rows of 5: th_pyramid_desc.  Blobs: 0 {err, sums_floats, max_samples, max_levels, launch};
+// 2 jobs, rows of 47: {wav, out, sums, n_samples, sums_half, n_levels, aligned16, level_off[40]}; 3 sums_at
+EMU_API void *emu_plan_pyramid(const uint64_t *rows, uint64_t n, uint64_t sums) {
+    std::vector<th_pyramid_desc> d(n);
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t *r = rows + 5 * i;
+        d[i] = th_pyramid_desc{emu_ptr<const float>(r[0]), emu_ptr<float>(r[1]), r[2], (uint32_t)r[3], (uint32_t)r[4]};
+    }
+    PyrPlan p = plan_pyramid(d.data(), n);
+    if (p.err == TH_OK) bind_pyramid(p, emu_ptr<float>(sums));
+    EmuBlobs *e = emu_status(p, {p.sums_floats, p.max_samples, p.max_levels, p.launch});
+    std::vector<uint64_t> jobs;
+    for (const PyrJob &j : p.jobs) {
+        jobs.insert(jobs.end(), {emu_addr(j.wav), emu_addr(j.out), emu_addr(j.sums), j.n_samples, j.sums_half, j.n_levels, j.aligned16});
+        jobs.insert(jobs.end(), j.level_off, j.level_off + PYR_MAX_LEVELS);
+    }
+    e->add(jobs);
+    e->add(p.sums_at);
+    return e;
+}
+// plan_lod_tile of tile (tx, ty) of level (lx, ly) of a W x H image (NULL: the tile is empty).  Blobs: 0 {err, y_lo, y_hi, n_rows, dw,
+// dh, y_at, taps_x, taps_y, lod_at, scratch_bytes, origin_x, origin_y, lod_w, lod_h}; 2 {left, top, crop_w, crop_h} (f64); 3 the tap blob
+EMU_API void *emu_plan_lod_tile(uint64_t W, uint64_t H, uint32_t lx, uint32_t ly, uint32_t tx, uint32_t ty) {
+    const TileGeom g = spectrogram_tile_geometry(W, H, lx, ly, tx, ty);
+    if (!g.width || !g.height) return nullptr;
+    const LodTilePlan p = plan_lod_tile(W, H, g, lx, ly);
+    EmuBlobs *e = emu_status(p, {(uint64_t)p.y_lo, (uint64_t)p.y_hi, p.n_rows, p.dw, p.dh, p.y_at, p.taps_x, p.taps_y, p.lod_at, p.scratch_bytes,
+                                 g.origin_x, g.origin_y, g.lod_w, g.lod_h});
+    e->add(std::vector<double>{p.left, p.top, p.crop_w, p.crop_h});
+    e->add(p.blob);
+    return e;
+}
+// the tile headers (host_math.h): 40 and 24 bytes into out; return the pixels / the bins of the tile
+EMU_API uint64_t emu_spectrogram_tile_header(uint8_t *out, uint64_t revision, uint64_t W, uint64_t H, uint32_t lx, uint32_t ly, uint32_t tx, uint32_t ty) {
+    const TileGeom g = spectrogram_tile_geometry(W, H, lx, ly, tx, ty);
+    put_spectrogram_tile_header(out, revision, g, lx, ly, tx, ty);
+    return g.width * g.height;
+}
+EMU_API uint64_t emu_waveform_tile_header(uint8_t *out, uint64_t revision, uint64_t n_samples, uint32_t level, uint32_t tile) {
+    size_t start, bins, spb;
+    waveform_tile_geometry(n_samples, level, tile, &start, &bins, &spb);
+    put_waveform_tile_header(out, revision, bins, spb, tile);
+    return bins;
+}

@@ -1045,6 +1045,10 @@ TH_API int th_calc_spec_host(th_plan *p, const float *wav, size_t n_samples, flo
 }
 
 // ------------------------------------------------------------------------------------------ spec → img
+// The batch entries below decide nothing here: batch_plan.h checks the descriptors and builds the job tables (plain data, tested on
+// the CPU), th_ctx's KeyedTables keep the device copies of the last batch, and what is left is upload and launch.
+static int plan_failed(const PlanStatus &p) { return fail(p.err, "%s", p.err_text.c_str()); }
+
 // shared body: host range (d_range == nullptr) or device-resident range [min_dB, max_dB]
 static int spec_to_img_impl(th_ctx *c, const th_img_desc *descs, size_t n, float min_dB, float max_dB, const float *d_range,
                             uint32_t colormap_len) {
@@ -1053,63 +1057,29 @@ static int spec_to_img_impl(th_ctx *c, const th_img_desc *descs, size_t n, float
     if (n == 0) return TH_OK;
     TH_REQUIRE(descs, "descs is NULL");
     TH_REQUIRE_ALIGNED(d_range, 4, "d_range must be 4-byte aligned");
-    for (size_t i = 0; i < n; i++) {
-        TH_REQUIRE_ALIGNED(descs[i].spec, 4, "desc %zu: spec must be 4-byte aligned", i);
-        TH_REQUIRE_ALIGNED(descs[i].img, 2, "desc %zu: img must be 2-byte aligned", i);
-    }
-    const bool all_neg_inf = !d_range && (min_dB == max_dB) && std::isinf(max_dB) && max_dB < 0;  // drawing.rs:16-18
-    if (!all_neg_inf && !d_range) TH_REQUIRE(std::isfinite(min_dB), "min_dB must be finite (drawing.rs:19)");
-    if (!all_neg_inf) {
-        // same batch as the previous call (re-quantise after a dB-range / colormap change, benchmark loops): the
-        // device tables are still valid, skip validation and table building
-        std::lock_guard<std::recursive_mutex> lk(c->mu);
-        if (c->img_descs_key.size() == n * sizeof(th_img_desc) && std::memcmp(c->img_descs_key.data(), descs, n * sizeof(th_img_desc)) == 0 &&
-            c->img_jobs.dptr && c->img_start.dptr) {
-            TH_HIP(hipSetDevice(c->device));
-            TH_HIP(launch_spec_to_img((const ImgJob *)c->img_jobs.dptr, (const uint32_t *)c->img_start.dptr, (uint32_t)n,
-                                      c->img_tiles_key, min_dB, max_dB, colormap_len, d_range, c->stream));
-            return TH_OK;
-        }
-    }
-    std::vector<ImgJob> jobs(n);
-    std::vector<uint32_t> start;  // job index of every block
-    uint64_t tiles = 0;
-    for (size_t i = 0; i < n; i++) {
-        const th_img_desc &d = descs[i];
-        TH_REQUIRE(d.i_end >= d.i_start, "desc %zu: i_end < i_start", i);
-        const uint64_t out_h = d.i_end - d.i_start;
-        TH_REQUIRE(d.n_frames < (1ull << 31) && d.height < (1ull << 31) && d.i_end < (1ull << 31), "desc %zu: too large", i);
-        TH_REQUIRE((d.spec && d.img) || out_h * d.n_frames == 0, "desc %zu: NULL device pointer", i);
-        TH_REQUIRE(d.spec_pitch == 0 || (d.spec_pitch >= d.height && d.spec_pitch < (1ull << 31)), "desc %zu: bad spec_pitch", i);
-        TH_REQUIRE(d.img_pitch == 0 || (d.img_pitch >= d.n_frames && d.img_pitch < (1ull << 31)), "desc %zu: bad img_pitch", i);
-        const uint64_t nt = ((d.n_frames + IMG_TILE_T - 1) / IMG_TILE_T) * ((out_h + IMG_TILE_F - 1) / IMG_TILE_F);
-        TH_REQUIRE(tiles + nt < (1ull << 27), "batch too large for one launch");
-        jobs[i] = ImgJob{d.spec, d.img, (uint32_t)d.n_frames, (uint32_t)d.height, (uint32_t)d.i_start, (uint32_t)d.i_end,
-                         (uint32_t)(d.spec_pitch ? d.spec_pitch : d.height), (uint32_t)(d.img_pitch ? d.img_pitch : d.n_frames),
-                         (uint32_t)tiles, (uint32_t)nt};
-        tiles += nt;
-        start.insert(start.end(), (size_t)nt, (uint32_t)i);  // block -> job table
-    }
+    const PlanStatus ok = check_img(descs, n, min_dB, max_dB, d_range);
+    if (ok.err != TH_OK) return plan_failed(ok);
+    const bool all_neg_inf = db_range_all_neg_inf(min_dB, max_dB, d_range);
+    const size_t key_bytes = n * sizeof(th_img_desc);
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     TH_HIP(hipSetDevice(c->device));
-    if (all_neg_inf) {
-        for (size_t i = 0; i < n; i++) {
-            const size_t rows = descs[i].i_end - descs[i].i_start, pitch = jobs[i].img_pitch;
-            if (rows && descs[i].n_frames)
-                TH_HIP(hipMemset2DAsync(descs[i].img, pitch * sizeof(uint16_t), 0, descs[i].n_frames * sizeof(uint16_t), rows,
-                                        c->stream));
+    if (all_neg_inf || !c->img.hit(descs, key_bytes)) {
+        const ImgPlan p = plan_img(descs, n);
+        if (p.err != TH_OK) return plan_failed(p);
+        if (all_neg_inf) {
+            for (size_t i = 0; i < n; i++) {
+                const size_t rows = descs[i].i_end - descs[i].i_start, pitch = p.jobs[i].img_pitch;
+                if (rows && descs[i].n_frames)
+                    TH_HIP(hipMemset2DAsync(descs[i].img, pitch * sizeof(uint16_t), 0, descs[i].n_frames * sizeof(uint16_t), rows,
+                                            c->stream));
+            }
+            return TH_OK;
         }
-        return TH_OK;
+        TH_CHECK(c->img.store(c->stream, descs, key_bytes, p.n_blocks,
+                              {{p.jobs.data(), p.jobs.size() * sizeof(ImgJob)}, {p.block_job.data(), p.block_job.size() * sizeof(uint32_t)}}));
     }
-    c->img_descs_key.clear();   // the tables are about to be overwritten: the key names them only once BOTH uploads succeeded
-    int rc = c->img_jobs.upload(c->stream, jobs.data(), jobs.size() * sizeof(ImgJob));
-    if (rc != TH_OK) return rc;
-    rc = c->img_start.upload(c->stream, start.data(), start.size() * sizeof(uint32_t));
-    if (rc != TH_OK) return rc;
-    c->img_descs_key.assign(reinterpret_cast<const unsigned char *>(descs), reinterpret_cast<const unsigned char *>(descs + n));
-    c->img_tiles_key = (uint32_t)tiles;
-    TH_HIP(launch_spec_to_img((const ImgJob *)c->img_jobs.dptr, (const uint32_t *)c->img_start.dptr, (uint32_t)n,
-                              (uint32_t)tiles, min_dB, max_dB, colormap_len, d_range, c->stream));
+    TH_HIP(launch_spec_to_img(c->img.at<ImgJob>(0), c->img.at<uint32_t>(1), (uint32_t)n, c->img.n_blocks, min_dB, max_dB, colormap_len,
+                              d_range, c->stream));
     return TH_OK;
     TH_CATCH
 }
@@ -1137,70 +1107,21 @@ TH_API int th_spec_to_img_raster_batch_dev(th_ctx *c, const th_img_tiles_desc *d
     TH_REQUIRE(n_colors <= 65536, "colormaps of more than 65536 entries are not supported");
     TH_REQUIRE_ALIGNED(d_colormap, 4, "d_colormap must be 4-byte aligned");
     TH_REQUIRE_ALIGNED(d_range, 4, "d_range must be 4-byte aligned");
-    for (size_t i = 0; i < n; i++) {  // (on every call: an identical batch skips the table building below)
-        TH_REQUIRE_ALIGNED(descs[i].img.spec, 4, "desc %zu: spec must be 4-byte aligned", i);
-        TH_REQUIRE_ALIGNED(descs[i].img.img, 2, "desc %zu: img must be 2-byte aligned", i);
-    }
-    const bool all_neg_inf = !d_range && (min_dB == max_dB) && std::isinf(max_dB) && max_dB < 0;  // drawing.rs:16-18
-    if (!all_neg_inf && !d_range) TH_REQUIRE(std::isfinite(min_dB), "min_dB must be finite (drawing.rs:19)");
-    // key of the batch: the descriptors and every tile pointer (identical batch -> the device tables are reused as they are)
     std::vector<unsigned char> key;
-    size_t n_ptrs = 0;
-    for (size_t i = 0; i < n; i++) n_ptrs += (size_t)descs[i].n_tiles_x * descs[i].n_tiles_y;
-    key.reserve(n * sizeof(th_img_tiles_desc) + n_ptrs * sizeof(void *));
-    for (size_t i = 0; i < n; i++) {
-        const th_img_tiles_desc &d = descs[i];
-        TH_REQUIRE(d.tiles || (size_t)d.n_tiles_x * d.n_tiles_y == 0, "desc %zu: tiles is NULL", i);
-        const unsigned char *p = reinterpret_cast<const unsigned char *>(&d);
-        key.insert(key.end(), p, p + sizeof(th_img_tiles_desc));
-        const unsigned char *q = reinterpret_cast<const unsigned char *>(d.tiles);
-        key.insert(key.end(), q, q + (size_t)d.n_tiles_x * d.n_tiles_y * sizeof(void *));
-    }
+    const PlanStatus ok = check_fused(descs, n, min_dB, max_dB, d_range, &key);
+    if (ok.err != TH_OK) return plan_failed(ok);
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     TH_HIP(hipSetDevice(c->device));
-    if (!(c->fused_key == key && c->fused_jobs.dptr && c->fused_start.dptr && c->fused_ptrs.dptr)) {
-        std::vector<FusedJob> jobs(n);
-        std::vector<uint32_t> start;
-        std::vector<uint8_t *> ptrs;
-        ptrs.reserve(n_ptrs);
-        uint64_t blocks = 0;
-        for (size_t i = 0; i < n; i++) {
-            const th_img_desc &d = descs[i].img;
-            TH_REQUIRE(d.i_end >= d.i_start, "desc %zu: i_end < i_start", i);
-            const uint64_t out_h = d.i_end - d.i_start;
-            TH_REQUIRE(d.n_frames < (1ull << 31) && d.height < (1ull << 31) && d.i_end < (1ull << 31), "desc %zu: too large", i);
-            TH_REQUIRE((d.spec && d.img && d.height >= 1) || out_h * d.n_frames == 0, "desc %zu: NULL device pointer or empty spec", i);
-            TH_REQUIRE(d.spec_pitch == 0 || (d.spec_pitch >= d.height && d.spec_pitch < (1ull << 31)), "desc %zu: bad spec_pitch", i);
-            TH_REQUIRE(d.img_pitch == 0 || (d.img_pitch >= d.n_frames && d.img_pitch < (1ull << 31)), "desc %zu: bad img_pitch", i);
-            const uint64_t n_tx = out_h && d.n_frames ? (d.n_frames + 511) / 512 : 0, n_ty = out_h && d.n_frames ? (out_h + 511) / 512 : 0;
-            TH_REQUIRE(descs[i].n_tiles_x == n_tx && descs[i].n_tiles_y == n_ty, "desc %zu: the image has %llu x %llu level-0 tiles, not %u x %u",
-                       i, (unsigned long long)n_tx, (unsigned long long)n_ty, descs[i].n_tiles_x, descs[i].n_tiles_y);
-            const uint64_t n_bands = (out_h + FUSED_FB - 1) / FUSED_FB, nb = n_tx * n_bands;
-            TH_REQUIRE(blocks + nb < (1ull << 27) && ptrs.size() + n_tx * n_ty < (1ull << 31), "batch too large for one launch");
-            for (uint64_t t = 0; t < n_tx * n_ty; t++) {
-                uint8_t *tp = descs[i].tiles[t];
-                TH_REQUIRE((reinterpret_cast<uintptr_t>(tp) & 3u) == 0, "desc %zu: tile %llu must be 4-byte aligned", i, (unsigned long long)t);
-                ptrs.push_back(tp);
-            }
-            jobs[i] = FusedJob{d.spec, d.img, (uint32_t)d.n_frames, (uint32_t)d.height, (uint32_t)d.i_start, (uint32_t)d.i_end,
-                               (uint32_t)(d.spec_pitch ? d.spec_pitch : d.height), (uint32_t)(d.img_pitch ? d.img_pitch : d.n_frames),
-                               (uint32_t)blocks, (uint32_t)std::max<uint64_t>(n_bands, 1), (uint32_t)n_tx, (uint32_t)n_ty,
-                               (uint32_t)(ptrs.size() - n_tx * n_ty), 0u};
-            blocks += nb;
-            start.insert(start.end(), (size_t)nb, (uint32_t)i);
-        }
-        if (ptrs.empty()) ptrs.push_back(nullptr);
-        c->fused_key.clear();   // the previous batch's key must not survive a partly failed re-upload of the three tables
-        int rc = c->fused_jobs.upload(c->stream, jobs.data(), jobs.size() * sizeof(FusedJob));
-        if (rc == TH_OK && !start.empty()) rc = c->fused_start.upload(c->stream, start.data(), start.size() * sizeof(uint32_t));
-        if (rc == TH_OK) rc = c->fused_ptrs.upload(c->stream, ptrs.data(), ptrs.size() * sizeof(uint8_t *));
-        if (rc != TH_OK) return rc;
-        c->fused_key.swap(key);
-        c->fused_blocks_key = (uint32_t)blocks;
+    if (!c->fused.hit(key.data(), key.size())) {
+        const FusedPlan p = plan_fused(descs, n);
+        if (p.err != TH_OK) return plan_failed(p);
+        TH_CHECK(c->fused.store(c->stream, key.data(), key.size(), p.n_blocks,
+                                {{p.jobs.data(), p.jobs.size() * sizeof(FusedJob)},
+                                 {p.block_job.data(), p.block_job.size() * sizeof(uint32_t)},
+                                 {p.ptrs.data(), p.ptrs.size() * sizeof(uint8_t *)}}));
     }
-    TH_HIP(launch_spec_to_img_raster((const FusedJob *)c->fused_jobs.dptr, (const uint32_t *)c->fused_start.dptr, c->fused_blocks_key,
-                                     (uint8_t *const *)c->fused_ptrs.dptr, min_dB, max_dB, d_range, all_neg_inf ? 1 : 0, d_colormap,
-                                     n_colors, c->stream));
+    TH_HIP(launch_spec_to_img_raster(c->fused.at<FusedJob>(0), c->fused.at<uint32_t>(1), c->fused.n_blocks, c->fused.at<uint8_t *>(2), min_dB,
+                                     max_dB, d_range, db_range_all_neg_inf(min_dB, max_dB, d_range) ? 1 : 0, d_colormap, n_colors, c->stream));
     return TH_OK;
     TH_CATCH
 }
@@ -1232,58 +1153,20 @@ TH_API int th_raster_tiles_dev(th_ctx *c, const th_raster_desc *descs, size_t n,
     TH_REQUIRE(descs && d_colormap && n_colors >= 1, "NULL descs/colormap or empty colormap");
     TH_REQUIRE(n_colors <= 65536, "colormaps of more than 65536 entries are not supported");
     TH_REQUIRE_ALIGNED(d_colormap, 4, "d_colormap must be 4-byte aligned");
-    {   // same batch as the previous call: the device tables are still valid
-        std::lock_guard<std::recursive_mutex> lk(c->mu);
-        if (c->raster_descs_key.size() == n * sizeof(th_raster_desc) &&
-            std::memcmp(c->raster_descs_key.data(), descs, n * sizeof(th_raster_desc)) == 0 && c->raster_jobs.dptr && c->raster_start.dptr) {
-            TH_HIP(hipSetDevice(c->device));
-            TH_HIP(launch_raster_level0((const RasterJob *)c->raster_jobs.dptr, (const uint32_t *)c->raster_start.dptr,
-                                        (uint32_t)n, c->raster_blocks_key, d_colormap, n_colors, c->stream));
-            return TH_OK;
-        }
-    }
-    std::vector<RasterJob> jobs(n);
-    std::vector<uint32_t> start;  // job index of every block
-    uint64_t blocks = 0;
-    for (size_t i = 0; i < n; i++) {
-        const th_raster_desc &d = descs[i];
-        TH_REQUIRE((uint64_t)d.origin_x + d.width <= d.img_width && (uint64_t)d.origin_y + d.height <= d.img_height,
-                   "desc %zu: tile rectangle outside the image", i);
-        const uint64_t px = (uint64_t)d.width * d.height;
-        TH_REQUIRE(px < (1ull << 31), "desc %zu: tile too large", i);
-        TH_REQUIRE(px == 0 || (d.img && d.rgba), "desc %zu: NULL device pointer", i);
-        TH_REQUIRE_ALIGNED(d.rgba, 4, "desc %zu: rgba must be 4-byte aligned", i);
-        TH_REQUIRE_ALIGNED(d.img, 2, "desc %zu: img must be 2-byte aligned", i);
-        TH_REQUIRE(d.img_pitch == 0 || d.img_pitch >= d.img_width, "desc %zu: img_pitch < img_width", i);
-        const uint32_t qpr = (d.width + 3) / 4;
-        const uint32_t inv = qpr > 1 ? (uint32_t)((1ull << 32) / qpr) + 1u : 0u;  // exact for q * qpr < 2^32
-        TH_REQUIRE(px == 0 || (px + 4) * d.width < (1ull << 32), "desc %zu: tile too large", i);
-        const uint32_t inv_w = d.width > 1 ? (uint32_t)((1ull << 32) / d.width) + 1u : 0u;
-        // (+1: a tile base off the 16-byte grid shifts the quads by up to 3 pixels, see raster_quads)
-        const uint64_t nb = ((uint64_t)qpr * d.height + 1 + RASTER_QUADS_PER_BLOCK - 1) / RASTER_QUADS_PER_BLOCK;
-        TH_REQUIRE(blocks + nb < (1ull << 27), "batch too large for one launch");
-        jobs[i] = RasterJob{d.img, d.rgba, d.img_width, d.img_height, d.origin_x, d.origin_y, d.width, d.height,
-                            d.img_pitch ? d.img_pitch : d.img_width, qpr, inv, inv_w, (uint32_t)blocks};
-        blocks += nb;
-        start.insert(start.end(), (size_t)nb, (uint32_t)i);  // block -> job table
-    }
+    const size_t key_bytes = n * sizeof(th_raster_desc);
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     TH_HIP(hipSetDevice(c->device));
-    c->raster_descs_key.clear();   // (as above: a failed second upload must not leave the old key on mixed tables)
-    int rc = c->raster_jobs.upload(c->stream, jobs.data(), jobs.size() * sizeof(RasterJob));
-    if (rc != TH_OK) return rc;
-    rc = c->raster_start.upload(c->stream, start.data(), start.size() * sizeof(uint32_t));
-    if (rc != TH_OK) return rc;
-    c->raster_descs_key.assign(reinterpret_cast<const unsigned char *>(descs), reinterpret_cast<const unsigned char *>(descs + n));
-    c->raster_blocks_key = (uint32_t)blocks;
-    TH_HIP(launch_raster_level0((const RasterJob *)c->raster_jobs.dptr, (const uint32_t *)c->raster_start.dptr,
-                                (uint32_t)n, (uint32_t)blocks, d_colormap, n_colors, c->stream));
+    if (!c->raster.hit(descs, key_bytes)) {
+        const RasterPlan p = plan_raster(descs, n);
+        if (p.err != TH_OK) return plan_failed(p);
+        TH_CHECK(c->raster.store(c->stream, descs, key_bytes, p.n_blocks,
+                                 {{p.jobs.data(), p.jobs.size() * sizeof(RasterJob)}, {p.block_job.data(), p.block_job.size() * sizeof(uint32_t)}}));
+    }
+    TH_HIP(launch_raster_level0(c->raster.at<RasterJob>(0), c->raster.at<uint32_t>(1), (uint32_t)n, c->raster.n_blocks, d_colormap, n_colors,
+                                c->stream));
     return TH_OK;
     TH_CATCH
 }
-
-static void put_u32(uint8_t *p, uint32_t v) { std::memcpy(p, &v, 4); }  // little-endian host (x86-64)
-static void put_u64(uint8_t *p, uint64_t v) { std::memcpy(p, &v, 8); }
 
 TH_API int th_encode_spectrogram_tile_dev(th_ctx *c, const uint16_t *d_img, size_t img_height, size_t img_width,
                                           size_t img_pitch, const uint8_t *colormap_rgba, size_t colormap_bytes, uint64_t revision,
@@ -1299,62 +1182,25 @@ TH_API int th_encode_spectrogram_tile_dev(th_ctx *c, const uint16_t *d_img, size
     const size_t need = 40 + g.width * g.height * 4;
     *out_len = need;
     if (cap < need) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", need);
-    put_u64(out, revision);
-    put_u32(out + 8, (uint32_t)g.width);
-    put_u32(out + 12, (uint32_t)g.height);
-    put_u32(out + 16, level_x);
-    put_u32(out + 20, level_y);
-    put_u32(out + 24, tile_x);
-    put_u32(out + 28, tile_y);
-    put_u32(out + 32, (uint32_t)g.origin_x);
-    put_u32(out + 36, (uint32_t)g.origin_y);
+    put_spectrogram_tile_header(out, revision, g, level_x, level_y, tile_x, tile_y);
     if (g.width == 0 || g.height == 0) return TH_OK;
     TH_REQUIRE(d_img, "d_img is NULL");
     const uint32_t n_colors = (uint32_t)(colormap_bytes / 4);
+    const uint32_t pitch = (uint32_t)(img_pitch ? img_pitch : img_width), dw = (uint32_t)g.width, dh = (uint32_t)g.height;
+    const bool lod = level_x != 0 || level_y != 0;
+    // LOD > 0: separable Lanczos3 of the crop box (render_tiles.rs:354-393), then the same raster
+    const LodTilePlan lp = lod ? plan_lod_tile(img_width, img_height, g, level_x, level_y) : LodTilePlan{};
+    if (lp.err != TH_OK) return plan_failed(lp);
     std::lock_guard<std::recursive_mutex> lk(c->mu);  // tile_out / colormap / lod scratch: whole request
     TH_HIP(hipSetDevice(c->device));
-    int rc = c->colormap.upload(c->stream, colormap_rgba, colormap_bytes);
-    if (rc != TH_OK) return rc;
-    rc = c->tile_out.ensure(g.width * g.height * 4);
-    if (rc != TH_OK) return rc;
-    const uint32_t pitch = (uint32_t)(img_pitch ? img_pitch : img_width);
-    if (level_x == 0 && level_y == 0) {
-        // integral crop box equal to the destination size: exact copy (pinned by render_tiles.rs:464-471)
-        th_raster_desc d{d_img, (uint8_t *)c->tile_out.dptr, (uint32_t)img_width, (uint32_t)img_height,
-                         (uint32_t)g.origin_x, (uint32_t)g.origin_y, (uint32_t)g.width, (uint32_t)g.height, pitch, 0};
-        rc = th_raster_tiles_dev(c, &d, 1, (const uint8_t *)c->colormap.dptr, n_colors);
-        if (rc != TH_OK) return rc;
-    } else {
-        // LOD > 0: separable Lanczos3 of the crop box (render_tiles.rs:354-393), then the same raster.
-        // Tap tables are built here in f64 exactly as the CPU restatement does, in the arithmetic of Pillow's
-        // ImagingResample (bit-identical to Pillow on the committed fixtures; formally unpinned against
-        // fast_image_resize itself).
-        const size_t dw = g.width, dh = g.height;
-        const double W = (double)img_width, Hh = (double)img_height;
-        const double left = (double)g.origin_x * W / (double)g.lod_w, top = (double)g.origin_y * Hh / (double)g.lod_h;
-        const double cw = (double)(g.origin_x + dw) * W / (double)g.lod_w - left;
-        const double chh = (double)(g.origin_y + dh) * Hh / (double)g.lod_h - top;
-        const double scy = chh / (double)dh, fy = scy < 1.0 ? 1.0 : scy, supy = 3.0 * fy;
-        long y_lo = (long)std::floor(top - supy) - 1, y_hi = (long)std::ceil(top + chh + supy) + 1;
-        if (y_lo < 0) y_lo = 0;
-        if (y_hi > (long)img_height) y_hi = (long)img_height;
-        const size_t n_rows = (size_t)(y_hi - y_lo);
-        // a tap table beyond this is a level no viewer asks for; refuse instead of allocating GBs
-        const double est_taps = 6.0 * std::max(cw / (double)dw, chh / (double)dh) + 4.0;
-        if (est_taps * 8.0 * (double)std::max(dw, dh) > 256.0 * 1024 * 1024)
-            return fail(TH_ERR_UNSUPPORTED, "LOD level (%u,%u) needs a tap table beyond 256 MB", level_x, level_y);
-        LodAxisHost ax, ay;
-        build_lod_axis(left, cw, dw, 0, (long)img_width, ax);
-        build_lod_axis(top, chh, dh, y_lo, y_hi, ay);
-        // one blob: [x: start,count,wsum,w][y: start,count,wsum,w], 8-byte aligned sections
-        const size_t bx = ax.blob_bytes(dw), by = ay.blob_bytes(dh);
-        std::vector<unsigned char> blob(bx + by);
-        ax.pack(blob.data(), dw);
-        ay.pack(blob.data() + bx, dh);
-        rc = c->lod_tabs.upload(c->stream, blob.data(), blob.size());
-        if (rc != TH_OK) return rc;
-        rc = c->lod_tmp.ensure((n_rows * dw + dw * dh) * sizeof(uint16_t) + 64);
-        if (rc != TH_OK) return rc;
+    TH_CHECK(c->colormap.upload(c->stream, colormap_rgba, colormap_bytes));
+    TH_CHECK(c->tile_out.ensure(g.width * g.height * 4));
+    // level (0, 0): integral crop box equal to the destination size: exact copy (pinned by render_tiles.rs:464-471)
+    th_raster_desc d{d_img, (uint8_t *)c->tile_out.dptr, (uint32_t)img_width, (uint32_t)img_height,
+                     (uint32_t)g.origin_x, (uint32_t)g.origin_y, dw, dh, pitch, 0};
+    if (lod) {
+        TH_CHECK(c->lod_tabs.upload(c->stream, lp.blob.data(), lp.blob.size()));
+        TH_CHECK(c->lod_tmp.ensure(lp.scratch_bytes));
         auto axis_dev = [](unsigned char *base, size_t n_out, uint32_t taps) {
             LodAxis a;
             a.start = reinterpret_cast<const int32_t *>(base);
@@ -1367,16 +1213,12 @@ TH_API int th_encode_spectrogram_tile_dev(th_ctx *c, const uint16_t *d_img, size
         };
         unsigned char *dtab = static_cast<unsigned char *>(c->lod_tabs.dptr);
         uint16_t *d_tmp = static_cast<uint16_t *>(c->lod_tmp.dptr);
-        uint16_t *d_lod = d_tmp + ((n_rows * dw + 3) / 4) * 4;
-        TH_HIP(launch_lod_hpass(d_img, pitch, (uint32_t)y_lo, (uint32_t)n_rows, axis_dev(dtab, dw, ax.max_taps), d_tmp,
-                                (uint32_t)dw, c->stream));
-        TH_HIP(launch_lod_vpass(d_tmp, (uint32_t)dw, (uint32_t)y_lo, axis_dev(dtab + bx, dh, ay.max_taps), (uint32_t)dw, d_lod,
-                                (uint32_t)dw, c->stream));
-        th_raster_desc d{d_lod, (uint8_t *)c->tile_out.dptr, (uint32_t)dw, (uint32_t)dh, 0, 0, (uint32_t)dw, (uint32_t)dh,
-                         (uint32_t)dw, 0};
-        rc = th_raster_tiles_dev(c, &d, 1, (const uint8_t *)c->colormap.dptr, n_colors);
-        if (rc != TH_OK) return rc;
+        uint16_t *d_lod = d_tmp + lp.lod_at;
+        TH_HIP(launch_lod_hpass(d_img, pitch, (uint32_t)lp.y_lo, (uint32_t)lp.n_rows, axis_dev(dtab, dw, lp.taps_x), d_tmp, dw, c->stream));
+        TH_HIP(launch_lod_vpass(d_tmp, dw, (uint32_t)lp.y_lo, axis_dev(dtab + lp.y_at, dh, lp.taps_y), dw, d_lod, dw, c->stream));
+        d = th_raster_desc{d_lod, (uint8_t *)c->tile_out.dptr, dw, dh, 0, 0, dw, dh, dw, 0};
     }
+    TH_CHECK(th_raster_tiles_dev(c, &d, 1, (const uint8_t *)c->colormap.dptr, n_colors));
     TH_HIP(hipMemcpyAsync(out + 40, c->tile_out.dptr, g.width * g.height * 4, hipMemcpyDeviceToHost, c->stream));
     TH_HIP(hipStreamSynchronize(c->stream));
     return TH_OK;
@@ -1389,35 +1231,13 @@ TH_API int th_waveform_tiles_dev(th_ctx *c, const th_wave_desc *descs, size_t n)
     TH_REQUIRE(c, "ctx is NULL");
     if (n == 0) return TH_OK;
     TH_REQUIRE(descs, "descs is NULL");
-    std::vector<WaveJob> jobs(n);
-    std::vector<uint32_t> start(n + 1);
-    uint64_t blocks = 0;
-    for (size_t i = 0; i < n; i++) {
-        const th_wave_desc &d = descs[i];
-        TH_REQUIRE(d.bin_count <= TH_WAVEFORM_TILE_BINS, "desc %zu: bin_count > 1024", i);
-        TH_REQUIRE(d.level < 40, "desc %zu: level %u too large", i, d.level);
-        TH_REQUIRE(d.bin_count == 0 || (d.wav && d.bins), "desc %zu: NULL device pointer", i);
-        TH_REQUIRE_ALIGNED(d.wav, 4, "desc %zu: wav must be 4-byte aligned", i);
-        TH_REQUIRE_ALIGNED(d.bins, 4, "desc %zu: bins must be 4-byte aligned", i);
-        if (d.bin_count) {
-            const uint64_t spb = 1ull << d.level;
-            TH_REQUIRE(d.start < d.n_samples && d.start + (uint64_t)(d.bin_count - 1) * spb < d.n_samples,
-                       "desc %zu: bins run past the end of the channel", i);
-        }
-        jobs[i] = WaveJob{d.wav, d.bins, d.n_samples, d.start, d.level, d.bin_count};
-        start[i] = (uint32_t)blocks;
-        blocks += waveform_blocks_for(d.level, d.bin_count);
-        TH_REQUIRE(blocks < (1ull << 31), "batch too large for one launch");
-    }
-    start[n] = (uint32_t)blocks;
+    const WavePlan p = plan_wave_tiles(descs, n);
+    if (p.err != TH_OK) return plan_failed(p);
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     TH_HIP(hipSetDevice(c->device));
-    int rc = c->wave_jobs.upload(c->stream, jobs.data(), jobs.size() * sizeof(WaveJob));
-    if (rc != TH_OK) return rc;
-    rc = c->wave_start.upload(c->stream, start.data(), start.size() * sizeof(uint32_t));
-    if (rc != TH_OK) return rc;
-    TH_HIP(launch_waveform((const WaveJob *)c->wave_jobs.dptr, (const uint32_t *)c->wave_start.dptr, (uint32_t)n,
-                           (uint32_t)blocks, c->stream));
+    TH_CHECK(c->wave_jobs.upload(c->stream, p.jobs.data(), p.jobs.size() * sizeof(WaveJob)));
+    TH_CHECK(c->wave_start.upload(c->stream, p.start.data(), p.start.size() * sizeof(uint32_t)));
+    TH_HIP(launch_waveform((const WaveJob *)c->wave_jobs.dptr, (const uint32_t *)c->wave_start.dptr, (uint32_t)n, p.n_blocks, c->stream));
     return TH_OK;
     TH_CATCH
 }
@@ -1429,26 +1249,16 @@ TH_API int th_channel_stats_dev(th_ctx *c, const th_stats_desc *descs, size_t n,
     TH_REQUIRE(c, "ctx is NULL");
     if (n == 0) return TH_OK;
     TH_REQUIRE(descs && out_sum_squares && out_abs_max, "NULL argument");
-    TH_REQUIRE(n <= 65535, "at most 65535 channels per call");
-    std::vector<StatsJob> jobs(n);
-    uint64_t max_samples = 0;
-    for (size_t i = 0; i < n; i++) {
-        TH_REQUIRE(descs[i].n_samples == 0 || descs[i].wav, "desc %zu: NULL device pointer", i);
-        TH_REQUIRE_ALIGNED(descs[i].wav, 4, "desc %zu: wav must be 4-byte aligned", i);
-        TH_REQUIRE(descs[i].n_samples < (1ull << 40), "desc %zu: too many samples", i);
-        jobs[i] = StatsJob{descs[i].wav, descs[i].n_samples, (reinterpret_cast<uintptr_t>(descs[i].wav) & 15u) == 0, 0};
-        max_samples = std::max<uint64_t>(max_samples, descs[i].n_samples);
-    }
+    const StatsPlan p = plan_stats(descs, n);
+    if (p.err != TH_OK) return plan_failed(p);
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     TH_HIP(hipSetDevice(c->device));
-    int rc = c->pyr_sums.ensure(n * (sizeof(double) + sizeof(uint32_t)));
-    if (rc != TH_OK) return rc;
+    TH_CHECK(c->pyr_sums.ensure(n * (sizeof(double) + sizeof(uint32_t))));
     double *d_sum = reinterpret_cast<double *>(c->pyr_sums.dptr);
     uint32_t *d_pk = reinterpret_cast<uint32_t *>(d_sum + n);
     TH_HIP(hipMemsetAsync(d_sum, 0, n * (sizeof(double) + sizeof(uint32_t)), c->stream));  // sum = 0, peak = +0.0 (:841,876)
-    rc = c->pyr_jobs.upload(c->stream, jobs.data(), jobs.size() * sizeof(StatsJob));
-    if (rc != TH_OK) return rc;
-    TH_HIP(launch_channel_stats((const StatsJob *)c->pyr_jobs.dptr, (uint32_t)n, max_samples, d_sum, d_pk, c->stream));
+    TH_CHECK(c->pyr_jobs.upload(c->stream, p.jobs.data(), p.jobs.size() * sizeof(StatsJob)));
+    TH_HIP(launch_channel_stats((const StatsJob *)c->pyr_jobs.dptr, (uint32_t)n, p.max_samples, d_sum, d_pk, c->stream));
     std::vector<double> hs(n);
     std::vector<uint32_t> hp(n);
     TH_HIP(hipMemcpyAsync(hs.data(), d_sum, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -1473,48 +1283,17 @@ TH_API int th_waveform_pyramid_dev(th_ctx *c, const th_pyramid_desc *descs, size
     TH_REQUIRE(c, "ctx is NULL");
     if (n == 0) return TH_OK;
     TH_REQUIRE(descs, "descs is NULL");
-    TH_REQUIRE(n <= 65535, "at most 65535 channels per call");
-    std::vector<PyrJob> jobs(n);
-    uint64_t max_samples = 0, sums_total = 0;
-    uint32_t max_levels = 0;
-    for (size_t i = 0; i < n; i++) {
-        const th_pyramid_desc &d = descs[i];
-        TH_REQUIRE(d.n_levels <= PYR_MAX_LEVELS, "desc %zu: more than %u levels", i, PYR_MAX_LEVELS);
-        TH_REQUIRE(d.n_samples == 0 || d.n_levels == 0 || (d.wav && d.out), "desc %zu: NULL device pointer", i);
-        TH_REQUIRE_ALIGNED(d.wav, 4, "desc %zu: wav must be 4-byte aligned", i);
-        TH_REQUIRE_ALIGNED(d.out, 4, "desc %zu: out must be 4-byte aligned", i);
-        TH_REQUIRE(d.n_samples < (1ull << 40), "desc %zu: too many samples", i);
-        PyrJob &j = jobs[i];
-        j = PyrJob{};
-        TH_REQUIRE(d.first_level <= 2, "desc %zu: first_level must be 0, 1 or 2", i);
-        j.wav = d.wav;
-        // first_level = 1: the kernels keep addressing level L at out + level_off[L]; shifting `out` back by the extent of the skipped levels
-        // (a multiple of 128 bytes) puts level first_level at the start of the caller's buffer; the levels below are never touched
-        j.out = d.first_level ? reinterpret_cast<float *>(reinterpret_cast<uintptr_t>(d.out) - pyramid_offset(d.n_samples, d.first_level) * sizeof(float)) : d.out;
-        j.n_samples = (d.n_levels > d.first_level) ? d.n_samples : 0;
-        j.n_levels = d.n_levels;
-        j.aligned16 = ((reinterpret_cast<uintptr_t>(d.wav) & 15u) == 0 ? 1u : 0u) | (d.first_level << 1);
-        for (uint32_t l = 0; l < PYR_MAX_LEVELS; l++) j.level_off[l] = pyramid_offset(d.n_samples, l);
-        j.sums_half = pyramid_bins(d.n_samples, 12);
-        sums_total += 2 * j.sums_half;
-        max_samples = std::max<uint64_t>(max_samples, j.n_samples);
-        max_levels = std::max(max_levels, d.n_levels);
-    }
-    if (!max_samples || !max_levels) return TH_OK;
+    PyrPlan p = plan_pyramid(descs, n);
+    if (p.err != TH_OK) return plan_failed(p);
+    if (!p.launch) return TH_OK;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     TH_HIP(hipSetDevice(c->device));
-    int rc = c->pyr_sums.ensure(std::max<uint64_t>(sums_total, 1) * sizeof(float));
-    if (rc != TH_OK) return rc;
-    uint64_t so = 0;
-    for (PyrJob &j : jobs) {
-        j.sums = reinterpret_cast<float *>(c->pyr_sums.dptr) + so;
-        so += 2 * j.sums_half;
-    }
-    rc = c->pyr_jobs.upload(c->stream, jobs.data(), jobs.size() * sizeof(PyrJob));
-    if (rc != TH_OK) return rc;
+    TH_CHECK(c->pyr_sums.ensure(std::max<uint64_t>(p.sums_floats, 1) * sizeof(float)));
+    bind_pyramid(p, reinterpret_cast<float *>(c->pyr_sums.dptr));
+    TH_CHECK(c->pyr_jobs.upload(c->stream, p.jobs.data(), p.jobs.size() * sizeof(PyrJob)));
     const PyrJob *dj = (const PyrJob *)c->pyr_jobs.dptr;
-    TH_HIP(launch_pyramid_base(dj, (uint32_t)n, max_samples, c->stream));
-    for (uint32_t l = 13; l < max_levels; l++) TH_HIP(launch_pyramid_up(dj, (uint32_t)n, max_samples, l, (l - 13) & 1u, c->stream));
+    TH_HIP(launch_pyramid_base(dj, (uint32_t)n, p.max_samples, c->stream));
+    for (uint32_t l = 13; l < p.max_levels; l++) TH_HIP(launch_pyramid_up(dj, (uint32_t)n, p.max_samples, l, (l - 13) & 1u, c->stream));
     return TH_OK;
     TH_CATCH
 }
@@ -1530,22 +1309,16 @@ TH_API int th_encode_waveform_tile_dev(th_ctx *c, const float *d_wav, size_t n_s
     const size_t need = 24 + bins * 12;
     *out_len = need;
     if (cap < need) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", need);
-    put_u64(out, revision);
-    put_u32(out + 8, (uint32_t)bins);
-    put_u32(out + 12, spb > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)spb);
-    put_u32(out + 16, tile_index);
-    put_u32(out + 20, 0);
+    put_waveform_tile_header(out, revision, bins, spb, tile_index);
     if (bins == 0) return TH_OK;
     TH_REQUIRE(d_wav, "d_wav is NULL");
     std::lock_guard<std::recursive_mutex> lk(c->mu);  // tile_out scratch: whole request
     TH_HIP(hipSetDevice(c->device));
-    int rc = c->tile_out.ensure(bins * 12);
-    if (rc != TH_OK) return rc;
+    TH_CHECK(c->tile_out.ensure(bins * 12));
     // levels whose bins are longer than the channel all give one bin; keep the shift in range
     const uint32_t level_eff = level < 39 ? level : 39;
     th_wave_desc d{d_wav, (float *)c->tile_out.dptr, n_samples, start, level_eff, (uint32_t)bins};
-    rc = th_waveform_tiles_dev(c, &d, 1);
-    if (rc != TH_OK) return rc;
+    TH_CHECK(th_waveform_tiles_dev(c, &d, 1));
     TH_HIP(hipMemcpyAsync(out + 24, c->tile_out.dptr, bins * 12, hipMemcpyDeviceToHost, c->stream));
     TH_HIP(hipStreamSynchronize(c->stream));
     return TH_OK;

@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <vector>
 
@@ -66,6 +68,36 @@ struct DeviceTable {
     ~DeviceTable() { release(); }
 };
 
+// The device tables built from one batch of descriptors, named by the bytes of that batch: an identical batch (re-quantising after a
+// dB-range or colormap change, benchmark loops) launches on them as they are.
+struct KeyedTables {
+    struct Src {
+        const void *data;
+        size_t bytes;
+    };
+    DeviceTable tab[3];
+    std::vector<unsigned char> key;
+    uint32_t n_blocks = 0;
+    // (the key is set only behind a complete store, so a matching key says that every table is the batch's; a batch without blocks
+    // never uploads its block table, and a launcher given no blocks reads none)
+    bool hit(const void *k, size_t bytes) const { return !key.empty() && key.size() == bytes && std::memcmp(key.data(), k, bytes) == 0; }
+    // The tables are about to be overwritten: the key is cleared first and names them again only once EVERY upload succeeded, so a
+    // partly failed store never leaves an old key on mixed tables.  An empty source is skipped.
+    int store(hipStream_t s, const void *k, size_t bytes, uint32_t blocks, std::initializer_list<Src> srcs) {
+        key.clear();
+        size_t i = 0;
+        for (const Src &src : srcs) {
+            if (src.bytes) TH_CHECK(tab[i].upload(s, src.data, src.bytes));
+            i++;
+        }
+        key.assign(static_cast<const unsigned char *>(k), static_cast<const unsigned char *>(k) + bytes);
+        n_blocks = blocks;
+        return TH_OK;
+    }
+    template <class T>
+    const T *at(size_t i) const { return static_cast<const T *>(tab[i].dptr); }
+};
+
 }  // namespace th
 
 struct th_ctx {
@@ -77,11 +109,9 @@ struct th_ctx {
     // Serialises use of the stream-side scratch below; recursive so composed entry points
     // (tile encoders → batched launchers) can hold it across the whole request.
     std::recursive_mutex mu;
-    th::DeviceTable img_jobs, img_start, raster_jobs, raster_start, wave_jobs, wave_start, colormap, tile_out, lod_tabs, lod_tmp,
-        pyr_jobs, pyr_sums, fused_jobs, fused_start, fused_ptrs, loud_mem;
-    // the descriptor batches the img / raster tables were built from (identical batch -> tables reused as they are)
-    std::vector<unsigned char> img_descs_key, raster_descs_key, fused_key;
-    uint32_t img_tiles_key = 0, raster_blocks_key = 0, fused_blocks_key = 0;
+    th::DeviceTable wave_jobs, wave_start, colormap, tile_out, lod_tabs, lod_tmp, pyr_jobs, pyr_sums, loud_mem;
+    // jobs, block -> job table (and, fused, the tile pointers) of the last spec -> img / raster / quantise + raster batch
+    th::KeyedTables img, raster, fused;
     ~th_ctx() {  // (th_ctx_destroy: device current, stream idle; the scratch tables above go after this body)
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);

@@ -229,6 +229,20 @@ void waveform_tile_geometry(size_t n, uint32_t level, uint32_t tile, size_t *sta
     *bins = st >= en ? 0 : div_ceil(en - st, s);
 }
 
+static void put_words(uint8_t *out, uint64_t revision, const uint32_t *w, size_t n) {  // little-endian host (x86-64)
+    std::memcpy(out, &revision, 8);
+    std::memcpy(out + 8, w, 4 * n);
+}
+void put_spectrogram_tile_header(uint8_t *out, uint64_t revision, const TileGeom &g, uint32_t level_x, uint32_t level_y, uint32_t tile_x,
+                                 uint32_t tile_y) {
+    const uint32_t w[8] = {(uint32_t)g.width, (uint32_t)g.height, level_x, level_y, tile_x, tile_y, (uint32_t)g.origin_x, (uint32_t)g.origin_y};
+    put_words(out, revision, w, 8);
+}
+void put_waveform_tile_header(uint8_t *out, uint64_t revision, size_t bins, size_t samples_per_bin, uint32_t tile_index) {
+    const uint32_t w[4] = {(uint32_t)bins, samples_per_bin > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)samples_per_bin, tile_index, 0u};
+    put_words(out, revision, w, 4);
+}
+
 // Lanczos3 taps in the arithmetic of the convolution fast_image_resize documents itself as following (Pillow's
 // ImagingResample, precompute_coeffs): lanczos(t) = sinc(t) sinc(t / 3) on -3 <= t < 3, sinc(t) = sin(pi t) / (pi t).
 static double pil_sinc(double x) {

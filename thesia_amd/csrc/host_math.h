@@ -37,6 +37,12 @@ struct TileGeom {
 };
 TileGeom spectrogram_tile_geometry(size_t W, size_t Hh, uint32_t lx, uint32_t ly, uint32_t tx, uint32_t ty);
 void waveform_tile_geometry(size_t n, uint32_t level, uint32_t tile, size_t *start, size_t *bins, size_t *spb);
+// The little-endian headers in front of a tile's payload (render_tiles.rs:171-188, :232-279): 40 bytes {revision u64, width, height,
+// level_x, level_y, tile_x, tile_y, origin_x, origin_y u32} and 24 bytes {revision u64, bins, samples per bin (saturated to u32),
+// tile_index, 0 u32}
+void put_spectrogram_tile_header(uint8_t *out, uint64_t revision, const TileGeom &g, uint32_t level_x, uint32_t level_y, uint32_t tile_x,
+                                 uint32_t tile_y);
+void put_waveform_tile_header(uint8_t *out, uint64_t revision, size_t bins, size_t samples_per_bin, uint32_t tile_index);
 
 // Lanczos3 tap table of one axis of resize_spectrogram_tile (render_tiles.rs:354-393; PARITY UNPINNED against
 // fast_image_resize 6.0.0, whose source is not vendored: the textbook filter, exactly as oracle/thesia_oracle.c builds

@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "../../include/thesia_amd.h"
+#include "batch_plan.h"  // ImgJob, FusedJob, RasterJob, WaveJob, PyrJob, StatsJob, their constants, pyramid_bins / pyramid_offset / waveform_blocks_for
 #include "host_math.h"
 #include "stft_core.h"
 #include "reader_plan.h"  // LoudJob, LoudTrackJob, TruePeakJob, ExportJob, ResampleJob, ResampleTiling and their constants
@@ -143,65 +144,18 @@ hipError_t launch_mel_band_rows(const MelJob *d_jobs, const uint32_t *d_tile_sta
                                 uint32_t amp_pitch, uint32_t n_freq, const uint32_t *d_tab, uint32_t words, uint32_t groups,
                                 const uint32_t *hdr, uint32_t n_mel, float *d_minmax, uint32_t n_cu, hipStream_t s);
 
-// ---- kernels_image.hip
-struct ImgJob {  // device-visible copy of th_img_desc
-    const float *spec;
-    uint16_t *img;
-    uint32_t n_frames, height, i_start, i_end;
-    uint32_t spec_pitch, img_pitch;  // elements per row (>= height / n_frames)
-    uint32_t first_tile, n_tiles;    // this job's block range in the launch
-};
+// ---- kernels_image.hip (ImgJob, FusedJob, RasterJob, IMG_TILE_*, FUSED_*, RASTER_*: batch_plan.h)
 hipError_t launch_spec_to_img(const ImgJob *d_jobs, const uint32_t *d_tile_job, uint32_t n_jobs,
                               uint32_t n_tiles, float min_dB, float max_dB, uint32_t colormap_len, const float *d_range,
                               hipStream_t s);
 hipError_t launch_db_range(const float *d_in, float dB_range, float *d_out, hipStream_t s);
 
-// Quantise + level-0 raster in one pass (round 4): one job per image; block b of a job = (tile column tx = local / n_bands,
-// band of FUSED_FB image rows = local % n_bands); tiles[tile0 + tx * n_ty + ty] = RGBA array of level-0 tile (tx, ty) or NULL
-struct FusedJob {
-    const float *spec;
-    uint16_t *img;
-    uint32_t n_frames, height, i_start, i_end;
-    uint32_t spec_pitch, img_pitch;
-    uint32_t first_block, n_bands;
-    uint32_t n_tx, n_ty;
-    uint32_t tile0, reserved;
-};
-static_assert(sizeof(FusedJob) == 64, "FusedJob must have no implicit padding");
-#if !defined(TH_FUSED_FB)
-#define TH_FUSED_FB 32
-#endif
-#if !defined(TH_FUSED_THREADS)
-#define TH_FUSED_THREADS 256
-#endif
-constexpr uint32_t FUSED_FB = TH_FUSED_FB;        // image rows (frequency bins) per block
-constexpr uint32_t FUSED_THREADS = TH_FUSED_THREADS;
 hipError_t launch_spec_to_img_raster(const FusedJob *d_jobs, const uint32_t *d_block_job, uint32_t n_blocks, uint8_t *const *d_tiles,
                                      float min_dB, float max_dB, const float *d_range, int all_zero, const uint8_t *d_colormap,
                                      uint32_t n_colors, hipStream_t s);
 
-struct RasterJob {  // device-visible copy of th_raster_desc (+ derived fields)
-    const uint16_t *img;
-    uint8_t *rgba;
-    uint32_t img_width, img_height, origin_x, origin_y, width, height;
-    uint32_t img_pitch;      // u16 elements per image row (>= img_width)
-    uint32_t quads_per_row;  // ceil(width / 4): a thread rasterises 4 horizontally adjacent pixels
-    uint32_t inv_qpr;        // floor(2^32 / quads_per_row) + 1: q / quads_per_row == umulhi(q, inv_qpr)
-    uint32_t inv_width;      // floor(2^32 / width) + 1 (flat-quad path of widths that are not multiples of 4)
-    uint32_t first_block;    // this job's first block in the launch
-};
 hipError_t launch_raster_level0(const RasterJob *d_jobs, const uint32_t *d_block_job, uint32_t n_jobs,
                                 uint32_t n_blocks, const uint8_t *d_colormap, uint32_t n_colors, hipStream_t s);
-#if !defined(TH_RASTER_THREADS)
-#define TH_RASTER_THREADS 256
-#endif
-#if !defined(TH_RASTER_QPB)
-#define TH_RASTER_QPB 1024
-#endif
-constexpr uint32_t RASTER_THREADS = TH_RASTER_THREADS;
-constexpr uint32_t RASTER_QUADS_PER_BLOCK = TH_RASTER_QPB;  // default: 256 threads x 4 quads of 4 pixels
-constexpr uint32_t IMG_TILE_T = 64;   // frames per quantise/transpose tile
-constexpr uint32_t IMG_TILE_F = 128;  // frequency rows per tile
 
 // Separable Lanczos3 LOD resample of a crop of a u16 image (encode_spectrogram_tile, LOD > 0,
 // render_tiles.rs:354-393).  Per output index of an axis the host tabulates the first source index,
@@ -239,42 +193,15 @@ hipError_t launch_raster_tile(const uint16_t *d_img, uint32_t img_width, uint32_
 // streaming 16-byte-per-lane device copy of bytes / 16 * 16 bytes (the bandwidth yardstick of bench.py)
 hipError_t launch_copy_f4(const void *d_src, void *d_dst, uint64_t bytes, hipStream_t s);
 
-// ---- kernels_waveform.hip
-struct WaveJob {  // device-visible copy of th_wave_desc
-    const float *wav;
-    float *bins;
-    uint64_t n_samples, start;
-    uint32_t level, bin_count;
-};
+// ---- kernels_waveform.hip (WaveJob, PyrJob, StatsJob, PYR_MAX_LEVELS: batch_plan.h)
 hipError_t launch_waveform(const WaveJob *d_jobs, const uint32_t *d_block_start, uint32_t n_jobs,
                            uint32_t n_blocks, hipStream_t s);
 
-// waveform pyramid (all levels of a channel in one pass over the audio)
-constexpr uint32_t PYR_MAX_LEVELS = 40;
-struct PyrJob {
-    const float *wav;
-    float *out;          // all levels, level L at float offset level_off[L]
-    float *sums;         // scratch: 2 * sums_half floats (bin sums of the level being reduced, ping-pong)
-    uint64_t n_samples;
-    uint64_t sums_half;
-    uint64_t level_off[PYR_MAX_LEVELS];
-    uint32_t n_levels;
-    uint32_t aligned16;  // bit 0: wav is 16-byte aligned (float4 loads); bits 1-2: th_pyramid_desc.first_level (levels below it are not written)
-};
-struct StatsJob {
-    const float *wav;
-    uint64_t n_samples;
-    uint32_t aligned16, pad_;
-};
 hipError_t launch_channel_stats(const StatsJob *d_jobs, uint32_t n_jobs, uint64_t max_samples, double *d_sumsq,
                                 uint32_t *d_peak_bits, hipStream_t s);
-uint64_t pyramid_bins(uint64_t n, uint32_t level);
-uint64_t pyramid_offset(uint64_t n, uint32_t level);
 hipError_t launch_pyramid_base(const PyrJob *d_jobs, uint32_t n_jobs, uint64_t max_samples, hipStream_t s);
 hipError_t launch_pyramid_up(const PyrJob *d_jobs, uint32_t n_jobs, uint64_t max_samples, uint32_t level, uint32_t parity,
                              hipStream_t s);
-uint32_t waveform_blocks_for(uint32_t level, uint32_t bin_count);
-
 
 // ---- kernels_loudness.hip: K-weighted chunk energies, per-channel sum of squares and peak, 400 ms block energies (LoudJob,
 // LoudTrackJob: reader_plan.h)

@@ -33,14 +33,6 @@ __device__ __forceinline__ uint64_t pyramid_dev_bins(uint64_t n, uint32_t level)
     return level >= 63 ? (n ? 1 : 0) : (n + (1ull << level) - 1) >> level;
 }
 
-constexpr uint32_t WAVE_SMALL_MAX_LEVEL = 5;  // spb <= 32: one thread per bin (sequential, like :270-278)
-
-uint32_t waveform_blocks_for(uint32_t level, uint32_t bin_count) {
-    if (!bin_count) return 0;
-    if (level <= WAVE_SMALL_MAX_LEVEL) return (bin_count + 255) / 256;
-    return (bin_count + 3) / 4;  // one wave per bin, 4 waves per block
-}
-
 __global__ __launch_bounds__(256) void waveform_kernel(const WaveJob *__restrict__ jobs,
                                                        const uint32_t *__restrict__ block_start, uint32_t n_jobs) {
     const uint32_t ji = find_wjob(block_start, n_jobs, blockIdx.x);
@@ -117,22 +109,6 @@ hipError_t launch_waveform(const WaveJob *d_jobs, const uint32_t *d_block_start,
 // contiguous bytes per wave.  (A first version built levels >= 5 with one launch per level from the level
 // below: those eight small launches took as long as the base pass.)
 // ------------------------------------------------------------------------------------------
-uint64_t pyramid_bins(uint64_t n, uint32_t level) {
-    if (n == 0) return 0;
-    if (level >= 63) return 1;
-    return (n + (1ull << level) - 1) >> level;
-}
-// Float offset of a level inside a channel's pyramid.  Every level starts on a 128-byte boundary (and the total is a
-// multiple of 32 floats, so channels packed back to back stay aligned): level 0 is written with 16-byte stores laid on the
-// output address, and a channel whose base was 4, 8 or 12 bytes off that grid took the dword-store fallback for half of
-// all the bytes — with the dense layout three of four packed channels of the 13-level pyramid did (config 3: 2.10 ms;
-// the same pass into an aligned 11-level pyramid 1.83 ms).
-uint64_t pyramid_offset(uint64_t n, uint32_t level) {
-    uint64_t off = 0;
-    for (uint32_t l = 0; l < level; l++) off += (3 * pyramid_bins(n, l) + 31) / 32 * 32;
-    return off;
-}
-
 constexpr uint32_t PYR_SPT = 16;                  // samples per thread
 constexpr uint32_t PYR_SEG = 256 * PYR_SPT;       // samples per block
 constexpr uint32_t PYR_LDS_STRIDE = 3 * PYR_SPT + 1;  // 49 dwords per lane: conflict-free staging

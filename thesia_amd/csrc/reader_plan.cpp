@@ -3,30 +3,15 @@
 #include "reader_plan.h"
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 
 #include "export_core.h"  // export_bytes_per_sample
+#include "plan_error.h"
 
 namespace th {
 
 namespace {
-template <class P>
-P plan_error(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-template <class P>
-P plan_error(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    P p;
-    p.err = code;
-    p.err_text = buf;
-    return p;
-}
-
 size_t up256(size_t x) { return (x + 255) / 256 * 256; }
 
 template <class T>

@@ -793,8 +793,6 @@ int acquire_slot(th_tm *tm, ReaderSlot **out) {
     }
 }
 
-void put_u32(uint8_t *p, uint32_t v) { std::memcpy(p, &v, 4); }  // little-endian host (x86-64)
-void put_u64(uint8_t *p, uint64_t v) { std::memcpy(p, &v, 8); }
 
 // a mutator's last act before it releases the write lock: readers use their own streams
 int writer_done(th_tm *tm, int rc) {
@@ -1124,54 +1122,24 @@ TH_API int th_tm_get_spectrogram_tile(th_tm *tm, size_t id, uint32_t ch, uint32_
                                       uint32_t tile_x, uint32_t tile_y, uint8_t *out, size_t cap, size_t *out_len) {
     TH_TRY
     TH_REQUIRE(tm && out && out_len, "NULL argument");
+    TH_CHECK(tmi::ensure_colormap(tm));  // (takes the lock exclusively when it has to upload the default map)
     std::shared_lock<std::shared_mutex> rl(tm->rw);
-    Channel *c = find_channel(tm, id, ch);
-    if (!c || !c->d_img) return fail(TH_ERR_NOT_FOUND, "Spectrogram %zu_%u does not exist", id, ch);
+    tmi::TileInfo it;
+    TH_CHECK(tmi::tile_request_info(tm, th_tile_request{id, ch, level_x, level_y, tile_x, tile_y, 0}, &it));
     const uint64_t revision = tm->spectrogram_revision();
-    const uint16_t *src = c->d_img;
-    uint32_t src_w = (uint32_t)c->img_w, src_h = (uint32_t)c->img_h, src_pitch = (uint32_t)c->img_pitch;
-    if (level_x != 0 || level_y != 0) {
-        auto im = c->mips.find({level_x, level_y});
-        if (tm->lod_source != 0 || im == c->mips.end()) {
-            // per-request resampling of the crop box from the level-0 image (the reference's own flow): the
-            // context-stream path, serialised by the context mutex
-            return th_encode_spectrogram_tile_dev(tm->ctx, c->d_img, c->img_h, c->img_w, c->img_pitch,
-                                                  tm->colormap_rgba.data(), tm->colormap_rgba.size(), revision, level_x,
-                                                  level_y, tile_x, tile_y, out, cap, out_len);
-        }
-        src = im->second.d;
-        src_w = im->second.w;
-        src_h = im->second.h;
-        src_pitch = im->second.pitch;
+    if (it.single) {
+        // per-request resampling of the crop box from the level-0 image (the reference's own flow): the
+        // context-stream path, serialised by the context mutex
+        return th_encode_spectrogram_tile_dev(tm->ctx, it.src, it.src_h, it.src_w, it.src_pitch, tm->colormap_rgba.data(),
+                                              tm->colormap_rgba.size(), revision, level_x, level_y, tile_x, tile_y, out, cap, out_len);
     }
-    const TileGeom g = spectrogram_tile_geometry(c->img_w, c->img_h, level_x, level_y, tile_x, tile_y);
+    const TileGeom &g = it.g;
     const size_t px_bytes = g.width * g.height * 4, need = 40 + px_bytes;
     *out_len = need;
     if (cap < need) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", need);
-    put_u64(out, revision);
-    put_u32(out + 8, (uint32_t)g.width);
-    put_u32(out + 12, (uint32_t)g.height);
-    put_u32(out + 16, level_x);
-    put_u32(out + 20, level_y);
-    put_u32(out + 24, tile_x);
-    put_u32(out + 28, tile_y);
-    put_u32(out + 32, (uint32_t)g.origin_x);
-    put_u32(out + 36, (uint32_t)g.origin_y);
+    put_spectrogram_tile_header(out, revision, g, level_x, level_y, tile_x, tile_y);
     if (g.width == 0 || g.height == 0) return TH_OK;
-    if (g.lod_w != src_w || g.lod_h != src_h) return fail(TH_ERR_INTERNAL, "mip level (%u, %u) has the wrong shape", level_x, level_y);
     if (px_bytes > TILE_BYTES_MAX) return fail(TH_ERR_INTERNAL, "tile larger than a reader slot");
-    if (!tm->d_colormap) {  // no th_tm_set_colormap yet: the default two-colour map
-        rl.unlock();
-        {
-            std::unique_lock<std::shared_mutex> wl(tm->rw);
-            TH_HIP(hipSetDevice(tm->ctx->device));
-            if (!tm->d_colormap) {
-                int rc = upload_colormap(tm);
-                if (rc != TH_OK) return rc;
-            }
-        }
-        return th_tm_get_spectrogram_tile(tm, id, ch, level_x, level_y, tile_x, tile_y, out, cap, out_len);
-    }
     TH_HIP(hipSetDevice(tm->ctx->device));
     SlotLease lease{tm, nullptr};
     int rc = acquire_slot(tm, &lease.slot);
@@ -1185,7 +1153,7 @@ TH_API int th_tm_get_spectrogram_tile(th_tm *tm, size_t id, uint32_t ch, uint32_
     }
     // The raster kernel writes the pixels straight into the slot's pinned, device-visible host buffer (16 bytes per lane,
     // 1 KB per wave-instruction over PCIe): no device staging tile, no copy-engine transfer queued behind other readers'.
-    TH_HIP(launch_raster_tile(src, src_w, src_h, src_pitch, (uint32_t)g.origin_x, (uint32_t)g.origin_y, (uint32_t)g.width,
+    TH_HIP(launch_raster_tile(it.src, it.src_w, it.src_h, it.src_pitch, (uint32_t)g.origin_x, (uint32_t)g.origin_y, (uint32_t)g.width,
                               (uint32_t)g.height, sl.h_tile_dev, tm->d_colormap, (uint32_t)(tm->colormap_rgba.size() / 4),
                               sl.stream));
     TH_HIP(hipStreamSynchronize(sl.stream));
@@ -1341,15 +1309,7 @@ int tiles_run(th_tm *tm, const th_tile_request *reqs, size_t n, const TileInfo *
             if (rc != TH_OK) return rc;
             continue;
         }
-        put_u64(rec, revision);
-        put_u32(rec + 8, (uint32_t)it.g.width);
-        put_u32(rec + 12, (uint32_t)it.g.height);
-        put_u32(rec + 16, r.level_x);
-        put_u32(rec + 20, r.level_y);
-        put_u32(rec + 24, r.tile_x);
-        put_u32(rec + 28, r.tile_y);
-        put_u32(rec + 32, (uint32_t)it.g.origin_x);
-        put_u32(rec + 36, (uint32_t)it.g.origin_y);
+        put_spectrogram_tile_header(rec, revision, it.g, r.level_x, r.level_y, r.tile_x, r.tile_y);
     }
     return TH_OK;
 }
@@ -1531,11 +1491,7 @@ TH_API int th_tm_get_waveform_tile(th_tm *tm, size_t id, uint32_t ch, uint32_t l
     const size_t need = 24 + bins * 12;
     *out_len = need;
     if (cap < need) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", need);
-    put_u64(out, revision);
-    put_u32(out + 8, (uint32_t)bins);
-    put_u32(out + 12, spb > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)spb);
-    put_u32(out + 16, tile_index);
-    put_u32(out + 20, 0);
+    put_waveform_tile_header(out, revision, bins, spb, tile_index);
     if (bins) {
         if (!c->d_draw || !c->pyr_levels) return fail(TH_ERR_INTERNAL, "channel %zu_%u has no waveform pyramid", id, ch);
         // a level above the pyramid's last one still has exactly one bin, over the same samples
