@@ -147,10 +147,30 @@ TH_API int th_ctx_destroy(th_ctx *ctx);
 TH_API int th_ctx_synchronize(th_ctx *ctx);
 /* HIP-graph capture of a sequence of this library's stream-ordered calls on the context's stream (a launch-bound
  * sequence like the 8 small kernels of a single-track update: STFT -> range -> quantise -> raster).  Run the sequence
- * once normally first: descriptor tables and scratch buffers are uploaded / sized on first use, which needs stream
- * synchronisation and is refused while capturing (the call then fails with TH_ERR_HIP and the capture must still be
- * ended).  The graph replays the same launches on the same device pointers; it stays valid while the plans, contexts
- * and buffers it touched are alive and unchanged.  Capture is per thread (hipStreamCaptureModeThreadLocal). */
+ * once normally first: descriptor tables and scratch buffers are uploaded / sized on first use, which needs the host.
+ *   - Entries that can be captured (with warm tables they only enqueue): th_calc_spec_batch_dev,
+ *     th_calc_spec_batch_ranged_dev, th_minmax_reduce_dev, th_global_db_range_dev, th_minmax_reduce_range_dev,
+ *     th_spec_to_img_dev, th_spec_to_img_batch_dev, th_spec_to_img_batch_dev_ranged, th_spec_to_img_raster_batch_dev,
+ *     th_raster_tiles_dev, th_waveform_tiles_dev, th_waveform_pyramid_dev, th_dev_copy.
+ *   - Entries that cannot, because they return to host memory or synchronise: th_calc_spec_host, th_encode_*_tile_dev,
+ *     th_channel_stats_dev, th_audio_stats_dev, th_dev_upload / th_dev_download (and th_dev_alloc / th_dev_free,
+ *     th_ctx_synchronize, th_plan_create / th_plan_destroy), every th_tm_* / th_tmg_*.
+ *   - A call of the first group that has to upload a table or size a scratch buffer, and every call of the second group
+ *     but th_tm_* / th_tmg_*, is refused while this thread is capturing: it fails with TH_ERR_HIP before it touches the
+ *     stream.  The capture must still be ended; th_ctx_capture_end then returns an error and *out = NULL.  Context,
+ *     plans and stream are usable afterwards, and the same call made directly works.  th_tm_* / th_tmg_* are not checked:
+ *     a synchronisation of theirs on a capturing stream invalidates the capture inside the HIP runtime, which can leave
+ *     that stream unusable.
+ *   - The graph replays the same launches with the same arguments: the same device pointers, the descriptor tables and
+ *     scratch buffers of the plans and the context as they were when it was captured.  It is INVALID after any later
+ *     call that uses other descriptors on a plan or a context the graph touched (descriptor tables are rewritten in
+ *     place and plan scratch may be reallocated: a replay would read another batch's tables or freed memory — undefined),
+ *     and once a plan, the context or a buffer it touched is gone.  Direct calls with the SAME descriptors in between
+ *     are fine.  What the data in the buffers is at replay time is the caller's: a replay reads its inputs anew.
+ *   - A context on the legacy default stream (which HIP cannot capture) records on a stream of its own and th_graph_launch
+ *     replays on the legacy default stream; on any other stream the capture is the stream's own, so the host's own work
+ *     enqueued on it between begin and end is recorded as well.
+ * Capture is per thread (hipStreamCaptureModeThreadLocal), one at a time. */
 typedef struct th_graph th_graph;
 TH_API int th_ctx_capture_begin(th_ctx *ctx);
 TH_API int th_ctx_capture_end(th_ctx *ctx, th_graph **out); /* *out = NULL and an error if the capture was invalidated */

@@ -191,6 +191,7 @@ TH_API int th_ctx_create_ex(int device, void *hip_stream, int use_given_stream, 
 
 TH_API int th_ctx_destroy(th_ctx *c) {
     TH_TRY
+    TH_CHECK(refuse_while_capturing("destroying the context"));
     if (!c) return TH_OK;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
@@ -201,6 +202,7 @@ TH_API int th_ctx_destroy(th_ctx *c) {
 
 TH_API int th_ctx_synchronize(th_ctx *c) {
     TH_TRY
+    TH_CHECK(refuse_while_capturing("synchronising the stream"));
     TH_REQUIRE(c, "ctx is NULL");
     TH_HIP(hipStreamSynchronize(c->stream));
     return TH_OK;
@@ -213,11 +215,43 @@ struct th_graph {
     hipGraphExec_t exec = nullptr;
 };
 
+// The capture of this thread (hipStreamCaptureModeThreadLocal: begin, the captured calls and end are one thread's)
+namespace {
+struct CaptureState {
+    th_ctx *ctx = nullptr;
+    bool refused = false;
+    char what[160] = "";
+};
+thread_local CaptureState g_capture;
+}  // namespace
+
+int th::refuse_while_capturing(const char *what) {
+    if (g_capture.ctx == nullptr) return TH_OK;
+    if (!g_capture.refused) snprintf(g_capture.what, sizeof g_capture.what, "%s", what);
+    g_capture.refused = true;
+    return fail(TH_ERR_HIP, "%s is not possible while this thread is capturing (th_ctx_capture_begin); end the capture: it yields "
+                            "no graph", what);
+}
+
 TH_API int th_ctx_capture_begin(th_ctx *c) {
     TH_TRY
     TH_REQUIRE(c, "ctx is NULL");
+    TH_REQUIRE(g_capture.ctx == nullptr, "this thread is capturing already (one capture per thread at a time)");
     TH_HIP(hipSetDevice(c->device));
-    TH_HIP(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+    if (c->stream == nullptr) {  // the legacy default stream: record on a stream of the context's own (context.h)
+        if (c->capture_stream == nullptr) TH_HIP(hipStreamCreateWithFlags(&c->capture_stream, hipStreamNonBlocking));
+        c->stream = c->capture_stream;
+        c->capture_swapped = true;
+    }
+    const hipError_t e = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        if (c->capture_swapped) c->stream = nullptr;
+        c->capture_swapped = false;
+        return fail(TH_ERR_HIP, "hipStreamBeginCapture: %s", hipGetErrorString(e));
+    }
+    g_capture = CaptureState();
+    g_capture.ctx = c;
     return TH_OK;
     TH_CATCH
 }
@@ -226,17 +260,24 @@ TH_API int th_ctx_capture_end(th_ctx *c, th_graph **out) {
     TH_TRY
     TH_REQUIRE(c && out, "NULL argument");
     *out = nullptr;
-    TH_HIP(hipSetDevice(c->device));
+    TH_REQUIRE(g_capture.ctx == c, "th_ctx_capture_begin was not called on this context by this thread");
+    const CaptureState cap = g_capture;
+    g_capture = CaptureState();
+    (void)hipSetDevice(c->device);
     hipGraph_t g = nullptr;
     const hipError_t e = hipStreamEndCapture(c->stream, &g);
-    if (e != hipSuccess || g == nullptr) {
+    if (c->capture_swapped) c->stream = nullptr;  // (back on the legacy default stream: the graph is launched there)
+    c->capture_swapped = false;
+    if (e != hipSuccess || g == nullptr || cap.refused) {
         (void)hipGetLastError();
         if (g) (void)hipGraphDestroy(g);
+        if (cap.refused) return fail(TH_ERR_HIP, "no graph: a call was refused while capturing (%s)", cap.what);
         return fail(TH_ERR_HIP, "stream capture failed or was invalidated: %s", hipGetErrorString(e));
     }
     hipGraphExec_t x = nullptr;
     const hipError_t e2 = hipGraphInstantiate(&x, g, nullptr, nullptr, 0);
     if (e2 != hipSuccess) {
+        (void)hipGetLastError();
         (void)hipGraphDestroy(g);
         return fail(TH_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e2));
     }
@@ -270,6 +311,7 @@ TH_API int th_graph_destroy(th_graph *g) {
 
 TH_API int th_dev_alloc(th_ctx *c, size_t bytes, void **dptr) {
     TH_TRY
+    TH_CHECK(refuse_while_capturing("th_dev_alloc"));
     TH_REQUIRE(c && dptr, "NULL argument");
     *dptr = nullptr;
     TH_HIP(hipSetDevice(c->device));
@@ -279,6 +321,7 @@ TH_API int th_dev_alloc(th_ctx *c, size_t bytes, void **dptr) {
 }
 TH_API int th_dev_free(th_ctx *c, void *dptr) {
     TH_TRY
+    TH_CHECK(refuse_while_capturing("th_dev_free"));
     TH_REQUIRE(c, "ctx is NULL");
     if (dptr) {
         TH_HIP(hipSetDevice(c->device));
@@ -290,6 +333,7 @@ TH_API int th_dev_free(th_ctx *c, void *dptr) {
 }
 TH_API int th_dev_upload(th_ctx *c, void *dst, const void *src, size_t bytes) {
     TH_TRY
+    TH_CHECK(refuse_while_capturing("th_dev_upload (a copy from host memory)"));
     TH_REQUIRE(c && (bytes == 0 || (dst && src)), "NULL argument");
     if (bytes) {
         TH_HIP(hipSetDevice(c->device));
@@ -301,6 +345,7 @@ TH_API int th_dev_upload(th_ctx *c, void *dst, const void *src, size_t bytes) {
 }
 TH_API int th_dev_download(th_ctx *c, void *dst, const void *src, size_t bytes) {
     TH_TRY
+    TH_CHECK(refuse_while_capturing("th_dev_download (a copy to host memory)"));
     TH_REQUIRE(c && (bytes == 0 || (dst && src)), "NULL argument");
     if (bytes) {
         TH_HIP(hipSetDevice(c->device));
@@ -330,6 +375,7 @@ TH_API int th_timer_start(th_ctx *c) {
 }
 TH_API int th_timer_stop_ms(th_ctx *c, float *ms) {
     TH_TRY
+    TH_CHECK(refuse_while_capturing("reading a timer"));
     TH_REQUIRE(c && ms, "NULL argument");
     TH_HIP(hipSetDevice(c->device));
     TH_HIP(hipEventRecord(c->ev1, c->stream));
@@ -344,6 +390,7 @@ namespace th {
 
 int DeviceTable::ensure(size_t bytes) {
     if (bytes <= cap) return TH_OK;
+    TH_CHECK(refuse_while_capturing("allocating a scratch buffer or a descriptor table"));
     if (dptr) {
         TH_HIP(hipFree(dptr));
         dptr = nullptr;
@@ -361,6 +408,7 @@ int DeviceTable::ensure(size_t bytes) {
 // previous launch may still be reading the old table.
 int DeviceTable::upload(hipStream_t s, const void *src, size_t bytes) {
     if (bytes == last.size() && bytes && std::memcmp(last.data(), src, bytes) == 0) return TH_OK;
+    TH_CHECK(refuse_while_capturing("uploading a descriptor table (a first call, or one with other descriptors)"));
     TH_HIP(hipStreamSynchronize(s));
     int rc = ensure(bytes);
     if (rc != TH_OK) return rc;
@@ -469,6 +517,7 @@ static void resolve_route(th_plan &p) {
 TH_API int th_plan_create(th_ctx *c, uint32_t sr, size_t win, size_t hop, size_t n_fft, int freq_scale,
                           size_t n_mel, th_plan **out) {
     TH_TRY
+    TH_CHECK(refuse_while_capturing("creating a plan"));
     TH_REQUIRE(c && out, "NULL argument");
     *out = nullptr;
     TH_REQUIRE(freq_scale == TH_FREQ_LINEAR || freq_scale == TH_FREQ_MEL, "bad freq_scale %d", freq_scale);
@@ -633,6 +682,7 @@ TH_API int th_plan_create(th_ctx *c, uint32_t sr, size_t win, size_t hop, size_t
 
 TH_API int th_plan_destroy(th_plan *p) {
     TH_TRY
+    TH_CHECK(refuse_while_capturing("destroying a plan"));
     if (!p) return TH_OK;
     (void)hipSetDevice(p->ctx->device);
     (void)hipStreamSynchronize(p->ctx->stream);
@@ -803,6 +853,7 @@ static int calc_spec_batch_impl(th_plan *p, const th_chan_desc *chans, size_t n_
     if (mel_mfma && l.amp_rows) {
         const size_t need = (size_t)l.amp_rows * amp_pitch * sizeof(float);
         if (need > p->amp_buf.cap || p->amp_zeroed < need) {
+            TH_CHECK(refuse_while_capturing("sizing the amplitude scratch"));
             TH_HIP(hipStreamSynchronize(c->stream));
             rc = p->amp_buf.ensure(need);
             if (rc != TH_OK) return rc;
@@ -836,7 +887,10 @@ static int calc_spec_batch_impl(th_plan *p, const th_chan_desc *chans, size_t n_
         const size_t need = !wave ? (r.main == StftRoute::Main::Bluestein ? th::stft_bluestein_scratch_bytes(g, (uint32_t)tiles, c->n_cu) : th::stft_generic_scratch_bytes(g, (uint32_t)tiles, c->n_cu))
                                   : (edge.empty() ? 0 : th::stft_generic_scratch_bytes(ge, (uint32_t)edge_tiles, c->n_cu));
         if (need) {
-            if (need > p->gen_scratch.cap) TH_HIP(hipStreamSynchronize(c->stream));  // (a launch may still use the old buffer)
+            if (need > p->gen_scratch.cap) {
+                TH_CHECK(refuse_while_capturing("sizing the frame scratch"));
+                TH_HIP(hipStreamSynchronize(c->stream));  // (a launch may still use the old buffer)
+            }
             rc = p->gen_scratch.ensure(need);
             if (rc != TH_OK) return rc;
         }
@@ -975,6 +1029,7 @@ TH_API int th_plan_time_kernel(th_plan *p, int enable) {
 
 TH_API int th_plan_kernel_ms_history(th_plan *p, float *out_ms, size_t capacity, size_t *n_out) {
     TH_TRY
+    TH_CHECK(refuse_while_capturing("reading kernel times"));
     TH_REQUIRE(p && n_out && (out_ms || capacity == 0), "NULL argument");
     std::lock_guard<std::recursive_mutex> lk(p->ctx->mu);
     const size_t have = (size_t)std::min<uint64_t>(p->timed_launches, th_plan::TIMER_SLOTS);
@@ -998,6 +1053,7 @@ TH_API int th_plan_kernel_ms_history(th_plan *p, float *out_ms, size_t capacity,
 
 TH_API int th_plan_last_kernel_ms(th_plan *p, float *ms) {
     TH_TRY
+    TH_CHECK(refuse_while_capturing("reading kernel times"));
     TH_REQUIRE(p && ms, "NULL argument");
     size_t n = 0;
     const int rc = th_plan_kernel_ms_history(p, ms, 1, &n);
@@ -1010,6 +1066,7 @@ TH_API int th_plan_last_kernel_ms(th_plan *p, float *ms) {
 TH_API int th_calc_spec_host(th_plan *p, const float *wav, size_t n_samples, float *out_spec, size_t cap,
                              size_t *n_frames, float *out_min, float *out_max) {
     TH_TRY
+    TH_CHECK(refuse_while_capturing("th_calc_spec_host (host buffers)"));
     TH_REQUIRE(p && wav && out_spec && n_frames, "NULL argument");
     TH_REQUIRE(n_samples >= 1, "empty input");
     const StftGeom &g = p->g;
@@ -1173,6 +1230,7 @@ TH_API int th_encode_spectrogram_tile_dev(th_ctx *c, const uint16_t *d_img, size
                                           uint32_t level_x, uint32_t level_y, uint32_t tile_x, uint32_t tile_y,
                                           uint8_t *out, size_t cap, size_t *out_len) {
     TH_TRY
+    TH_CHECK(refuse_while_capturing("th_encode_spectrogram_tile_dev (it returns the tile to host memory)"));
     TH_REQUIRE(c && out && out_len, "NULL argument");
     TH_REQUIRE(colormap_rgba && colormap_bytes >= 4 && colormap_bytes % 4 == 0, "colormap must be a non-empty RGBA8 array");
     TH_REQUIRE(img_width < (1ull << 31) && img_height < (1ull << 31), "image too large");
@@ -1246,6 +1304,7 @@ TH_API int th_waveform_tiles_dev(th_ctx *c, const th_wave_desc *descs, size_t n)
 TH_API int th_channel_stats_dev(th_ctx *c, const th_stats_desc *descs, size_t n, float *out_sum_squares,
                                 float *out_abs_max) {
     TH_TRY
+    TH_CHECK(refuse_while_capturing("th_channel_stats_dev (it returns to host memory)"));
     TH_REQUIRE(c, "ctx is NULL");
     if (n == 0) return TH_OK;
     TH_REQUIRE(descs && out_sum_squares && out_abs_max, "NULL argument");
@@ -1302,6 +1361,7 @@ TH_API int th_encode_waveform_tile_dev(th_ctx *c, const float *d_wav, size_t n_s
                                        uint32_t level, uint32_t tile_index, uint8_t *out, size_t cap,
                                        size_t *out_len) {
     TH_TRY
+    TH_CHECK(refuse_while_capturing("th_encode_waveform_tile_dev (it returns the tile to host memory)"));
     TH_REQUIRE(c && out && out_len, "NULL argument");
     TH_REQUIRE_ALIGNED(d_wav, 4, "d_wav must be 4-byte aligned");
     size_t start, bins, spb;
@@ -1691,6 +1751,7 @@ void loudness_result(const LoudnessBatch &b, size_t t, th_audio_stats *out) {
 
 TH_API int th_audio_stats_dev(th_ctx *c, const th_audio_desc *descs, size_t n, th_audio_stats *out_host) {
     TH_TRY
+    TH_CHECK(refuse_while_capturing("th_audio_stats_dev (it returns to host memory)"));
     TH_REQUIRE(c, "ctx is NULL");
     if (n == 0) return TH_OK;
     TH_REQUIRE(descs && out_host, "NULL argument");

@@ -52,10 +52,14 @@ inline int fail(int code, const char *fmt, ...) {
         if (rc_ != TH_OK) return rc_; \
     } while (0)
 
+// (The runtime keeps a failed call's error until hipGetLastError() is called, and every launcher reports its launch with
+// hipGetLastError(): the error is taken out here, with the failure it is reported by, or the next, unrelated launch would report it.)
 #define TH_HIP(call)                                                    \
     do {                                                                  \
         hipError_t e_ = (call);                                           \
-        if (e_ != hipSuccess)                                             \
+        if (e_ != hipSuccess) {                                           \
+            (void)hipGetLastError();                                      \
             return th::fail(e_ == hipErrorOutOfMemory ? TH_ERR_OOM : TH_ERR_HIP, "%s failed: %s (%s:%d)", #call, \
                             hipGetErrorString(e_), __FILE__, __LINE__);   \
+        }                                                                 \
     } while (0)

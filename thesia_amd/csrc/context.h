@@ -98,6 +98,13 @@ struct KeyedTables {
     const T *at(size_t i) const { return static_cast<const T *>(tab[i].dptr); }
 };
 
+// Between th_ctx_capture_begin and th_ctx_capture_end on this thread: TH_ERR_HIP, and the capture marked as failed
+// (th_ctx_capture_end then returns an error and no graph); TH_OK otherwise.  Called in front of everything that needs the host —
+// a table upload, a scratch allocation, a synchronisation, a result read back — so that the HIP call the capture forbids is never
+// made: it would invalidate the capture, and a stream whose capture was invalidated stays unusable after hipStreamEndCapture
+// (hipStreamIsCapturing goes on reporting it: ROCm 7.2), and with it a context on a caller's stream.
+int refuse_while_capturing(const char *what);
+
 }  // namespace th
 
 struct th_ctx {
@@ -105,6 +112,10 @@ struct th_ctx {
     uint32_t n_cu = 256;  // compute units (persistent-grid size of the wave kernel)
     hipStream_t stream = nullptr;
     bool own_stream = false;
+    // The legacy default stream cannot be captured (hipStreamBeginCapture refuses it), but a graph can be launched on it: a
+    // context on it records on this stream of its own, which `stream` names between th_ctx_capture_begin and _end.
+    hipStream_t capture_stream = nullptr;
+    bool capture_swapped = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // Serialises use of the stream-side scratch below; recursive so composed entry points
     // (tile encoders → batched launchers) can hold it across the whole request.
@@ -116,6 +127,7 @@ struct th_ctx {
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         if (own_stream && stream) (void)hipStreamDestroy(stream);
+        if (capture_stream) (void)hipStreamDestroy(capture_stream);
     }
 };
 
