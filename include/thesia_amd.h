@@ -824,6 +824,76 @@ TH_API int th_tm_export_pcm_at(th_tm *tm, const th_export_at_request *reqs, size
 TH_API int th_tm_export_wav_at(th_tm *tm, const th_export_at_request *req, uint8_t *out, size_t cap_bytes,
                                th_export_info *info /* may be NULL */, size_t *out_len);
 
+/* ---------------------------------------------------------------- Export as figures: a spectrogram region at any pixel size */
+/* Any region of a channel's resident u16 image, resampled on the device to any pixel size and coloured (or left as 16-bit grey): what
+ * a host saves as a figure, without fetching tiles, stitching them and resampling a second time (upstream's roadmap item "export as
+ * figures"; no reference implementation exists, these definitions are the contract).
+ *   A figure is the region box = (left, top, width, height) of the image resampled to out_w x out_h pixels.  Box coordinates are
+ *   doubles in image pixels: x = frame columns, y = image rows, row 0 = the lowest frequency (the coordinates of a LOD tile's crop
+ *   box).  The resampling is the separable Lanczos3 of the LOD tiles: the horizontal pass, then the vertical one; a pass takes the
+ *   taps of th_figure_axis (normalised on the host), adds pixel x tap in ascending tap order from 0.0 in f64 (a multiplication, then an
+ *   addition), rounds half up (floor(v + 0.5)) and clamps to [0, 65535].  The filter is clipped at the IMAGE, never at the box: a
+ *   figure of a region is filtered with the pixels around the region.
+ *   TH_FIGURE_RGBA: out_h x out_w x 4 bytes, the top row = the highest frequency (output row j = vertical output out_h - 1 - j); the
+ *   colour is entry (v (n_colors - 1) + 32767) / 65535 of the manager's colormap, as in a tile.  TH_FIGURE_GREY16: out_h x out_w
+ *   little-endian u16 in the same row order.  The whole image at its own size is an exact copy (rows flipped).
+ *   th_figure_axis (host): the taps of one axis of n_in source pixels: for output o, source pixels start[o] .. start[o] + count[o] - 1
+ *   with the weights w[o * *max_taps + t].  scale = extent / n_out, f = max(scale, 1), centre = origin + (o + 0.5) scale, the window
+ *   [(long)(centre - 3 f + 0.5), (long)(centre + 3 f + 0.5)) clipped to [0, n_in), tap t = L(((t + start) - centre + 0.5) / f),
+ *   L(x) = sinc(x) sinc(x / 3) on -3 <= x < 3, sinc(x) = sin(pi x) / (pi x), each tap divided by the window's sum; C double (Pillow's
+ *   ImagingResample coefficients with the box kept in double).  start and count: n_out entries; weights may be NULL or
+ *   cap_weights < n_out x *max_taps: TH_ERR_BUFFER_TOO_SMALL with start, count and *max_taps filled.
+ *   th_figure_box (host): the box of (start_sec, end_sec, hz_min, hz_max) for a track of n_samples at sr whose image is img_width
+ *   columns x img_height rows over a spectrogram of spec_height rows.  x(sec) = sec sr / n_samples img_width (the viewer's mapping:
+ *   pixels per second = image width / track seconds); y(hz) = r(hz) spec_height, r = hz / (sr / 2) under TH_FREQ_LINEAR and
+ *   mel(hz) / mel(sr / 2) under TH_FREQ_MEL, mel = the library's Slaney scale; all in C double, so that integral results are the rows
+ *   of th_hz_range_to_idx.  end_sec = +inf: the track's end; hz_max = +inf: the image's top row.  The result is clamped to the image.
+ *   TH_ERR_INVALID_ARG: a NaN argument, a negative or infinite start_sec or hz_min, an end not above its start after clamping, a zero
+ *   sr, n_samples, img_width, spec_height or img_height.  th_tm_figure_box fills in what the manager knows of (id, ch).
+ * th_tm_render_figures: request i's record starts at out + info[i].offset, a multiple of 64, and holds info[i].bytes bytes; the bytes
+ * between two records are not written; *out_len = the last record's end.  A reader like th_tm_export_pcm: shared lock, a reader
+ * slot's own streams; out == NULL or cap_bytes < *out_len: TH_ERR_BUFFER_TOO_SMALL with info and *out_len filled.  The first faulty
+ * request decides: an unknown id or a channel without a resident image: TH_ERR_NOT_FOUND; a bad channel or kind, out_w or out_h zero
+ * or above TH_FIGURE_MAX_DIM, a box with a non-finite or non-positive extent or one that is not inside the image:
+ * TH_ERR_INVALID_ARG; a tap table beyond 256 MB (the rule of the LOD tiles): TH_ERR_UNSUPPORTED.  On any error nothing is written to
+ * out.  A request's bytes depend on its image, box, size, kind and the colormap alone: not on the batch, the slot, the pieces below,
+ * or th_tm against th_tmg.  spectrogram_revision: the revision the bytes belong to.
+ * Device memory is BOUNDED: a call is cut into pieces, bands of whole output rows of one or more requests; a piece is at most
+ * TH_FIGURE_PIECE_BYTES of output in one of two staging buffers (piece p + 1 is computed while piece p is copied out; into pinned
+ * memory, th_host_alloc, that copy is the only one), and the horizontal pass's intermediate of a piece (u16, the source rows its
+ * bands' filter windows span x out_w) is at most TH_FIGURE_TMP_BYTES, or what ONE output row needs where that alone is more (at
+ * most 6 r + 2 source rows, r = the vertical reduction, of out_w pixels rounded up to 8: the 256 MB rule, (6 r + 4) x 8 x out_w <=
+ * 256 MB, keeps that at 64 MiB for out_w >= 8, and it is never more than the image's rows).  Adjacent bands recompute the source rows their windows share: a row's
+ * horizontal pass does not depend on the band.  Tap tables are built and uploaded once per call and distinct (axis length, origin,
+ * extent, output size).  A slot's figure scratch is made on its first figure and only grows. */
+#define TH_FIGURE_RGBA 0
+#define TH_FIGURE_GREY16 1
+#define TH_FIGURE_MAX_DIM 16384u
+#define TH_FIGURE_PIECE_BYTES (8u << 20)
+#define TH_FIGURE_TMP_BYTES (16u << 20)
+typedef struct {
+    size_t id;
+    uint32_t ch;
+    uint32_t kind;         /* TH_FIGURE_* */
+    uint32_t out_w, out_h; /* 1 .. TH_FIGURE_MAX_DIM */
+    double left, top, width, height;
+} th_figure_request;
+typedef struct {
+    uint64_t offset, bytes; /* into out */
+    uint32_t out_w, out_h;
+    uint64_t spectrogram_revision;
+} th_figure_info;
+TH_API int th_figure_axis(double origin, double extent, uint32_t n_out, uint32_t n_in, int32_t *start /* n_out */,
+                          int32_t *count /* n_out */, double *weights, size_t cap_weights, uint32_t *max_taps);
+TH_API int th_figure_box(double start_sec, double end_sec, double hz_min, double hz_max, uint32_t sr, size_t n_samples,
+                         size_t img_width, size_t spec_height, size_t img_height, int freq_scale, double *left, double *top,
+                         double *width, double *height);
+TH_API int th_tm_figure_box(th_tm *tm, size_t id, uint32_t ch, double start_sec, double end_sec, double hz_min, double hz_max,
+                            double *left, double *top, double *width, double *height);
+TH_API int th_tm_render_figures(th_tm *tm, const th_figure_request *reqs, size_t n, uint8_t *out, size_t cap_bytes,
+                                th_figure_info *info /* n */, size_t *out_len);
+TH_API int th_tm_render_figure(th_tm *tm, const th_figure_request *req, uint8_t *out, size_t cap_bytes, th_figure_info *info);
+
 /* ---------------------------------------------------------------- TrackManager over several devices (one process) */
 /* th_tmg: the th_tm_* calls above, call for call, with a th_tmg * in place of the th_tm *; a multi-GPU host swaps one for
  * the other.  Every result — updated ids, max_sr, db state, revisions, specs, images, tile bytes, batch offsets, render
@@ -913,6 +983,14 @@ TH_API int th_tmg_export_pcm_at(th_tmg *tmg, const th_export_at_request *reqs, s
                                 th_export_info *info /* n */, size_t *out_len);
 TH_API int th_tmg_export_wav_at(th_tmg *tmg, const th_export_at_request *req, uint8_t *out, size_t cap_bytes,
                                 th_export_info *info /* may be NULL */, size_t *out_len);
+
+/* figures: every request goes to its owning slot and the slots are served side by side, each copying its records straight into the
+ * caller's buffer; bytes, offsets and infos are those of one th_tm, the revision stamped is the manager's own */
+TH_API int th_tmg_figure_box(th_tmg *tmg, size_t id, uint32_t ch, double start_sec, double end_sec, double hz_min, double hz_max,
+                             double *left, double *top, double *width, double *height);
+TH_API int th_tmg_render_figures(th_tmg *tmg, const th_figure_request *reqs, size_t n, uint8_t *out, size_t cap_bytes,
+                                 th_figure_info *info /* n */, size_t *out_len);
+TH_API int th_tmg_render_figure(th_tmg *tmg, const th_figure_request *req, uint8_t *out, size_t cap_bytes, th_figure_info *info);
 
 /* Test and measurement entry points (kernel selectors for A/B runs, per-launch kernel timing, replacing a resident image
  * with given pixels) are NOT part of this interface: include/thesia_amd_testing.h declares them; a thesia host binds none. */

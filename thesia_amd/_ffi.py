@@ -128,6 +128,16 @@ class ExportAtRequest(C.Structure):  # th_export_at_request
     _fields_ = [("base", ExportRequest), ("sr_out", C.c_uint32)]
 
 
+class FigureRequest(C.Structure):  # th_figure_request
+    _fields_ = [("id", C.c_size_t), ("ch", C.c_uint32), ("kind", C.c_uint32), ("out_w", C.c_uint32), ("out_h", C.c_uint32),
+                ("left", C.c_double), ("top", C.c_double), ("width", C.c_double), ("height", C.c_double)]
+
+
+class FigureInfo(C.Structure):  # th_figure_info
+    _fields_ = [("offset", C.c_uint64), ("bytes", C.c_uint64), ("out_w", C.c_uint32), ("out_h", C.c_uint32),
+                ("spectrogram_revision", C.c_uint64)]
+
+
 class PyramidDesc(C.Structure):
     _fields_ = [("wav", C.c_void_p), ("out", C.c_void_p), ("n_samples", C.c_uint64), ("n_levels", C.c_uint32),
                 ("first_level", C.c_uint32)]
@@ -337,6 +347,18 @@ _SIGS = {
     "th_tm_export_wav_at": [vp, C.POINTER(ExportAtRequest), C.c_void_p, C.c_size_t, C.POINTER(ExportInfo), c_szp],
     "th_tmg_export_pcm_at": [vp, C.POINTER(ExportAtRequest), C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(ExportInfo), c_szp],
     "th_tmg_export_wav_at": [vp, C.POINTER(ExportAtRequest), C.c_void_p, C.c_size_t, C.POINTER(ExportInfo), c_szp],
+    "th_figure_axis": [C.c_double, C.c_double, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                       C.c_size_t, C.POINTER(C.c_uint32)],
+    "th_figure_box": [C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint32, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int,
+                      C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)],
+    "th_tm_figure_box": [vp, C.c_size_t, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double),
+                         C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)],
+    "th_tmg_figure_box": [vp, C.c_size_t, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double),
+                          C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)],
+    "th_tm_render_figures": [vp, C.POINTER(FigureRequest), C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(FigureInfo), c_szp],
+    "th_tm_render_figure": [vp, C.POINTER(FigureRequest), C.c_void_p, C.c_size_t, C.POINTER(FigureInfo)],
+    "th_tmg_render_figures": [vp, C.POINTER(FigureRequest), C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(FigureInfo), c_szp],
+    "th_tmg_render_figure": [vp, C.POINTER(FigureRequest), C.c_void_p, C.c_size_t, C.POINTER(FigureInfo)],
     "th_tile_cache_create": [C.c_size_t, C.POINTER(vp)],
     "th_tile_cache_destroy": [vp],
     "th_tile_cache_lookup": [vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), c_u8p, C.c_size_t,

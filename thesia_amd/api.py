@@ -31,6 +31,10 @@ EXPORT_MAX_CHANNELS = 1024         # TH_EXPORT_MAX_CHANNELS
 EXPORT_CHUNK_SAMPLES = 4096        # samples (frames x channels) of one workgroup of the export kernel, at most
 RESAMPLE_MAX_TAPS = 16384          # TH_RESAMPLE_MAX_TAPS
 RESAMPLE_MAX_COEFS = 1 << 24       # TH_RESAMPLE_MAX_COEFS
+FIGURE_RGBA, FIGURE_GREY16 = 0, 1
+FIGURE_MAX_DIM = 16384             # TH_FIGURE_MAX_DIM
+FIGURE_PIECE_BYTES = 8 << 20       # TH_FIGURE_PIECE_BYTES
+FIGURE_TMP_BYTES = 16 << 20        # TH_FIGURE_TMP_BYTES
 WAVEFORM_TILE_MAX_BYTES = 24 + 1024 * 12
 SPECTROGRAM_TILE_MAX_BYTES = 40 + 520 * 520 * 4
 
@@ -437,6 +441,95 @@ class _ExportAtMethods:
         out = np.empty(need.value, np.uint8)
         check(fn(self.handle, C.byref(req), out.ctypes.data, out.size, C.byref(info), C.byref(need)))
         return out.tobytes(), _export_info_dict(info)
+
+
+def figure_axis(origin: float, extent: float, n_out: int, n_in: int):
+    """th_figure_axis -> (start int32[n_out], count int32[n_out], weights f64[n_out, max_taps]): the normalised Lanczos3 taps of one
+    axis of a figure, n_out pixels over [origin, origin + extent) of n_in source pixels (host)"""
+    start, count = np.empty(n_out, np.int32), np.empty(n_out, np.int32)
+    mt = C.c_uint32()
+    i32p, f64p = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+    rc = lib.th_figure_axis(origin, extent, n_out, n_in, _ptr(start, i32p), _ptr(count, i32p), None, 0, C.byref(mt))
+    if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+        check(rc)
+    w = np.empty((n_out, mt.value), np.float64)
+    check(lib.th_figure_axis(origin, extent, n_out, n_in, _ptr(start, i32p), _ptr(count, i32p), _ptr(w, f64p), w.size, C.byref(mt)))
+    return start, count, w
+
+
+def figure_box(start_sec: float, end_sec: float, hz_min: float, hz_max: float, sr: int, n_samples: int, img_width: int,
+               spec_height: int, img_height: int, freq_scale: int):
+    """th_figure_box -> (left, top, width, height) in image pixels of a time / frequency range (host)"""
+    b = [C.c_double() for _ in range(4)]
+    check(lib.th_figure_box(start_sec, end_sec, hz_min, hz_max, sr, n_samples, img_width, spec_height, img_height, freq_scale,
+                            *[C.byref(v) for v in b]))
+    return tuple(v.value for v in b)
+
+
+def _figure_request(r) -> "_ffi.FigureRequest":
+    """(track_id, ch, kind, out_w, out_h, (left, top, width, height)) or a dict with those names (the box under "box")"""
+    if isinstance(r, dict):
+        r = (r["track_id"], r["ch"], r.get("kind", FIGURE_RGBA), r["out_w"], r["out_h"], r["box"])
+    track_id, ch, kind, out_w, out_h, box = r
+    return _ffi.FigureRequest(track_id, ch, kind, out_w, out_h, *[float(v) for v in box])
+
+
+class _FigureMethods:
+    """any region of a resident spectrogram image at any pixel size, coloured or 16-bit grey (th_tm_* and th_tmg_*: _PFX)"""
+
+    def figure_box(self, track_id: int, ch: int, start_sec: float = 0.0, end_sec: float = float("inf"), hz_min: float = 0.0,
+                   hz_max: float = float("inf")):
+        """th_tm_figure_box -> (left, top, width, height) of the range in the channel's resident image"""
+        b = [C.c_double() for _ in range(4)]
+        check(getattr(lib, self._PFX + "figure_box")(self.handle, track_id, ch, start_sec, end_sec, hz_min, hz_max,
+                                                     *[C.byref(v) for v in b]))
+        return tuple(v.value for v in b)
+
+    def render_figures(self, requests, out=None, cap: Optional[int] = None):
+        """th_tm_render_figures: requests = iterable of (track_id, ch, kind, out_w, out_h, (left, top, width, height)) ->
+        (list of arrays, list of info dicts); array i is uint8 [out_h, out_w, 4] (FIGURE_RGBA) or uint16 [out_h, out_w]
+        (FIGURE_GREY16), the top row the highest frequency.  out: a uint8 array to fill instead of a new one, or the address of
+        cap bytes (pinned memory of th_host_alloc, say); the arrays are then views into it."""
+        reqs = [_figure_request(r) for r in requests]
+        n = len(reqs)
+        if n == 0:
+            return [], []
+        arr = (_ffi.FigureRequest * n)(*reqs)
+        info = (_ffi.FigureInfo * n)()
+        need = C.c_size_t()
+        fn = getattr(lib, self._PFX + "render_figures")
+        if out is None:
+            rc = fn(self.handle, arr, n, None, 0, info, C.byref(need))
+            if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+                check(rc)
+            out = np.empty(max(need.value, 1), np.uint8)
+        if isinstance(out, np.ndarray):
+            addr, cap, buf = out.ctypes.data, out.size, out
+        else:
+            addr = out.value if isinstance(out, C.c_void_p) else int(out)
+            buf = None
+        check(fn(self.handle, arr, n, addr, cap, info, C.byref(need)))
+        if buf is None:
+            buf = np.frombuffer((C.c_uint8 * need.value).from_address(addr), np.uint8)
+        figs = []
+        for r, o in zip(reqs, info):
+            raw = buf[o.offset: o.offset + o.bytes]
+            figs.append(raw.view(np.uint16).reshape(o.out_h, o.out_w) if r.kind == FIGURE_GREY16 else raw.reshape(o.out_h, o.out_w, 4))
+        return figs, [_export_info_dict(o) for o in info]
+
+    def render_figure(self, track_id: int, ch: int, kind: int, out_w: int, out_h: int, box):
+        """th_tm_render_figure -> (array, info dict) of one figure"""
+        req = _figure_request((track_id, ch, kind, out_w, out_h, box))
+        info = _ffi.FigureInfo()
+        fn = getattr(lib, self._PFX + "render_figure")
+        rc = fn(self.handle, C.byref(req), None, 0, C.byref(info))
+        if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+            check(rc)
+        out = np.empty(max(info.bytes, 1), np.uint8)
+        check(fn(self.handle, C.byref(req), out.ctypes.data, out.size, C.byref(info)))
+        raw = out[:info.bytes]
+        fig = raw.view(np.uint16).reshape(out_h, out_w) if kind == FIGURE_GREY16 else raw.reshape(out_h, out_w, 4)
+        return fig, _export_info_dict(info)
 
 
 def true_peak_filter(sr: int):
@@ -952,7 +1045,7 @@ class TileCache:
                 "spectrogram_revision": sr.value, "hits": h.value, "misses": m.value}
 
 
-class TrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods, _ExportAtMethods):
+class TrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods, _ExportAtMethods, _FigureMethods):
     """th_tm: mirror of core/mod.rs TrackManager with HBM-resident audio / specs / images."""
     _PFX = "th_tm_"
 
@@ -1152,7 +1245,7 @@ class TrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _E
         return out[: n.value].tobytes()
 
 
-class MultiTrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods, _ExportAtMethods):
+class MultiTrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods, _ExportAtMethods, _FigureMethods):
     """th_tmg: the TrackManager over several devices of one process (duplicates allowed: [0, 0] is two slots on one card).
     Same method names as TrackManager; results are bit-identical to one TrackManager holding every track."""
     _PFX = "th_tmg_"

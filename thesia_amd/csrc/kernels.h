@@ -11,6 +11,7 @@
 #include "batch_plan.h"  // ImgJob, FusedJob, RasterJob, WaveJob, PyrJob, StatsJob, their constants, pyramid_bins / pyramid_offset / waveform_blocks_for
 #include "host_math.h"
 #include "stft_core.h"
+#include "figure_plan.h"  // FigHJob, FigVJob, FIG_* (the tile shape of kernels_figure.hip)
 #include "reader_plan.h"  // LoudJob, LoudTrackJob, TruePeakJob, ExportJob, ResampleJob, ResampleTiling and their constants
 #include "stft_plan.h"  // WavePostJob, MelJob, MEL_TILE_FRAMES, MEL_ROWS_*
 
@@ -281,5 +282,11 @@ hipError_t launch_export(const ExportJob *d_jobs, uint32_t n_jobs, uint32_t n_ch
 // table: L rows of `taps` floats (host_math.h resample_table); n_blocks: the sum over the jobs
 hipError_t launch_resample(const ResampleJob *d_jobs, uint32_t n_jobs, uint32_t n_blocks, const float *d_table, const ResampleTiling &t,
                            hipStream_t s);
+
+// ---- kernels_figure.hip: a region of a u16 image at any pixel size (FigHJob, FigVJob: figure_plan.h).  n_blocks: the sum over the jobs
+hipError_t launch_figure_hpass(const FigHJob *d_jobs, uint32_t n_jobs, uint32_t n_blocks, hipStream_t s);
+// d_colormap: n_colors RGBA entries (read by the TH_FIGURE_RGBA jobs only)
+hipError_t launch_figure_vpass(const FigVJob *d_jobs, uint32_t n_jobs, uint32_t n_blocks, const uint8_t *d_colormap, uint32_t n_colors,
+                               hipStream_t s);
 
 }  // namespace th

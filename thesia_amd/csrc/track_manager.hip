@@ -29,6 +29,7 @@
 #include "common.h"
 #include "context.h"
 #include "export_core.h"
+#include "figure_plan.h"
 #include "host_math.h"
 #include "kernels.h"
 #include "resample_core.h"
@@ -91,6 +92,14 @@ struct ReaderSlot {
     th::DeviceBuf<float> rs_scratch, rs_table;
     size_t rs_scratch_cap = 0, rs_table_cap = 0;  // floats
     uint32_t rs_sr_in = 0, rs_sr_out = 0;         // the pair rs_table holds (0: none)
+    // th_tm_render_figures: two staging buffers (each at most TH_FIGURE_PIECE_BYTES), the horizontal pass's intermediate of one piece
+    // (u16; at most TH_FIGURE_TMP_BYTES unless one output row alone needs more) and the call's table (tap tables, then the job tables).
+    // The copy stream and its events are the export's.  Empty until the slot's first figure
+    th::DeviceBuf<uint8_t> fig_stage[2];
+    size_t fig_stage_cap[2] = {0, 0};
+    th::DeviceBuf<uint16_t> fig_tmp;
+    size_t fig_tmp_cap = 0;  // elements
+    th::DeviceTable fig_tab;
 };
 constexpr size_t TILE_BYTES_MAX = 520 * 520 * 4;  // 512 core + 2 x 4 gutter (render_tiles.rs:15-16); >= 1024 * 12 waveform bins
 constexpr size_t MAX_READER_SLOTS = 16;
@@ -2729,5 +2738,189 @@ TH_API int th_tm_export_pcm_at(th_tm *tm, const th_export_at_request *reqs, size
 TH_API int th_tm_export_wav_at(th_tm *tm, const th_export_at_request *req, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
     TH_TRY
     return export_wav_at(tm, req, out, cap, info, out_len);
+    TH_CATCH
+}
+
+// ---------------------------------------------------------------------------------------------- figures
+// th_tm_render_figures: a reader.  plan_figures (figure_plan.h) checks the requests, builds the tap tables and cuts the call into
+// pieces; bind_figures gives the jobs their addresses; what is left here is the slot, its buffers, the upload and the pipeline of the
+// two streams: per piece the two launches of kernels_figure.hip into staging buffer p & 1 and one copy per part into the caller's
+// buffer on the slot's copy stream, while the next piece is computed.
+namespace th {
+namespace tmi {
+int figure_request_info(th_tm *tm, const th_figure_request &r, size_t i, FigureInfo *info) {
+    auto it = tm->tracks.find(r.id);
+    if (it == tm->tracks.end()) return fail(TH_ERR_NOT_FOUND, "request %zu: Track %zu does not exist", i, r.id);
+    TH_REQUIRE(r.ch < it->second.ch.size(), "request %zu: Track %zu has no channel %u", i, r.id, r.ch);
+    const Channel &c = it->second.ch[r.ch];
+    if (!c.d_img) return fail(TH_ERR_NOT_FOUND, "request %zu: Spectrogram %zu_%u does not exist", i, r.id, r.ch);
+    *info = FigureInfo{};
+    info->plan = FigurePlanRequest{c.d_img, (uint32_t)c.img_w, (uint32_t)c.img_h, (uint32_t)c.img_pitch, r.kind, r.out_w, r.out_h,
+                                   r.left, r.top, r.width, r.height, 0};
+    const FigureStatus st = check_figure(info->plan, i);
+    if (st.err != TH_OK) return fail(st.err, "%s", st.err_text.c_str());
+    info->bytes = (uint64_t)r.out_w * r.out_h * figure_bytes_per_pixel(r.kind);
+    info->out_w = r.out_w;
+    info->out_h = r.out_h;
+    info->spectrogram_revision = tm->spectrogram_revision();
+    return TH_OK;
+}
+
+size_t figures_layout(FigureInfo *info, size_t n) {
+    uint64_t at = 0, end = 0;
+    for (size_t i = 0; i < n; i++) {
+        info[i].offset = info[i].plan.offset = at;
+        end = at + info[i].bytes;
+        at = (end + 63) & ~(uint64_t)63;
+    }
+    return (size_t)end;
+}
+
+int figures_run(th_tm *tm, size_t n, const FigureInfo *info, uint8_t *out) {
+    std::vector<FigurePlanRequest> prs(n);
+    for (size_t i = 0; i < n; i++) prs[i] = info[i].plan;
+    FigurePlan pl = plan_figures(prs.data(), n);
+    if (pl.err != TH_OK) return fail(pl.err, "%s", pl.err_text.c_str());
+    const std::vector<FigurePiece> &pieces = pl.pieces;
+    if (pieces.empty()) return TH_OK;
+
+    TH_HIP(hipSetDevice(tm->ctx->device));
+    SlotLease lease{tm, nullptr};
+    int rc = acquire_slot(tm, &lease.slot);
+    if (rc != TH_OK) return rc;
+    ReaderSlot &sl = *lease.slot;
+    if (!sl.exp_copy) {
+        TH_HIP(hipStreamCreateWithFlags(&sl.exp_copy, hipStreamNonBlocking));
+        for (int b = 0; b < 2; b++) {
+            TH_HIP(hipEventCreateWithFlags(&sl.exp_done[b], hipEventDisableTiming));
+            TH_HIP(hipEventCreateWithFlags(&sl.exp_copied[b], hipEventDisableTiming));
+        }
+    }
+    std::vector<unsigned char> tab;  // (behind the drain: alive until the upload is done)
+    ExportDrain drain{&sl};
+    for (int b = 0; b < 2; b++)  // powers of two from 1 MiB, never above one piece; the copy stream reads them too
+        TH_CHECK(grow_export_buf(sl, sl.fig_stage[b], sl.fig_stage_cap[b], pl.stage_need[b], 1 << 20, TH_FIGURE_PIECE_BYTES, sl.exp_copy));
+    // (elements) powers of two from 1 MiB up to the bound; a single output row that needs more gets exactly what it needs
+    TH_CHECK(grow_export_buf(sl, sl.fig_tmp, sl.fig_tmp_cap, pl.tmp_need, 1 << 19,
+                             std::max<size_t>(TH_FIGURE_TMP_BYTES / sizeof(uint16_t), pl.tmp_need), nullptr));
+    TH_CHECK(sl.fig_tab.ensure(pl.tab_bytes));
+    unsigned char *d_tab = static_cast<unsigned char *>(sl.fig_tab.dptr);
+    tab = bind_figures(pl, FigureBases{{sl.fig_stage[0].get(), sl.fig_stage[1].get()}, sl.fig_tmp.get(), d_tab}, prs.data());
+    TH_CHECK(sl.fig_tab.upload(sl.stream, tab.data(), tab.size()));
+    const FigHJob *d_hjobs = reinterpret_cast<const FigHJob *>(d_tab + pl.o_hjobs);
+    const FigVJob *d_vjobs = reinterpret_cast<const FigVJob *>(d_tab + pl.o_vjobs);
+    const uint32_t n_colors = (uint32_t)(tm->colormap_rgba.size() / 4);
+    auto launch_piece = [&](size_t p) -> int {
+        const FigurePiece &pc = pieces[p];
+        const uint32_t nj = (uint32_t)(pc.part1 - pc.part0);
+        // (the stream's order keeps the intermediate from the last piece's vertical pass)
+        TH_HIP(launch_figure_hpass(d_hjobs + pc.part0, nj, pc.n_hblocks, sl.stream));
+        if (p >= 2) TH_HIP(hipStreamWaitEvent(sl.stream, sl.exp_copied[p & 1], 0));  // (the buffer's last piece has left it)
+        TH_HIP(launch_figure_vpass(d_vjobs + pc.part0, nj, pc.n_vblocks, tm->d_colormap, n_colors, sl.stream));
+        TH_HIP(hipEventRecord(sl.exp_done[p & 1], sl.stream));
+        return TH_OK;
+    };
+    TH_CHECK(launch_piece(0));
+    for (size_t p = 0; p < pieces.size(); p++) {
+        if (p + 1 < pieces.size()) TH_CHECK(launch_piece(p + 1));  // (ahead of the copy: a copy into pageable memory holds the host)
+        TH_HIP(hipStreamWaitEvent(sl.exp_copy, sl.exp_done[p & 1], 0));
+        for (size_t k = pieces[p].part0; k < pieces[p].part1; k++) {
+            const FigurePart &pt = pl.parts[k];
+            TH_HIP(hipMemcpyAsync(out + pt.out_at, sl.fig_stage[p & 1].get() + pt.stage_at, pt.bytes, hipMemcpyDeviceToHost, sl.exp_copy));
+        }
+        TH_HIP(hipEventRecord(sl.exp_copied[p & 1], sl.exp_copy));
+    }
+    TH_HIP(hipStreamSynchronize(sl.stream));
+    TH_HIP(hipStreamSynchronize(sl.exp_copy));
+    return TH_OK;
+}
+
+int figure_box_of(th_tm *tm, size_t id, uint32_t ch, double start_sec, double end_sec, double hz_min, double hz_max, double box[4]) {
+    auto it = tm->tracks.find(id);
+    if (it == tm->tracks.end()) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", id);
+    TH_REQUIRE(ch < it->second.ch.size(), "Track %zu has no channel %u", id, ch);
+    const Channel &c = it->second.ch[ch];
+    if (!c.d_img) return fail(TH_ERR_NOT_FOUND, "Spectrogram %zu_%u does not exist", id, ch);
+    TH_REQUIRE(figure_box(start_sec, end_sec, hz_min, hz_max, it->second.sr, c.n, c.img_w, c.H, c.img_h, tm->freq_scale, box) == 0,
+               "bad figure range: [%g, %g) s, [%g, %g) Hz", start_sec, end_sec, hz_min, hz_max);
+    return TH_OK;
+}
+}  // namespace tmi
+}  // namespace th
+
+TH_API int th_figure_axis(double origin, double extent, uint32_t n_out, uint32_t n_in, int32_t *start, int32_t *count, double *weights,
+                          size_t cap_weights, uint32_t *max_taps) {
+    TH_TRY
+    TH_REQUIRE(start && count && max_taps, "NULL argument");
+    TH_REQUIRE(n_out > 0 && n_in > 0 && n_in <= 0x7fffffffu, "an axis needs source and output pixels");
+    TH_REQUIRE(std::isfinite(origin) && std::isfinite(extent) && extent > 0.0, "the extent must be finite and positive");
+    LodAxisHost ax;
+    build_lod_axis(origin, extent, n_out, 0, (long)n_in, ax);
+    std::memcpy(start, ax.start.data(), (size_t)n_out * sizeof(int32_t));
+    std::memcpy(count, ax.count.data(), (size_t)n_out * sizeof(int32_t));
+    *max_taps = ax.max_taps;
+    if (!weights || cap_weights < ax.w.size()) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu weights", ax.w.size());
+    std::memcpy(weights, ax.w.data(), ax.w.size() * sizeof(double));
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_figure_box(double start_sec, double end_sec, double hz_min, double hz_max, uint32_t sr, size_t n_samples, size_t img_width,
+                         size_t spec_height, size_t img_height, int freq_scale, double *left, double *top, double *width, double *height) {
+    TH_TRY
+    TH_REQUIRE(left && top && width && height, "NULL argument");
+    double box[4];
+    TH_REQUIRE(figure_box(start_sec, end_sec, hz_min, hz_max, sr, n_samples, img_width, spec_height, img_height, freq_scale, box) == 0,
+               "bad figure range: [%g, %g) s, [%g, %g) Hz of %zu samples at %u Hz, image %zu x %zu over %zu rows", start_sec, end_sec, hz_min,
+               hz_max, n_samples, sr, img_width, img_height, spec_height);
+    *left = box[0];
+    *top = box[1];
+    *width = box[2];
+    *height = box[3];
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_tm_figure_box(th_tm *tm, size_t id, uint32_t ch, double start_sec, double end_sec, double hz_min, double hz_max, double *left,
+                            double *top, double *width, double *height) {
+    TH_TRY
+    TH_REQUIRE(tm && left && top && width && height, "NULL argument");
+    std::shared_lock<std::shared_mutex> rl(tm->rw);
+    double box[4];
+    TH_CHECK(tmi::figure_box_of(tm, id, ch, start_sec, end_sec, hz_min, hz_max, box));
+    *left = box[0];
+    *top = box[1];
+    *width = box[2];
+    *height = box[3];
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_tm_render_figures(th_tm *tm, const th_figure_request *reqs, size_t n, uint8_t *out, size_t cap, th_figure_info *info,
+                                size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(tm && out_len && (n == 0 || (reqs && info)), "NULL argument");
+    *out_len = 0;
+    if (n == 0) return TH_OK;
+    TH_CHECK(tmi::ensure_colormap(tm));  // (takes the lock exclusively when it has to upload the default map)
+    std::shared_lock<std::shared_mutex> rl(tm->rw);
+    std::vector<tmi::FigureInfo> infos(n);
+    for (size_t i = 0; i < n; i++) TH_CHECK(tmi::figure_request_info(tm, reqs[i], i, &infos[i]));
+    const size_t total = tmi::figures_layout(infos.data(), n);
+    for (size_t i = 0; i < n; i++) info[i] = infos[i];
+    *out_len = total;
+    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
+    return tmi::figures_run(tm, n, infos.data(), out);
+    TH_CATCH
+}
+
+TH_API int th_tm_render_figure(th_tm *tm, const th_figure_request *req, uint8_t *out, size_t cap, th_figure_info *info) {
+    TH_TRY
+    TH_REQUIRE(tm && req, "NULL argument");
+    th_figure_info one{};
+    size_t len = 0;
+    const int rc = th_tm_render_figures(tm, req, 1, out, cap, &one, &len);
+    if (info && (rc == TH_OK || rc == TH_ERR_BUFFER_TOO_SMALL)) *info = one;
+    return rc;
     TH_CATCH
 }

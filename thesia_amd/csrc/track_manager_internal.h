@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "common.h"
+#include "figure_plan.h"
 #include "host_math.h"
 
 namespace th {
@@ -119,6 +120,18 @@ std::vector<th_export_at_request> export_at_requests(const th_export_request *re
 // th_wav_header with the status reported (host_math.h wav_header)
 int wav_header_checked(uint32_t format, uint32_t sr, uint32_t n_ch, uint64_t n_frames, uint8_t out[TH_WAV_HEADER_MAX], size_t *header_len,
                        size_t *pad_len);
+
+// Figures.  *info: the record's size and what the plan needs of the request (the resident image; its offset is the layout's to set).
+// figures_layout: offsets that are multiples of 64; returns the last record's end.  figures_run: request i's record to
+// out + info[i].offset, nothing between the records.  The device colormap must exist (ensure_colormap, before the shared lock)
+struct FigureInfo : th_figure_info {
+    FigurePlanRequest plan;
+};
+int figure_request_info(th_tm *tm, const th_figure_request &r, size_t i, FigureInfo *info);
+size_t figures_layout(FigureInfo *info, size_t n);
+int figures_run(th_tm *tm, size_t n, const FigureInfo *info, uint8_t *out);
+// th_tm_figure_box without the lock
+int figure_box_of(th_tm *tm, size_t id, uint32_t ch, double start_sec, double end_sec, double hz_min, double hz_max, double box[4]);
 
 // update_spec_imgs against `global` (NULL: the manager's own tracks, as th_tm_* does), then the writer's final wait:
 // for the images only (apply_track_list_changes, set_dB_range) or for everything (set_setting, set_colormap)

@@ -703,6 +703,53 @@ TH_API int th_tmg_export_wav_at(th_tmg *g, const th_export_at_request *req, uint
     TH_CATCH
 }
 
+// Figures: the same shape as the spectra; every busy slot needs its device colormap first, as for the tiles
+TH_API int th_tmg_render_figures(th_tmg *g, const th_figure_request *reqs, size_t n, uint8_t *out, size_t cap, th_figure_info *info,
+                                 size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(g && out_len && (n == 0 || (reqs && info)), "NULL argument");
+    *out_len = 0;
+    if (n == 0) return TH_OK;
+    std::shared_lock<std::shared_mutex> rl(g->rw);
+    std::vector<tmi::FigureInfo> infos(n);
+    Split sp;
+    TH_CHECK(check_and_split(g, n, [&](size_t i) { return reqs[i].id; },
+                             [&](th_tm *tm, size_t i) { return tmi::figure_request_info(tm, reqs[i], i, &infos[i]); }, &sp));
+    const size_t total = tmi::figures_layout(infos.data(), n);
+    const uint64_t revision = revisions(g).second;
+    for (size_t i = 0; i < n; i++) {
+        infos[i].spectrogram_revision = revision;
+        info[i] = infos[i];
+    }
+    *out_len = total;
+    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
+    for (uint32_t s : sp.busy) TH_CHECK(tmi::ensure_colormap(g->slots[s].tm));
+    return run_on_owners(g, sp, [&](th_tm *tm, const std::vector<size_t> &idx) -> int {
+        return tmi::figures_run(tm, idx.size(), gather(infos.data(), idx).data(), out);
+    });
+    TH_CATCH
+}
+
+TH_API int th_tmg_render_figure(th_tmg *g, const th_figure_request *req, uint8_t *out, size_t cap, th_figure_info *info) {
+    TH_TRY
+    TH_REQUIRE(g && req, "NULL argument");
+    th_figure_info one{};
+    size_t len = 0;
+    const int rc = th_tmg_render_figures(g, req, 1, out, cap, &one, &len);
+    if (info && (rc == TH_OK || rc == TH_ERR_BUFFER_TOO_SMALL)) *info = one;
+    return rc;
+    TH_CATCH
+}
+
+TH_API int th_tmg_figure_box(th_tmg *g, size_t id, uint32_t ch, double start_sec, double end_sec, double hz_min, double hz_max,
+                             double *left, double *top, double *width, double *height) {
+    TH_TRY
+    TH_REQUIRE(left && top && width && height, "NULL argument");
+    TMG_OWNER(g, id, "Track %zu", id);
+    return th_tm_figure_box(tm_, id, ch, start_sec, end_sec, hz_min, hz_max, left, top, width, height);
+    TH_CATCH
+}
+
 // set_common_normalize / set_common_guard_clipping: every slot re-derives its tracks into staged buffers; all commit, or all discard
 namespace {
 int set_common_dynamics_all(th_tmg *g, int kind, float target, int mode) {
