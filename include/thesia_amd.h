@@ -894,6 +894,92 @@ TH_API int th_tm_render_figures(th_tm *tm, const th_figure_request *reqs, size_t
                                 th_figure_info *info /* n */, size_t *out_len);
 TH_API int th_tm_render_figure(th_tm *tm, const th_figure_request *req, uint8_t *out, size_t cap_bytes, th_figure_info *info);
 
+/* ---------------------------------------------------------------- Waveform envelope: any time range at any pixel width */
+/* The exact (min, max, mean, rms) of every pixel column of a time range of a channel's resident audio, and that envelope rasterised
+ * as the RGBA waveform lane that sits under a figure: one streaming pass over the samples the request covers, without picking a
+ * pyramid level, fetching its tiles and re-binning them (no reference implementation exists, these definitions are the contract).
+ *   A request is (id, ch, which, start_sec, end_sec, n_cols); which as in th_tm_copy_audio: 0 the audio the spectrogram is made
+ *   from, 1 the audio the waveform is drawn from, 2 the original.  The channel has n >= 1 samples at rate sr; all of this in C double:
+ *   A = clamp(start_sec (double)sr, 0, n); B = n for end_sec = +inf, else clamp(end_sec (double)sr, 0, n); B > A is required; W = n_cols;
+ *   e[W] = ceil(B); e[j] = min(ceil(A + (B - A) (double)j / (double)W), e[W]) for j < W (a product, a quotient, a sum).  Column j owns
+ *   samples [e[j], e[j + 1]): those whose index lies in the column's real interval.  The edges never decrease.  A range between
+ *   two samples (B > A, ceil(A) = ceil(B)) is a valid request: every column is empty and holds the sample below.
+ *   th_envelope_edges (host) is that definition.  TH_ERR_INVALID_ARG: a NaN argument, a negative or infinite start_sec, an end not
+ *   above the start after clamping, a zero sr, n_samples or n_cols, n_cols above TH_ENVELOPE_MAX_COLS.
+ *   Values: four f32 per column, interleaved (min, max, mean, rms), 16 bytes per column.  With c = e[j + 1] - e[j] > 0: min and max by
+ *   fminf / fmaxf, which ignore NaN, as the waveform tiles do (an all-NaN column gives (+inf, -inf); where an extremum is zero and the
+ *   column holds both +0 and -0, which of the two comes back is not specified); mean = (f32)((sum x) / c) and
+ *   rms = (f32)sqrt((sum x x) / c) with both sums in f64, so any NaN sample makes both NaN.  c = 0 (a view zoomed in past one sample
+ *   per column): a zero-order hold of sample max(e[j], 1) - 1: min = max = mean = x, rms = |x| (a NaN sample: NaN in all four).
+ *   The order of the f64 sums is fixed by the channel, the request's edges and the kernels' absolute chunk grid alone (4096-sample
+ *   chunks counted from sample 0 of the channel): a request's bytes do not depend on the rest of the batch, the reader slot, how the
+ *   call was cut into pieces, the call itself, or th_tm against th_tmg.
+ *   A waveform figure (lane) is an envelope request whose n_cols is out_w, plus out_h, amp_lo < amp_hi (finite f32), thickness in
+ *   1/256 pixel (0 .. 256 out_h), fill[4] and background[4] (RGBA bytes).  Everything behind the envelope is integer arithmetic:
+ *   1. join to the left neighbour (j > 0, both columns not all-NaN, the neighbour's values un-joined): max_j < min_(j-1): max_j :=
+ *   min_(j-1); min_j > max_(j-1): min_j := max_(j-1).  2. Y(v) = clamp(floor(((double)amp_hi - v) / ((double)amp_hi - amp_lo) out_h
+ *   256 + 0.5), 0, 256 out_h), one rounded f64 operation per step in that order, v the f32 widened; Ytop = Y(max), Ybot = Y(min).
+ *   3. a column with max < min (all NaN) or a NaN mean draws nothing.  4. Ybot - Ytop < thickness: Ytop := floor((Ytop + Ybot -
+ *   thickness) / 2), Ybot := Ytop + thickness, both clamped to [0, 256 out_h].  5. row r counts from the top (amp_hi): cov = max(0,
+ *   min(Ybot, 256 (r + 1)) - max(Ytop, 256 r)), and each of the four bytes is (fill cov + background (256 - cov) + 128) >> 8.
+ *   th_waveform_figure_span (host): (Ytop, Ybot) of one column, *draws = 0 where it draws nothing; col and left are the four values of
+ *   the column and of its left neighbour (NULL for column 0).  TH_ERR_INVALID_ARG: out_h zero or above TH_FIGURE_MAX_DIM, an amplitude
+ *   range that is not finite and ascending, a thickness above 256 out_h.
+ * th_tm_get_envelopes: request i's 4 n_cols floats start at out + info[i].offset (floats, requests back to back); *out_len = the
+ * floats of all.  th_tm_render_waveform_figures: request i's record is out_h x out_w x 4 bytes, the top row = amp_hi, starts at
+ * out + info[i].offset, a multiple of 64; the bytes between two records are not written; *out_len = the last record's end.  Readers
+ * like th_tm_get_spectra and th_tm_render_figures: shared lock, a reader slot's own streams; out == NULL or a cap below *out_len:
+ * TH_ERR_BUFFER_TOO_SMALL with info and *out_len filled.  The first faulty request in request order decides: an unknown id:
+ * TH_ERR_NOT_FOUND; a bad channel, which, time range, size, amplitude range or thickness: TH_ERR_INVALID_ARG.  On any error nothing
+ * is written to out.  info[i]: sample_start = e[0], sample_end = e[n_cols], waveform_revision: the revision the values belong to.
+ * Device memory is BOUNDED.  An envelope call is cut into pieces of whole requests of at most TH_ENVELOPE_PIECE_BYTES of results
+ * (one request is at most TH_ENVELOPE_MAX_COLS x 16 bytes = 1 MiB); beside the results a piece holds its edge tables (8 bytes per
+ * column) and, for requests of 64 samples per column or more, 48 bytes of partial sums per 16 KiB chunk of audio it reads (0.3 %),
+ * at most TH_ENVELOPE_PART_BYTES unless ONE request alone needs more.  A lane call computes the envelopes of such a piece once (16
+ * bytes per column, and 8 for the spans), keeps them on the device across the bands, and rasterises bands of whole output rows of at
+ * most TH_FIGURE_PIECE_BYTES through two staging buffers, piece p + 1 computed while piece p is copied out.  The edge tables of a
+ * call are built and uploaded once.  A slot's scratch is made on first use and only grows. */
+#define TH_ENVELOPE_MAX_COLS 65536u
+#define TH_ENVELOPE_PIECE_BYTES (4u << 20)
+#define TH_ENVELOPE_PART_BYTES (32u << 20)
+typedef struct {
+    size_t id;
+    uint32_t ch;
+    uint32_t which;   /* 0 audio, 1 drawn, 2 original */
+    double start_sec, end_sec;
+    uint32_t n_cols;  /* 1 .. TH_ENVELOPE_MAX_COLS */
+    uint32_t reserved;
+} th_envelope_request;
+typedef struct {
+    uint64_t offset, length;            /* into out, floats; length = 4 n_cols */
+    uint64_t sample_start, sample_end;  /* e[0], e[n_cols] */
+    uint64_t waveform_revision;
+} th_envelope_info;
+typedef struct {
+    th_envelope_request env; /* n_cols = out_w: 1 .. TH_FIGURE_MAX_DIM */
+    uint32_t out_h;          /* 1 .. TH_FIGURE_MAX_DIM */
+    float amp_lo, amp_hi;
+    uint32_t thickness;      /* 1/256 pixel: 0 .. 256 out_h */
+    uint8_t fill[4], background[4];
+} th_waveform_figure_request;
+typedef struct {
+    uint64_t offset, bytes; /* into out */
+    uint32_t out_w, out_h;
+    uint64_t sample_start, sample_end;
+    uint64_t waveform_revision;
+} th_waveform_figure_info;
+TH_API int th_envelope_edges(uint32_t sr, size_t n_samples, double start_sec, double end_sec, uint32_t n_cols,
+                             uint64_t *edges /* n_cols + 1 */);
+TH_API int th_waveform_figure_span(const float *col /* 4 */, const float *left /* 4, or NULL */, uint32_t out_h, float amp_lo,
+                                   float amp_hi, uint32_t thickness, int32_t *y_top, int32_t *y_bot, int *draws);
+TH_API int th_tm_get_envelopes(th_tm *tm, const th_envelope_request *reqs, size_t n, float *out, size_t cap_floats,
+                               th_envelope_info *info /* n */, size_t *out_len);
+TH_API int th_tm_get_envelope(th_tm *tm, const th_envelope_request *req, float *out, size_t cap_floats, th_envelope_info *info);
+TH_API int th_tm_render_waveform_figures(th_tm *tm, const th_waveform_figure_request *reqs, size_t n, uint8_t *out, size_t cap_bytes,
+                                         th_waveform_figure_info *info /* n */, size_t *out_len);
+TH_API int th_tm_render_waveform_figure(th_tm *tm, const th_waveform_figure_request *req, uint8_t *out, size_t cap_bytes,
+                                        th_waveform_figure_info *info);
+
 /* ---------------------------------------------------------------- TrackManager over several devices (one process) */
 /* th_tmg: the th_tm_* calls above, call for call, with a th_tmg * in place of the th_tm *; a multi-GPU host swaps one for
  * the other.  Every result — updated ids, max_sr, db state, revisions, specs, images, tile bytes, batch offsets, render
@@ -991,6 +1077,15 @@ TH_API int th_tmg_figure_box(th_tmg *tmg, size_t id, uint32_t ch, double start_s
 TH_API int th_tmg_render_figures(th_tmg *tmg, const th_figure_request *reqs, size_t n, uint8_t *out, size_t cap_bytes,
                                  th_figure_info *info /* n */, size_t *out_len);
 TH_API int th_tmg_render_figure(th_tmg *tmg, const th_figure_request *req, uint8_t *out, size_t cap_bytes, th_figure_info *info);
+
+/* waveform envelopes and lanes: the same; a request's bytes are those of one th_tm, bit for bit */
+TH_API int th_tmg_get_envelopes(th_tmg *tmg, const th_envelope_request *reqs, size_t n, float *out, size_t cap_floats,
+                                th_envelope_info *info /* n */, size_t *out_len);
+TH_API int th_tmg_get_envelope(th_tmg *tmg, const th_envelope_request *req, float *out, size_t cap_floats, th_envelope_info *info);
+TH_API int th_tmg_render_waveform_figures(th_tmg *tmg, const th_waveform_figure_request *reqs, size_t n, uint8_t *out,
+                                          size_t cap_bytes, th_waveform_figure_info *info /* n */, size_t *out_len);
+TH_API int th_tmg_render_waveform_figure(th_tmg *tmg, const th_waveform_figure_request *req, uint8_t *out, size_t cap_bytes,
+                                         th_waveform_figure_info *info);
 
 /* Test and measurement entry points (kernel selectors for A/B runs, per-launch kernel timing, replacing a resident image
  * with given pixels) are NOT part of this interface: include/thesia_amd_testing.h declares them; a thesia host binds none. */

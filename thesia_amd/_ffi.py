@@ -138,6 +138,26 @@ class FigureInfo(C.Structure):  # th_figure_info
                 ("spectrogram_revision", C.c_uint64)]
 
 
+class EnvelopeRequest(C.Structure):  # th_envelope_request
+    _fields_ = [("id", C.c_size_t), ("ch", C.c_uint32), ("which", C.c_uint32), ("start_sec", C.c_double), ("end_sec", C.c_double),
+                ("n_cols", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class EnvelopeInfo(C.Structure):  # th_envelope_info
+    _fields_ = [("offset", C.c_uint64), ("length", C.c_uint64), ("sample_start", C.c_uint64), ("sample_end", C.c_uint64),
+                ("waveform_revision", C.c_uint64)]
+
+
+class WaveformFigureRequest(C.Structure):  # th_waveform_figure_request
+    _fields_ = [("env", EnvelopeRequest), ("out_h", C.c_uint32), ("amp_lo", C.c_float), ("amp_hi", C.c_float), ("thickness", C.c_uint32),
+                ("fill", C.c_uint8 * 4), ("background", C.c_uint8 * 4)]
+
+
+class WaveformFigureInfo(C.Structure):  # th_waveform_figure_info
+    _fields_ = [("offset", C.c_uint64), ("bytes", C.c_uint64), ("out_w", C.c_uint32), ("out_h", C.c_uint32),
+                ("sample_start", C.c_uint64), ("sample_end", C.c_uint64), ("waveform_revision", C.c_uint64)]
+
+
 class PyramidDesc(C.Structure):
     _fields_ = [("wav", C.c_void_p), ("out", C.c_void_p), ("n_samples", C.c_uint64), ("n_levels", C.c_uint32),
                 ("first_level", C.c_uint32)]
@@ -359,6 +379,19 @@ _SIGS = {
     "th_tm_render_figure": [vp, C.POINTER(FigureRequest), C.c_void_p, C.c_size_t, C.POINTER(FigureInfo)],
     "th_tmg_render_figures": [vp, C.POINTER(FigureRequest), C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(FigureInfo), c_szp],
     "th_tmg_render_figure": [vp, C.POINTER(FigureRequest), C.c_void_p, C.c_size_t, C.POINTER(FigureInfo)],
+    "th_envelope_edges": [C.c_uint32, C.c_size_t, C.c_double, C.c_double, C.c_uint32, C.POINTER(C.c_uint64)],
+    "th_waveform_figure_span": [c_f32p, c_f32p, C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                C.POINTER(C.c_int)],
+    "th_tm_get_envelopes": [vp, C.POINTER(EnvelopeRequest), C.c_size_t, c_f32p, C.c_size_t, C.POINTER(EnvelopeInfo), c_szp],
+    "th_tm_get_envelope": [vp, C.POINTER(EnvelopeRequest), c_f32p, C.c_size_t, C.POINTER(EnvelopeInfo)],
+    "th_tmg_get_envelopes": [vp, C.POINTER(EnvelopeRequest), C.c_size_t, c_f32p, C.c_size_t, C.POINTER(EnvelopeInfo), c_szp],
+    "th_tmg_get_envelope": [vp, C.POINTER(EnvelopeRequest), c_f32p, C.c_size_t, C.POINTER(EnvelopeInfo)],
+    "th_tm_render_waveform_figures": [vp, C.POINTER(WaveformFigureRequest), C.c_size_t, C.c_void_p, C.c_size_t,
+                                      C.POINTER(WaveformFigureInfo), c_szp],
+    "th_tm_render_waveform_figure": [vp, C.POINTER(WaveformFigureRequest), C.c_void_p, C.c_size_t, C.POINTER(WaveformFigureInfo)],
+    "th_tmg_render_waveform_figures": [vp, C.POINTER(WaveformFigureRequest), C.c_size_t, C.c_void_p, C.c_size_t,
+                                       C.POINTER(WaveformFigureInfo), c_szp],
+    "th_tmg_render_waveform_figure": [vp, C.POINTER(WaveformFigureRequest), C.c_void_p, C.c_size_t, C.POINTER(WaveformFigureInfo)],
     "th_tile_cache_create": [C.c_size_t, C.POINTER(vp)],
     "th_tile_cache_destroy": [vp],
     "th_tile_cache_lookup": [vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), c_u8p, C.c_size_t,

@@ -35,6 +35,11 @@ FIGURE_RGBA, FIGURE_GREY16 = 0, 1
 FIGURE_MAX_DIM = 16384             # TH_FIGURE_MAX_DIM
 FIGURE_PIECE_BYTES = 8 << 20       # TH_FIGURE_PIECE_BYTES
 FIGURE_TMP_BYTES = 16 << 20        # TH_FIGURE_TMP_BYTES
+ENVELOPE_MAX_COLS = 65536          # TH_ENVELOPE_MAX_COLS
+ENVELOPE_PIECE_BYTES = 4 << 20     # TH_ENVELOPE_PIECE_BYTES
+ENVELOPE_PART_BYTES = 32 << 20     # TH_ENVELOPE_PART_BYTES
+ENVELOPE_CHUNK = 4096              # samples of one chunk of the envelope kernels' absolute grid (ENV_CHUNK, envelope_plan.h)
+ENVELOPE_DENSE_MIN = 64            # samples per column, on average, from which a request goes through the chunk reduction
 WAVEFORM_TILE_MAX_BYTES = 24 + 1024 * 12
 SPECTROGRAM_TILE_MAX_BYTES = 40 + 520 * 520 * 4
 
@@ -530,6 +535,117 @@ class _FigureMethods:
         raw = out[:info.bytes]
         fig = raw.view(np.uint16).reshape(out_h, out_w) if kind == FIGURE_GREY16 else raw.reshape(out_h, out_w, 4)
         return fig, _export_info_dict(info)
+
+
+def envelope_edges(sr: int, n_samples: int, start_sec: float = 0.0, end_sec: float = float("inf"), n_cols: int = 1) -> np.ndarray:
+    """th_envelope_edges -> uint64[n_cols + 1]: column j of the envelope of a time range owns samples [edges[j], edges[j + 1]) (host)"""
+    e = np.empty(max(int(n_cols), 0) + 1, np.uint64)
+    check(lib.th_envelope_edges(sr, n_samples, start_sec, end_sec, n_cols, _ptr(e, C.POINTER(C.c_uint64))))
+    return e
+
+
+edges = envelope_edges
+
+
+def waveform_figure_span(col, left, out_h: int, amp_lo: float, amp_hi: float, thickness: int):
+    """th_waveform_figure_span -> (y_top, y_bot) in 1/256 pixel of one column of a waveform lane, or None where it draws nothing; col and
+    left: (min, max, mean, rms) of the column and of its left neighbour (None for column 0) (host)"""
+    c = _f32(col)
+    lf = None if left is None else _f32(left)
+    yt, yb, dr = C.c_int32(), C.c_int32(), C.c_int()
+    check(lib.th_waveform_figure_span(_ptr(c, c_f32p), None if lf is None else _ptr(lf, c_f32p), out_h, amp_lo, amp_hi, thickness,
+                                      C.byref(yt), C.byref(yb), C.byref(dr)))
+    return (yt.value, yb.value) if dr.value else None
+
+
+def _envelope_request(r) -> "_ffi.EnvelopeRequest":
+    """(track_id, ch, which, start_sec, end_sec, n_cols) or a dict with those names"""
+    if isinstance(r, dict):
+        r = (r["track_id"], r["ch"], r.get("which", 1), r.get("start_sec", 0.0), r.get("end_sec", float("inf")), r["n_cols"])
+    track_id, ch, which, start_sec, end_sec, n_cols = r
+    return _ffi.EnvelopeRequest(track_id, ch, which, start_sec, end_sec, n_cols, 0)
+
+
+def _waveform_figure_request(r) -> "_ffi.WaveformFigureRequest":
+    """(track_id, ch, which, start_sec, end_sec, out_w, out_h, amp_lo, amp_hi, thickness, fill, background) or a dict with those names"""
+    if isinstance(r, dict):
+        r = (r["track_id"], r["ch"], r.get("which", 1), r.get("start_sec", 0.0), r.get("end_sec", float("inf")), r["out_w"], r["out_h"],
+             r.get("amp_lo", -1.0), r.get("amp_hi", 1.0), r.get("thickness", 256), r.get("fill", (255, 255, 255, 255)),
+             r.get("background", (0, 0, 0, 0)))
+    track_id, ch, which, start_sec, end_sec, out_w, out_h, amp_lo, amp_hi, thickness, fill, background = r
+    return _ffi.WaveformFigureRequest(_ffi.EnvelopeRequest(track_id, ch, which, start_sec, end_sec, out_w, 0), out_h, amp_lo, amp_hi,
+                                      thickness, (C.c_uint8 * 4)(*fill), (C.c_uint8 * 4)(*background))
+
+
+class _EnvelopeMethods:
+    """the exact (min, max, mean, rms) envelope of a time range at any pixel width, and its raster as a waveform lane (th_tm_* and
+    th_tmg_*: _PFX)"""
+
+    def get_envelopes(self, requests, out: Optional[np.ndarray] = None):
+        """th_tm_get_envelopes: requests = iterable of (track_id, ch, which, start_sec, end_sec, n_cols) -> (list of float32
+        [n_cols, 4] arrays (min, max, mean, rms), list of info dicts).  out: a float32 array to fill instead of a new one; the arrays
+        are then views into it."""
+        reqs = [_envelope_request(r) for r in requests]
+        n = len(reqs)
+        if n == 0:
+            return [], []
+        arr = (_ffi.EnvelopeRequest * n)(*reqs)
+        info = (_ffi.EnvelopeInfo * n)()
+        need = C.c_size_t()
+        fn = getattr(lib, self._PFX + "get_envelopes")
+        if out is None:
+            rc = fn(self.handle, arr, n, None, 0, info, C.byref(need))
+            if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+                check(rc)
+            out = np.empty(max(need.value, 1), np.float32)
+        check(fn(self.handle, arr, n, _ptr(out, c_f32p), out.size, info, C.byref(need)))
+        return [out[o.offset: o.offset + o.length].reshape(-1, 4) for o in info], [_export_info_dict(o) for o in info]
+
+    def get_envelope(self, track_id: int, ch: int, which: int = 1, start_sec: float = 0.0, end_sec: float = float("inf"), n_cols: int = 1):
+        """th_tm_get_envelope -> (float32 [n_cols, 4], info dict) of one request"""
+        req = _envelope_request((track_id, ch, which, start_sec, end_sec, n_cols))
+        info = _ffi.EnvelopeInfo()
+        fn = getattr(lib, self._PFX + "get_envelope")
+        rc = fn(self.handle, C.byref(req), None, 0, C.byref(info))
+        if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+            check(rc)
+        out = np.empty(max(info.length, 1), np.float32)
+        check(fn(self.handle, C.byref(req), _ptr(out, c_f32p), out.size, C.byref(info)))
+        return out[:info.length].reshape(-1, 4), _export_info_dict(info)
+
+    def render_waveform_figures(self, requests, out: Optional[np.ndarray] = None):
+        """th_tm_render_waveform_figures: requests = iterable of (track_id, ch, which, start_sec, end_sec, out_w, out_h, amp_lo,
+        amp_hi, thickness, fill, background) -> (list of uint8 [out_h, out_w, 4] arrays, the top row = amp_hi, list of info dicts).
+        out: a uint8 array to fill instead of a new one; the arrays are then views into it."""
+        reqs = [_waveform_figure_request(r) for r in requests]
+        n = len(reqs)
+        if n == 0:
+            return [], []
+        arr = (_ffi.WaveformFigureRequest * n)(*reqs)
+        info = (_ffi.WaveformFigureInfo * n)()
+        need = C.c_size_t()
+        fn = getattr(lib, self._PFX + "render_waveform_figures")
+        if out is None:
+            rc = fn(self.handle, arr, n, None, 0, info, C.byref(need))
+            if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+                check(rc)
+            out = np.empty(max(need.value, 1), np.uint8)
+        check(fn(self.handle, arr, n, out.ctypes.data, out.size, info, C.byref(need)))
+        return ([out[o.offset: o.offset + o.bytes].reshape(o.out_h, o.out_w, 4) for o in info], [_export_info_dict(o) for o in info])
+
+    def render_waveform_figure(self, track_id: int, ch: int, which: int, start_sec: float, end_sec: float, out_w: int, out_h: int,
+                               amp_lo: float = -1.0, amp_hi: float = 1.0, thickness: int = 256, fill=(255, 255, 255, 255),
+                               background=(0, 0, 0, 0)):
+        """th_tm_render_waveform_figure -> (uint8 [out_h, out_w, 4], info dict) of one lane"""
+        req = _waveform_figure_request((track_id, ch, which, start_sec, end_sec, out_w, out_h, amp_lo, amp_hi, thickness, fill, background))
+        info = _ffi.WaveformFigureInfo()
+        fn = getattr(lib, self._PFX + "render_waveform_figure")
+        rc = fn(self.handle, C.byref(req), None, 0, C.byref(info))
+        if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+            check(rc)
+        out = np.empty(max(info.bytes, 1), np.uint8)
+        check(fn(self.handle, C.byref(req), out.ctypes.data, out.size, C.byref(info)))
+        return out[:info.bytes].reshape(out_h, out_w, 4), _export_info_dict(info)
 
 
 def true_peak_filter(sr: int):
@@ -1045,7 +1161,7 @@ class TileCache:
                 "spectrogram_revision": sr.value, "hits": h.value, "misses": m.value}
 
 
-class TrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods, _ExportAtMethods, _FigureMethods):
+class TrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods, _ExportAtMethods, _FigureMethods, _EnvelopeMethods):
     """th_tm: mirror of core/mod.rs TrackManager with HBM-resident audio / specs / images."""
     _PFX = "th_tm_"
 
@@ -1245,7 +1361,7 @@ class TrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _E
         return out[: n.value].tobytes()
 
 
-class MultiTrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods, _ExportAtMethods, _FigureMethods):
+class MultiTrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods, _ExportAtMethods, _FigureMethods, _EnvelopeMethods):
     """th_tmg: the TrackManager over several devices of one process (duplicates allowed: [0, 0] is two slots on one card).
     Same method names as TrackManager; results are bit-identical to one TrackManager holding every track."""
     _PFX = "th_tmg_"

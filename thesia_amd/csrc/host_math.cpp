@@ -2,6 +2,7 @@
 // (paths relative to the reference checkout).
 #include "host_math.h"
 
+#include "envelope_core.h"
 #include "stft_plan.h"
 
 #include <algorithm>
@@ -1003,6 +1004,40 @@ bool spectrum_frame_range(uint32_t sr, size_t hop, size_t n_frames, double start
     *f0 = first_at_or_after(start_sec);
     *f1 = std::isinf(end_sec) ? n_frames : std::max(*f0, first_at_or_after(end_sec));
     return true;
+}
+
+int envelope_range(uint32_t sr, uint64_t n_samples, double start_sec, double end_sec, uint32_t n_cols, double *A, double *B) {
+    if (std::isnan(start_sec) || std::isnan(end_sec) || start_sec < 0.0 || std::isinf(start_sec)) return 1;
+    if (sr == 0 || n_samples == 0 || n_cols == 0 || n_cols > TH_ENVELOPE_MAX_COLS) return 1;
+    const double N = (double)n_samples;
+    auto clamp = [N](double v) { return v < 0.0 ? 0.0 : (v > N ? N : v); };
+    *A = clamp(start_sec * (double)sr);
+    *B = end_sec == INFINITY ? N : clamp(end_sec * (double)sr);
+    return *B > *A ? 0 : 1;
+}
+
+int envelope_edges(uint32_t sr, uint64_t n_samples, double start_sec, double end_sec, uint32_t n_cols, uint64_t *edges) {
+    double A, B;
+    if (envelope_range(sr, n_samples, start_sec, end_sec, n_cols, &A, &B) != 0) return 1;
+    const double W = (double)n_cols;
+    const uint64_t last = (uint64_t)std::ceil(B);
+    for (uint32_t j = 0; j < n_cols; j++) {
+        const double t = (B - A) * (double)j;  // (named steps: a product, a quotient, a sum, each rounded once)
+        const double q = t / W;
+        edges[j] = std::min((uint64_t)std::ceil(A + q), last);
+    }
+    edges[n_cols] = last;
+    return 0;
+}
+
+int waveform_figure_span(const float col[4], const float *left, uint32_t out_h, float amp_lo, float amp_hi, uint32_t thickness, int32_t *y_top,
+                         int32_t *y_bot, int *draws) {
+    if (out_h == 0 || out_h > TH_FIGURE_MAX_DIM || !std::isfinite(amp_lo) || !std::isfinite(amp_hi) || !(amp_lo < amp_hi) ||
+        thickness > 256u * out_h)
+        return 1;
+    *y_top = *y_bot = 0;
+    *draws = lane_span(col, left, out_h, amp_lo, amp_hi, thickness, y_top, y_bot) ? 1 : 0;
+    return 0;
 }
 
 int wav_header(uint32_t bps, uint32_t sr, uint32_t n_ch, uint64_t n_frames, uint8_t out[64], size_t *header_len, size_t *pad_len) {

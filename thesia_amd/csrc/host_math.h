@@ -124,6 +124,15 @@ float db_from_amp(float x);
 // in double.  false: start_sec NaN, negative or infinite, end_sec NaN or below start_sec, sr or hop zero.
 bool spectrum_frame_range(uint32_t sr, size_t hop, size_t n_frames, double start_sec, double end_sec, size_t *f0, size_t *f1);
 
+// ---- waveform envelope (th_envelope_edges, th_waveform_figure_span; include/thesia_amd.h "Waveform envelope")
+// envelope_range: A and B of the definition, in samples; 0, or 1 for an invalid argument (a NaN, a negative or infinite start, an end
+// not above the start after clamping, a zero sr, n_samples or n_cols, n_cols above TH_ENVELOPE_MAX_COLS).  envelope_edges: the n_cols + 1
+// edges, the same status.  waveform_figure_span: one column of a lane (envelope_core.h lane_span); 0, or 1 for an invalid argument
+int envelope_range(uint32_t sr, uint64_t n_samples, double start_sec, double end_sec, uint32_t n_cols, double *A, double *B);
+int envelope_edges(uint32_t sr, uint64_t n_samples, double start_sec, double end_sec, uint32_t n_cols, uint64_t *edges);
+int waveform_figure_span(const float col[4], const float *left, uint32_t out_h, float amp_lo, float amp_hi, uint32_t thickness, int32_t *y_top,
+                         int32_t *y_bot, int *draws);
+
 // ---- PCM / WAV export (th_wav_header): the RIFF header around n_frames frames of n_ch channels; bytes_per_sample 2 or 3 (PCM, 44
 // bytes, tag 1) or 4 (float32, 58 bytes: an 18-byte "fmt " with tag 3 and a "fact" chunk).  *pad_len: the zero byte behind an odd
 // data size.  Returns 0, 1 for an invalid argument (no channels, no rate), 2 for a file RIFF cannot describe (a size above

@@ -11,6 +11,7 @@
 #include "batch_plan.h"  // ImgJob, FusedJob, RasterJob, WaveJob, PyrJob, StatsJob, their constants, pyramid_bins / pyramid_offset / waveform_blocks_for
 #include "host_math.h"
 #include "stft_core.h"
+#include "envelope_plan.h"  // EnvJob, LaneSpanJob, LaneRasterJob, ENV_* (the chunk grid of kernels_envelope.hip)
 #include "figure_plan.h"  // FigHJob, FigVJob, FIG_* (the tile shape of kernels_figure.hip)
 #include "reader_plan.h"  // LoudJob, LoudTrackJob, TruePeakJob, ExportJob, ResampleJob, ResampleTiling and their constants
 #include "stft_plan.h"  // WavePostJob, MelJob, MEL_TILE_FRAMES, MEL_ROWS_*
@@ -288,5 +289,13 @@ hipError_t launch_figure_hpass(const FigHJob *d_jobs, uint32_t n_jobs, uint32_t 
 // d_colormap: n_colors RGBA entries (read by the TH_FIGURE_RGBA jobs only)
 hipError_t launch_figure_vpass(const FigVJob *d_jobs, uint32_t n_jobs, uint32_t n_blocks, const uint8_t *d_colormap, uint32_t n_colors,
                                hipStream_t s);
+
+// ---- kernels_envelope.hip: (min, max, mean, rms) per pixel column of a time range of resident audio, and its raster as a waveform
+// lane (EnvJob, LaneSpanJob, LaneRasterJob: envelope_plan.h).  n_units: the chunks of the dense jobs; n_cblocks, n_blocks: the sum
+// over the jobs.  The reduction runs in front of the column kernel, which adds the partials it leaves
+hipError_t launch_envelope_reduce(const EnvJob *d_jobs, uint32_t n_jobs, uint32_t n_units, hipStream_t s);
+hipError_t launch_envelope_columns(const EnvJob *d_jobs, uint32_t n_jobs, uint32_t n_cblocks, hipStream_t s);
+hipError_t launch_lane_spans(const LaneSpanJob *d_jobs, uint32_t n_jobs, uint32_t n_blocks, hipStream_t s);
+hipError_t launch_lane_raster(const LaneRasterJob *d_jobs, uint32_t n_jobs, uint32_t n_blocks, hipStream_t s);
 
 }  // namespace th

@@ -100,6 +100,10 @@ struct ReaderSlot {
     th::DeviceBuf<uint16_t> fig_tmp;
     size_t fig_tmp_cap = 0;  // elements
     th::DeviceTable fig_tab;
+    // th_tm_get_envelopes / th_tm_render_waveform_figures: the call's table (edge tables, then the job tables), the envelopes of one
+    // piece (at most TH_ENVELOPE_PIECE_BYTES), its partial sums (at most TH_ENVELOPE_PART_BYTES unless one request needs more) and,
+    // for the lanes, its spans; the lanes' staging buffers, copy stream and events are the figures'.  Empty until the first such call
+    th::DeviceTable env_tab, env_out, env_part, lane_span;
 };
 constexpr size_t TILE_BYTES_MAX = 520 * 520 * 4;  // 512 core + 2 x 4 gutter (render_tiles.rs:15-16); >= 1024 * 12 waveform bins
 constexpr size_t MAX_READER_SLOTS = 16;
@@ -2920,6 +2924,267 @@ TH_API int th_tm_render_figure(th_tm *tm, const th_figure_request *req, uint8_t 
     th_figure_info one{};
     size_t len = 0;
     const int rc = th_tm_render_figures(tm, req, 1, out, cap, &one, &len);
+    if (info && (rc == TH_OK || rc == TH_ERR_BUFFER_TOO_SMALL)) *info = one;
+    return rc;
+    TH_CATCH
+}
+
+// ---------------------------------------------------------------------------------------------- waveform envelopes and lanes
+// th_tm_get_envelopes / th_tm_render_waveform_figures: readers.  plan_envelopes / plan_lanes (envelope_plan.h) check the requests,
+// build the edge tables and cut the call into pieces; the bind functions give the jobs their addresses; what is left here is the
+// slot, its buffers, the upload and the launches of kernels_envelope.hip.  An envelope piece is two launches and one copy per run of
+// adjacent records (a call of one piece of at most the slot's pinned staging is written there by the kernels); a lane piece is one
+// raster launch into staging buffer p & 1 and one copy per part on the slot's copy stream while the next piece is computed, with
+// the envelopes and spans of its group computed once in front of the group's first piece.
+namespace th {
+namespace tmi {
+namespace {
+int envelope_channel(th_tm *tm, const th_envelope_request &r, size_t i, EnvelopePlanRequest *pr) {
+    auto it = tm->tracks.find(r.id);
+    if (it == tm->tracks.end()) return fail(TH_ERR_NOT_FOUND, "request %zu: Track %zu does not exist", i, r.id);
+    TH_REQUIRE(r.ch < it->second.ch.size(), "request %zu: Track %zu has no channel %u", i, r.id, r.ch);
+    TH_REQUIRE(r.which <= 2, "request %zu: which must be 0 (audio), 1 (drawn) or 2 (original)", i);
+    const Channel &c = it->second.ch[r.ch];
+    const float *src = r.which == 0 ? c.d_wav : r.which == 1 ? c.d_draw : c.d_orig;
+    *pr = EnvelopePlanRequest{src, c.n, it->second.sr, r.n_cols, r.start_sec, r.end_sec, 0};
+    return TH_OK;
+}
+}  // namespace
+
+int envelope_request_info(th_tm *tm, const th_envelope_request &r, size_t i, EnvelopeInfo *info) {
+    *info = EnvelopeInfo{};
+    TH_CHECK(envelope_channel(tm, r, i, &info->plan));
+    const EnvelopeStatus st = check_envelope(info->plan, i, &info->sample_start, &info->sample_end);
+    if (st.err != TH_OK) return fail(st.err, "%s", st.err_text.c_str());
+    info->length = (uint64_t)r.n_cols * 4;
+    info->waveform_revision = tm->waveform_revision();
+    return TH_OK;
+}
+
+size_t envelopes_layout(EnvelopeInfo *info, size_t n) {
+    uint64_t at = 0;
+    for (size_t i = 0; i < n; i++) {
+        info[i].offset = info[i].plan.offset = at;
+        at += info[i].length;
+    }
+    return (size_t)at;
+}
+
+int envelopes_run(th_tm *tm, size_t n, const EnvelopeInfo *info, float *out) {
+    std::vector<EnvelopePlanRequest> prs(n);
+    for (size_t i = 0; i < n; i++) prs[i] = info[i].plan;
+    EnvelopePlan pl = plan_envelopes(prs.data(), n);
+    if (pl.err != TH_OK) return fail(pl.err, "%s", pl.err_text.c_str());
+    if (pl.pieces.empty()) return TH_OK;
+
+    TH_HIP(hipSetDevice(tm->ctx->device));
+    SlotLease lease{tm, nullptr};
+    int rc = acquire_slot(tm, &lease.slot);
+    if (rc != TH_OK) return rc;
+    ReaderSlot &sl = *lease.slot;
+    std::vector<unsigned char> tab(pl.tab_bytes);  // (behind the drain: alive until the upload is done)
+    ExportDrain drain{&sl};
+    const bool pinned = pl.pieces.size() == 1 && pl.out_need * sizeof(float) <= TILE_BYTES_MAX;
+    if (!pinned) TH_CHECK(sl.env_out.ensure(pl.out_need * sizeof(float)));
+    TH_CHECK(sl.env_part.ensure(std::max<size_t>(pl.part_need, 1) * sizeof(EnvPartial)));
+    TH_CHECK(sl.env_tab.ensure(pl.tab_bytes));
+    float *res = pinned ? reinterpret_cast<float *>(sl.h_tile_dev) : static_cast<float *>(sl.env_out.dptr);
+    unsigned char *d_tab = static_cast<unsigned char *>(sl.env_tab.dptr);
+    bind_envelopes(pl, EnvelopeBases{res, static_cast<EnvPartial *>(sl.env_part.dptr), d_tab}, prs.data(), tab.data());
+    TH_CHECK(sl.env_tab.upload(sl.stream, tab.data(), tab.size()));
+    const EnvJob *d_jobs = reinterpret_cast<const EnvJob *>(d_tab + pl.o_jobs);
+    for (const EnvelopePiece &pc : pl.pieces) {
+        const uint32_t nj = (uint32_t)(pc.req1 - pc.req0);
+        TH_HIP(launch_envelope_reduce(d_jobs + pc.req0, nj, pc.n_units, sl.stream));
+        TH_HIP(launch_envelope_columns(d_jobs + pc.req0, nj, pc.n_cblocks, sl.stream));
+        if (pinned) TH_HIP(hipStreamSynchronize(sl.stream));
+        // one copy per maximal run of adjacent destinations (the piece's results are adjacent in the slot's area)
+        for (size_t i = pc.req0, k; i < pc.req1; i = k) {
+            k = i + 1;
+            while (k < pc.req1 && info[k].offset == info[k - 1].offset + info[k - 1].length) k++;
+            const size_t bytes = (pl.out_at[k - 1] + (size_t)info[k - 1].length - pl.out_at[i]) * sizeof(float);
+            if (pinned)
+                std::memcpy(out + info[i].offset, reinterpret_cast<const float *>(sl.h_tile) + pl.out_at[i], bytes);
+            else
+                TH_HIP(hipMemcpyAsync(out + info[i].offset, res + pl.out_at[i], bytes, hipMemcpyDeviceToHost, sl.stream));
+        }
+    }
+    TH_HIP(hipStreamSynchronize(sl.stream));
+    return TH_OK;
+}
+
+int waveform_figure_request_info(th_tm *tm, const th_waveform_figure_request &r, size_t i, WaveformFigureInfo *info) {
+    *info = WaveformFigureInfo{};
+    EnvelopePlanRequest er;
+    TH_CHECK(envelope_channel(tm, r.env, i, &er));
+    static_cast<EnvelopePlanRequest &>(info->plan) = er;
+    info->plan.out_h = r.out_h;
+    info->plan.amp_lo = r.amp_lo;
+    info->plan.amp_hi = r.amp_hi;
+    info->plan.thickness = r.thickness;
+    std::memcpy(info->plan.fill, r.fill, 4);
+    std::memcpy(info->plan.background, r.background, 4);
+    const EnvelopeStatus st = check_lane(info->plan, i, &info->sample_start, &info->sample_end);
+    if (st.err != TH_OK) return fail(st.err, "%s", st.err_text.c_str());
+    info->bytes = (uint64_t)r.env.n_cols * r.out_h * 4;
+    info->out_w = r.env.n_cols;
+    info->out_h = r.out_h;
+    info->waveform_revision = tm->waveform_revision();
+    return TH_OK;
+}
+
+size_t waveform_figures_layout(WaveformFigureInfo *info, size_t n) {
+    uint64_t at = 0, end = 0;
+    for (size_t i = 0; i < n; i++) {
+        info[i].offset = info[i].plan.offset = at;
+        end = at + info[i].bytes;
+        at = (end + 63) & ~(uint64_t)63;
+    }
+    return (size_t)end;
+}
+
+int waveform_figures_run(th_tm *tm, size_t n, const WaveformFigureInfo *info, uint8_t *out) {
+    std::vector<LanePlanRequest> prs(n);
+    for (size_t i = 0; i < n; i++) prs[i] = info[i].plan;
+    LanePlan pl = plan_lanes(prs.data(), n);
+    if (pl.err != TH_OK) return fail(pl.err, "%s", pl.err_text.c_str());
+    const std::vector<LanePiece> &pieces = pl.pieces;
+    if (pieces.empty()) return TH_OK;
+
+    TH_HIP(hipSetDevice(tm->ctx->device));
+    SlotLease lease{tm, nullptr};
+    int rc = acquire_slot(tm, &lease.slot);
+    if (rc != TH_OK) return rc;
+    ReaderSlot &sl = *lease.slot;
+    if (!sl.exp_copy) {
+        TH_HIP(hipStreamCreateWithFlags(&sl.exp_copy, hipStreamNonBlocking));
+        for (int b = 0; b < 2; b++) {
+            TH_HIP(hipEventCreateWithFlags(&sl.exp_done[b], hipEventDisableTiming));
+            TH_HIP(hipEventCreateWithFlags(&sl.exp_copied[b], hipEventDisableTiming));
+        }
+    }
+    std::vector<unsigned char> tab(pl.tab_bytes);  // (behind the drain: alive until the upload is done)
+    ExportDrain drain{&sl};
+    for (int b = 0; b < 2; b++)  // the figures' staging buffers: powers of two from 1 MiB, never above one piece
+        TH_CHECK(grow_export_buf(sl, sl.fig_stage[b], sl.fig_stage_cap[b], pl.stage_need[b], 1 << 20, TH_FIGURE_PIECE_BYTES, sl.exp_copy));
+    TH_CHECK(sl.env_out.ensure(pl.env.out_need * sizeof(float)));
+    TH_CHECK(sl.env_part.ensure(std::max<size_t>(pl.env.part_need, 1) * sizeof(EnvPartial)));
+    TH_CHECK(sl.lane_span.ensure(pl.span_need * sizeof(int32_t)));
+    TH_CHECK(sl.env_tab.ensure(pl.tab_bytes));
+    unsigned char *d_tab = static_cast<unsigned char *>(sl.env_tab.dptr);
+    LaneBases bases{};
+    bases.env = EnvelopeBases{static_cast<float *>(sl.env_out.dptr), static_cast<EnvPartial *>(sl.env_part.dptr), d_tab};
+    bases.span = static_cast<int32_t *>(sl.lane_span.dptr);
+    bases.stage[0] = sl.fig_stage[0].get();
+    bases.stage[1] = sl.fig_stage[1].get();
+    bind_lanes(pl, bases, prs.data(), tab.data());
+    TH_CHECK(sl.env_tab.upload(sl.stream, tab.data(), tab.size()));
+    const EnvJob *d_ejobs = reinterpret_cast<const EnvJob *>(d_tab + pl.env.o_jobs);
+    const LaneSpanJob *d_sjobs = reinterpret_cast<const LaneSpanJob *>(d_tab + pl.o_sjobs);
+    const LaneRasterJob *d_rjobs = reinterpret_cast<const LaneRasterJob *>(d_tab + pl.o_rjobs);
+    auto launch_piece = [&](size_t p) -> int {
+        const LanePiece &pc = pieces[p];
+        if (pc.first_of_group) {  // (the stream's order keeps the envelopes and spans from the last group's rasters)
+            const EnvelopePiece &g = pl.env.pieces[pc.group];
+            const uint32_t nj = (uint32_t)(g.req1 - g.req0);
+            TH_HIP(launch_envelope_reduce(d_ejobs + g.req0, nj, g.n_units, sl.stream));
+            TH_HIP(launch_envelope_columns(d_ejobs + g.req0, nj, g.n_cblocks, sl.stream));
+            TH_HIP(launch_lane_spans(d_sjobs + g.req0, nj, pl.group_sblocks[pc.group], sl.stream));
+        }
+        if (p >= 2) TH_HIP(hipStreamWaitEvent(sl.stream, sl.exp_copied[p & 1], 0));  // (the buffer's last piece has left it)
+        TH_HIP(launch_lane_raster(d_rjobs + pc.part0, (uint32_t)(pc.part1 - pc.part0), pc.n_blocks, sl.stream));
+        TH_HIP(hipEventRecord(sl.exp_done[p & 1], sl.stream));
+        return TH_OK;
+    };
+    TH_CHECK(launch_piece(0));
+    for (size_t p = 0; p < pieces.size(); p++) {
+        if (p + 1 < pieces.size()) TH_CHECK(launch_piece(p + 1));  // (ahead of the copy: a copy into pageable memory holds the host)
+        TH_HIP(hipStreamWaitEvent(sl.exp_copy, sl.exp_done[p & 1], 0));
+        for (size_t k = pieces[p].part0; k < pieces[p].part1; k++) {
+            const LanePart &pt = pl.parts[k];
+            TH_HIP(hipMemcpyAsync(out + pt.out_at, sl.fig_stage[p & 1].get() + pt.stage_at, pt.bytes, hipMemcpyDeviceToHost, sl.exp_copy));
+        }
+        TH_HIP(hipEventRecord(sl.exp_copied[p & 1], sl.exp_copy));
+    }
+    TH_HIP(hipStreamSynchronize(sl.stream));
+    TH_HIP(hipStreamSynchronize(sl.exp_copy));
+    return TH_OK;
+}
+}  // namespace tmi
+}  // namespace th
+
+TH_API int th_envelope_edges(uint32_t sr, size_t n_samples, double start_sec, double end_sec, uint32_t n_cols, uint64_t *edges) {
+    TH_TRY
+    TH_REQUIRE(edges, "NULL argument");
+    TH_REQUIRE(envelope_edges(sr, n_samples, start_sec, end_sec, n_cols, edges) == 0,
+               "bad envelope: [%g, %g) s of %zu samples at %u Hz in %u columns (1 .. %u)", start_sec, end_sec, n_samples, sr, n_cols,
+               TH_ENVELOPE_MAX_COLS);
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_waveform_figure_span(const float *col, const float *left, uint32_t out_h, float amp_lo, float amp_hi, uint32_t thickness,
+                                   int32_t *y_top, int32_t *y_bot, int *draws) {
+    TH_TRY
+    TH_REQUIRE(col && y_top && y_bot && draws, "NULL argument");
+    TH_REQUIRE(waveform_figure_span(col, left, out_h, amp_lo, amp_hi, thickness, y_top, y_bot, draws) == 0,
+               "bad lane: %u rows, amplitudes [%g, %g], thickness %u / 256", out_h, (double)amp_lo, (double)amp_hi, thickness);
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_tm_get_envelopes(th_tm *tm, const th_envelope_request *reqs, size_t n, float *out, size_t cap, th_envelope_info *info,
+                               size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(tm && out_len && (n == 0 || (reqs && info)), "NULL argument");
+    *out_len = 0;
+    if (n == 0) return TH_OK;
+    std::shared_lock<std::shared_mutex> rl(tm->rw);
+    std::vector<tmi::EnvelopeInfo> infos(n);
+    for (size_t i = 0; i < n; i++) TH_CHECK(tmi::envelope_request_info(tm, reqs[i], i, &infos[i]));
+    const size_t total = tmi::envelopes_layout(infos.data(), n);
+    for (size_t i = 0; i < n; i++) info[i] = infos[i];
+    *out_len = total;
+    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu floats", total);
+    return tmi::envelopes_run(tm, n, infos.data(), out);
+    TH_CATCH
+}
+
+TH_API int th_tm_get_envelope(th_tm *tm, const th_envelope_request *req, float *out, size_t cap, th_envelope_info *info) {
+    TH_TRY
+    TH_REQUIRE(tm && req, "NULL argument");
+    th_envelope_info one{};
+    size_t len = 0;
+    const int rc = th_tm_get_envelopes(tm, req, 1, out, cap, &one, &len);
+    if (info && (rc == TH_OK || rc == TH_ERR_BUFFER_TOO_SMALL)) *info = one;
+    return rc;
+    TH_CATCH
+}
+
+TH_API int th_tm_render_waveform_figures(th_tm *tm, const th_waveform_figure_request *reqs, size_t n, uint8_t *out, size_t cap,
+                                         th_waveform_figure_info *info, size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(tm && out_len && (n == 0 || (reqs && info)), "NULL argument");
+    *out_len = 0;
+    if (n == 0) return TH_OK;
+    std::shared_lock<std::shared_mutex> rl(tm->rw);
+    std::vector<tmi::WaveformFigureInfo> infos(n);
+    for (size_t i = 0; i < n; i++) TH_CHECK(tmi::waveform_figure_request_info(tm, reqs[i], i, &infos[i]));
+    const size_t total = tmi::waveform_figures_layout(infos.data(), n);
+    for (size_t i = 0; i < n; i++) info[i] = infos[i];
+    *out_len = total;
+    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
+    return tmi::waveform_figures_run(tm, n, infos.data(), out);
+    TH_CATCH
+}
+
+TH_API int th_tm_render_waveform_figure(th_tm *tm, const th_waveform_figure_request *req, uint8_t *out, size_t cap,
+                                        th_waveform_figure_info *info) {
+    TH_TRY
+    TH_REQUIRE(tm && req, "NULL argument");
+    th_waveform_figure_info one{};
+    size_t len = 0;
+    const int rc = th_tm_render_waveform_figures(tm, req, 1, out, cap, &one, &len);
     if (info && (rc == TH_OK || rc == TH_ERR_BUFFER_TOO_SMALL)) *info = one;
     return rc;
     TH_CATCH

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "common.h"
+#include "envelope_plan.h"
 #include "figure_plan.h"
 #include "host_math.h"
 
@@ -132,6 +133,23 @@ size_t figures_layout(FigureInfo *info, size_t n);
 int figures_run(th_tm *tm, size_t n, const FigureInfo *info, uint8_t *out);
 // th_tm_figure_box without the lock
 int figure_box_of(th_tm *tm, size_t id, uint32_t ch, double start_sec, double end_sec, double hz_min, double hz_max, double box[4]);
+
+// Waveform envelopes and lanes.  *info: the record's size, edges[0] and edges[n_cols], and what the plan needs of the request (the
+// resident channel `which` names; its offset is the layout's to set).  envelopes_layout: requests back to back, in floats;
+// waveform_figures_layout: offsets that are multiples of 64, returns the last record's end.  *_run: request i's record to
+// out + info[i].offset, nothing between the records
+struct EnvelopeInfo : th_envelope_info {
+    EnvelopePlanRequest plan;
+};
+int envelope_request_info(th_tm *tm, const th_envelope_request &r, size_t i, EnvelopeInfo *info);
+size_t envelopes_layout(EnvelopeInfo *info, size_t n);
+int envelopes_run(th_tm *tm, size_t n, const EnvelopeInfo *info, float *out);
+struct WaveformFigureInfo : th_waveform_figure_info {
+    LanePlanRequest plan;
+};
+int waveform_figure_request_info(th_tm *tm, const th_waveform_figure_request &r, size_t i, WaveformFigureInfo *info);
+size_t waveform_figures_layout(WaveformFigureInfo *info, size_t n);
+int waveform_figures_run(th_tm *tm, size_t n, const WaveformFigureInfo *info, uint8_t *out);
 
 // update_spec_imgs against `global` (NULL: the manager's own tracks, as th_tm_* does), then the writer's final wait:
 // for the images only (apply_track_list_changes, set_dB_range) or for everything (set_setting, set_colormap)

@@ -849,3 +849,77 @@ TH_API int th_tmg_set_lod_source(th_tmg *g, int per_request) {
     return TH_OK;
     TH_CATCH
 }
+
+// Waveform envelopes and lanes: the same shape as the spectra and the figures; the revision stamped is the manager's own
+TH_API int th_tmg_get_envelopes(th_tmg *g, const th_envelope_request *reqs, size_t n, float *out, size_t cap, th_envelope_info *info,
+                                size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(g && out_len && (n == 0 || (reqs && info)), "NULL argument");
+    *out_len = 0;
+    if (n == 0) return TH_OK;
+    std::shared_lock<std::shared_mutex> rl(g->rw);
+    std::vector<tmi::EnvelopeInfo> infos(n);
+    Split sp;
+    TH_CHECK(check_and_split(g, n, [&](size_t i) { return reqs[i].id; },
+                             [&](th_tm *tm, size_t i) { return tmi::envelope_request_info(tm, reqs[i], i, &infos[i]); }, &sp));
+    const size_t total = tmi::envelopes_layout(infos.data(), n);
+    const uint64_t revision = revisions(g).first;
+    for (size_t i = 0; i < n; i++) {
+        infos[i].waveform_revision = revision;
+        info[i] = infos[i];
+    }
+    *out_len = total;
+    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu floats", total);
+    return run_on_owners(g, sp, [&](th_tm *tm, const std::vector<size_t> &idx) -> int {
+        return tmi::envelopes_run(tm, idx.size(), gather(infos.data(), idx).data(), out);
+    });
+    TH_CATCH
+}
+
+TH_API int th_tmg_get_envelope(th_tmg *g, const th_envelope_request *req, float *out, size_t cap, th_envelope_info *info) {
+    TH_TRY
+    TH_REQUIRE(g && req, "NULL argument");
+    th_envelope_info one{};
+    size_t len = 0;
+    const int rc = th_tmg_get_envelopes(g, req, 1, out, cap, &one, &len);
+    if (info && (rc == TH_OK || rc == TH_ERR_BUFFER_TOO_SMALL)) *info = one;
+    return rc;
+    TH_CATCH
+}
+
+TH_API int th_tmg_render_waveform_figures(th_tmg *g, const th_waveform_figure_request *reqs, size_t n, uint8_t *out, size_t cap,
+                                          th_waveform_figure_info *info, size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(g && out_len && (n == 0 || (reqs && info)), "NULL argument");
+    *out_len = 0;
+    if (n == 0) return TH_OK;
+    std::shared_lock<std::shared_mutex> rl(g->rw);
+    std::vector<tmi::WaveformFigureInfo> infos(n);
+    Split sp;
+    TH_CHECK(check_and_split(g, n, [&](size_t i) { return reqs[i].env.id; },
+                             [&](th_tm *tm, size_t i) { return tmi::waveform_figure_request_info(tm, reqs[i], i, &infos[i]); }, &sp));
+    const size_t total = tmi::waveform_figures_layout(infos.data(), n);
+    const uint64_t revision = revisions(g).first;
+    for (size_t i = 0; i < n; i++) {
+        infos[i].waveform_revision = revision;
+        info[i] = infos[i];
+    }
+    *out_len = total;
+    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
+    return run_on_owners(g, sp, [&](th_tm *tm, const std::vector<size_t> &idx) -> int {
+        return tmi::waveform_figures_run(tm, idx.size(), gather(infos.data(), idx).data(), out);
+    });
+    TH_CATCH
+}
+
+TH_API int th_tmg_render_waveform_figure(th_tmg *g, const th_waveform_figure_request *req, uint8_t *out, size_t cap,
+                                         th_waveform_figure_info *info) {
+    TH_TRY
+    TH_REQUIRE(g && req, "NULL argument");
+    th_waveform_figure_info one{};
+    size_t len = 0;
+    const int rc = th_tmg_render_waveform_figures(g, req, 1, out, cap, &one, &len);
+    if (info && (rc == TH_OK || rc == TH_ERR_BUFFER_TOO_SMALL)) *info = one;
+    return rc;
+    TH_CATCH
+}
