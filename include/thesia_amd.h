@@ -824,6 +824,68 @@ TH_API int th_tm_export_pcm_at(th_tm *tm, const th_export_at_request *reqs, size
 TH_API int th_tm_export_wav_at(th_tm *tm, const th_export_at_request *req, uint8_t *out, size_t cap_bytes,
                                th_export_info *info /* may be NULL */, size_t *out_len);
 
+/* ---------------------------------------------------------------- Export what a spectrogram box holds: band-limited audio */
+/* th_tm_export_pcm_band / th_tm_export_wav_band: th_tm_export_pcm / _wav with the audio filtered to a frequency band first (or with
+ * that band taken out), by a linear-phase FIR on the device: a box on the spectrogram has seconds AND hertz, th_tm_figure_box takes
+ * both, and these entries take the same two frequency edges (upstream's "region selection and loop playback": listen to the box,
+ * save it, save everything but it).  No reference implementation exists; these definitions are the contract.  Host arithmetic is
+ * C double.
+ *   Edges.  f_hi = min(f_hi_hz, sr / 2) (+inf is allowed), f_lo = f_lo_hz.  TH_ERR_INVALID_ARG: a NaN, f_lo < 0, f_lo >= f_hi after
+ *   the clamp, an unknown mode, trans_hz NaN, negative or above sr / 2, sr == 0, TH_BAND_STOP of the whole band (f_lo == 0 and
+ *   f_hi == sr / 2).
+ *   Length.  K = TH_BAND_DEFAULT_HALF_TAPS when trans_hz == 0, else ceil((16.0 sr) / (5.0 trans_hz)); TH_ERR_UNSUPPORTED when
+ *   2K > TH_BAND_MAX_TAPS (at 48 kHz: anything narrower than 4.6875 Hz).  The window below puts the -6.02 dB point on each edge and
+ *   the stopband within 3.2 sr / K Hz of it (the 0.05-of-Nyquist at Z = 128 of the resampler); th_band_plan.trans_hz reports that
+ *   width, 16 sr / (5 K).
+ *   Row (th_band_coefs).  2K taps, k = 0 .. 2K - 1, t = k - K + 1 (an integer), a = 2 f_hi / sr, c = 2 f_lo / sr:
+ *   h_pass(t) = (A(t) - c sinc(c t)) w(t / K), A(t) = a sinc(a t) when a < 1 and [t == 0] exactly when a == 1; sinc and w (the
+ *   squared 4-term Blackman-Harris window, 0 for |u| >= 1) are those of "Export at a target sample rate", character for character.
+ *   h_stop(t) = [t == 0] - h_pass(t).  c32[k] = (float)h; tap 2K - 1 is +-0 and is kept.
+ *   Output.  y[j] = sum over k of c32[k] x[j - K + 1 + k], x = 0 outside [0, n): no delay, n_out = n, the rate is unchanged.
+ *   Summation: that of "Export at a target sample rate", unchanged: tap k goes into partial sum k mod 4 by one fmaf, all four from
+ *   +0, taps outside the track included; y = (a0 + a1) + (a2 + a3).  The order depends on k alone: tile, tap block, piece, range
+ *   and slot cannot change a bit, and th_band_f32 (host, one channel, x = the whole channel) runs the same functions.
+ *   Ranges.  th_audio_sample_range(sr, n, start_sec, end_sec) gives [s0, s1); the dither index is the absolute j; the bytes of a
+ *   range are a slice of the whole-track export with the same filter.  A NaN sample i makes exactly the 2K outputs
+ *   j = i - K .. i + K - 1 NaN, the zero tap included.
+ *   Identity.  TH_BAND_PASS with f_lo == 0 and f_hi == sr / 2 applies no filter: bytes, counts and infos are exactly those of
+ *   th_tm_export_pcm / _wav for `base` (th_band_plan.half_taps == 0).
+ *   th_band_response (host): the magnitude of the f32 row at hz[i], in dB (20 log10 |sum of c32[k] e^(-i 2 pi hz t / sr)|),
+ *   evaluated in f64: what a host draws over th_tm_get_spectrum.
+ * Infos: th_export_info unchanged; n_nan / n_clamped count OUTPUT samples.  Layout and errors are those of th_tm_export_pcm word for
+ * word (offsets multiples of 16, zero padding between requests, the first faulty request decides, nothing written on error, the
+ * size query, an empty range is valid), plus the two rules above.
+ * A reader like th_tm_export_pcm_at, through the same pieces, staging buffers and planar scratch; a piece holds one filter.  A slot
+ * that filters also holds the row of the LAST filter it served (at most TH_BAND_MAX_TAPS floats, 256 KiB); a manager that never
+ * filters holds none. */
+#define TH_BAND_PASS 0
+#define TH_BAND_STOP 1
+#define TH_BAND_MAX_TAPS 65536u
+#define TH_BAND_DEFAULT_HALF_TAPS 2048u
+typedef struct {
+    th_export_request base;  /* id, which, format, dither, seed, start_sec, end_sec: unchanged meaning */
+    uint32_t mode;           /* TH_BAND_PASS / TH_BAND_STOP */
+    double f_lo_hz, f_hi_hz; /* the box's frequency edges: the same numbers th_tm_figure_box takes */
+    double trans_hz;         /* half transition width; 0 = default */
+} th_export_band_request;
+typedef struct {
+    uint32_t half_taps;      /* K; 0 = no filter (identity) */
+    uint32_t mode;
+    double f_lo_hz, f_hi_hz; /* after clamping */
+    double trans_hz;         /* the width the filter has: 16 sr / (5 K) */
+} th_band_plan;
+/* host arithmetic.  th_band_coefs: the row of a plan with half_taps > 0, as f64 (h64, may be NULL) and rounded to f32 (c32, may be
+ * NULL).  th_band_response: see above.  th_band_f32: outputs [j0, j0 + n) of one channel under the row c32 of 2 half_taps taps,
+ * j0 + n <= n_in */
+TH_API int th_band_plan_for(uint32_t sr, uint32_t mode, double f_lo_hz, double f_hi_hz, double trans_hz, th_band_plan *out);
+TH_API int th_band_coefs(uint32_t sr, const th_band_plan *plan, double *h64, float *c32);
+TH_API int th_band_response(uint32_t sr, const th_band_plan *plan, const double *hz, size_t n, double *db);
+TH_API int th_band_f32(const float *x, size_t n_in, const float *c32, uint32_t half_taps, uint64_t j0, size_t n, float *y);
+TH_API int th_tm_export_pcm_band(th_tm *tm, const th_export_band_request *reqs, size_t n, uint8_t *out, size_t cap_bytes,
+                                 th_export_info *info /* n */, size_t *out_len);
+TH_API int th_tm_export_wav_band(th_tm *tm, const th_export_band_request *req, uint8_t *out, size_t cap_bytes,
+                                 th_export_info *info /* may be NULL */, size_t *out_len);
+
 /* ---------------------------------------------------------------- Export as figures: a spectrogram region at any pixel size */
 /* Any region of a channel's resident u16 image, resampled on the device to any pixel size and coloured (or left as 16-bit grey): what
  * a host saves as a figure, without fetching tiles, stitching them and resampling a second time (upstream's roadmap item "export as
@@ -1069,6 +1131,11 @@ TH_API int th_tmg_export_pcm_at(th_tmg *tmg, const th_export_at_request *reqs, s
                                 th_export_info *info /* n */, size_t *out_len);
 TH_API int th_tmg_export_wav_at(th_tmg *tmg, const th_export_at_request *req, uint8_t *out, size_t cap_bytes,
                                 th_export_info *info /* may be NULL */, size_t *out_len);
+/* band-limited export: as above, bit-identical to one th_tm; every slot keeps the row of its own last filter */
+TH_API int th_tmg_export_pcm_band(th_tmg *tmg, const th_export_band_request *reqs, size_t n, uint8_t *out, size_t cap_bytes,
+                                  th_export_info *info /* n */, size_t *out_len);
+TH_API int th_tmg_export_wav_band(th_tmg *tmg, const th_export_band_request *req, uint8_t *out, size_t cap_bytes,
+                                  th_export_info *info /* may be NULL */, size_t *out_len);
 
 /* figures: every request goes to its owning slot and the slots are served side by side, each copying its records straight into the
  * caller's buffer; bytes, offsets and infos are those of one th_tm, the revision stamped is the manager's own */

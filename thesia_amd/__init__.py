@@ -10,6 +10,7 @@ from .api import (LINEAR, MEL, SPECTRUM_MAX, SPECTRUM_MEAN_AMP, SPECTRUM_MEAN_PO
                   limiter_params, loudness_n_blocks, loudness_n_short_term, loudness_range, true_peak_filter, normalize_gain, mel_default_n_mel, pitch_f32, pitch_u16, shard_assign, spectrogram_tile_geometry, spectrum_frame_range, stft_n_frames, waveform_tile_geometry,
                   PCM_S16, PCM_S24, PCM_F32, DITHER_NONE, DITHER_TPDF, audio_sample_range, export_chunk_frames, export_dither, export_quantize, wav_header,
                   resample_plan, resample_n_out, resample_coefs, resample_f32, resample_tile,
+                  BAND_PASS, BAND_STOP, band_plan, band_coefs, band_response, band_f32,
                   FIGURE_RGBA, FIGURE_GREY16, figure_axis, figure_box,
                   edges, envelope_edges, waveform_figure_span)
 
@@ -18,6 +19,7 @@ __all__ = ["LINEAR", "MEL", "SPECTRUM_MEAN_AMP", "SPECTRUM_MEAN_POWER", "SPECTRU
            "limiter_params", "loudness_n_blocks", "loudness_n_short_term", "loudness_range", "true_peak_filter", "normalize_gain", "mel_default_n_mel", "pitch_f32", "pitch_u16", "shard_assign", "spectrogram_tile_geometry", "spectrum_frame_range", "stft_n_frames", "waveform_tile_geometry",
            "PCM_S16", "PCM_S24", "PCM_F32", "DITHER_NONE", "DITHER_TPDF", "audio_sample_range", "export_chunk_frames", "export_dither", "export_quantize", "wav_header",
            "resample_plan", "resample_n_out", "resample_coefs", "resample_f32", "resample_tile",
+           "BAND_PASS", "BAND_STOP", "band_plan", "band_coefs", "band_response", "band_f32",
            "FIGURE_RGBA", "FIGURE_GREY16", "figure_axis", "figure_box",
            "edges", "envelope_edges", "waveform_figure_span",
            "ChanDesc", "ImgDesc", "RasterDesc", "WaveDesc", "TileGeom", "LIB_PATH"]

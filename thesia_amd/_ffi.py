@@ -128,6 +128,14 @@ class ExportAtRequest(C.Structure):  # th_export_at_request
     _fields_ = [("base", ExportRequest), ("sr_out", C.c_uint32)]
 
 
+class ExportBandRequest(C.Structure):  # th_export_band_request
+    _fields_ = [("base", ExportRequest), ("mode", C.c_uint32), ("f_lo_hz", C.c_double), ("f_hi_hz", C.c_double), ("trans_hz", C.c_double)]
+
+
+class BandPlan(C.Structure):  # th_band_plan
+    _fields_ = [("half_taps", C.c_uint32), ("mode", C.c_uint32), ("f_lo_hz", C.c_double), ("f_hi_hz", C.c_double), ("trans_hz", C.c_double)]
+
+
 class FigureRequest(C.Structure):  # th_figure_request
     _fields_ = [("id", C.c_size_t), ("ch", C.c_uint32), ("kind", C.c_uint32), ("out_w", C.c_uint32), ("out_h", C.c_uint32),
                 ("left", C.c_double), ("top", C.c_double), ("width", C.c_double), ("height", C.c_double)]
@@ -367,6 +375,14 @@ _SIGS = {
     "th_tm_export_wav_at": [vp, C.POINTER(ExportAtRequest), C.c_void_p, C.c_size_t, C.POINTER(ExportInfo), c_szp],
     "th_tmg_export_pcm_at": [vp, C.POINTER(ExportAtRequest), C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(ExportInfo), c_szp],
     "th_tmg_export_wav_at": [vp, C.POINTER(ExportAtRequest), C.c_void_p, C.c_size_t, C.POINTER(ExportInfo), c_szp],
+    "th_band_plan_for": [C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double, C.POINTER(BandPlan)],
+    "th_band_coefs": [C.c_uint32, C.POINTER(BandPlan), C.POINTER(C.c_double), c_f32p],
+    "th_band_response": [C.c_uint32, C.POINTER(BandPlan), C.POINTER(C.c_double), C.c_size_t, C.POINTER(C.c_double)],
+    "th_band_f32": [c_f32p, C.c_size_t, c_f32p, C.c_uint32, C.c_uint64, C.c_size_t, c_f32p],
+    "th_tm_export_pcm_band": [vp, C.POINTER(ExportBandRequest), C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(ExportInfo), c_szp],
+    "th_tm_export_wav_band": [vp, C.POINTER(ExportBandRequest), C.c_void_p, C.c_size_t, C.POINTER(ExportInfo), c_szp],
+    "th_tmg_export_pcm_band": [vp, C.POINTER(ExportBandRequest), C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(ExportInfo), c_szp],
+    "th_tmg_export_wav_band": [vp, C.POINTER(ExportBandRequest), C.c_void_p, C.c_size_t, C.POINTER(ExportInfo), c_szp],
     "th_figure_axis": [C.c_double, C.c_double, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
                        C.c_size_t, C.POINTER(C.c_uint32)],
     "th_figure_box": [C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint32, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int,

@@ -31,6 +31,10 @@ EXPORT_MAX_CHANNELS = 1024         # TH_EXPORT_MAX_CHANNELS
 EXPORT_CHUNK_SAMPLES = 4096        # samples (frames x channels) of one workgroup of the export kernel, at most
 RESAMPLE_MAX_TAPS = 16384          # TH_RESAMPLE_MAX_TAPS
 RESAMPLE_MAX_COEFS = 1 << 24       # TH_RESAMPLE_MAX_COEFS
+BAND_PASS, BAND_STOP = 0, 1        # TH_BAND_*
+BAND_MAX_TAPS = 65536              # TH_BAND_MAX_TAPS
+BAND_DEFAULT_HALF_TAPS = 2048      # TH_BAND_DEFAULT_HALF_TAPS
+BAND_TILE, BAND_TAP_BLOCK = 2048, 64   # outputs of a workgroup and taps per step of the band kernel (reader_plan.h)
 FIGURE_RGBA, FIGURE_GREY16 = 0, 1
 FIGURE_MAX_DIM = 16384             # TH_FIGURE_MAX_DIM
 FIGURE_PIECE_BYTES = 8 << 20       # TH_FIGURE_PIECE_BYTES
@@ -440,6 +444,98 @@ class _ExportAtMethods:
         info = _ffi.ExportInfo()
         need = C.c_size_t()
         fn = getattr(lib, self._PFX + "export_wav_at")
+        rc = fn(self.handle, C.byref(req), None, 0, C.byref(info), C.byref(need))
+        if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+            check(rc)
+        out = np.empty(need.value, np.uint8)
+        check(fn(self.handle, C.byref(req), out.ctypes.data, out.size, C.byref(info), C.byref(need)))
+        return out.tobytes(), _export_info_dict(info)
+
+
+def _band_plan(plan) -> "_ffi.BandPlan":
+    if isinstance(plan, _ffi.BandPlan):
+        return plan
+    return _ffi.BandPlan(plan["half_taps"], plan["mode"], plan["f_lo_hz"], plan["f_hi_hz"], plan["trans_hz"])
+
+
+def band_plan(sr: int, mode: int, f_lo_hz: float, f_hi_hz: float, trans_hz: float = 0.0) -> dict:
+    """th_band_plan_for -> {half_taps, mode, f_lo_hz, f_hi_hz, trans_hz} of the band filter at sr (host); half_taps 0: the identity"""
+    p = _ffi.BandPlan()
+    check(lib.th_band_plan_for(sr, mode, f_lo_hz, f_hi_hz, trans_hz, C.byref(p)))
+    return {k: getattr(p, k) for k, _ in p._fields_}
+
+
+def band_coefs(sr: int, plan):
+    """-> (f64 row, f32 row): the 2K taps of the filter of a band_plan (host)"""
+    p = _band_plan(plan)
+    h64, c32 = np.empty(2 * p.half_taps, np.float64), np.empty(2 * p.half_taps, np.float32)
+    check(lib.th_band_coefs(sr, C.byref(p), h64.ctypes.data_as(C.POINTER(C.c_double)), _ptr(c32, c_f32p)))
+    return h64, c32
+
+
+def band_response(sr: int, plan, hz) -> np.ndarray:
+    """the magnitude of the filter's f32 row at the frequencies hz, in dB (host, summed in f64)"""
+    p = _band_plan(plan)
+    hz = np.ascontiguousarray(hz, np.float64).ravel()
+    db = np.empty(hz.size, np.float64)
+    f64p = C.POINTER(C.c_double)
+    check(lib.th_band_response(sr, C.byref(p), hz.ctypes.data_as(f64p), hz.size, db.ctypes.data_as(f64p)))
+    return db
+
+
+def band_f32(x, c32, j0: int = 0, n: Optional[int] = None) -> np.ndarray:
+    """outputs [j0, j0 + n) of one channel x (the whole channel) under the row c32 on the host: what the band kernel computes, the
+    same order and bits (n None: up to the end)"""
+    x, c32 = _f32(x).ravel(), _f32(c32).ravel()
+    if n is None:
+        n = x.size - j0
+    y = np.empty(max(n, 0), np.float32)
+    check(lib.th_band_f32(_ptr(x, c_f32p), x.size, _ptr(c32, c_f32p), c32.size // 2, j0, y.size, _ptr(y, c_f32p)))
+    return y
+
+
+def _export_band_request(r) -> "_ffi.ExportBandRequest":
+    """(track_id, mode, f_lo_hz, f_hi_hz, trans_hz, fmt[, dither[, seed[, start_sec[, end_sec[, which]]]]]) or a dict with those names"""
+    if isinstance(r, dict):
+        band = (r.get("mode", BAND_PASS), r["f_lo_hz"], r["f_hi_hz"], r.get("trans_hz", 0.0))
+        base = _export_request(r)
+    else:
+        r = tuple(r)
+        band = r[1:5]
+        base = _export_request((r[0],) + r[5:])
+    return _ffi.ExportBandRequest(base, *band)
+
+
+class _ExportBandMethods:
+    """_ExportMethods through a band filter: what a box on the spectrogram holds, or everything but it (th_tm_* and th_tmg_*)"""
+
+    def export_pcm_band(self, requests, out: Optional[np.ndarray] = None):
+        """th_tm_export_pcm_band: requests = iterable of (track_id, mode, f_lo_hz, f_hi_hz, trans_hz, fmt[, dither[, seed[, start_sec[,
+        end_sec[, which]]]]]) -> (uint8 buffer, list of info dicts), as export_pcm"""
+        reqs = [_export_band_request(r) for r in requests]
+        n = len(reqs)
+        if n == 0:
+            return np.empty(0, np.uint8), []
+        arr = (_ffi.ExportBandRequest * n)(*reqs)
+        info = (_ffi.ExportInfo * n)()
+        need = C.c_size_t()
+        fn = getattr(lib, self._PFX + "export_pcm_band")
+        if out is None:
+            rc = fn(self.handle, arr, n, None, 0, info, C.byref(need))
+            if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+                check(rc)
+            out = np.empty(max(need.value, 1), np.uint8)
+        check(fn(self.handle, arr, n, out.ctypes.data, out.size, info, C.byref(need)))
+        return out[:need.value], [_export_info_dict(o) for o in info]
+
+    def export_wav_band(self, track_id: int, mode: int, f_lo_hz: float, f_hi_hz: float, trans_hz: float, fmt: int,
+                        dither: int = DITHER_NONE, seed: int = 0, start_sec: float = 0.0, end_sec: float = float("inf"), which: int = 0):
+        """th_tm_export_wav_band: -> (the complete file image of the filtered audio as bytes, info dict)"""
+        req = _ffi.ExportBandRequest(_ffi.ExportRequest(track_id, which, fmt, dither, seed, start_sec, end_sec), mode, f_lo_hz, f_hi_hz,
+                                     trans_hz)
+        info = _ffi.ExportInfo()
+        need = C.c_size_t()
+        fn = getattr(lib, self._PFX + "export_wav_band")
         rc = fn(self.handle, C.byref(req), None, 0, C.byref(info), C.byref(need))
         if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
             check(rc)
@@ -1161,7 +1257,7 @@ class TileCache:
                 "spectrogram_revision": sr.value, "hits": h.value, "misses": m.value}
 
 
-class TrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods, _ExportAtMethods, _FigureMethods, _EnvelopeMethods):
+class TrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods, _ExportAtMethods, _ExportBandMethods, _FigureMethods, _EnvelopeMethods):
     """th_tm: mirror of core/mod.rs TrackManager with HBM-resident audio / specs / images."""
     _PFX = "th_tm_"
 
@@ -1361,7 +1457,7 @@ class TrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _E
         return out[: n.value].tobytes()
 
 
-class MultiTrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods, _ExportAtMethods, _FigureMethods, _EnvelopeMethods):
+class MultiTrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods, _ExportAtMethods, _ExportBandMethods, _FigureMethods, _EnvelopeMethods):
     """th_tmg: the TrackManager over several devices of one process (duplicates allowed: [0, 0] is two slots on one card).
     Same method names as TrackManager; results are bit-identical to one TrackManager holding every track."""
     _PFX = "th_tmg_"

@@ -1596,6 +1596,68 @@ TH_API int th_resample_f32(const float *x, size_t n_in, uint32_t sr_in, uint32_t
     TH_CATCH
 }
 
+// ---- the host arithmetic of the band filter (the summation is the resampler's: resample_core.h)
+TH_API int th_band_plan_for(uint32_t sr, uint32_t mode, double f_lo_hz, double f_hi_hz, double trans_hz, th_band_plan *out) {
+    TH_TRY
+    TH_REQUIRE(out, "NULL argument");
+    const int rc = th::band_plan_for(sr, mode, f_lo_hz, f_hi_hz, trans_hz, out);
+    TH_REQUIRE(rc != 1, "bad band (mode %u, [%g, %g] Hz, transition %g Hz) at %u Hz", mode, f_lo_hz, f_hi_hz, trans_hz, sr);
+    if (rc != 0) return fail(TH_ERR_UNSUPPORTED, "a transition of %g Hz at %u Hz needs more than %u taps", trans_hz, sr, TH_BAND_MAX_TAPS);
+    return TH_OK;
+    TH_CATCH
+}
+
+namespace {
+int band_plan_usable(uint32_t sr, const th_band_plan *p) {
+    TH_REQUIRE(p, "NULL argument");
+    TH_REQUIRE(sr != 0 && p->half_taps != 0 && 2 * (uint64_t)p->half_taps <= TH_BAND_MAX_TAPS && p->mode <= TH_BAND_STOP,
+               "not a filter's plan (%u half taps, mode %u, %u Hz)", p->half_taps, p->mode, sr);
+    return TH_OK;
+}
+}  // namespace
+
+TH_API int th_band_coefs(uint32_t sr, const th_band_plan *plan, double *h64, float *c32) {
+    TH_TRY
+    TH_CHECK(band_plan_usable(sr, plan));
+    band_row(sr, *plan, h64, c32);
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_band_response(uint32_t sr, const th_band_plan *plan, const double *hz, size_t n, double *db) {
+    TH_TRY
+    TH_CHECK(band_plan_usable(sr, plan));
+    TH_REQUIRE(n == 0 || (hz && db), "NULL argument");
+    std::vector<float> row(2 * (size_t)plan->half_taps);
+    band_row(sr, *plan, nullptr, row.data());
+    band_response(sr, row.data(), plan->half_taps, hz, n, db);
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_band_f32(const float *x, size_t n_in, const float *c32, uint32_t half_taps, uint64_t j0, size_t n, float *y) {
+    TH_TRY
+    TH_REQUIRE(n == 0 || y, "NULL argument");
+    TH_REQUIRE(n_in == 0 || x, "NULL argument");
+    TH_REQUIRE(c32 && half_taps != 0 && 2 * (uint64_t)half_taps <= TH_BAND_MAX_TAPS, "a row of 2 x %u taps", half_taps);
+    TH_REQUIRE(j0 <= n_in && n <= n_in - j0, "outputs [%llu, +%zu) of %zu", (unsigned long long)j0, n, n_in);
+    const uint32_t taps = 2 * half_taps;
+    const int64_t K = half_taps;
+    // x with K - 1 zeros in front and K behind outputs [j0, j0 + n): output i's window starts at padded[i]
+    std::vector<float> padded(n + taps - 1, 0.0f);
+    for (size_t p = 0; p < padded.size(); p++) {
+        const int64_t at = (int64_t)j0 - K + 1 + (int64_t)p;
+        if (at >= 0 && at < (int64_t)n_in) padded[p] = x[at];
+    }
+    for (size_t i = 0; i < n; i++) {
+        ResampleAcc acc;
+        resample_taps(acc, c32, padded.data() + i, taps);
+        y[i] = resample_fold(acc);
+    }
+    return TH_OK;
+    TH_CATCH
+}
+
 namespace th {
 
 LoudnessBatch::~LoudnessBatch() {

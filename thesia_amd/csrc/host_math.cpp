@@ -1112,31 +1112,22 @@ bool resample_n_out(size_t n_in, const th_resample_plan &p, size_t *n_out) {
     return true;
 }
 
-void resample_row(const th_resample_plan &p, uint32_t r, double *h64, float *c32) {
-    const double pi = 3.14159265358979323846, Z = 128.0;
-    const int64_t K = p.half_taps;
-    const double frac = (double)r / (double)p.L;
-    for (int64_t k = 0; k < 2 * K; k++) {
-        const double t = (double)(k - K + 1) - frac;
-        const double x = p.cutoff * t;
-        const double sinc = x == 0.0 ? 1.0 : std::sin(pi * x) / (pi * x);
-        const double u = p.rho * t / Z;
-        double h = 0.0;
-        if (std::fabs(u) < 1.0) {
-            const double bh = 0.35875 + 0.48829 * std::cos(pi * u) + 0.14128 * std::cos(2.0 * pi * u) + 0.01168 * std::cos(3.0 * pi * u);
-            h = p.cutoff * sinc * (bh * bh);
-        }
-        if (h64) h64[k] = h;
-        if (c32) c32[k] = (float)h;
-    }
+namespace {
+const double RS_PI = 3.14159265358979323846;
+double rs_sinc(double x) { return x == 0.0 ? 1.0 : std::sin(RS_PI * x) / (RS_PI * x); }
+// the squared 4-term Blackman-Harris window, 0 for |u| >= 1
+double rs_window(double u) {
+    if (!(std::fabs(u) < 1.0)) return 0.0;
+    const double bh = 0.35875 + 0.48829 * std::cos(RS_PI * u) + 0.14128 * std::cos(2.0 * RS_PI * u) + 0.01168 * std::cos(3.0 * RS_PI * u);
+    return bh * bh;
 }
-
-void resample_table(const th_resample_plan &p, float *table) {
-    const size_t taps = 2 * (size_t)p.half_taps;
-    const size_t n_thr = std::min<size_t>(std::max<size_t>(1, (size_t)p.L * taps / 65536), std::max(1u, std::min(16u, std::thread::hardware_concurrency())));
+// work(i) for i in [0, n) on up to max_thr threads (at most 16, at most the machine's), this thread among them
+template <class F>
+void on_threads(uint32_t n, size_t max_thr, F work_one) {
+    const size_t n_thr = std::min<size_t>(std::max<size_t>(1, max_thr), std::max(1u, std::min(16u, std::thread::hardware_concurrency())));
     std::atomic<uint32_t> next{0};
     auto work = [&]() {
-        for (uint32_t r = next.fetch_add(1); r < p.L; r = next.fetch_add(1)) resample_row(p, r, nullptr, table + (size_t)r * taps);
+        for (uint32_t i = next.fetch_add(1); i < n; i = next.fetch_add(1)) work_one(i);
     };
     std::vector<std::thread> thr;
     try {
@@ -1145,6 +1136,86 @@ void resample_table(const th_resample_plan &p, float *table) {
     }
     work();
     for (auto &t : thr) t.join();
+}
+}  // namespace
+
+void resample_row(const th_resample_plan &p, uint32_t r, double *h64, float *c32) {
+    const double Z = 128.0;
+    const int64_t K = p.half_taps;
+    const double frac = (double)r / (double)p.L;
+    for (int64_t k = 0; k < 2 * K; k++) {
+        const double t = (double)(k - K + 1) - frac;
+        const double u = p.rho * t / Z;
+        double h = 0.0;
+        if (std::fabs(u) < 1.0) h = p.cutoff * rs_sinc(p.cutoff * t) * rs_window(u);
+        if (h64) h64[k] = h;
+        if (c32) c32[k] = (float)h;
+    }
+}
+
+void resample_table(const th_resample_plan &p, float *table) {
+    const size_t taps = 2 * (size_t)p.half_taps;
+    on_threads(p.L, (size_t)p.L * taps / 65536, [&](uint32_t r) { resample_row(p, r, nullptr, table + (size_t)r * taps); });
+}
+
+// ---- band filter of the export (include/thesia_amd.h "Export what a spectrogram box holds")
+int band_plan_for(uint32_t sr, uint32_t mode, double f_lo_hz, double f_hi_hz, double trans_hz, th_band_plan *out) {
+    if (sr == 0 || mode > TH_BAND_STOP) return 1;
+    const double nyq = (double)sr / 2.0;
+    if (f_lo_hz != f_lo_hz || f_hi_hz != f_hi_hz || trans_hz != trans_hz) return 1;
+    const double f_hi = std::min(f_hi_hz, nyq), f_lo = f_lo_hz;
+    if (f_lo < 0.0 || f_lo >= f_hi || trans_hz < 0.0 || trans_hz > nyq) return 1;
+    const bool whole = f_lo == 0.0 && f_hi == nyq;
+    if (whole && mode == TH_BAND_STOP) return 1;
+    *out = th_band_plan{};
+    out->mode = mode;
+    out->f_lo_hz = f_lo;
+    out->f_hi_hz = f_hi;
+    if (whole) return 0;  // (identity: no filter, whatever the width asked for)
+    const double K = trans_hz == 0.0 ? (double)TH_BAND_DEFAULT_HALF_TAPS : std::ceil((16.0 * (double)sr) / (5.0 * trans_hz));
+    if (!(2.0 * K <= (double)TH_BAND_MAX_TAPS)) return 2;
+    out->half_taps = (uint32_t)K;
+    out->trans_hz = (16.0 * (double)sr) / (5.0 * K);
+    return 0;
+}
+
+namespace {
+double band_tap(uint32_t sr, const th_band_plan &p, int64_t k) {
+    const int64_t K = p.half_taps, ti = k - K + 1;
+    const double t = (double)ti, a = 2.0 * p.f_hi_hz / (double)sr, c = 2.0 * p.f_lo_hz / (double)sr;
+    const double delta = ti == 0 ? 1.0 : 0.0;
+    const double A = a < 1.0 ? a * rs_sinc(a * t) : delta;
+    const double pass = (A - c * rs_sinc(c * t)) * rs_window(t / (double)K);
+    return p.mode == TH_BAND_STOP ? delta - pass : pass;
+}
+}  // namespace
+
+void band_row(uint32_t sr, const th_band_plan &p, double *h64, float *c32) {
+    const uint32_t taps = 2 * p.half_taps, per = 4096, n_parts = (taps + per - 1) / per;
+    on_threads(n_parts, n_parts, [&](uint32_t part) {
+        for (uint32_t k = part * per; k < std::min(taps, (part + 1) * per); k++) {
+            const double h = band_tap(sr, p, k);
+            if (h64) h64[k] = h;
+            if (c32) c32[k] = (float)h;
+        }
+    });
+}
+
+void band_response(uint32_t sr, const float *c32, uint32_t half_taps, const double *hz, size_t n, double *db) {
+    const int64_t K = half_taps;
+    const uint32_t per = 8, n_parts = (uint32_t)((n + per - 1) / per);
+    on_threads(n_parts, (size_t)n_parts * half_taps / 32768, [&](uint32_t part) {
+        for (size_t i = (size_t)part * per; i < std::min(n, ((size_t)part + 1) * per); i++) {
+            const double w = 2.0 * RS_PI * hz[i] / (double)sr;
+            double re = 0.0, im = 0.0;
+            for (int64_t k = 0; k < 2 * K; k++) {
+                const double ph = w * (double)(k - K + 1);
+                re += (double)c32[k] * std::cos(ph);
+                im -= (double)c32[k] * std::sin(ph);
+            }
+            db[i] = 20.0 * std::log10(std::sqrt(re * re + im * im));
+        }
+    });
 }
 
 }  // namespace th

@@ -149,6 +149,14 @@ bool resample_n_out(size_t n_in, const th_resample_plan &p, size_t *n_out);
 void resample_row(const th_resample_plan &p, uint32_t r, double *h64, float *c32);
 void resample_table(const th_resample_plan &p, float *table);
 
+// ---- band filter of the export (th_band_plan_for; include/thesia_amd.h "Export what a spectrogram box holds").  band_plan_for: 0, 1
+// for a bad argument, 2 for a row beyond TH_BAND_MAX_TAPS; a plan with half_taps == 0 is the identity.  band_row: the 2K taps of a plan
+// with half_taps > 0, in f64 and / or rounded to f32, with the resampler's sinc and window, built on up to 16 threads.  band_response:
+// the magnitude in dB of the f32 row c32 at n frequencies, summed in f64
+int band_plan_for(uint32_t sr, uint32_t mode, double f_lo_hz, double f_hi_hz, double trans_hz, th_band_plan *out);
+void band_row(uint32_t sr, const th_band_plan &p, double *h64, float *c32);
+void band_response(uint32_t sr, const float *c32, uint32_t half_taps, const double *hz, size_t n, double *db);
+
 inline bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
 inline unsigned ilog2(size_t n) {
     unsigned l = 0;

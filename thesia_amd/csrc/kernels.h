@@ -284,6 +284,10 @@ hipError_t launch_export(const ExportJob *d_jobs, uint32_t n_jobs, uint32_t n_ch
 hipError_t launch_resample(const ResampleJob *d_jobs, uint32_t n_jobs, uint32_t n_blocks, const float *d_table, const ResampleTiling &t,
                            hipStream_t s);
 
+// ---- kernels_band.hip: one FIR row for every output (BandJob, BandTiling: reader_plan.h)
+// row: t.taps floats (host_math.h band_row); n_blocks: the sum over the jobs
+hipError_t launch_band(const BandJob *d_jobs, uint32_t n_jobs, uint32_t n_blocks, const float *d_row, const BandTiling &t, hipStream_t s);
+
 // ---- kernels_figure.hip: a region of a u16 image at any pixel size (FigHJob, FigVJob: figure_plan.h).  n_blocks: the sum over the jobs
 hipError_t launch_figure_hpass(const FigHJob *d_jobs, uint32_t n_jobs, uint32_t n_blocks, hipStream_t s);
 // d_colormap: n_colors RGBA entries (read by the TH_FIGURE_RGBA jobs only)

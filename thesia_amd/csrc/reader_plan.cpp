@@ -34,8 +34,9 @@ struct ExportSpan {
 // the bound (take then says of how many frames).
 ExportSpan next_span(const ExportPiece &cur, uint64_t out_end, const ExportPlanRequest &r, uint64_t f) {
     ExportSpan s;
-    const bool resampled = r.sr_out != r.sr_in;
+    const bool resampled = r.sr_out != r.sr_in, filtered = r.band.half_taps != 0;
     if (resampled && cur.sr_out != 0 && (cur.sr_in != r.sr_in || cur.sr_out != r.sr_out)) return s;  // (one table per launch)
+    if (filtered && cur.band.half_taps != 0 && (cur.band_sr != r.sr_in || !same_band(cur.band, r.band))) return s;  // (and one row)
     const uint64_t fbytes = (uint64_t)r.n_ch * export_bytes_per_sample(r.format);
     s.out_at = r.offset + (f - r.s0) * fbytes;
     s.contiguous = !cur.runs.empty() && s.out_at == out_end;
@@ -43,9 +44,9 @@ ExportSpan next_span(const ExportPiece &cur, uint64_t out_end, const ExportPlanR
     const uint64_t room = s.stage_at < TH_EXPORT_PIECE_BYTES ? (TH_EXPORT_PIECE_BYTES - s.stage_at) / fbytes : 0;
     if (room == 0) return s;  // (a frame is at most 4 KiB: an empty piece always has room)
     s.take = std::min<uint64_t>(room, r.s1 - f);
-    // a resampled request is cut on the export kernel's chunk grid, and its hull on the grid of 4 frames is what the resampler
-    // makes: the export kernel's 16-byte loads then stay aligned and inside what was written
-    if (resampled) {
+    // a resampled or filtered request is cut on the export kernel's chunk grid, and its hull on the grid of 4 frames is what the
+    // resampler or the band filter makes: the export kernel's 16-byte loads then stay aligned and inside what was written
+    if (resampled || filtered) {
         if (f + s.take < r.s1) {
             const uint64_t F = export_chunk_frames(r.n_ch);
             const uint64_t cut = (f + s.take) / F * F;
@@ -53,7 +54,7 @@ ExportSpan next_span(const ExportPiece &cur, uint64_t out_end, const ExportPlanR
             s.take = cut - f;
         }
         s.hull0 = f & ~(uint64_t)3;
-        const uint64_t hull1 = std::min<uint64_t>((f + s.take + 3) & ~(uint64_t)3, r.n_out);
+        const uint64_t hull1 = std::min<uint64_t>((f + s.take + 3) & ~(uint64_t)3, resampled ? r.n_out : r.n_in);
         s.stride = (hull1 - s.hull0 + 3) & ~(uint64_t)3;
         if ((cur.scratch_floats + s.stride * r.n_ch) * sizeof(float) > RESAMPLE_SCRATCH_MAX) return s;
     }
@@ -72,14 +73,17 @@ ExportPlan plan_export(const ExportPlanRequest *reqs, size_t n) {
     auto close_piece = [&]() {
         cur.job1 = p.jobs.size();
         cur.rjob1 = p.rjobs.size();
+        cur.bjob1 = p.bjobs.size();
         p.pieces.push_back(std::move(cur));
         cur = ExportPiece{};
         cur.job0 = p.jobs.size();
         cur.rjob0 = p.rjobs.size();
+        cur.bjob0 = p.bjobs.size();
     };
     for (size_t i = 0; i < n; i++) {
         const ExportPlanRequest &r = reqs[i];
-        const bool resampled = r.sr_out != r.sr_in;
+        const bool resampled = r.sr_out != r.sr_in, filtered = r.band.half_taps != 0;
+        if (resampled && filtered) return plan_error<ExportPlan>(TH_ERR_INTERNAL, "request %zu: a band and a rate conversion in one request", i);
         const ResampleTiling tiling = resampled ? resample_tiling(r.plan) : ResampleTiling{};
         const uint64_t fbytes = (uint64_t)r.n_ch * export_bytes_per_sample(r.format);
         p.ptr0[i] = p.n_ptrs;
@@ -108,7 +112,7 @@ ExportPlan plan_export(const ExportPlanRequest *reqs, size_t n) {
             j.pad = pd;
             const uint64_t chunks = (uint64_t)cur.n_chunks + export_n_chunks(j.f0, j.f1, r.n_ch);
             if (chunks > INT32_MAX) return plan_error<ExportPlan>(TH_ERR_UNSUPPORTED, "request %zu: too many chunks in one piece", i);
-            ExportPlace place{i, s.stage_at, 0, 0, s.hull0, s.stride, resampled};
+            ExportPlace place{i, s.stage_at, 0, 0, s.hull0, s.stride, resampled, filtered};
             if (resampled) {
                 ResampleJob rj{};
                 rj.ja = s.hull0;
@@ -132,6 +136,28 @@ ExportPlan plan_export(const ExportPlanRequest *reqs, size_t n) {
                 cur.plan = r.plan;
                 p.rjobs.push_back(rj);
             }
+            if (filtered) {
+                BandJob bj{};
+                bj.ja = s.hull0;
+                bj.jb = std::min<uint64_t>(s.hull0 + s.stride, r.n_in);
+                bj.n_in = r.n_in;
+                bj.ch_stride = s.stride;
+                bj.n_ch = r.n_ch;
+                const uint64_t n_tiles = band_n_tiles(bj.ja, bj.jb);
+                const uint64_t blocks = (uint64_t)cur.n_bblocks + n_tiles * r.n_ch;
+                if (n_tiles > UINT32_MAX || blocks > INT32_MAX)
+                    return plan_error<ExportPlan>(TH_ERR_UNSUPPORTED, "request %zu: too many filter tiles in one piece", i);
+                bj.n_tiles = (uint32_t)n_tiles;
+                bj.first_block = cur.n_bblocks;
+                cur.n_bblocks = (uint32_t)blocks;
+                place.scratch_at = cur.scratch_floats;
+                place.ptr_at = p.n_ptrs;
+                p.n_ptrs += r.n_ch;
+                cur.scratch_floats += s.stride * r.n_ch;
+                cur.band_sr = r.sr_in;
+                cur.band = r.band;
+                p.bjobs.push_back(bj);
+            }
             cur.n_chunks = (uint32_t)chunks;
             p.jobs.push_back(j);
             p.places.push_back(place);
@@ -150,7 +176,8 @@ ExportPlan plan_export(const ExportPlanRequest *reqs, size_t n) {
         p.scratch_need = std::max(p.scratch_need, p.pieces[k].scratch_floats);
     }
     p.o_rjobs = p.jobs.size() * sizeof(ExportJob);
-    p.o_ptrs = p.o_rjobs + p.rjobs.size() * sizeof(ResampleJob);
+    p.o_bjobs = p.o_rjobs + p.rjobs.size() * sizeof(ResampleJob);
+    p.o_ptrs = p.o_bjobs + p.bjobs.size() * sizeof(BandJob);
     p.tab_bytes = p.o_ptrs + p.n_ptrs * sizeof(const float *);
     return p;
 }
@@ -163,26 +190,33 @@ std::vector<unsigned char> bind_export(ExportPlan &p, const ExportBases &b, cons
         chan += p.req_ch[i];
     }
     for (size_t k = 0; k < p.pieces.size(); k++) {
-        size_t rj = p.pieces[k].rjob0;
+        size_t rj = p.pieces[k].rjob0, bj = p.pieces[k].bjob0;
         for (size_t j = p.pieces[k].job0; j < p.pieces[k].job1; j++) {
             const ExportPlace &pl = p.places[j];
             p.jobs[j].chan = d_ptrs + p.ptr0[pl.req];
             p.jobs[j].dst = b.stage[k & 1] + pl.stage_at;
             p.jobs[j].cnt = b.cnt + 2 * pl.req;
-            if (!pl.resampled) continue;
+            if (!pl.resampled && !pl.filtered) continue;
             float *run = b.scratch + pl.scratch_at;
             for (uint32_t c = 0; c < p.jobs[j].n_ch; c++)
                 ptrs[pl.ptr_at + c] = reinterpret_cast<const float *>(reinterpret_cast<uintptr_t>(run + (size_t)c * pl.stride) -
                                                                       (uintptr_t)pl.hull0 * sizeof(float));
             p.jobs[j].chan = d_ptrs + pl.ptr_at;
-            p.rjobs[rj].chan = d_ptrs + p.ptr0[pl.req];
-            p.rjobs[rj].dst = run;
-            rj++;
+            if (pl.resampled) {
+                p.rjobs[rj].chan = d_ptrs + p.ptr0[pl.req];
+                p.rjobs[rj].dst = run;
+                rj++;
+            } else {
+                p.bjobs[bj].chan = d_ptrs + p.ptr0[pl.req];
+                p.bjobs[bj].dst = run;
+                bj++;
+            }
         }
     }
     std::vector<unsigned char> tab(p.tab_bytes);
     put(tab, 0, p.jobs);
     put(tab, p.o_rjobs, p.rjobs);
+    put(tab, p.o_bjobs, p.bjobs);
     put(tab, p.o_ptrs, ptrs);
     return tab;
 }

@@ -133,9 +133,38 @@ inline uint64_t resample_n_sb(uint64_t ja, uint64_t jb, const ResampleTiling &t)
     return (jb - ja + per - 1) / per;
 }
 
-// ---- the export reader's plan (th_tm_export_pcm / _wav / _at).  The requests are cut into PIECES of at most TH_EXPORT_PIECE_BYTES
+// ---- kernels_band.hip: one FIR row for every output (the band filter of th_tm_export_pcm_band; the summation is resample_core.h).
+// A workgroup takes ONE channel and a tile of BAND_TILE consecutive outputs, a thread BAND_R consecutive ones of them; the 2K taps are
+// walked in blocks of BAND_TAP_BLOCK, and per block the tile's input span (tile + block - 1 samples) is staged once
+constexpr uint32_t BAND_THREADS = 256;
+constexpr uint32_t BAND_R = 8;                         // consecutive outputs of one thread (4 partial sums each)
+constexpr uint32_t BAND_TILE = BAND_THREADS * BAND_R;  // outputs of one workgroup
+constexpr uint32_t BAND_TAP_BLOCK = 64;                // taps per step (a multiple of 4)
+struct BandTiling {
+    uint32_t taps;       // 2K
+    uint32_t tile, R;    // outputs of a workgroup and of a thread
+    uint32_t tap_block;
+};
+static_assert(sizeof(BandTiling) == 16, "BandTiling must have no implicit padding");
+inline BandTiling band_tiling(const th_band_plan &p) { return BandTiling{2 * p.half_taps, BAND_TILE, BAND_R, BAND_TAP_BLOCK}; }
+struct BandJob {               // outputs [ja, jb) of every channel of one request
+    const float *const *chan;  // n_ch channel pointers (device memory), each of n_in samples
+    float *dst;                // output ja of channel 0; channel c's run starts ch_stride floats further per channel
+    uint64_t ja, jb;           // ja <= jb <= n_in
+    uint64_t n_in;
+    uint64_t ch_stride;
+    uint32_t n_ch;
+    uint32_t n_tiles;          // tiles of BAND_TILE outputs that [ja, jb) takes, counted from ja
+    uint32_t first_block;      // blocks [first_block, first_block of the next job) of the grid are this job's: n_ch x n_tiles
+    uint32_t pad;
+};
+static_assert(sizeof(BandJob) == 64, "BandJob must have no implicit padding");
+inline uint64_t band_n_tiles(uint64_t ja, uint64_t jb) { return (jb - ja + BAND_TILE - 1) / BAND_TILE; }
+
+// ---- the export reader's plan (th_tm_export_pcm / _wav / _at / _band).  The requests are cut into PIECES of at most TH_EXPORT_PIECE_BYTES
 // staged bytes, at frame boundaries; a piece is one launch of the export kernel into one of two staging buffers (piece p: buffer
-// p & 1), in front of it one launch of the resampler for the piece's resampled jobs, and one copy per RUN of contiguous output bytes.
+// p & 1), in front of it one launch of the resampler for the piece's resampled jobs and one of the band filter for its filtered ones
+// (both write the piece's planar scratch), and one copy per RUN of contiguous output bytes.
 // A job's bytes sit in staging at the same address modulo 16 as in the caller's image, so a run is one copy.
 constexpr size_t EXPORT_STAGE_MAX = (size_t)TH_EXPORT_PIECE_BYTES + 64;  // a staging buffer: a piece and its alignment slack
 // the planar scratch of a piece: frames x channels x 4 bytes, and per job up to 7 frames more (the hull on the grid of 4 frames and
@@ -148,6 +177,7 @@ struct ExportPlanRequest {     // what the check found of one request (export_re
     uint64_t n_in;             // samples of a channel of the track
     th_resample_plan plan;     // resampled requests: the rate pair's plan and the track's length at sr_out
     uint64_t n_out;
+    th_band_plan band;         // filtered requests (half_taps != 0; never resampled as well): the filter; all zero: none
     uint32_t format, dither, seed;
     uint64_t s0, s1;           // frames [s0, s1) at sr_out
     uint64_t offset;           // of frame s0's first byte in the caller's buffer
@@ -156,12 +186,13 @@ struct ExportPlanRequest {     // what the check found of one request (export_re
 struct ExportPlace {           // where one export job lives
     size_t req;
     size_t stage_at;           // byte offset in the piece's staging buffer
-    // resampled jobs: the job's channel runs in the scratch (float offset; channel c's starts c stride further), its own channel
+    // resampled and filtered jobs: the job's channel runs in the scratch (float offset; channel c's starts c stride further), its own channel
     // pointers in the pointer table, and the hull on the grid of 4 frames that the resampler makes: [hull0, hull0 + stride) holds
     // the job's frames and the 16-byte loads around them
     size_t scratch_at, ptr_at;
     uint64_t hull0, stride;
     bool resampled;
+    bool filtered = false;
 };
 struct ExportRun {             // one copy: bytes from staging offset stage_at to the caller's out + out_at
     size_t stage_at;
@@ -178,20 +209,29 @@ struct ExportPiece {
     uint32_t n_rblocks = 0, sr_in = 0, sr_out = 0;
     size_t scratch_floats = 0;
     th_resample_plan plan{};
+    // the band filter's launch, also in front of the export's: every filtered request of a piece has the piece's filter
+    size_t bjob0 = 0, bjob1 = 0;
+    uint32_t n_bblocks = 0, band_sr = 0;
+    th_band_plan band{};
 };
+inline bool same_band(const th_band_plan &a, const th_band_plan &b) {
+    return a.half_taps == b.half_taps && a.mode == b.mode && a.f_lo_hz == b.f_lo_hz && a.f_hi_hz == b.f_hi_hz;
+}
 struct ExportPlan {
     int err = TH_OK;              // (nothing else below is valid then)
     std::string err_text;
     std::vector<ExportJob> jobs;  // pointer fields unset until bind_export
     std::vector<ResampleJob> rjobs;
-    std::vector<ExportPlace> places;  // places[j]: of jobs[j]; the resampled ones among a piece's jobs are its rjobs, in order
+    std::vector<BandJob> bjobs;
+    // places[j]: of jobs[j]; the resampled ones among a piece's jobs are its rjobs, the filtered ones its bjobs, in order
+    std::vector<ExportPlace> places;
     std::vector<ExportPiece> pieces;
     // the pointer table: request i's n_ch channel pointers at ptr0[i], a resampled job's at its ptr_at
     std::vector<size_t> ptr0;
     std::vector<uint32_t> req_ch;  // request i's channel count
     size_t n_ptrs = 0;
-    // the uploaded table: jobs, then rjobs at o_rjobs, then the pointer table at o_ptrs
-    size_t o_rjobs = 0, o_ptrs = 0, tab_bytes = 0;
+    // the uploaded table: jobs, then rjobs at o_rjobs, bjobs at o_bjobs, then the pointer table at o_ptrs
+    size_t o_rjobs = 0, o_bjobs = 0, o_ptrs = 0, tab_bytes = 0;
     size_t stage_need[2] = {0, 0}, scratch_need = 0;  // the largest piece of either parity (bytes), the largest scratch (floats)
 };
 ExportPlan plan_export(const ExportPlanRequest *reqs, size_t n);
@@ -202,7 +242,7 @@ struct ExportBases {
     unsigned long long *cnt;   // two counters per request
 };
 // Fills the pointer fields of p's jobs and returns the table to upload.  chan: every request's n_ch channel pointers, in request
-// order.  A resampled export job reads channel c at (its run in the scratch) - hull0: the export kernel indexes a channel by the
+// order.  A resampled or filtered export job reads channel c at (its run in the scratch) - hull0: the export kernel indexes a channel by the
 // absolute output frame, and run and hull both start on 16-byte boundaries, so the biased pointer is 16-byte aligned as well
 std::vector<unsigned char> bind_export(ExportPlan &p, const ExportBases &b, const float *const *chan);
 

@@ -92,6 +92,12 @@ struct ReaderSlot {
     th::DeviceBuf<float> rs_scratch, rs_table;
     size_t rs_scratch_cap = 0, rs_table_cap = 0;  // floats
     uint32_t rs_sr_in = 0, rs_sr_out = 0;         // the pair rs_table holds (0: none)
+    // th_tm_export_pcm_band: the row of the last filter served (at most TH_BAND_MAX_TAPS floats); the scratch is the resampler's.
+    // Empty until the slot first filters
+    th::DeviceBuf<float> band_table;
+    size_t band_table_cap = 0;  // floats
+    uint32_t band_sr = 0;       // the rate and the plan band_table holds (0: none)
+    th_band_plan band{};
     // th_tm_render_figures: two staging buffers (each at most TH_FIGURE_PIECE_BYTES), the horizontal pass's intermediate of one piece
     // (u16; at most TH_FIGURE_TMP_BYTES unless one output row alone needs more) and the call's table (tap tables, then the job tables).
     // The copy stream and its events are the export's.  Empty until the slot's first figure
@@ -2474,7 +2480,7 @@ TH_API int th_tm_copy_audio(th_tm *tm, size_t id, uint32_t ch, int which, float 
 // staging sit at the same address modulo 16 as in the caller's image, so a run is one copy.
 namespace {
 // the check of one request; *info: the track, the resampler of a request that leaves the track's rate, the sample range at info->sr
-int check_export_request(th_tm *tm, const th_export_at_request &ar, size_t i, tmi::ExportInfo *info) {
+int check_export_request(th_tm *tm, const tmi::ExportReq &ar, size_t i, tmi::ExportInfo *info) {
     const th_export_request &r = ar.base;
     auto it = tm->tracks.find(r.id);
     if (it == tm->tracks.end()) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", r.id);
@@ -2493,6 +2499,14 @@ int check_export_request(th_tm *tm, const th_export_at_request &ar, size_t i, tm
                         i, tr.sr, ar.sr_out, TH_RESAMPLE_MAX_TAPS, TH_RESAMPLE_MAX_COEFS);
         n = info->n_out;
         info->sr = ar.sr_out;
+    }
+    if (ar.has_band) {
+        const int rc = band_plan_for(tr.sr, ar.mode, ar.f_lo_hz, ar.f_hi_hz, ar.trans_hz, &info->band);
+        TH_REQUIRE(rc != 1, "request %zu: bad band (mode %u, [%g, %g] Hz, transition %g Hz) at %u Hz", i, ar.mode, ar.f_lo_hz, ar.f_hi_hz,
+                   ar.trans_hz, tr.sr);
+        if (rc != 0)
+            return fail(TH_ERR_UNSUPPORTED, "request %zu: a transition of %g Hz at %u Hz needs more than %u taps", i, ar.trans_hz, tr.sr,
+                        TH_BAND_MAX_TAPS);
     }
     size_t s0 = 0, s1 = 0;
     TH_REQUIRE(spectrum_frame_range(info->sr, 1, n, r.start_sec, r.end_sec, &s0, &s1), "request %zu: bad time range [%g, %g) s", i,
@@ -2544,6 +2558,21 @@ int ensure_resample_table(ReaderSlot &sl, uint32_t sr_in, uint32_t sr_out, const
     sl.rs_sr_out = sr_out;
     return TH_OK;
 }
+
+// the slot's filter row becomes that of (sr, band): built on the host (host_math.h band_row, the row th_band_coefs returns) into
+// *host, which must outlive the upload, and sent on the slot's stream
+int ensure_band_table(ReaderSlot &sl, uint32_t sr, const th_band_plan &band, std::vector<float> *host) {
+    if (sl.band_sr == sr && same_band(sl.band, band)) return TH_OK;
+    const size_t floats = 2 * (size_t)band.half_taps;
+    host->resize(floats);
+    band_row(sr, band, nullptr, host->data());
+    sl.band_sr = 0;
+    TH_CHECK(grow_export_buf(sl, sl.band_table, sl.band_table_cap, floats, floats, floats, nullptr));  // (exactly the row)
+    TH_HIP(hipMemcpyAsync(sl.band_table.get(), host->data(), floats * sizeof(float), hipMemcpyHostToDevice, sl.stream));
+    sl.band_sr = sr;
+    sl.band = band;
+    return TH_OK;
+}
 }  // namespace
 
 namespace th {
@@ -2559,18 +2588,12 @@ int wav_header_checked(uint32_t format, uint32_t sr, uint32_t n_ch, uint64_t n_f
     return TH_OK;
 }
 
-int export_request_info(th_tm *tm, const th_export_at_request &r, size_t i, ExportInfo *info) {
+int export_request_info(th_tm *tm, const ExportReq &r, size_t i, ExportInfo *info) {
     TH_CHECK(check_export_request(tm, r, i, info));
     info->n_channels = (uint32_t)static_cast<const Track *>(info->track)->ch.size();
     info->n_bytes = (uint64_t)(info->sample_end - info->sample_start) * info->n_channels * export_bytes_per_sample(r.base.format);
     info->waveform_revision = tm->waveform_revision();
     return TH_OK;
-}
-
-std::vector<th_export_at_request> export_at_requests(const th_export_request *reqs, size_t n) {
-    std::vector<th_export_at_request> out(n);
-    for (size_t i = 0; i < n; i++) out[i] = th_export_at_request{reqs[i], 0u};
-    return out;
 }
 
 void export_layout(ExportInfo *info, size_t n, size_t *out_len) {
@@ -2587,7 +2610,7 @@ void export_layout(ExportInfo *info, size_t n, size_t *out_len) {
 
 // plan_export (reader_plan.h) cuts the requests into pieces and bind_export gives the jobs their addresses; what is left here is the
 // slot, its buffers, the upload and the pipeline of the two streams
-int export_run(th_tm *tm, const th_export_at_request *reqs, size_t n, ExportInfo *info, uint8_t *out) {
+int export_run(th_tm *tm, const ExportReq *reqs, size_t n, ExportInfo *info, uint8_t *out) {
     std::vector<ExportPlanRequest> prs(n);
     std::vector<const float *> chan;
     for (size_t i = 0; i < n; i++) {
@@ -2600,6 +2623,7 @@ int export_run(th_tm *tm, const th_export_at_request *reqs, size_t n, ExportInfo
         pr.n_in = tr.ch[0].n;
         pr.plan = info[i].plan;
         pr.n_out = info[i].n_out;
+        pr.band = info[i].band;
         pr.format = r.format;
         pr.dither = r.dither;
         pr.seed = r.seed;
@@ -2627,13 +2651,13 @@ int export_run(th_tm *tm, const th_export_at_request *reqs, size_t n, ExportInfo
             TH_HIP(hipEventCreateWithFlags(&sl.exp_copied[b], hipEventDisableTiming));
         }
     }
-    std::vector<std::vector<float>> host_tables(pieces.size());  // (behind the drain: alive until the uploads are done)
+    std::vector<std::vector<float>> host_tables(pieces.size()), host_rows(pieces.size());  // (behind the drain: alive until the uploads are done)
     ExportDrain drain{&sl};
     for (int b = 0; b < 2; b++)  // powers of two from 1 MiB, never above one piece; the copy stream reads them too
         TH_CHECK(grow_export_buf(sl, sl.exp_stage[b], sl.exp_stage_cap[b], pl.stage_need[b], 1 << 20, EXPORT_STAGE_MAX, sl.exp_copy));
     // (floats) powers of two from 1 MiB, never above the bound
     TH_CHECK(grow_export_buf(sl, sl.rs_scratch, sl.rs_scratch_cap, pl.scratch_need, 1 << 18, RESAMPLE_SCRATCH_MAX / sizeof(float), nullptr));
-    // one table for the whole call: the export jobs of every piece, the resampler's jobs, then the channel pointers
+    // one table for the whole call: the export jobs of every piece, the resampler's jobs, the band filter's, then the channel pointers
     TH_CHECK(sl.exp_tab.ensure(pl.tab_bytes));
     TH_CHECK(sl.exp_cnt.ensure(n * 2 * sizeof(unsigned long long)));
     unsigned char *d_tab = static_cast<unsigned char *>(sl.exp_tab.dptr);
@@ -2644,11 +2668,16 @@ int export_run(th_tm *tm, const th_export_at_request *reqs, size_t n, ExportInfo
     TH_HIP(hipMemsetAsync(d_cnt, 0, n * 2 * sizeof(unsigned long long), sl.stream));
     const ExportJob *d_jobs = reinterpret_cast<const ExportJob *>(d_tab);
     const ResampleJob *d_rjobs = reinterpret_cast<const ResampleJob *>(d_tab + pl.o_rjobs);
+    const BandJob *d_bjobs = reinterpret_cast<const BandJob *>(d_tab + pl.o_bjobs);
     auto launch_piece = [&](size_t p) -> int {
         const ExportPiece &pc = pieces[p];
         if (pc.n_rblocks) {  // (the stream's order keeps the scratch and the table from the last piece's readers)
             TH_CHECK(ensure_resample_table(sl, pc.sr_in, pc.sr_out, pc.plan, &host_tables[p]));
             TH_HIP(launch_resample(d_rjobs + pc.rjob0, (uint32_t)(pc.rjob1 - pc.rjob0), pc.n_rblocks, sl.rs_table.get(), resample_tiling(pc.plan), sl.stream));
+        }
+        if (pc.n_bblocks) {
+            TH_CHECK(ensure_band_table(sl, pc.band_sr, pc.band, &host_rows[p]));
+            TH_HIP(launch_band(d_bjobs + pc.bjob0, (uint32_t)(pc.bjob1 - pc.bjob0), pc.n_bblocks, sl.band_table.get(), band_tiling(pc.band), sl.stream));
         }
         if (p >= 2) TH_HIP(hipStreamWaitEvent(sl.stream, sl.exp_copied[p & 1], 0));  // (the buffer's last piece has left it)
         TH_HIP(launch_export(d_jobs + pc.job0, (uint32_t)(pc.job1 - pc.job0), pc.n_chunks, sl.stream));
@@ -2677,7 +2706,7 @@ int export_run(th_tm *tm, const th_export_at_request *reqs, size_t n, ExportInfo
 }  // namespace th
 
 namespace {
-int export_pcm_at(th_tm *tm, const th_export_at_request *reqs, size_t n, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
+int export_pcm_any(th_tm *tm, const tmi::ExportReq *reqs, size_t n, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
     TH_REQUIRE(tm && out_len && (n == 0 || (reqs && info)), "NULL argument");
     *out_len = 0;
     if (n == 0) return TH_OK;
@@ -2694,7 +2723,7 @@ int export_pcm_at(th_tm *tm, const th_export_at_request *reqs, size_t n, uint8_t
     return TH_OK;
 }
 
-int export_wav_at(th_tm *tm, const th_export_at_request *req, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
+int export_wav_any(th_tm *tm, const tmi::ExportReq *req, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
     TH_REQUIRE(tm && req && out_len, "NULL argument");
     *out_len = 0;
     std::shared_lock<std::shared_mutex> rl(tm->rw);
@@ -2720,28 +2749,48 @@ TH_API int th_tm_export_pcm(th_tm *tm, const th_export_request *reqs, size_t n, 
                             size_t *out_len) {
     TH_TRY
     TH_REQUIRE(n == 0 || reqs, "NULL argument");
-    return export_pcm_at(tm, tmi::export_at_requests(reqs, n).data(), n, out, cap, info, out_len);
+    return export_pcm_any(tm, tmi::export_requests(reqs, n).data(), n, out, cap, info, out_len);
     TH_CATCH
 }
 
 TH_API int th_tm_export_wav(th_tm *tm, const th_export_request *req, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
     TH_TRY
     TH_REQUIRE(req, "NULL argument");
-    const th_export_at_request at{*req, 0u};
-    return export_wav_at(tm, &at, out, cap, info, out_len);
+    const tmi::ExportReq one = tmi::export_req(*req);
+    return export_wav_any(tm, &one, out, cap, info, out_len);
     TH_CATCH
 }
 
 TH_API int th_tm_export_pcm_at(th_tm *tm, const th_export_at_request *reqs, size_t n, uint8_t *out, size_t cap, th_export_info *info,
                                size_t *out_len) {
     TH_TRY
-    return export_pcm_at(tm, reqs, n, out, cap, info, out_len);
+    TH_REQUIRE(n == 0 || reqs, "NULL argument");
+    return export_pcm_any(tm, tmi::export_requests(reqs, n).data(), n, out, cap, info, out_len);
     TH_CATCH
 }
 
 TH_API int th_tm_export_wav_at(th_tm *tm, const th_export_at_request *req, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
     TH_TRY
-    return export_wav_at(tm, req, out, cap, info, out_len);
+    TH_REQUIRE(req, "NULL argument");
+    const tmi::ExportReq one = tmi::export_req(*req);
+    return export_wav_any(tm, &one, out, cap, info, out_len);
+    TH_CATCH
+}
+
+TH_API int th_tm_export_pcm_band(th_tm *tm, const th_export_band_request *reqs, size_t n, uint8_t *out, size_t cap, th_export_info *info,
+                                 size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(n == 0 || reqs, "NULL argument");
+    return export_pcm_any(tm, tmi::export_requests(reqs, n).data(), n, out, cap, info, out_len);
+    TH_CATCH
+}
+
+TH_API int th_tm_export_wav_band(th_tm *tm, const th_export_band_request *req, uint8_t *out, size_t cap, th_export_info *info,
+                                 size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(req, "NULL argument");
+    const tmi::ExportReq one = tmi::export_req(*req);
+    return export_wav_any(tm, &one, out, cap, info, out_len);
     TH_CATCH
 }
 

@@ -104,20 +104,38 @@ int tile_request_info(th_tm *tm, const th_tile_request &r, TileInfo *info);
 size_t tiles_layout(TileInfo *info, size_t n, size_t *offsets);
 int tiles_run(th_tm *tm, const th_tile_request *reqs, size_t n, const TileInfo *info, uint8_t *out);
 
-// Export.  Every request carries its output rate (th_export_at_request; sr_out 0: the track's own, which is all th_tm_export_pcm asks
-// for: export_at_requests); info->sr is the rate the request comes out at, and a request whose info->sr is not the track's is resampled.
+// Export.  Every request carries its output rate (sr_out 0: the track's own, which is all th_tm_export_pcm asks for) and its band
+// (none: th_tm_export_pcm and _at; never both a band and another rate): export_requests makes them of each entry's own request type.
+// info->sr is the rate the request comes out at, and a request whose info->sr is not the track's is resampled; one whose info->band has
+// taps is filtered.
 // export_layout: offsets that are multiples of 16, and in info[i].pad the zero bytes up to the next one (0 behind the last).
 // export_run: request i's bytes, then info[i].pad zero bytes, and its two counts into info[i]
-struct ExportInfo : th_export_info {  // + the track (a Track of track_manager.hip), its resampler, the zero bytes behind the request
+struct ExportReq {
+    th_export_request base;
+    uint32_t sr_out;  // 0 = the track's own
+    bool has_band;    // mode, f_lo_hz, f_hi_hz, trans_hz: those of th_export_band_request
+    uint32_t mode;
+    double f_lo_hz, f_hi_hz, trans_hz;
+};
+struct ExportInfo : th_export_info {  // + the track (a Track of track_manager.hip), its resampler, its filter, the zero bytes behind the request
     const void *track;
     th_resample_plan plan;  // of (the track's rate, sr) when they differ, and the track's length at sr
     size_t n_out;
+    th_band_plan band;      // half_taps == 0: no filter
     uint32_t pad;
 };
-int export_request_info(th_tm *tm, const th_export_at_request &r, size_t i, ExportInfo *info);
+int export_request_info(th_tm *tm, const ExportReq &r, size_t i, ExportInfo *info);
 void export_layout(ExportInfo *info, size_t n, size_t *out_len);
-int export_run(th_tm *tm, const th_export_at_request *reqs, size_t n, ExportInfo *info, uint8_t *out);
-std::vector<th_export_at_request> export_at_requests(const th_export_request *reqs, size_t n);
+int export_run(th_tm *tm, const ExportReq *reqs, size_t n, ExportInfo *info, uint8_t *out);
+inline ExportReq export_req(const th_export_request &r) { return ExportReq{r, 0u, false, 0u, 0.0, 0.0, 0.0}; }
+inline ExportReq export_req(const th_export_at_request &r) { return ExportReq{r.base, r.sr_out, false, 0u, 0.0, 0.0, 0.0}; }
+inline ExportReq export_req(const th_export_band_request &r) { return ExportReq{r.base, 0u, true, r.mode, r.f_lo_hz, r.f_hi_hz, r.trans_hz}; }
+template <class R>
+std::vector<ExportReq> export_requests(const R *reqs, size_t n) {
+    std::vector<ExportReq> out(n);
+    for (size_t i = 0; i < n; i++) out[i] = export_req(reqs[i]);
+    return out;
+}
 // th_wav_header with the status reported (host_math.h wav_header)
 int wav_header_checked(uint32_t format, uint32_t sr, uint32_t n_ch, uint64_t n_frames, uint8_t out[TH_WAV_HEADER_MAX], size_t *header_len,
                        size_t *pad_len);

@@ -611,7 +611,7 @@ TH_API int th_tmg_get_loudness_meter(th_tmg *g, size_t id, th_loudness_meter *me
 
 // Export: the same shape; a slot also writes the zero padding behind each of its requests, and its two counts come back into infos
 namespace {
-int export_on_slots(th_tmg *g, const Split &sp, const th_export_at_request *reqs, std::vector<tmi::ExportInfo> &infos, uint8_t *out) {
+int export_on_slots(th_tmg *g, const Split &sp, const tmi::ExportReq *reqs, std::vector<tmi::ExportInfo> &infos, uint8_t *out) {
     return run_on_owners(g, sp, [&](th_tm *tm, const std::vector<size_t> &idx) -> int {
         std::vector<tmi::ExportInfo> si = gather(infos.data(), idx);
         TH_CHECK(tmi::export_run(tm, gather(reqs, idx).data(), idx.size(), si.data(), out));
@@ -623,7 +623,7 @@ int export_on_slots(th_tmg *g, const Split &sp, const th_export_at_request *reqs
     });
 }
 
-int export_check_all(th_tmg *g, const th_export_at_request *reqs, size_t n, std::vector<tmi::ExportInfo> &infos, Split *sp) {
+int export_check_all(th_tmg *g, const tmi::ExportReq *reqs, size_t n, std::vector<tmi::ExportInfo> &infos, Split *sp) {
     TH_CHECK(check_and_split(g, n, [&](size_t i) { return reqs[i].base.id; },
                              [&](th_tm *tm, size_t i) { return tmi::export_request_info(tm, reqs[i], i, &infos[i]); }, sp));
     const uint64_t revision = revisions(g).first;
@@ -633,7 +633,7 @@ int export_check_all(th_tmg *g, const th_export_at_request *reqs, size_t n, std:
 }  // namespace
 
 namespace {
-int tmg_export_pcm_at(th_tmg *g, const th_export_at_request *reqs, size_t n, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
+int tmg_export_pcm_any(th_tmg *g, const tmi::ExportReq *reqs, size_t n, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
     TH_REQUIRE(g && out_len && (n == 0 || (reqs && info)), "NULL argument");
     *out_len = 0;
     if (n == 0) return TH_OK;
@@ -651,7 +651,7 @@ int tmg_export_pcm_at(th_tmg *g, const th_export_at_request *reqs, size_t n, uin
     return TH_OK;
 }
 
-int tmg_export_wav_at(th_tmg *g, const th_export_at_request *req, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
+int tmg_export_wav_any(th_tmg *g, const tmi::ExportReq *req, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
     TH_REQUIRE(g && req && out_len, "NULL argument");
     *out_len = 0;
     std::shared_lock<std::shared_mutex> rl(g->rw);
@@ -678,28 +678,48 @@ TH_API int th_tmg_export_pcm(th_tmg *g, const th_export_request *reqs, size_t n,
                              size_t *out_len) {
     TH_TRY
     TH_REQUIRE(n == 0 || reqs, "NULL argument");
-    return tmg_export_pcm_at(g, tmi::export_at_requests(reqs, n).data(), n, out, cap, info, out_len);
+    return tmg_export_pcm_any(g, tmi::export_requests(reqs, n).data(), n, out, cap, info, out_len);
     TH_CATCH
 }
 
 TH_API int th_tmg_export_wav(th_tmg *g, const th_export_request *req, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
     TH_TRY
     TH_REQUIRE(req, "NULL argument");
-    const th_export_at_request at{*req, 0u};
-    return tmg_export_wav_at(g, &at, out, cap, info, out_len);
+    const tmi::ExportReq one = tmi::export_req(*req);
+    return tmg_export_wav_any(g, &one, out, cap, info, out_len);
     TH_CATCH
 }
 
 TH_API int th_tmg_export_pcm_at(th_tmg *g, const th_export_at_request *reqs, size_t n, uint8_t *out, size_t cap, th_export_info *info,
                                 size_t *out_len) {
     TH_TRY
-    return tmg_export_pcm_at(g, reqs, n, out, cap, info, out_len);
+    TH_REQUIRE(n == 0 || reqs, "NULL argument");
+    return tmg_export_pcm_any(g, tmi::export_requests(reqs, n).data(), n, out, cap, info, out_len);
     TH_CATCH
 }
 
 TH_API int th_tmg_export_wav_at(th_tmg *g, const th_export_at_request *req, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
     TH_TRY
-    return tmg_export_wav_at(g, req, out, cap, info, out_len);
+    TH_REQUIRE(req, "NULL argument");
+    const tmi::ExportReq one = tmi::export_req(*req);
+    return tmg_export_wav_any(g, &one, out, cap, info, out_len);
+    TH_CATCH
+}
+
+TH_API int th_tmg_export_pcm_band(th_tmg *g, const th_export_band_request *reqs, size_t n, uint8_t *out, size_t cap, th_export_info *info,
+                                  size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(n == 0 || reqs, "NULL argument");
+    return tmg_export_pcm_any(g, tmi::export_requests(reqs, n).data(), n, out, cap, info, out_len);
+    TH_CATCH
+}
+
+TH_API int th_tmg_export_wav_band(th_tmg *g, const th_export_band_request *req, uint8_t *out, size_t cap, th_export_info *info,
+                                  size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(req, "NULL argument");
+    const tmi::ExportReq one = tmi::export_req(*req);
+    return tmg_export_wav_any(g, &one, out, cap, info, out_len);
     TH_CATCH
 }
 
