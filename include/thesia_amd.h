@@ -1042,6 +1042,118 @@ TH_API int th_tm_render_waveform_figures(th_tm *tm, const th_waveform_figure_req
 TH_API int th_tm_render_waveform_figure(th_tm *tm, const th_waveform_figure_request *req, uint8_t *out, size_t cap_bytes,
                                         th_waveform_figure_info *info);
 
+/* ---------------------------------------------------------------- Formant candidates of a time range (LPC on resident audio) */
+/* Per analysis frame of a channel's resident audio: an autocorrelation-LPC fit of the decimated, pre-emphasised, windowed frame, the
+ * roots of the prediction polynomial, and those roots as (frequency, bandwidth) pairs in ascending frequency: the candidates a
+ * formant overlay draws.  Which candidate is F1 .. F4 along time is a tracker's decision and is not made here.  No reference
+ * implementation exists; these definitions are the contract.  The parameters are Praat's ("To Formant (burg)": 2 x 5 formants up to
+ * 5500 Hz, a Gaussian window of 2 x 25 ms, pre-emphasis from 50 Hz); the fit is the autocorrelation method, not Burg's.
+ *   Request and plan.  th_formant_request: id, ch, which as th_tm_copy_audio; [start_sec, end_sec); sr_analysis (0 = the track's rate);
+ *   n_poles p, even, 2 .. TH_FORMANT_MAX_POLES; win_sec, step_sec; preemph_hz; window TH_FORMANT_WIN_*; kind TH_FORMANT_OUT_*.
+ *   th_formant_defaults fills the speech settings: sr_analysis 11000, p 10, win_sec 0.05, step_sec 0.0125, preemph_hz 50, Gaussian,
+ *   formants, the whole track.  th_formant_plan_for(sr, n_samples, req, &plan) (host) is the one place where numbers are made from
+ *   seconds, all in C double: sr_a = sr_analysis or sr; when sr_a != sr, th_resample_plan_for(sr, sr_a) must accept the pair (its
+ *   TH_ERR_UNSUPPORTED is this reader's; so is that of th_resample_n_out) and n_a = th_resample_n_out, else n_a = n_samples;
+ *   W = rint(win_sec sr_a), p + 2 <= W <= TH_FORMANT_MAX_WIN; H = max(1, rint(step_sec sr_a)), H <= TH_FORMANT_MAX_HOP;
+ *   alpha = exp(-2 pi preemph_hz / sr_a) (libm), and preemph_hz = +inf gives alpha = 0: no pre-emphasis.
+ *   Frames are ABSOLUTE: frame f has its centre at analysis sample c_f = f H, f = 0 .. ceil(n_a / H) - 1 (n_frames_total; 0 for an
+ *   empty track), its window covers analysis samples [b, b + W), b = c_f - floor(W / 2) (signed 64-bit), and the signal is zero
+ *   outside [0, n_a).  The time range selects frames [f0, f1): with [s0, s1) = th_audio_sample_range(sr_a, n_a, start_sec, end_sec),
+ *   f0 = ceil(s0 / H), f1 = ceil(s1 / H) in integers: the frames whose centre lies in [s0, s1).  A range is therefore a slice of the
+ *   whole-track analysis, and an empty range is valid.  TH_ERR_INVALID_ARG: a zero sr, anything NaN, a bad time range, an odd or
+ *   out-of-range p, W or H out of range (win_sec and step_sec must be finite and win_sec > 0, step_sec >= 0), a negative preemph_hz,
+ *   an unknown window, kind or which, a bad channel.
+ *   Analysis signal u: the channel itself when sr_a = sr, else exactly the resampler's output at sr_a, the bits of th_resample_f32
+ *   (f32).
+ *   Per frame, in f64, ONE rounded operation per written operation, no fma, no libm:
+ *   1. d[n] = (double)u[n] - alpha (double)u[n - 1] for 0 <= n < n_a, with u[-1] = +0, and d[n] = +0 outside [0, n_a) (the
+ *      pre-emphasised signal is what is zero outside the track: d[n_a] is 0, not -alpha u[n_a - 1]); s[k] = d[b + k] g[k], g the f64
+ *      table of th_formant_window: Gaussian
+ *      g[k] = (exp(-48 (k - (W - 1) / 2)^2 / (W + 1)^2) - e^-12) / (1 - e^-12) (libm, host-built), rectangular all ones.
+ *   2. Autocorrelation r[m], m = 0 .. p: partial sum q (0 .. 63) takes k = q, q + 64, ... in ascending k over k = 0 .. W - 1 - m, each
+ *      step acc = acc + (s[k] s[k + m]) from +0; then part[q] = part[q] + part[q + h] for q < h, h = 32, 16, 8, 4, 2, 1; r[m] = part[0].
+ *   3. The frame is INVALID if r[0] is not finite or r[0] <= 0.  Else r0' = r[0] (1 + 2^-30) (the product of r[0] and the double
+ *      1 + 2^-30): a white-noise loading that keeps a pure tone solvable.
+ *   4. Levinson-Durbin, literally: E = r0'; for i = 1 .. p: acc = r[i]; for j = 1 .. i - 1: acc = acc + a[j] r[i - j];
+ *      kappa = -acc / E (the negation of acc, divided); new a[j] = a[j] + kappa a[i - j] for j < i (from the old a), a[i] = kappa;
+ *      E = E (1 - kappa kappa); if !(E > 0) the frame is INVALID.
+ *   5. (kind TH_FORMANT_OUT_FORMANTS only) The roots of z^p + a1 z^(p-1) + .. + ap by Aberth-Ehrlich in Jacobi form: z_i starts at
+ *      0.9 (cos t_i, sin t_i), t_i = 2 pi (i + 1/4) / p (th_formant_start_points, libm, host-built); at most TH_FORMANT_MAX_SWEEPS = 64
+ *      sweeps; in a sweep, for every i from the OLD z: Horner P = (1, 0), D = (0, 0), for k = 1 .. p: D = D z + P, then P = P z + a[k];
+ *      q = P / D; sigma = sum over j != i in ascending j of 1 / (z_i - z_j), from (0, 0); w_i = q / (1 - q sigma); z_i = z_i - w_i.
+ *      Complex product (ar br - ai bi, ar bi + ai br); complex sum and difference by components; quotient u / v =
+ *      ((ur vr + ui vi) / n, (ui vr - ur vi) / n), n = vr vr + vi vi; 1 / v and 1 - v are that quotient and that difference with
+ *      (1, 0), nothing simplified; "+ a[k]" adds a[k] to the real part alone.  The sweeps stop after the one in which every w_r^2 + w_i^2 <= 2^-80 (a NaN never stops).  A frame that
+ *      has not stopped after 64 sweeps is INVALID and counted in n_unconverged.  The sweep count of a frame is the number run.
+ *   6. Host only, after the read-back, C double with libm: per root with imag > 0: f = atan2(im, re) sr_a / (2 pi),
+ *      bw = -log(re^2 + im^2) sr_a / (2 pi); keep 50 <= f <= sr_a / 2 - 50; sort by ascending f, ties by ascending bw; keep the first p / 2.
+ *   Output: doubles, requests back to back in request order, frames in order, 2 + p doubles per frame.  TH_FORMANT_OUT_FORMANTS:
+ *   (n_found, E / r0', f_1 .. f_(p/2), bw_1 .. bw_(p/2)), NaN in the unused slots.  TH_FORMANT_OUT_LPC: (r0', E, a_1 .. a_p): the LPC
+ *   envelope is E / |A(e^jw)|^2; step 5 is not run and n_unconverged is 0.  An invalid frame is all NaN.  info[i]: offset and length
+ *   in doubles, [frame_first, frame_end) = [f0, f1), sr_analysis, win = W, hop = H, n_invalid (every invalid frame, the unconverged
+ *   ones included), n_unconverged, waveform_revision.
+ *   A frame's doubles depend on the channel's audio, the plan and f alone: not on the range, the batch, the reader slot, the pieces,
+ *   the call, or th_tm against th_tmg.  th_formants_f64 (host, one channel, x = the whole channel at rate sr) runs the very
+ *   functions the kernel runs and gives the same bits; counts = {n_invalid, n_unconverged} (may be NULL).  th_formant_frame_f64: one
+ *   frame's raw fit: r (p + 1), a (p + 1, a[0] = 1), r0e = {r0', E}, roots (2 p: p real parts, then p imaginary parts), *sweeps,
+ *   *status (0 valid, 1 invalid at step 3 or 4, 2 unconverged); what the steps did not reach is zero; step 5 runs for either kind.
+ * th_tm_get_formants / th_tm_get_formant_track: a reader like th_tm_get_envelopes: shared lock, a reader slot's own stream; out ==
+ * NULL or a cap below *out_len: TH_ERR_BUFFER_TOO_SMALL with info (the two counts zero) and *out_len filled.  The first faulty request
+ * in request order decides: an unknown id: TH_ERR_NOT_FOUND; a bad argument: TH_ERR_INVALID_ARG; a refused rate pair:
+ * TH_ERR_UNSUPPORTED.  On any error nothing is written to out.
+ * Device memory is BOUNDED.  A call is cut into pieces of runs of frames, each run of one request, of at most
+ * TH_FORMANT_PIECE_FRAMES frames and at most TH_FORMANT_PIECE_SAMPLES analysis samples of resampled signal (a run's hull:
+ * (frames - 1) H + W + 1 samples; one frame always fits) and of one rate pair; a piece is one launch of the resampler for its resampled
+ * runs, one of the formant kernel (4 + 3 p doubles of raw record per frame, into one of two buffers) and one copy; step 6 and the
+ * packing of piece k run on the host while piece k + 1 computes.  A slot's scratch is made on first use and only grows. */
+#define TH_FORMANT_MAX_POLES 32u
+#define TH_FORMANT_MAX_WIN 4096u
+#define TH_FORMANT_MAX_HOP 65536u
+#define TH_FORMANT_MAX_SWEEPS 64u
+#define TH_FORMANT_PIECE_FRAMES 16384u
+#define TH_FORMANT_PIECE_SAMPLES (4u << 20)
+#define TH_FORMANT_WIN_GAUSS 0
+#define TH_FORMANT_WIN_RECT 1
+#define TH_FORMANT_OUT_FORMANTS 0
+#define TH_FORMANT_OUT_LPC 1
+typedef struct {
+    size_t id;
+    uint32_t ch;
+    uint32_t which;       /* 0 audio, 1 drawn, 2 original */
+    double start_sec, end_sec;
+    uint32_t sr_analysis; /* 0 = the track's rate */
+    uint32_t n_poles;     /* even, 2 .. TH_FORMANT_MAX_POLES */
+    double win_sec, step_sec, preemph_hz;
+    uint32_t window, kind; /* TH_FORMANT_WIN_*, TH_FORMANT_OUT_* */
+} th_formant_request;
+typedef struct {
+    uint32_t sr, sr_analysis;
+    uint32_t resampled;    /* 1: sr_analysis != sr, and rs is the pair's plan */
+    uint32_t n_poles, win, hop, window, kind;
+    th_resample_plan rs;
+    uint64_t n_analysis;   /* n_a */
+    uint64_t n_frames_total, frame_first, frame_end;
+    double alpha;
+} th_formant_plan;
+typedef struct {
+    uint64_t offset, length; /* into out, doubles; length = (frame_end - frame_first) (2 + n_poles) */
+    uint64_t frame_first, frame_end;
+    uint32_t sr_analysis, win, hop, reserved;
+    uint64_t n_invalid, n_unconverged;
+    uint64_t waveform_revision;
+} th_formant_info;
+TH_API int th_formant_defaults(th_formant_request *req);
+TH_API int th_formant_plan_for(uint32_t sr, size_t n_samples, const th_formant_request *req, th_formant_plan *plan);
+TH_API int th_formant_window(uint32_t window, uint32_t win, double *g /* win */);
+TH_API int th_formant_start_points(uint32_t n_poles, double *z /* 2 n_poles: real parts, then imaginary parts */);
+TH_API int th_formants_f64(const float *x, size_t n, uint32_t sr, const th_formant_request *req, uint64_t frame0, size_t n_frames,
+                           double *out /* n_frames (2 + n_poles) */, uint64_t *counts /* 2, or NULL */);
+TH_API int th_formant_frame_f64(const float *x, size_t n, uint32_t sr, const th_formant_request *req, uint64_t frame, double *r,
+                                double *a, double *r0e, double *roots, uint32_t *sweeps, uint32_t *status);
+TH_API int th_tm_get_formants(th_tm *tm, const th_formant_request *reqs, size_t n, double *out, size_t cap_doubles,
+                              th_formant_info *info /* n */, size_t *out_len);
+TH_API int th_tm_get_formant_track(th_tm *tm, const th_formant_request *req, double *out, size_t cap_doubles, th_formant_info *info);
+
 /* ---------------------------------------------------------------- TrackManager over several devices (one process) */
 /* th_tmg: the th_tm_* calls above, call for call, with a th_tmg * in place of the th_tm *; a multi-GPU host swaps one for
  * the other.  Every result — updated ids, max_sr, db state, revisions, specs, images, tile bytes, batch offsets, render
@@ -1153,6 +1265,11 @@ TH_API int th_tmg_render_waveform_figures(th_tmg *tmg, const th_waveform_figure_
                                           size_t cap_bytes, th_waveform_figure_info *info /* n */, size_t *out_len);
 TH_API int th_tmg_render_waveform_figure(th_tmg *tmg, const th_waveform_figure_request *req, uint8_t *out, size_t cap_bytes,
                                          th_waveform_figure_info *info);
+
+/* formant candidates: the same; a request's doubles and counts are those of one th_tm, bit for bit */
+TH_API int th_tmg_get_formants(th_tmg *tmg, const th_formant_request *reqs, size_t n, double *out, size_t cap_doubles,
+                               th_formant_info *info /* n */, size_t *out_len);
+TH_API int th_tmg_get_formant_track(th_tmg *tmg, const th_formant_request *req, double *out, size_t cap_doubles, th_formant_info *info);
 
 /* Test and measurement entry points (kernel selectors for A/B runs, per-launch kernel timing, replacing a resident image
  * with given pixels) are NOT part of this interface: include/thesia_amd_testing.h declares them; a thesia host binds none. */

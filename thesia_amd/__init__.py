@@ -12,7 +12,9 @@ from .api import (LINEAR, MEL, SPECTRUM_MAX, SPECTRUM_MEAN_AMP, SPECTRUM_MEAN_PO
                   resample_plan, resample_n_out, resample_coefs, resample_f32, resample_tile,
                   BAND_PASS, BAND_STOP, band_plan, band_coefs, band_response, band_f32,
                   FIGURE_RGBA, FIGURE_GREY16, figure_axis, figure_box,
-                  edges, envelope_edges, waveform_figure_span)
+                  edges, envelope_edges, waveform_figure_span,
+                  FORMANT_WIN_GAUSS, FORMANT_WIN_RECT, FORMANT_OUT_FORMANTS, FORMANT_OUT_LPC, formant_request, formant_plan, formant_window,
+                  formant_start_points, formants_f64, formant_frame_f64)
 
 __all__ = ["LINEAR", "MEL", "SPECTRUM_MEAN_AMP", "SPECTRUM_MEAN_POWER", "SPECTRUM_MAX", "Context", "ab_variants", "DeviceBuffer", "Graph", "MultiTrackManager", "Plan", "TileCache", "TrackManager", "ThError", "calc_framing_params",
            "calc_mel_fb", "calc_normalized_win", "device_count", "gated_loudness", "global_db_range", "hz_range_to_idx", "k_weighting",
@@ -22,4 +24,6 @@ __all__ = ["LINEAR", "MEL", "SPECTRUM_MEAN_AMP", "SPECTRUM_MEAN_POWER", "SPECTRU
            "BAND_PASS", "BAND_STOP", "band_plan", "band_coefs", "band_response", "band_f32",
            "FIGURE_RGBA", "FIGURE_GREY16", "figure_axis", "figure_box",
            "edges", "envelope_edges", "waveform_figure_span",
+           "FORMANT_WIN_GAUSS", "FORMANT_WIN_RECT", "FORMANT_OUT_FORMANTS", "FORMANT_OUT_LPC", "formant_request", "formant_plan", "formant_window",
+           "formant_start_points", "formants_f64", "formant_frame_f64",
            "ChanDesc", "ImgDesc", "RasterDesc", "WaveDesc", "TileGeom", "LIB_PATH"]

@@ -156,6 +156,28 @@ class EnvelopeInfo(C.Structure):  # th_envelope_info
                 ("waveform_revision", C.c_uint64)]
 
 
+class ResamplePlanC(C.Structure):  # th_resample_plan (as a member of th_formant_plan)
+    _fields_ = [("L", C.c_uint32), ("M", C.c_uint32), ("half_taps", C.c_uint32), ("rho", C.c_double), ("cutoff", C.c_double)]
+
+
+class FormantRequest(C.Structure):  # th_formant_request
+    _fields_ = [("id", C.c_size_t), ("ch", C.c_uint32), ("which", C.c_uint32), ("start_sec", C.c_double), ("end_sec", C.c_double),
+                ("sr_analysis", C.c_uint32), ("n_poles", C.c_uint32), ("win_sec", C.c_double), ("step_sec", C.c_double),
+                ("preemph_hz", C.c_double), ("window", C.c_uint32), ("kind", C.c_uint32)]
+
+
+class FormantPlan(C.Structure):  # th_formant_plan
+    _fields_ = [("sr", C.c_uint32), ("sr_analysis", C.c_uint32), ("resampled", C.c_uint32), ("n_poles", C.c_uint32), ("win", C.c_uint32),
+                ("hop", C.c_uint32), ("window", C.c_uint32), ("kind", C.c_uint32), ("rs", ResamplePlanC), ("n_analysis", C.c_uint64),
+                ("n_frames_total", C.c_uint64), ("frame_first", C.c_uint64), ("frame_end", C.c_uint64), ("alpha", C.c_double)]
+
+
+class FormantInfo(C.Structure):  # th_formant_info
+    _fields_ = [("offset", C.c_uint64), ("length", C.c_uint64), ("frame_first", C.c_uint64), ("frame_end", C.c_uint64),
+                ("sr_analysis", C.c_uint32), ("win", C.c_uint32), ("hop", C.c_uint32), ("reserved", C.c_uint32),
+                ("n_invalid", C.c_uint64), ("n_unconverged", C.c_uint64), ("waveform_revision", C.c_uint64)]
+
+
 class WaveformFigureRequest(C.Structure):  # th_waveform_figure_request
     _fields_ = [("env", EnvelopeRequest), ("out_h", C.c_uint32), ("amp_lo", C.c_float), ("amp_hi", C.c_float), ("thickness", C.c_uint32),
                 ("fill", C.c_uint8 * 4), ("background", C.c_uint8 * 4)]
@@ -402,6 +424,19 @@ _SIGS = {
     "th_tm_get_envelope": [vp, C.POINTER(EnvelopeRequest), c_f32p, C.c_size_t, C.POINTER(EnvelopeInfo)],
     "th_tmg_get_envelopes": [vp, C.POINTER(EnvelopeRequest), C.c_size_t, c_f32p, C.c_size_t, C.POINTER(EnvelopeInfo), c_szp],
     "th_tmg_get_envelope": [vp, C.POINTER(EnvelopeRequest), c_f32p, C.c_size_t, C.POINTER(EnvelopeInfo)],
+    "th_formant_defaults": [C.POINTER(FormantRequest)],
+    "th_formant_plan_for": [C.c_uint32, C.c_size_t, C.POINTER(FormantRequest), C.POINTER(FormantPlan)],
+    "th_formant_window": [C.c_uint32, C.c_uint32, C.POINTER(C.c_double)],
+    "th_formant_start_points": [C.c_uint32, C.POINTER(C.c_double)],
+    "th_formants_f64": [c_f32p, C.c_size_t, C.c_uint32, C.POINTER(FormantRequest), C.c_uint64, C.c_size_t, C.POINTER(C.c_double),
+                        C.POINTER(C.c_uint64)],
+    "th_formant_frame_f64": [c_f32p, C.c_size_t, C.c_uint32, C.POINTER(FormantRequest), C.c_uint64, C.POINTER(C.c_double),
+                             C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32),
+                             C.POINTER(C.c_uint32)],
+    "th_tm_get_formants": [vp, C.POINTER(FormantRequest), C.c_size_t, C.POINTER(C.c_double), C.c_size_t, C.POINTER(FormantInfo), c_szp],
+    "th_tm_get_formant_track": [vp, C.POINTER(FormantRequest), C.POINTER(C.c_double), C.c_size_t, C.POINTER(FormantInfo)],
+    "th_tmg_get_formants": [vp, C.POINTER(FormantRequest), C.c_size_t, C.POINTER(C.c_double), C.c_size_t, C.POINTER(FormantInfo), c_szp],
+    "th_tmg_get_formant_track": [vp, C.POINTER(FormantRequest), C.POINTER(C.c_double), C.c_size_t, C.POINTER(FormantInfo)],
     "th_tm_render_waveform_figures": [vp, C.POINTER(WaveformFigureRequest), C.c_size_t, C.c_void_p, C.c_size_t,
                                       C.POINTER(WaveformFigureInfo), c_szp],
     "th_tm_render_waveform_figure": [vp, C.POINTER(WaveformFigureRequest), C.c_void_p, C.c_size_t, C.POINTER(WaveformFigureInfo)],

@@ -744,6 +744,112 @@ class _EnvelopeMethods:
         return out[:info.bytes].reshape(out_h, out_w, 4), _export_info_dict(info)
 
 
+FORMANT_WIN_GAUSS, FORMANT_WIN_RECT = 0, 1
+FORMANT_OUT_FORMANTS, FORMANT_OUT_LPC = 0, 1
+c_f64p = C.POINTER(C.c_double)
+
+
+def formant_request(track_id: int = 0, ch: int = 0, which: int = 0, start_sec: float = 0.0, end_sec: float = float("inf"), **kw) -> "_ffi.FormantRequest":
+    """th_formant_defaults (the speech settings: sr_analysis 11000, n_poles 10, win_sec 0.05, step_sec 0.0125, preemph_hz 50, Gaussian
+    window, formants) with the given fields replaced; keywords are the fields of th_formant_request"""
+    r = _ffi.FormantRequest()
+    check(lib.th_formant_defaults(C.byref(r)))
+    r.id, r.ch, r.which, r.start_sec, r.end_sec = track_id, ch, which, start_sec, end_sec
+    for k, v in kw.items():
+        if k not in dict(r._fields_):
+            raise TypeError("th_formant_request has no field %r" % k)
+        setattr(r, k, v)
+    return r
+
+
+def _formant_request(r) -> "_ffi.FormantRequest":
+    """a FormantRequest (formant_request), or a dict of its keywords"""
+    return r if isinstance(r, _ffi.FormantRequest) else formant_request(**r)
+
+
+def formant_plan(sr: int, n_samples: int, req) -> dict:
+    """th_formant_plan_for -> the numbers of a request as a dict (host); rs: the resampler's (L, M, half_taps)"""
+    req, pl = _formant_request(req), _ffi.FormantPlan()
+    check(lib.th_formant_plan_for(sr, n_samples, C.byref(req), C.byref(pl)))
+    d = {k: getattr(pl, k) for k, _ in pl._fields_ if k != "rs"}
+    d["rs"] = (pl.rs.L, pl.rs.M, pl.rs.half_taps)
+    return d
+
+
+def formant_window(window: int, win: int) -> np.ndarray:
+    """th_formant_window -> float64[win] (host)"""
+    g = np.empty(max(int(win), 1), np.float64)
+    check(lib.th_formant_window(window, win, _ptr(g, c_f64p)))
+    return g
+
+
+def formant_start_points(n_poles: int) -> np.ndarray:
+    """th_formant_start_points -> complex128[n_poles] (host)"""
+    z = np.empty(2 * max(int(n_poles), 1), np.float64)
+    check(lib.th_formant_start_points(n_poles, _ptr(z, c_f64p)))
+    return z[:n_poles] + 1j * z[n_poles:]
+
+
+def formants_f64(x, sr: int, req, frame0: int = 0, n_frames: Optional[int] = None):
+    """th_formants_f64: frames [frame0, frame0 + n_frames) (default: to the track's last) of one channel on the host, through the
+    functions the kernel runs -> (float64 [n_frames, 2 + n_poles], (n_invalid, n_unconverged))"""
+    x, req = _f32(x).ravel(), _formant_request(req)
+    if n_frames is None:
+        n_frames = formant_plan(sr, x.size, req)["n_frames_total"] - frame0
+    out = np.empty((max(int(n_frames), 0), 2 + req.n_poles), np.float64)
+    cnt = (C.c_uint64 * 2)()
+    check(lib.th_formants_f64(_ptr(x, c_f32p), x.size, sr, C.byref(req), frame0, out.shape[0], _ptr(out, c_f64p), cnt))
+    return out, (int(cnt[0]), int(cnt[1]))
+
+
+def formant_frame_f64(x, sr: int, req, frame: int) -> dict:
+    """th_formant_frame_f64: one frame's raw fit on the host -> dict(r, a, r0_loaded, E, roots (complex128), sweeps, status)"""
+    x, req = _f32(x).ravel(), _formant_request(req)
+    p = max(int(req.n_poles), 1)
+    r, a, r0e, z = np.zeros(p + 1), np.zeros(p + 1), np.zeros(2), np.zeros(2 * p)
+    sw, st = C.c_uint32(), C.c_uint32()
+    check(lib.th_formant_frame_f64(_ptr(x, c_f32p), x.size, sr, C.byref(req), frame, _ptr(r, c_f64p), _ptr(a, c_f64p), _ptr(r0e, c_f64p),
+                                   _ptr(z, c_f64p), C.byref(sw), C.byref(st)))
+    return {"r": r, "a": a, "r0_loaded": r0e[0], "E": r0e[1], "roots": z[:p] + 1j * z[p:], "sweeps": sw.value, "status": st.value}
+
+
+class _FormantMethods:
+    """formant candidates (LPC fit, roots, (frequency, bandwidth) pairs) of a time range of resident audio (th_tm_* and th_tmg_*: _PFX)"""
+
+    def get_formants(self, requests, out: Optional[np.ndarray] = None):
+        """th_tm_get_formants: requests = iterable of formant_request(...) or dicts of its keywords -> (list of float64
+        [n_frames, 2 + n_poles] arrays, list of info dicts).  out: a float64 array to fill instead of a new one; the arrays are then
+        views into it."""
+        reqs = [_formant_request(r) for r in requests]
+        n = len(reqs)
+        if n == 0:
+            return [], []
+        arr = (_ffi.FormantRequest * n)(*reqs)
+        info = (_ffi.FormantInfo * n)()
+        need = C.c_size_t()
+        fn = getattr(lib, self._PFX + "get_formants")
+        if out is None:
+            rc = fn(self.handle, arr, n, None, 0, info, C.byref(need))
+            if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+                check(rc)
+            out = np.empty(max(need.value, 1), np.float64)
+        check(fn(self.handle, arr, n, _ptr(out, c_f64p), out.size, info, C.byref(need)))
+        return ([out[o.offset: o.offset + o.length].reshape(-1, 2 + r.n_poles) for o, r in zip(info, reqs)],
+                [_export_info_dict(o) for o in info])
+
+    def get_formant_track(self, track_id: int, ch: int, which: int = 0, start_sec: float = 0.0, end_sec: float = float("inf"), **kw):
+        """th_tm_get_formant_track -> (float64 [n_frames, 2 + n_poles], info dict) of one request (keywords: formant_request)"""
+        req = formant_request(track_id, ch, which, start_sec, end_sec, **kw)
+        info = _ffi.FormantInfo()
+        fn = getattr(lib, self._PFX + "get_formant_track")
+        rc = fn(self.handle, C.byref(req), None, 0, C.byref(info))
+        if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+            check(rc)
+        out = np.empty(max(info.length, 1), np.float64)
+        check(fn(self.handle, C.byref(req), _ptr(out, c_f64p), out.size, C.byref(info)))
+        return out[:info.length].reshape(-1, 2 + req.n_poles), _export_info_dict(info)
+
+
 def true_peak_filter(sr: int):
     """-> (factor, coef f64, phase, delay) of the kept taps of the true-peak interpolator at rate sr, ascending tap index (host)"""
     f, n = C.c_uint32(), C.c_uint32()
@@ -1257,7 +1363,7 @@ class TileCache:
                 "spectrogram_revision": sr.value, "hits": h.value, "misses": m.value}
 
 
-class TrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods, _ExportAtMethods, _ExportBandMethods, _FigureMethods, _EnvelopeMethods):
+class TrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods, _ExportAtMethods, _ExportBandMethods, _FigureMethods, _EnvelopeMethods, _FormantMethods):
     """th_tm: mirror of core/mod.rs TrackManager with HBM-resident audio / specs / images."""
     _PFX = "th_tm_"
 
@@ -1457,7 +1563,7 @@ class TrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _E
         return out[: n.value].tobytes()
 
 
-class MultiTrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods, _ExportAtMethods, _ExportBandMethods, _FigureMethods, _EnvelopeMethods):
+class MultiTrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods, _ExportAtMethods, _ExportBandMethods, _FigureMethods, _EnvelopeMethods, _FormantMethods):
     """th_tmg: the TrackManager over several devices of one process (duplicates allowed: [0, 0] is two slots on one card).
     Same method names as TrackManager; results are bit-identical to one TrackManager holding every track."""
     _PFX = "th_tmg_"

@@ -12,6 +12,7 @@
 #include "host_math.h"
 #include "stft_core.h"
 #include "envelope_plan.h"  // EnvJob, LaneSpanJob, LaneRasterJob, ENV_* (the chunk grid of kernels_envelope.hip)
+#include "formant_plan.h"  // FormantJob
 #include "figure_plan.h"  // FigHJob, FigVJob, FIG_* (the tile shape of kernels_figure.hip)
 #include "reader_plan.h"  // LoudJob, LoudTrackJob, TruePeakJob, ExportJob, ResampleJob, ResampleTiling and their constants
 #include "stft_plan.h"  // WavePostJob, MelJob, MEL_TILE_FRAMES, MEL_ROWS_*
@@ -301,5 +302,9 @@ hipError_t launch_envelope_reduce(const EnvJob *d_jobs, uint32_t n_jobs, uint32_
 hipError_t launch_envelope_columns(const EnvJob *d_jobs, uint32_t n_jobs, uint32_t n_cblocks, hipStream_t s);
 hipError_t launch_lane_spans(const LaneSpanJob *d_jobs, uint32_t n_jobs, uint32_t n_blocks, hipStream_t s);
 hipError_t launch_lane_raster(const LaneRasterJob *d_jobs, uint32_t n_jobs, uint32_t n_blocks, hipStream_t s);
+
+// ---- kernels_formant.hip: the raw LPC / root record of every frame of a piece (FormantJob: formant_plan.h).  n_blocks: the piece's
+// frames; max_W, max_p: the largest of its jobs (they size the launch's LDS)
+hipError_t launch_formants(const FormantJob *d_jobs, uint32_t n_jobs, uint32_t n_blocks, uint32_t max_W, uint32_t max_p, hipStream_t s);
 
 }  // namespace th

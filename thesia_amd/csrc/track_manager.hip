@@ -110,6 +110,13 @@ struct ReaderSlot {
     // piece (at most TH_ENVELOPE_PIECE_BYTES), its partial sums (at most TH_ENVELOPE_PART_BYTES unless one request needs more) and,
     // for the lanes, its spans; the lanes' staging buffers, copy stream and events are the figures'.  Empty until the first such call
     th::DeviceTable env_tab, env_out, env_part, lane_span;
+    // th_tm_get_formants: the call's table (windows, start points, jobs, the resampler's jobs, channel pointers) and the raw records
+    // of two pieces (each at most TH_FORMANT_PIECE_FRAMES x (4 + 3 p) doubles); the analysis signal of a resampled piece lies in the
+    // resampler's scratch (at most TH_FORMANT_PIECE_SAMPLES floats of it), the copy stream and its events are the export's.  Empty
+    // until the slot's first formant call
+    th::DeviceTable fm_tab;
+    th::DeviceBuf<double> fm_rec[2];
+    size_t fm_rec_cap[2] = {0, 0};  // doubles
 };
 constexpr size_t TILE_BYTES_MAX = 520 * 520 * 4;  // 512 core + 2 x 4 gutter (render_tiles.rs:15-16); >= 1024 * 12 waveform bins
 constexpr size_t MAX_READER_SLOTS = 16;
@@ -3159,6 +3166,126 @@ int waveform_figures_run(th_tm *tm, size_t n, const WaveformFigureInfo *info, ui
     TH_HIP(hipStreamSynchronize(sl.exp_copy));
     return TH_OK;
 }
+
+// ---------------------------------------------------------------------------------------------- formant candidates
+// th_tm_get_formants: a reader.  formant_plan_for checks a request and makes its numbers; plan_formants (formant_plan.h) cuts the call
+// into pieces of runs of frames and bind_formants gives the jobs their addresses; what is left here is the slot, its buffers, the
+// upload, and per piece the resampler's launch for the resampled runs (export's resample_kernel and the slot's table, unchanged),
+// the formant kernel's launch into record buffer p & 1, one copy on the slot's copy stream, and step 6 with the packing on the host
+// while the next piece computes.
+int formant_request_info(th_tm *tm, const th_formant_request &r, size_t i, FormantInfo *info) {
+    *info = FormantInfo{};
+    auto it = tm->tracks.find(r.id);
+    if (it == tm->tracks.end()) return fail(TH_ERR_NOT_FOUND, "request %zu: Track %zu does not exist", i, r.id);
+    TH_REQUIRE(r.ch < it->second.ch.size(), "request %zu: Track %zu has no channel %u", i, r.id, r.ch);
+    TH_REQUIRE(r.which <= 2, "request %zu: which must be 0 (audio), 1 (drawn) or 2 (original)", i);
+    const Channel &c = it->second.ch[r.ch];
+    const uint32_t sr = it->second.sr;
+    const int rc = formant_plan_for(sr, c.n, r, &info->plan.pl);
+    TH_REQUIRE(rc != 1,
+               "request %zu: bad formant request: [%g, %g) s at %u Hz, analysis at %u Hz, %u poles (even, 2 .. %u), window %g s (%u .. %u "
+               "samples), step %g s (at most %u samples), pre-emphasis from %g Hz, window %u, kind %u",
+               i, r.start_sec, r.end_sec, sr, r.sr_analysis, r.n_poles, TH_FORMANT_MAX_POLES, r.win_sec, r.n_poles + 2, TH_FORMANT_MAX_WIN,
+               r.step_sec, TH_FORMANT_MAX_HOP, r.preemph_hz, r.window, r.kind);
+    if (rc != 0)
+        return fail(TH_ERR_UNSUPPORTED, "request %zu: %u -> %u Hz is beyond the resampler's limits (%u taps, %u coefficients, 64-bit indices)",
+                    i, sr, r.sr_analysis, TH_RESAMPLE_MAX_TAPS, TH_RESAMPLE_MAX_COEFS);
+    const th_formant_plan &pl = info->plan.pl;
+    info->plan.src = r.which == 0 ? c.d_wav : r.which == 1 ? c.d_draw : c.d_orig;
+    info->plan.n_in = c.n;
+    info->frame_first = pl.frame_first;
+    info->frame_end = pl.frame_end;
+    info->length = (pl.frame_end - pl.frame_first) * (2 + pl.n_poles);
+    info->sr_analysis = pl.sr_analysis;
+    info->win = pl.win;
+    info->hop = pl.hop;
+    info->waveform_revision = tm->waveform_revision();
+    return TH_OK;
+}
+
+size_t formants_layout(FormantInfo *info, size_t n) {
+    uint64_t at = 0;
+    for (size_t i = 0; i < n; i++) {
+        info[i].offset = info[i].plan.offset = at;
+        at += info[i].length;
+    }
+    return (size_t)at;
+}
+
+int formants_run(th_tm *tm, size_t n, FormantInfo *info, double *out) {
+    std::vector<FormantPlanRequest> prs(n);
+    for (size_t i = 0; i < n; i++) {
+        prs[i] = info[i].plan;
+        info[i].n_invalid = info[i].n_unconverged = 0;
+    }
+    FormantPlan pl = plan_formants(prs.data(), n);
+    if (pl.err != TH_OK) return fail(pl.err, "%s", pl.err_text.c_str());
+    const std::vector<FormantPiece> &pieces = pl.pieces;
+    if (pieces.empty()) return TH_OK;
+
+    TH_HIP(hipSetDevice(tm->ctx->device));
+    SlotLease lease{tm, nullptr};
+    int rc = acquire_slot(tm, &lease.slot);
+    if (rc != TH_OK) return rc;
+    ReaderSlot &sl = *lease.slot;
+    if (!sl.exp_copy) {
+        TH_HIP(hipStreamCreateWithFlags(&sl.exp_copy, hipStreamNonBlocking));
+        for (int b = 0; b < 2; b++) {
+            TH_HIP(hipEventCreateWithFlags(&sl.exp_done[b], hipEventDisableTiming));
+            TH_HIP(hipEventCreateWithFlags(&sl.exp_copied[b], hipEventDisableTiming));
+        }
+    }
+    std::vector<std::vector<float>> host_tables(pieces.size());  // (behind the drain: alive until the uploads are done)
+    std::vector<double> host_rec[2];
+    ExportDrain drain{&sl};
+    const size_t rec_ceil = (size_t)TH_FORMANT_PIECE_FRAMES * formant_rec_doubles(TH_FORMANT_MAX_POLES);
+    for (int b = 0; b < 2; b++) {  // (doubles) powers of two from 64 Ki, never above one piece; the copy stream reads them too
+        if ((size_t)b < pieces.size()) TH_CHECK(grow_export_buf(sl, sl.fm_rec[b], sl.fm_rec_cap[b], (size_t)pl.rec_need, 1 << 16, rec_ceil, sl.exp_copy));
+        host_rec[b].resize((size_t)pl.rec_need);
+    }
+    if (pl.scratch_need)
+        TH_CHECK(grow_export_buf(sl, sl.rs_scratch, sl.rs_scratch_cap, (size_t)pl.scratch_need, 1 << 18, RESAMPLE_SCRATCH_MAX / sizeof(float), nullptr));
+    TH_CHECK(sl.fm_tab.ensure(pl.tab_bytes));
+    unsigned char *d_tab = static_cast<unsigned char *>(sl.fm_tab.dptr);
+    const std::vector<unsigned char> tab =
+        bind_formants(pl, FormantBases{{sl.fm_rec[0].get(), sl.fm_rec[1].get()}, sl.rs_scratch.get(), d_tab}, prs.data(), n);
+    TH_CHECK(sl.fm_tab.upload(sl.stream, tab.data(), tab.size()));
+    const FormantJob *d_jobs = reinterpret_cast<const FormantJob *>(d_tab + pl.o_jobs);
+    const ResampleJob *d_rjobs = reinterpret_cast<const ResampleJob *>(d_tab + pl.o_rjobs);
+    auto launch_piece = [&](size_t p) -> int {
+        const FormantPiece &pc = pieces[p];
+        if (pc.n_rblocks) {  // (the stream's order keeps the scratch and the table from the last piece's readers)
+            TH_CHECK(ensure_resample_table(sl, pc.sr_in, pc.sr_out, pc.rs, &host_tables[p]));
+            TH_HIP(launch_resample(d_rjobs + pc.rjob0, (uint32_t)(pc.rjob1 - pc.rjob0), pc.n_rblocks, sl.rs_table.get(), resample_tiling(pc.rs), sl.stream));
+        }
+        TH_HIP(launch_formants(d_jobs + pc.run0, (uint32_t)(pc.run1 - pc.run0), pc.n_blocks, pc.max_W, pc.max_p, sl.stream));
+        TH_HIP(hipEventRecord(sl.exp_done[p & 1], sl.stream));
+        return TH_OK;
+    };
+    TH_CHECK(launch_piece(0));
+    for (size_t p = 0; p < pieces.size(); p++) {
+        // (piece p + 1 goes into the other buffer; the copy of piece p - 1 out of it has been waited for below)
+        if (p + 1 < pieces.size()) TH_CHECK(launch_piece(p + 1));
+        const FormantPiece &pc = pieces[p];
+        double *h = host_rec[p & 1].data();
+        TH_HIP(hipStreamWaitEvent(sl.exp_copy, sl.exp_done[p & 1], 0));
+        TH_HIP(hipMemcpyAsync(h, sl.fm_rec[p & 1].get(), (size_t)pc.rec_doubles * sizeof(double), hipMemcpyDeviceToHost, sl.exp_copy));
+        TH_HIP(hipStreamSynchronize(sl.exp_copy));
+        for (size_t j = pc.run0; j < pc.run1; j++) {  // step 6 and the packing, while the next piece computes
+            const FormantRun &run = pl.runs[j];
+            FormantInfo &fi = info[run.req];
+            const th_formant_plan &fp = fi.plan.pl;
+            const uint32_t stride = formant_rec_doubles(fp.n_poles), per = 2 + fp.n_poles;
+            double *dst = out + fi.offset + (run.f0 - fp.frame_first) * per;
+            uint64_t cnt[2] = {0, 0};
+            for (uint32_t k = 0; k < run.n_frames; k++) formant_pack(h + run.rec_at + (uint64_t)k * stride, fp, dst + (uint64_t)k * per, cnt);
+            fi.n_invalid += cnt[0];
+            fi.n_unconverged += cnt[1];
+        }
+    }
+    TH_HIP(hipStreamSynchronize(sl.stream));
+    return TH_OK;
+}
 }  // namespace tmi
 }  // namespace th
 
@@ -3205,6 +3332,36 @@ TH_API int th_tm_get_envelope(th_tm *tm, const th_envelope_request *req, float *
     th_envelope_info one{};
     size_t len = 0;
     const int rc = th_tm_get_envelopes(tm, req, 1, out, cap, &one, &len);
+    if (info && (rc == TH_OK || rc == TH_ERR_BUFFER_TOO_SMALL)) *info = one;
+    return rc;
+    TH_CATCH
+}
+
+TH_API int th_tm_get_formants(th_tm *tm, const th_formant_request *reqs, size_t n, double *out, size_t cap, th_formant_info *info,
+                              size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(tm && out_len && (n == 0 || (reqs && info)), "NULL argument");
+    *out_len = 0;
+    if (n == 0) return TH_OK;
+    std::shared_lock<std::shared_mutex> rl(tm->rw);
+    std::vector<tmi::FormantInfo> infos(n);
+    for (size_t i = 0; i < n; i++) TH_CHECK(tmi::formant_request_info(tm, reqs[i], i, &infos[i]));
+    const size_t total = tmi::formants_layout(infos.data(), n);
+    for (size_t i = 0; i < n; i++) info[i] = infos[i];
+    *out_len = total;
+    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu doubles", total);
+    TH_CHECK(tmi::formants_run(tm, n, infos.data(), out));
+    for (size_t i = 0; i < n; i++) info[i] = infos[i];
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_tm_get_formant_track(th_tm *tm, const th_formant_request *req, double *out, size_t cap, th_formant_info *info) {
+    TH_TRY
+    TH_REQUIRE(tm && req, "NULL argument");
+    th_formant_info one{};
+    size_t len = 0;
+    const int rc = th_tm_get_formants(tm, req, 1, out, cap, &one, &len);
     if (info && (rc == TH_OK || rc == TH_ERR_BUFFER_TOO_SMALL)) *info = one;
     return rc;
     TH_CATCH

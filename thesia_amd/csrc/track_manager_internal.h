@@ -11,6 +11,7 @@
 #include "common.h"
 #include "envelope_plan.h"
 #include "figure_plan.h"
+#include "formant_plan.h"
 #include "host_math.h"
 
 namespace th {
@@ -168,6 +169,16 @@ struct WaveformFigureInfo : th_waveform_figure_info {
 int waveform_figure_request_info(th_tm *tm, const th_waveform_figure_request &r, size_t i, WaveformFigureInfo *info);
 size_t waveform_figures_layout(WaveformFigureInfo *info, size_t n);
 int waveform_figures_run(th_tm *tm, size_t n, const WaveformFigureInfo *info, uint8_t *out);
+
+// Formant candidates.  *info: the frames, the record's length and the request's plan with its resident channel (its offset is the
+// layout's to set).  formants_layout: requests back to back, in doubles.  formants_run: request i's doubles to out + info[i].offset
+// and its two counts into info[i]
+struct FormantInfo : th_formant_info {
+    FormantPlanRequest plan;
+};
+int formant_request_info(th_tm *tm, const th_formant_request &r, size_t i, FormantInfo *info);
+size_t formants_layout(FormantInfo *info, size_t n);
+int formants_run(th_tm *tm, size_t n, FormantInfo *info, double *out);
 
 // update_spec_imgs against `global` (NULL: the manager's own tracks, as th_tm_* does), then the writer's final wait:
 // for the images only (apply_track_list_changes, set_dB_range) or for everything (set_setting, set_colormap)

@@ -907,6 +907,48 @@ TH_API int th_tmg_get_envelope(th_tmg *g, const th_envelope_request *req, float 
     TH_CATCH
 }
 
+// Formant candidates: the same shape; a slot's two counts come back into infos
+TH_API int th_tmg_get_formants(th_tmg *g, const th_formant_request *reqs, size_t n, double *out, size_t cap, th_formant_info *info,
+                               size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(g && out_len && (n == 0 || (reqs && info)), "NULL argument");
+    *out_len = 0;
+    if (n == 0) return TH_OK;
+    std::shared_lock<std::shared_mutex> rl(g->rw);
+    std::vector<tmi::FormantInfo> infos(n);
+    Split sp;
+    TH_CHECK(check_and_split(g, n, [&](size_t i) { return reqs[i].id; },
+                             [&](th_tm *tm, size_t i) { return tmi::formant_request_info(tm, reqs[i], i, &infos[i]); }, &sp));
+    const size_t total = tmi::formants_layout(infos.data(), n);
+    const uint64_t revision = revisions(g).first;
+    for (size_t i = 0; i < n; i++) {
+        infos[i].waveform_revision = revision;
+        info[i] = infos[i];
+    }
+    *out_len = total;
+    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu doubles", total);
+    TH_CHECK(run_on_owners(g, sp, [&](th_tm *tm, const std::vector<size_t> &idx) -> int {
+        std::vector<tmi::FormantInfo> sub = gather(infos.data(), idx);
+        TH_CHECK(tmi::formants_run(tm, idx.size(), sub.data(), out));
+        for (size_t j = 0; j < idx.size(); j++) infos[idx[j]] = sub[j];
+        return TH_OK;
+    }));
+    for (size_t i = 0; i < n; i++) info[i] = infos[i];
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_tmg_get_formant_track(th_tmg *g, const th_formant_request *req, double *out, size_t cap, th_formant_info *info) {
+    TH_TRY
+    TH_REQUIRE(g && req, "NULL argument");
+    th_formant_info one{};
+    size_t len = 0;
+    const int rc = th_tmg_get_formants(g, req, 1, out, cap, &one, &len);
+    if (info && (rc == TH_OK || rc == TH_ERR_BUFFER_TOO_SMALL)) *info = one;
+    return rc;
+    TH_CATCH
+}
+
 TH_API int th_tmg_render_waveform_figures(th_tmg *g, const th_waveform_figure_request *reqs, size_t n, uint8_t *out, size_t cap,
                                           th_waveform_figure_info *info, size_t *out_len) {
     TH_TRY
