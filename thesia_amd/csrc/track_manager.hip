@@ -220,6 +220,20 @@ struct th_tm {
 
 namespace {
 
+// th_tm as the manager of a batched reader (batched_reader.h): one owner.  The default colormap is uploaded before the shared lock
+// is taken (ensure_colormap takes the lock exclusively when it has to)
+struct TmReaders {
+    static constexpr bool single_owner = true;
+    th_tm *tm;
+    bool null() const { return !tm; }
+    int before_lock(bool colormap) const { return colormap ? tmi::ensure_colormap(tm) : TH_OK; }
+    std::shared_lock<std::shared_mutex> lock() const { return std::shared_lock<std::shared_mutex>(tm->rw); }
+    uint64_t revision(br::Revision which) const {
+        return which == br::Revision::waveform ? tm->waveform_revision() : tm->spectrogram_revision();
+    }
+    th_tm *owner() const { return tm; }
+};
+
 void free_mips(Channel &c) {
     c.d_mips.reset();
     c.mips_elems = 0;
@@ -1228,7 +1242,7 @@ int tile_request_info(th_tm *tm, const th_tile_request &r, TileInfo *info) {
     if (!c || !c->d_img) return fail(TH_ERR_NOT_FOUND, "Spectrogram %zu_%u does not exist", r.id, r.ch);
     TileInfo &it = *info;
     it = TileInfo{spectrogram_tile_geometry(c->img_w, c->img_h, r.level_x, r.level_y, r.tile_x, r.tile_y), c->d_img,
-                  (uint32_t)c->img_w, (uint32_t)c->img_h, (uint32_t)c->img_pitch, false, 0};
+                  (uint32_t)c->img_w, (uint32_t)c->img_h, (uint32_t)c->img_pitch, false, 0, r};
     if (r.level_x != 0 || r.level_y != 0) {
         auto im = c->mips.find({r.level_x, r.level_y});
         if (tm->lod_source != 0 || im == c->mips.end()) {
@@ -1254,7 +1268,7 @@ size_t tiles_layout(TileInfo *info, size_t n, size_t *offsets) {
     return offsets[n] = total;
 }
 
-int tiles_run(th_tm *tm, const th_tile_request *reqs, size_t n, const TileInfo *info, uint8_t *out) {
+int tiles_run(th_tm *tm, size_t n, const TileInfo *info, uint8_t *out) {
     TH_HIP(hipSetDevice(tm->ctx->device));
     const uint64_t revision = tm->spectrogram_revision();
     // where the kernel writes: the caller's buffer when the GPU can reach it, else the manager's pinned staging buffer
@@ -1324,8 +1338,8 @@ int tiles_run(th_tm *tm, const th_tile_request *reqs, size_t n, const TileInfo *
         bl.unlock();
     }
     for (size_t i = 0; i < n; i++) {
-        const th_tile_request &r = reqs[i];
         const TileInfo &it = info[i];
+        const th_tile_request &r = it.r;
         uint8_t *rec = out + it.offset;
         if (it.single) {
             size_t len = 0;
@@ -1358,7 +1372,7 @@ TH_API int th_tm_get_spectrogram_tiles(th_tm *tm, const th_tile_request *reqs, s
     const size_t total = tmi::tiles_layout(infos.data(), n, offsets);
     *out_len = total;
     if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
-    return tmi::tiles_run(tm, reqs, n, infos.data(), out);
+    return tmi::tiles_run(tm, n, infos.data(), out);
     TH_CATCH
 }
 
@@ -1384,11 +1398,16 @@ int spectrum_request_info(th_tm *tm, const th_spectrum_request &r, size_t i, Spe
         return fail(TH_ERR_UNSUPPORTED, "Spectrogram %zu_%u: %zu x %zu rows of pitch %zu", r.id, r.ch, c.T, c.H, c.spec_pitch);
     const SpectrumShape sh = spectrum_shape((uint32_t)c.H, (uint32_t)(f1 - f0));
     if ((uint64_t)sh.n_ctiles * sh.n_slices > INT32_MAX) return fail(TH_ERR_UNSUPPORTED, "Spectrogram %zu_%u: too many blocks", r.id, r.ch);
-    *info = SpectrumInfo{{0, c.H, f0, f1, 0}, c.d_spec, c.spec_pitch};
+    *info = SpectrumInfo{{0, c.H, f0, f1, 0}, r.kind, c.d_spec, c.spec_pitch};
     return TH_OK;
 }
 
-size_t spectra_layout(SpectrumInfo *info, size_t n) {
+int SpectrumReader::fit(const SpectrumInfo *, size_t n) {
+    TH_REQUIRE(n <= UINT32_MAX, "too many requests");
+    return TH_OK;
+}
+
+size_t SpectrumReader::layout(SpectrumInfo *info, size_t n) {
     size_t total = 0;
     for (size_t i = 0; i < n; i++) {
         info[i].offset = total;
@@ -1397,7 +1416,7 @@ size_t spectra_layout(SpectrumInfo *info, size_t n) {
     return total;
 }
 
-int spectra_run(th_tm *tm, const th_spectrum_request *reqs, size_t n, const SpectrumInfo *info, float *out) {
+int spectra_run(th_tm *tm, size_t n, SpectrumInfo *info, float *out) {
     TH_REQUIRE(n <= UINT32_MAX, "too many requests");
     std::vector<SpectrumJob> jobs(n);
     std::vector<size_t> part0(n), res0(n);  // job i in the slot's areas: its first partial, in doubles, and its first result, in floats
@@ -1411,7 +1430,7 @@ int spectra_run(th_tm *tm, const th_spectrum_request *reqs, size_t n, const Spec
         j.H = (uint32_t)info[i].height;
         j.f0 = (uint32_t)info[i].frame_start;
         j.f1 = (uint32_t)info[i].frame_end;
-        j.kind = reqs[i].kind;
+        j.kind = info[i].kind;
         j.log_ct = sh.log_ct;
         j.n_ctiles = sh.n_ctiles;
         j.n_slices = sh.n_slices;
@@ -1464,22 +1483,7 @@ int spectra_run(th_tm *tm, const th_spectrum_request *reqs, size_t n, const Spec
 TH_API int th_tm_get_spectra(th_tm *tm, const th_spectrum_request *reqs, size_t n, float *out, size_t cap, th_spectrum_info *info,
                              size_t *out_len) {
     TH_TRY
-    TH_REQUIRE(tm && out_len && (n == 0 || (reqs && info)), "NULL argument");
-    *out_len = 0;
-    if (n == 0) return TH_OK;
-    TH_REQUIRE(n <= UINT32_MAX, "too many requests");
-    std::shared_lock<std::shared_mutex> rl(tm->rw);
-    std::vector<tmi::SpectrumInfo> infos(n);
-    for (size_t i = 0; i < n; i++) TH_CHECK(tmi::spectrum_request_info(tm, reqs[i], i, &infos[i]));
-    const size_t total = tmi::spectra_layout(infos.data(), n);
-    const uint64_t revision = tm->spectrogram_revision();
-    for (size_t i = 0; i < n; i++) {
-        infos[i].spectrogram_revision = revision;
-        info[i] = infos[i];
-    }
-    *out_len = total;
-    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu floats", total);
-    return tmi::spectra_run(tm, reqs, n, infos.data(), out);
+    return br::batched_read<tmi::SpectrumReader>(TmReaders{tm}, reqs, n, out, cap, info, out_len);
     TH_CATCH
 }
 
@@ -1489,11 +1493,7 @@ TH_API int th_tm_get_spectrum(th_tm *tm, size_t id, uint32_t ch, int kind, doubl
     TH_REQUIRE(tm, "tm is NULL");
     TH_REQUIRE(kind >= 0, "unknown spectrum kind %d", kind);
     const th_spectrum_request r{id, ch, (uint32_t)kind, start_sec, end_sec};
-    th_spectrum_info one{};
-    size_t len = 0;
-    const int rc = th_tm_get_spectra(tm, &r, 1, out, cap, &one, &len);
-    if (info && (rc == TH_OK || rc == TH_ERR_BUFFER_TOO_SMALL)) *info = one;
-    return rc;
+    return br::single_read(info, [&](th_spectrum_info *one, size_t *len) { return th_tm_get_spectra(tm, &r, 1, out, cap, one, len); });
     TH_CATCH
 }
 
@@ -1586,13 +1586,6 @@ void meter_counts(const Track &tr, th_loudness_meter *m) {
     }
 }
 
-// the limits of one launch (its grid: reader_plan.h), as the entry point reports them before a short buffer
-int meters_fit_one_launch(const tmi::MeterInfo *ms, size_t n) {
-    size_t n_ch = 0;
-    for (size_t i = 0; i < n; i++) n_ch += ms[i].n_channels;
-    if (const char *text = meter_limits_text(n, n_ch)) return fail(TH_ERR_INVALID_ARG, "%s", text);
-    return TH_OK;
-}
 }  // namespace
 
 namespace th {
@@ -1601,12 +1594,21 @@ int loudness_meter_info(th_tm *tm, size_t id, MeterInfo *m) {
     auto it = tm->tracks.find(id);
     if (it == tm->tracks.end()) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", id);
     meter_counts(it->second, m);
+    m->id = id;
     m->track = &it->second;
     m->n_channels = it->second.ch.size();
     return TH_OK;
 }
 
-size_t meters_layout(MeterInfo *m, size_t n) {
+// as th_tm's entry point reports them before a short buffer
+int MeterReader::fit(const MeterInfo *ms, size_t n) {
+    size_t n_ch = 0;
+    for (size_t i = 0; i < n; i++) n_ch += ms[i].n_channels;
+    if (const char *text = meter_limits_text(n, n_ch)) return fail(TH_ERR_INVALID_ARG, "%s", text);
+    return TH_OK;
+}
+
+size_t MeterReader::layout(MeterInfo *m, size_t n) {
     size_t total = 0;
     for (size_t i = 0; i < n; i++) {
         m[i].momentary_offset = total;
@@ -1624,16 +1626,16 @@ size_t meters_layout(MeterInfo *m, size_t n) {
 // pinned staging when they fit) and meter_results turns them into LUFS, maxima and the loudness range.
 namespace th {
 namespace tmi {
-int meters_run(th_tm *tm, const size_t *ids, size_t n, MeterInfo *ms, double *series) {
-    TH_CHECK(meters_fit_one_launch(ms, n));  // (before n tracks are gathered)
+int meters_run(th_tm *tm, size_t n, MeterInfo *ms, double *series) {
+    TH_CHECK(MeterReader::fit(ms, n));  // (before n tracks are gathered)
     std::vector<MeterPlanTrack> trs(n);
     std::vector<const float *> wav;
     for (size_t i = 0; i < n; i++) {
         const Track &tr = *static_cast<const Track *>(ms[i].track);
         const uint64_t ns = tr.ch.empty() ? 0 : tr.ch[0].n;
-        trs[i] = MeterPlanTrack{ids[i], tr.sr, (uint32_t)tr.ch.size(), ms[i].oversampling, ns, ms[i].n_momentary, ms[i].n_short_term};
+        trs[i] = MeterPlanTrack{ms[i].id, tr.sr, (uint32_t)tr.ch.size(), ms[i].oversampling, ns, ms[i].n_momentary, ms[i].n_short_term};
         for (size_t k = 0; k < tr.ch.size(); k++) {
-            TH_REQUIRE(ns == 0 || tr.ch[k].d_wav, "track %zu channel %zu has no audio", ids[i], k);
+            TH_REQUIRE(ns == 0 || tr.ch[k].d_wav, "track %zu channel %zu has no audio", ms[i].id, k);
             wav.push_back(tr.ch[k].d_wav);
         }
     }
@@ -1682,25 +1684,8 @@ int meters_run(th_tm *tm, const size_t *ids, size_t n, MeterInfo *ms, double *se
 TH_API int th_tm_get_loudness_meters(th_tm *tm, const size_t *ids, size_t n, th_loudness_meter *meters, double *series, size_t cap,
                                      size_t *out_len) {
     TH_TRY
-    TH_REQUIRE(tm && meters && out_len && (n == 0 || ids), "NULL argument");
-    *out_len = 0;
-    if (n == 0) return TH_OK;
-    TH_REQUIRE(n <= 65535, "at most 65535 tracks per call");  // (before 65536 infos are made)
-    std::shared_lock<std::shared_mutex> rl(tm->rw);
-    std::vector<tmi::MeterInfo> ms(n);
-    for (size_t i = 0; i < n; i++) TH_CHECK(tmi::loudness_meter_info(tm, ids[i], &ms[i]));
-    TH_CHECK(meters_fit_one_launch(ms.data(), n));  // (reported before a short buffer)
-    const size_t total = tmi::meters_layout(ms.data(), n);
-    const uint64_t revision = tm->waveform_revision();
-    for (size_t i = 0; i < n; i++) {
-        ms[i].waveform_revision = revision;
-        meters[i] = ms[i];
-    }
-    *out_len = total;
-    if (series && cap < total) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu doubles", total);
-    TH_CHECK(tmi::meters_run(tm, ids, n, ms.data(), series));
-    for (size_t i = 0; i < n; i++) meters[i] = ms[i];
-    return TH_OK;
+    TH_REQUIRE(meters, "NULL argument");  // (also for n == 0)
+    return br::batched_read<tmi::MeterReader>(TmReaders{tm}, ids, n, series, cap, meters, out_len);
     TH_CATCH
 }
 
@@ -2599,11 +2584,11 @@ int export_request_info(th_tm *tm, const ExportReq &r, size_t i, ExportInfo *inf
     TH_CHECK(check_export_request(tm, r, i, info));
     info->n_channels = (uint32_t)static_cast<const Track *>(info->track)->ch.size();
     info->n_bytes = (uint64_t)(info->sample_end - info->sample_start) * info->n_channels * export_bytes_per_sample(r.base.format);
-    info->waveform_revision = tm->waveform_revision();
+    info->req = r.base;
     return TH_OK;
 }
 
-void export_layout(ExportInfo *info, size_t n, size_t *out_len) {
+size_t ExportReader::layout(ExportInfo *info, size_t n) {
     uint64_t at = 0;
     for (size_t i = 0; i < n; i++) {
         info[i].offset = at;
@@ -2612,16 +2597,16 @@ void export_layout(ExportInfo *info, size_t n, size_t *out_len) {
         info[i].pad = i + 1 < n ? (uint32_t)(at - end) : 0u;
         if (i + 1 == n) at = end;
     }
-    *out_len = (size_t)at;
+    return (size_t)at;
 }
 
 // plan_export (reader_plan.h) cuts the requests into pieces and bind_export gives the jobs their addresses; what is left here is the
 // slot, its buffers, the upload and the pipeline of the two streams
-int export_run(th_tm *tm, const ExportReq *reqs, size_t n, ExportInfo *info, uint8_t *out) {
+int export_run(th_tm *tm, size_t n, ExportInfo *info, uint8_t *out) {
     std::vector<ExportPlanRequest> prs(n);
     std::vector<const float *> chan;
     for (size_t i = 0; i < n; i++) {
-        const th_export_request &r = reqs[i].base;
+        const th_export_request &r = info[i].req;
         const Track &tr = *static_cast<const Track *>(info[i].track);
         ExportPlanRequest &pr = prs[i];
         pr.n_ch = info[i].n_channels;
@@ -2714,20 +2699,7 @@ int export_run(th_tm *tm, const ExportReq *reqs, size_t n, ExportInfo *info, uin
 
 namespace {
 int export_pcm_any(th_tm *tm, const tmi::ExportReq *reqs, size_t n, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
-    TH_REQUIRE(tm && out_len && (n == 0 || (reqs && info)), "NULL argument");
-    *out_len = 0;
-    if (n == 0) return TH_OK;
-    std::shared_lock<std::shared_mutex> rl(tm->rw);
-    std::vector<tmi::ExportInfo> infos(n);
-    for (size_t i = 0; i < n; i++) TH_CHECK(tmi::export_request_info(tm, reqs[i], i, &infos[i]));
-    size_t total = 0;
-    tmi::export_layout(infos.data(), n, &total);
-    for (size_t i = 0; i < n; i++) info[i] = infos[i];
-    *out_len = total;
-    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
-    TH_CHECK(tmi::export_run(tm, reqs, n, infos.data(), out));
-    for (size_t i = 0; i < n; i++) info[i] = infos[i];
-    return TH_OK;
+    return br::batched_read<tmi::ExportReader>(TmReaders{tm}, reqs, n, out, cap, info, out_len);
 }
 
 int export_wav_any(th_tm *tm, const tmi::ExportReq *req, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
@@ -2736,6 +2708,7 @@ int export_wav_any(th_tm *tm, const tmi::ExportReq *req, uint8_t *out, size_t ca
     std::shared_lock<std::shared_mutex> rl(tm->rw);
     tmi::ExportInfo one{};
     TH_CHECK(tmi::export_request_info(tm, *req, 0, &one));
+    one.waveform_revision = tm->waveform_revision();
     uint8_t hdr[TH_WAV_HEADER_MAX];
     size_t hl = 0, pl = 0;
     TH_CHECK(tmi::wav_header_checked(req->base.format, one.sr, one.n_channels, one.sample_end - one.sample_start, hdr, &hl, &pl));
@@ -2744,7 +2717,7 @@ int export_wav_any(th_tm *tm, const tmi::ExportReq *req, uint8_t *out, size_t ca
     if (info) *info = one;
     *out_len = total;
     if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
-    TH_CHECK(tmi::export_run(tm, req, 1, &one, out));
+    TH_CHECK(tmi::export_run(tm, 1, &one, out));
     std::memcpy(out, hdr, hl);
     if (pl) out[hl + one.n_bytes] = 0;
     if (info) *info = one;
@@ -2822,21 +2795,10 @@ int figure_request_info(th_tm *tm, const th_figure_request &r, size_t i, FigureI
     info->bytes = (uint64_t)r.out_w * r.out_h * figure_bytes_per_pixel(r.kind);
     info->out_w = r.out_w;
     info->out_h = r.out_h;
-    info->spectrogram_revision = tm->spectrogram_revision();
     return TH_OK;
 }
 
-size_t figures_layout(FigureInfo *info, size_t n) {
-    uint64_t at = 0, end = 0;
-    for (size_t i = 0; i < n; i++) {
-        info[i].offset = info[i].plan.offset = at;
-        end = at + info[i].bytes;
-        at = (end + 63) & ~(uint64_t)63;
-    }
-    return (size_t)end;
-}
-
-int figures_run(th_tm *tm, size_t n, const FigureInfo *info, uint8_t *out) {
+int figures_run(th_tm *tm, size_t n, FigureInfo *info, uint8_t *out) {
     std::vector<FigurePlanRequest> prs(n);
     for (size_t i = 0; i < n; i++) prs[i] = info[i].plan;
     FigurePlan pl = plan_figures(prs.data(), n);
@@ -2959,29 +2921,14 @@ TH_API int th_tm_figure_box(th_tm *tm, size_t id, uint32_t ch, double start_sec,
 TH_API int th_tm_render_figures(th_tm *tm, const th_figure_request *reqs, size_t n, uint8_t *out, size_t cap, th_figure_info *info,
                                 size_t *out_len) {
     TH_TRY
-    TH_REQUIRE(tm && out_len && (n == 0 || (reqs && info)), "NULL argument");
-    *out_len = 0;
-    if (n == 0) return TH_OK;
-    TH_CHECK(tmi::ensure_colormap(tm));  // (takes the lock exclusively when it has to upload the default map)
-    std::shared_lock<std::shared_mutex> rl(tm->rw);
-    std::vector<tmi::FigureInfo> infos(n);
-    for (size_t i = 0; i < n; i++) TH_CHECK(tmi::figure_request_info(tm, reqs[i], i, &infos[i]));
-    const size_t total = tmi::figures_layout(infos.data(), n);
-    for (size_t i = 0; i < n; i++) info[i] = infos[i];
-    *out_len = total;
-    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
-    return tmi::figures_run(tm, n, infos.data(), out);
+    return br::batched_read<tmi::FigureReader>(TmReaders{tm}, reqs, n, out, cap, info, out_len);
     TH_CATCH
 }
 
 TH_API int th_tm_render_figure(th_tm *tm, const th_figure_request *req, uint8_t *out, size_t cap, th_figure_info *info) {
     TH_TRY
     TH_REQUIRE(tm && req, "NULL argument");
-    th_figure_info one{};
-    size_t len = 0;
-    const int rc = th_tm_render_figures(tm, req, 1, out, cap, &one, &len);
-    if (info && (rc == TH_OK || rc == TH_ERR_BUFFER_TOO_SMALL)) *info = one;
-    return rc;
+    return br::single_read(info, [&](th_figure_info *one, size_t *len) { return th_tm_render_figures(tm, req, 1, out, cap, one, len); });
     TH_CATCH
 }
 
@@ -3013,20 +2960,10 @@ int envelope_request_info(th_tm *tm, const th_envelope_request &r, size_t i, Env
     const EnvelopeStatus st = check_envelope(info->plan, i, &info->sample_start, &info->sample_end);
     if (st.err != TH_OK) return fail(st.err, "%s", st.err_text.c_str());
     info->length = (uint64_t)r.n_cols * 4;
-    info->waveform_revision = tm->waveform_revision();
     return TH_OK;
 }
 
-size_t envelopes_layout(EnvelopeInfo *info, size_t n) {
-    uint64_t at = 0;
-    for (size_t i = 0; i < n; i++) {
-        info[i].offset = info[i].plan.offset = at;
-        at += info[i].length;
-    }
-    return (size_t)at;
-}
-
-int envelopes_run(th_tm *tm, size_t n, const EnvelopeInfo *info, float *out) {
+int envelopes_run(th_tm *tm, size_t n, EnvelopeInfo *info, float *out) {
     std::vector<EnvelopePlanRequest> prs(n);
     for (size_t i = 0; i < n; i++) prs[i] = info[i].plan;
     EnvelopePlan pl = plan_envelopes(prs.data(), n);
@@ -3085,21 +3022,10 @@ int waveform_figure_request_info(th_tm *tm, const th_waveform_figure_request &r,
     info->bytes = (uint64_t)r.env.n_cols * r.out_h * 4;
     info->out_w = r.env.n_cols;
     info->out_h = r.out_h;
-    info->waveform_revision = tm->waveform_revision();
     return TH_OK;
 }
 
-size_t waveform_figures_layout(WaveformFigureInfo *info, size_t n) {
-    uint64_t at = 0, end = 0;
-    for (size_t i = 0; i < n; i++) {
-        info[i].offset = info[i].plan.offset = at;
-        end = at + info[i].bytes;
-        at = (end + 63) & ~(uint64_t)63;
-    }
-    return (size_t)end;
-}
-
-int waveform_figures_run(th_tm *tm, size_t n, const WaveformFigureInfo *info, uint8_t *out) {
+int waveform_figures_run(th_tm *tm, size_t n, WaveformFigureInfo *info, uint8_t *out) {
     std::vector<LanePlanRequest> prs(n);
     for (size_t i = 0; i < n; i++) prs[i] = info[i].plan;
     LanePlan pl = plan_lanes(prs.data(), n);
@@ -3199,17 +3125,7 @@ int formant_request_info(th_tm *tm, const th_formant_request &r, size_t i, Forma
     info->sr_analysis = pl.sr_analysis;
     info->win = pl.win;
     info->hop = pl.hop;
-    info->waveform_revision = tm->waveform_revision();
     return TH_OK;
-}
-
-size_t formants_layout(FormantInfo *info, size_t n) {
-    uint64_t at = 0;
-    for (size_t i = 0; i < n; i++) {
-        info[i].offset = info[i].plan.offset = at;
-        at += info[i].length;
-    }
-    return (size_t)at;
 }
 
 int formants_run(th_tm *tm, size_t n, FormantInfo *info, double *out) {
@@ -3312,75 +3228,35 @@ TH_API int th_waveform_figure_span(const float *col, const float *left, uint32_t
 TH_API int th_tm_get_envelopes(th_tm *tm, const th_envelope_request *reqs, size_t n, float *out, size_t cap, th_envelope_info *info,
                                size_t *out_len) {
     TH_TRY
-    TH_REQUIRE(tm && out_len && (n == 0 || (reqs && info)), "NULL argument");
-    *out_len = 0;
-    if (n == 0) return TH_OK;
-    std::shared_lock<std::shared_mutex> rl(tm->rw);
-    std::vector<tmi::EnvelopeInfo> infos(n);
-    for (size_t i = 0; i < n; i++) TH_CHECK(tmi::envelope_request_info(tm, reqs[i], i, &infos[i]));
-    const size_t total = tmi::envelopes_layout(infos.data(), n);
-    for (size_t i = 0; i < n; i++) info[i] = infos[i];
-    *out_len = total;
-    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu floats", total);
-    return tmi::envelopes_run(tm, n, infos.data(), out);
+    return br::batched_read<tmi::EnvelopeReader>(TmReaders{tm}, reqs, n, out, cap, info, out_len);
     TH_CATCH
 }
 
 TH_API int th_tm_get_envelope(th_tm *tm, const th_envelope_request *req, float *out, size_t cap, th_envelope_info *info) {
     TH_TRY
     TH_REQUIRE(tm && req, "NULL argument");
-    th_envelope_info one{};
-    size_t len = 0;
-    const int rc = th_tm_get_envelopes(tm, req, 1, out, cap, &one, &len);
-    if (info && (rc == TH_OK || rc == TH_ERR_BUFFER_TOO_SMALL)) *info = one;
-    return rc;
+    return br::single_read(info, [&](th_envelope_info *one, size_t *len) { return th_tm_get_envelopes(tm, req, 1, out, cap, one, len); });
     TH_CATCH
 }
 
 TH_API int th_tm_get_formants(th_tm *tm, const th_formant_request *reqs, size_t n, double *out, size_t cap, th_formant_info *info,
                               size_t *out_len) {
     TH_TRY
-    TH_REQUIRE(tm && out_len && (n == 0 || (reqs && info)), "NULL argument");
-    *out_len = 0;
-    if (n == 0) return TH_OK;
-    std::shared_lock<std::shared_mutex> rl(tm->rw);
-    std::vector<tmi::FormantInfo> infos(n);
-    for (size_t i = 0; i < n; i++) TH_CHECK(tmi::formant_request_info(tm, reqs[i], i, &infos[i]));
-    const size_t total = tmi::formants_layout(infos.data(), n);
-    for (size_t i = 0; i < n; i++) info[i] = infos[i];
-    *out_len = total;
-    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu doubles", total);
-    TH_CHECK(tmi::formants_run(tm, n, infos.data(), out));
-    for (size_t i = 0; i < n; i++) info[i] = infos[i];
-    return TH_OK;
+    return br::batched_read<tmi::FormantReader>(TmReaders{tm}, reqs, n, out, cap, info, out_len);
     TH_CATCH
 }
 
 TH_API int th_tm_get_formant_track(th_tm *tm, const th_formant_request *req, double *out, size_t cap, th_formant_info *info) {
     TH_TRY
     TH_REQUIRE(tm && req, "NULL argument");
-    th_formant_info one{};
-    size_t len = 0;
-    const int rc = th_tm_get_formants(tm, req, 1, out, cap, &one, &len);
-    if (info && (rc == TH_OK || rc == TH_ERR_BUFFER_TOO_SMALL)) *info = one;
-    return rc;
+    return br::single_read(info, [&](th_formant_info *one, size_t *len) { return th_tm_get_formants(tm, req, 1, out, cap, one, len); });
     TH_CATCH
 }
 
 TH_API int th_tm_render_waveform_figures(th_tm *tm, const th_waveform_figure_request *reqs, size_t n, uint8_t *out, size_t cap,
                                          th_waveform_figure_info *info, size_t *out_len) {
     TH_TRY
-    TH_REQUIRE(tm && out_len && (n == 0 || (reqs && info)), "NULL argument");
-    *out_len = 0;
-    if (n == 0) return TH_OK;
-    std::shared_lock<std::shared_mutex> rl(tm->rw);
-    std::vector<tmi::WaveformFigureInfo> infos(n);
-    for (size_t i = 0; i < n; i++) TH_CHECK(tmi::waveform_figure_request_info(tm, reqs[i], i, &infos[i]));
-    const size_t total = tmi::waveform_figures_layout(infos.data(), n);
-    for (size_t i = 0; i < n; i++) info[i] = infos[i];
-    *out_len = total;
-    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
-    return tmi::waveform_figures_run(tm, n, infos.data(), out);
+    return br::batched_read<tmi::WaveformFigureReader>(TmReaders{tm}, reqs, n, out, cap, info, out_len);
     TH_CATCH
 }
 
@@ -3388,10 +3264,7 @@ TH_API int th_tm_render_waveform_figure(th_tm *tm, const th_waveform_figure_requ
                                         th_waveform_figure_info *info) {
     TH_TRY
     TH_REQUIRE(tm && req, "NULL argument");
-    th_waveform_figure_info one{};
-    size_t len = 0;
-    const int rc = th_tm_render_waveform_figures(tm, req, 1, out, cap, &one, &len);
-    if (info && (rc == TH_OK || rc == TH_ERR_BUFFER_TOO_SMALL)) *info = one;
-    return rc;
+    return br::single_read(info,
+                           [&](th_waveform_figure_info *one, size_t *len) { return th_tm_render_waveform_figures(tm, req, 1, out, cap, one, len); });
     TH_CATCH
 }

@@ -8,6 +8,7 @@
 #include <shared_mutex>
 #include <vector>
 
+#include "batched_reader.h"
 #include "common.h"
 #include "envelope_plan.h"
 #include "figure_plan.h"
@@ -54,42 +55,75 @@ int prepare_dynamics(th_tm *tm, int kind, float target, int mode, StagedPtr *out
 void get_common_dynamics(th_tm *tm, int *kind, float *target, int *mode);
 void commit(th_tm *tm, StagedPtr staged);
 
-// The batched readers (spectra, loudness meters, spectrogram tiles, export) in three steps each, so that th_tm's entry point and
-// th_tmg's are the same lines: check every request in request order, lay the output out, publish the infos and the length, report
-// a short buffer, run.  th_tmg checks each request against its owning slot and hands every slot its subset for the run.
+// The batched readers (spectra, loudness meters, export, figures, envelopes, waveform figures, formants): each is a traits struct,
+// beside its Info, that batched_reader.h's br::batched_read drives over either manager: NULL arguments, n == 0, the shared lock, every
+// request checked in request order, the layout, the manager's revision stamped, the infos and the length published, a short buffer
+// reported, the run, the infos published again where the run updates them.  th_tm is one owner: every request is checked against it
+// and the run gets the caller's arrays as they are.  th_tmg checks each request against its owning slot and hands every slot its
+// subset for the run.  The spectrogram tiles (an offsets array instead of infos) and the WAV entries (a header in front of one
+// request) have entry points of their own that use the same pieces.
 //   Locks: none of these takes rw; the caller holds rw_of(tm) shared around each call (ensure_colormap is the exception).
-//   *_info: the check of ONE request, with the codes and in the order the th_tm entry reports them (i: the request's index in the
+//   check (*_request_info): ONE request, with the codes and in the order the th_tm entry reports them (i: the request's index in the
 //     caller's batch, for the message).  *info then holds everything that is known without the GPU, with its offset(s) 0, and what
-//     the run needs of the manager for this request, so that the run looks nothing up again (valid until a writer gets in: th_tm
+//     the run needs of the request and of the manager, so that the run looks nothing up again (valid until a writer gets in: th_tm
 //     holds rw from the check to the run, th_tmg its own rw, which every writer of its slots takes first).  The revision is the
-//     entry point's to stamp, its own manager's (export_request_info stamps the slot's, which th_tmg overwrites).
-//   *_layout: the offset of every info, in request order; returns the length of the whole output.
-//   *_run: the device work for n requests that were checked and laid out.  It takes a reader slot, packs its own n results in the
-//     slot's areas and writes request i's to out + info[i].offset and nowhere else: the destinations ascend with i and need not be
+//     driver's to stamp, its own manager's.
+//   layout: the offset of every info, in request order; returns the length of the whole output.
+//   run (*_run): the device work for n requests that were checked and laid out.  It takes a reader slot, packs its own n results in
+//     the slot's areas and writes request i's to out + info[i].offset and nowhere else: the destinations ascend with i and need not be
 //     adjacent (the caller may hold a subset of a larger batch), so whatever lies between them is left alone.  The limits of one
 //     launch are checked here (for the meters and the export: by their planners, reader_plan.h, which the run calls).
-struct SpectrumInfo : th_spectrum_info {  // + the channel's resident rows
+using br::Revision;
+struct SpectrumInfo : th_spectrum_info {  // + the request's kind and the channel's resident rows
+    uint32_t kind;
     const float *rows;
     size_t pitch;
 };
 int spectrum_request_info(th_tm *tm, const th_spectrum_request &r, size_t i, SpectrumInfo *info);
-size_t spectra_layout(SpectrumInfo *info, size_t n);
-int spectra_run(th_tm *tm, const th_spectrum_request *reqs, size_t n, const SpectrumInfo *info, float *out);
+int spectra_run(th_tm *tm, size_t n, SpectrumInfo *info, float *out);
+struct SpectrumReader : br::ReaderDefaults {
+    using Request = th_spectrum_request;
+    using Info = SpectrumInfo;
+    using Public = th_spectrum_info;
+    using Out = float;
+    static constexpr const char *unit = "floats";
+    static constexpr Revision revision = Revision::spectrogram;
+    static constexpr bool needs_colormap = false, run_updates_infos = false;
+    static size_t id_of(const Request &r) { return r.id; }
+    static int check(th_tm *tm, const Request &r, size_t i, Info *info) { return spectrum_request_info(tm, r, i, info); }
+    static int fit(const Info *, size_t n);  // one launch's job count
+    static size_t layout(Info *info, size_t n);
+    static int run(th_tm *tm, size_t n, Info *info, Out *out) { return spectra_run(tm, n, info, out); }
+};
 
 // *m: the oversampling and the two counts, everything else zero.  meters_run fills meters[i] in place (it keeps the oversampling,
-// the counts, the offsets and the revision as the caller set them) and, with series, writes track i's LUFS to
-// series + meters[i].momentary_offset (the short-term values follow the momentary ones, as meters_layout places them)
-struct MeterInfo : th_loudness_meter {  // + the track (a Track of track_manager.hip) and its channel count
+// the counts, the offsets and the revision as the driver set them) and, with series, writes track i's LUFS to
+// series + meters[i].momentary_offset (the short-term values follow the momentary ones, as the layout places them)
+struct MeterInfo : th_loudness_meter {  // + the track's id, the track (a Track of track_manager.hip) and its channel count
+    size_t id;
     const void *track;
     size_t n_channels;
 };
 int loudness_meter_info(th_tm *tm, size_t id, MeterInfo *m);
-size_t meters_layout(MeterInfo *m, size_t n);
-int meters_run(th_tm *tm, const size_t *ids, size_t n, MeterInfo *meters, double *series);
+int meters_run(th_tm *tm, size_t n, MeterInfo *meters, double *series);
+struct MeterReader : br::ReaderDefaults {
+    using Request = size_t;
+    using Info = MeterInfo;
+    using Public = th_loudness_meter;
+    using Out = double;
+    static constexpr const char *unit = "doubles";
+    static constexpr Revision revision = Revision::waveform;
+    static constexpr bool needs_colormap = false, run_updates_infos = true, out_optional = true;
+    static size_t id_of(const Request &id) { return id; }
+    static int check(th_tm *tm, const Request &id, size_t, Info *m) { return loudness_meter_info(tm, id, m); }
+    static int fit(const Info *m, size_t n);  // the limits of one launch (its grid: reader_plan.h)
+    static size_t layout(Info *m, size_t n);
+    static int run(th_tm *tm, size_t n, Info *m, Out *series) { return meters_run(tm, n, m, series); }
+};
 
-// Spectrogram tiles: what the run needs of one request (the crop box, the image or mip level it is cut from; single: no such level
-// is held, the request goes through the single-tile path) and where its record starts.  Records are 40-byte header + RGBA, padded
-// to 64 bytes (tile_record_bytes); tiles_layout also writes the n + 1 offsets the ABI returns.  tiles_run writes headers and
+// Spectrogram tiles: what the run needs of one request (the request, the crop box, the image or mip level it is cut from; single: no
+// such level is held, the request goes through the single-tile path) and where its record starts.  Records are 40-byte header + RGBA,
+// padded to 64 bytes (tile_record_bytes); tiles_layout also writes the n + 1 offsets the ABI returns.  tiles_run writes headers and
 // pixels, never the padding.  It needs the device colormap: ensure_colormap uploads the default one if none was set, taking the
 // WRITE lock for that, so callers invoke it before they take the shared lock
 struct TileInfo {
@@ -98,18 +132,19 @@ struct TileInfo {
     uint32_t src_w, src_h, src_pitch;
     bool single;
     size_t offset;
+    th_tile_request r;
 };
 inline size_t tile_record_bytes(const TileGeom &g) { return (40 + g.width * g.height * 4 + 63) / 64 * 64; }
 int ensure_colormap(th_tm *tm);
 int tile_request_info(th_tm *tm, const th_tile_request &r, TileInfo *info);
 size_t tiles_layout(TileInfo *info, size_t n, size_t *offsets);
-int tiles_run(th_tm *tm, const th_tile_request *reqs, size_t n, const TileInfo *info, uint8_t *out);
+int tiles_run(th_tm *tm, size_t n, const TileInfo *info, uint8_t *out);
 
 // Export.  Every request carries its output rate (sr_out 0: the track's own, which is all th_tm_export_pcm asks for) and its band
 // (none: th_tm_export_pcm and _at; never both a band and another rate): export_requests makes them of each entry's own request type.
 // info->sr is the rate the request comes out at, and a request whose info->sr is not the track's is resampled; one whose info->band has
 // taps is filtered.
-// export_layout: offsets that are multiples of 16, and in info[i].pad the zero bytes up to the next one (0 behind the last).
+// layout: offsets that are multiples of 16, and in info[i].pad the zero bytes up to the next one (0 behind the last).
 // export_run: request i's bytes, then info[i].pad zero bytes, and its two counts into info[i]
 struct ExportReq {
     th_export_request base;
@@ -118,7 +153,8 @@ struct ExportReq {
     uint32_t mode;
     double f_lo_hz, f_hi_hz, trans_hz;
 };
-struct ExportInfo : th_export_info {  // + the track (a Track of track_manager.hip), its resampler, its filter, the zero bytes behind the request
+struct ExportInfo : th_export_info {  // + the request, the track (a Track of track_manager.hip), its resampler, its filter, the zero bytes behind the request
+    th_export_request req;
     const void *track;
     th_resample_plan plan;  // of (the track's rate, sr) when they differ, and the track's length at sr
     size_t n_out;
@@ -126,8 +162,20 @@ struct ExportInfo : th_export_info {  // + the track (a Track of track_manager.h
     uint32_t pad;
 };
 int export_request_info(th_tm *tm, const ExportReq &r, size_t i, ExportInfo *info);
-void export_layout(ExportInfo *info, size_t n, size_t *out_len);
-int export_run(th_tm *tm, const ExportReq *reqs, size_t n, ExportInfo *info, uint8_t *out);
+int export_run(th_tm *tm, size_t n, ExportInfo *info, uint8_t *out);
+struct ExportReader : br::ReaderDefaults {
+    using Request = ExportReq;
+    using Info = ExportInfo;
+    using Public = th_export_info;
+    using Out = uint8_t;
+    static constexpr const char *unit = "bytes";
+    static constexpr Revision revision = Revision::waveform;
+    static constexpr bool needs_colormap = false, run_updates_infos = true;
+    static size_t id_of(const Request &r) { return r.base.id; }
+    static int check(th_tm *tm, const Request &r, size_t i, Info *info) { return export_request_info(tm, r, i, info); }
+    static size_t layout(Info *info, size_t n);
+    static int run(th_tm *tm, size_t n, Info *info, Out *out) { return export_run(tm, n, info, out); }
+};
 inline ExportReq export_req(const th_export_request &r) { return ExportReq{r, 0u, false, 0u, 0.0, 0.0, 0.0}; }
 inline ExportReq export_req(const th_export_at_request &r) { return ExportReq{r.base, r.sr_out, false, 0u, 0.0, 0.0, 0.0}; }
 inline ExportReq export_req(const th_export_band_request &r) { return ExportReq{r.base, 0u, true, r.mode, r.f_lo_hz, r.f_hi_hz, r.trans_hz}; }
@@ -142,43 +190,91 @@ int wav_header_checked(uint32_t format, uint32_t sr, uint32_t n_ch, uint64_t n_f
                        size_t *pad_len);
 
 // Figures.  *info: the record's size and what the plan needs of the request (the resident image; its offset is the layout's to set).
-// figures_layout: offsets that are multiples of 64; returns the last record's end.  figures_run: request i's record to
+// layout: offsets that are multiples of 64; returns the last record's end.  figures_run: request i's record to
 // out + info[i].offset, nothing between the records.  The device colormap must exist (ensure_colormap, before the shared lock)
 struct FigureInfo : th_figure_info {
     FigurePlanRequest plan;
 };
 int figure_request_info(th_tm *tm, const th_figure_request &r, size_t i, FigureInfo *info);
-size_t figures_layout(FigureInfo *info, size_t n);
-int figures_run(th_tm *tm, size_t n, const FigureInfo *info, uint8_t *out);
+int figures_run(th_tm *tm, size_t n, FigureInfo *info, uint8_t *out);
+struct FigureReader : br::ReaderDefaults {
+    using Request = th_figure_request;
+    using Info = FigureInfo;
+    using Public = th_figure_info;
+    using Out = uint8_t;
+    static constexpr const char *unit = "bytes";
+    static constexpr Revision revision = Revision::spectrogram;
+    static constexpr bool needs_colormap = true, run_updates_infos = false;
+    static size_t id_of(const Request &r) { return r.id; }
+    static int check(th_tm *tm, const Request &r, size_t i, Info *info) { return figure_request_info(tm, r, i, info); }
+    static size_t layout(Info *info, size_t n) { return br::layout_aligned_64(info, n); }
+    static int run(th_tm *tm, size_t n, Info *info, Out *out) { return figures_run(tm, n, info, out); }
+};
 // th_tm_figure_box without the lock
 int figure_box_of(th_tm *tm, size_t id, uint32_t ch, double start_sec, double end_sec, double hz_min, double hz_max, double box[4]);
 
 // Waveform envelopes and lanes.  *info: the record's size, edges[0] and edges[n_cols], and what the plan needs of the request (the
-// resident channel `which` names; its offset is the layout's to set).  envelopes_layout: requests back to back, in floats;
-// waveform_figures_layout: offsets that are multiples of 64, returns the last record's end.  *_run: request i's record to
-// out + info[i].offset, nothing between the records
+// resident channel `which` names; its offset is the layout's to set).  Envelopes: requests back to back, in floats; waveform
+// figures: offsets that are multiples of 64, the last record's end.  *_run: request i's record to out + info[i].offset, nothing
+// between the records
 struct EnvelopeInfo : th_envelope_info {
     EnvelopePlanRequest plan;
 };
 int envelope_request_info(th_tm *tm, const th_envelope_request &r, size_t i, EnvelopeInfo *info);
-size_t envelopes_layout(EnvelopeInfo *info, size_t n);
-int envelopes_run(th_tm *tm, size_t n, const EnvelopeInfo *info, float *out);
+int envelopes_run(th_tm *tm, size_t n, EnvelopeInfo *info, float *out);
+struct EnvelopeReader : br::ReaderDefaults {
+    using Request = th_envelope_request;
+    using Info = EnvelopeInfo;
+    using Public = th_envelope_info;
+    using Out = float;
+    static constexpr const char *unit = "floats";
+    static constexpr Revision revision = Revision::waveform;
+    static constexpr bool needs_colormap = false, run_updates_infos = false;
+    static size_t id_of(const Request &r) { return r.id; }
+    static int check(th_tm *tm, const Request &r, size_t i, Info *info) { return envelope_request_info(tm, r, i, info); }
+    static size_t layout(Info *info, size_t n) { return br::layout_back_to_back(info, n, &Info::length); }
+    static int run(th_tm *tm, size_t n, Info *info, Out *out) { return envelopes_run(tm, n, info, out); }
+};
 struct WaveformFigureInfo : th_waveform_figure_info {
     LanePlanRequest plan;
 };
 int waveform_figure_request_info(th_tm *tm, const th_waveform_figure_request &r, size_t i, WaveformFigureInfo *info);
-size_t waveform_figures_layout(WaveformFigureInfo *info, size_t n);
-int waveform_figures_run(th_tm *tm, size_t n, const WaveformFigureInfo *info, uint8_t *out);
+int waveform_figures_run(th_tm *tm, size_t n, WaveformFigureInfo *info, uint8_t *out);
+struct WaveformFigureReader : br::ReaderDefaults {
+    using Request = th_waveform_figure_request;
+    using Info = WaveformFigureInfo;
+    using Public = th_waveform_figure_info;
+    using Out = uint8_t;
+    static constexpr const char *unit = "bytes";
+    static constexpr Revision revision = Revision::waveform;
+    static constexpr bool needs_colormap = false, run_updates_infos = false;
+    static size_t id_of(const Request &r) { return r.env.id; }
+    static int check(th_tm *tm, const Request &r, size_t i, Info *info) { return waveform_figure_request_info(tm, r, i, info); }
+    static size_t layout(Info *info, size_t n) { return br::layout_aligned_64(info, n); }
+    static int run(th_tm *tm, size_t n, Info *info, Out *out) { return waveform_figures_run(tm, n, info, out); }
+};
 
 // Formant candidates.  *info: the frames, the record's length and the request's plan with its resident channel (its offset is the
-// layout's to set).  formants_layout: requests back to back, in doubles.  formants_run: request i's doubles to out + info[i].offset
-// and its two counts into info[i]
+// layout's to set).  Requests back to back, in doubles.  formants_run: request i's doubles to out + info[i].offset and its two counts
+// into info[i]
 struct FormantInfo : th_formant_info {
     FormantPlanRequest plan;
 };
 int formant_request_info(th_tm *tm, const th_formant_request &r, size_t i, FormantInfo *info);
-size_t formants_layout(FormantInfo *info, size_t n);
 int formants_run(th_tm *tm, size_t n, FormantInfo *info, double *out);
+struct FormantReader : br::ReaderDefaults {
+    using Request = th_formant_request;
+    using Info = FormantInfo;
+    using Public = th_formant_info;
+    using Out = double;
+    static constexpr const char *unit = "doubles";
+    static constexpr Revision revision = Revision::waveform;
+    static constexpr bool needs_colormap = false, run_updates_infos = true;
+    static size_t id_of(const Request &r) { return r.id; }
+    static int check(th_tm *tm, const Request &r, size_t i, Info *info) { return formant_request_info(tm, r, i, info); }
+    static size_t layout(Info *info, size_t n) { return br::layout_back_to_back(info, n, &Info::length); }
+    static int run(th_tm *tm, size_t n, Info *info, Out *out) { return formants_run(tm, n, info, out); }
+};
 
 // update_spec_imgs against `global` (NULL: the manager's own tracks, as th_tm_* does), then the writer's final wait:
 // for the images only (apply_track_list_changes, set_dB_range) or for everything (set_setting, set_colormap)

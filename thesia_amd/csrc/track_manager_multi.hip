@@ -148,45 +148,46 @@ const th_tmg::Placement *find_track(const th_tmg *g, size_t id) {
     return it == g->where.end() ? nullptr : &it->second;
 }
 
-// A batch of n requests split by owner (id_of(i): request i's track).  Every request is checked in request order against its
-// owning slot, under that slot's shared lock (check(tm, i): the codes and the order of one th_tm, the first faulty request
-// decides).  mine[s]: the requests of slot s in request order; busy: the slots that have any.  The caller holds g->rw.
-struct Split {
-    std::vector<std::vector<size_t>> mine;
-    std::vector<uint32_t> busy;
-};
-template <class IdOf, class Check>
-int check_and_split(th_tmg *g, size_t n, IdOf id_of, Check check, Split *sp) {
-    sp->mine.assign(g->slots.size(), {});
-    for (size_t i = 0; i < n; i++) {
-        const th_tmg::Placement *p = find_track(g, id_of(i));
-        if (!p) return fail(TH_ERR_NOT_FOUND, "Track %zu does not exist", (size_t)id_of(i));
-        th_tm *tm = g->slots[p->slot].tm;
-        std::shared_lock<std::shared_mutex> sl(tmi::rw_of(tm));
-        TH_CHECK(check(tm, i));
-        sp->mine[p->slot].push_back(i);
+// th_tmg as the manager of a batched reader (batched_reader.h): every track has one owning slot.  The caller's lock is g->rw; a slot's
+// default colormap is uploaded after the short-buffer report, for the busy slots only
+struct TmgReaders {
+    static constexpr bool single_owner = false;
+    th_tmg *g;
+    bool null() const { return !g; }
+    int before_lock(bool) const { return TH_OK; }
+    std::shared_lock<std::shared_mutex> lock() const { return std::shared_lock<std::shared_mutex>(g->rw); }
+    uint64_t revision(br::Revision which) const { return which == br::Revision::waveform ? revisions(g).first : revisions(g).second; }
+    size_t n_slots() const { return g->slots.size(); }
+    bool find(size_t id, uint32_t *slot) const {
+        const th_tmg::Placement *p = find_track(g, id);
+        if (p) *slot = p->slot;
+        return p != nullptr;
     }
-    for (uint32_t s = 0; s < g->slots.size(); s++)
-        if (!sp->mine[s].empty()) sp->busy.push_back(s);
+    th_tm *owner(uint32_t s) const { return g->slots[s].tm; }
+    std::shared_lock<std::shared_mutex> lock_owner(uint32_t s) const { return std::shared_lock<std::shared_mutex>(tmi::rw_of(owner(s))); }
+    int before_run(bool colormap, const std::vector<uint32_t> &busy) const {
+        if (colormap)
+            for (uint32_t s : busy) TH_CHECK(tmi::ensure_colormap(owner(s)));
+        return TH_OK;
+    }
+    template <class F>
+    int for_slots(const std::vector<uint32_t> &which, F fn) const { return ::for_slots(g, which, fn); }
+};
+
+// Every slot of `which` prepares into a StagedPtr under its write lock (prepare(slot, &staged)); a failure returns with all of them
+// discarded, otherwise every one is committed
+template <class Prepare>
+int prepare_and_commit(th_tmg *g, const std::vector<uint32_t> &which, Prepare prepare) {
+    std::vector<tmi::StagedPtr> staged(g->slots.size());
+    TH_CHECK(for_slots(g, which, [&](uint32_t s) -> int {
+        std::unique_lock<std::shared_mutex> sl(tmi::rw_of(g->slots[s].tm));
+        return prepare(s, &staged[s]);
+    }));
+    for (uint32_t s : which) {
+        std::unique_lock<std::shared_mutex> sl(tmi::rw_of(g->slots[s].tm));
+        tmi::commit(g->slots[s].tm, std::move(staged[s]));
+    }
     return TH_OK;
-}
-
-// run(tm, idx) on every busy slot side by side (one slot: on the caller's thread), under the slot's shared lock; idx = mine[slot]
-template <class Run>
-int run_on_owners(th_tmg *g, const Split &sp, Run run) {
-    return for_slots(g, sp.busy, [&](uint32_t s) -> int {
-        th_tm *tm = g->slots[s].tm;
-        std::shared_lock<std::shared_mutex> sl(tmi::rw_of(tm));
-        return run(tm, sp.mine[s]);
-    });
-}
-
-// a slot's subset of the batch's requests or infos
-template <class T>
-std::vector<T> gather(const T *all, const std::vector<size_t> &idx) {
-    std::vector<T> sub(idx.size());
-    for (size_t j = 0; j < idx.size(); j++) sub[j] = all[idx[j]];
-    return sub;
 }
 
 }  // namespace
@@ -270,17 +271,10 @@ TH_API int th_tmg_set_setting(th_tmg *g, double win_ms, uint32_t t_overlap, uint
     TH_REQUIRE(freq_scale == TH_FREQ_LINEAR || freq_scale == TH_FREQ_MEL, "bad freq_scale");
     std::unique_lock<std::shared_mutex> wl(g->rw);
     // every slot prepares (new plans and specs beside the resident ones); all commit, or all discard
-    std::vector<tmi::StagedPtr> staged(g->slots.size());
-    int rc = for_slots(g, all_slots(g), [&](uint32_t s) -> int {
-        std::unique_lock<std::shared_mutex> sl(tmi::rw_of(g->slots[s].tm));
-        return tmi::prepare_setting(g->slots[s].tm, win_ms, t_overlap, f_overlap, freq_scale, &staged[s]);
-    });
-    if (rc != TH_OK) return rc;  // (staged: discarded on the way out)
-    for (size_t s = 0; s < staged.size(); s++) {
-        std::unique_lock<std::shared_mutex> sl(tmi::rw_of(g->slots[s].tm));
-        tmi::commit(g->slots[s].tm, std::move(staged[s]));
-    }
-    rc = requantise_all(g, true, false, nullptr);
+    TH_CHECK(prepare_and_commit(g, all_slots(g), [&](uint32_t s, tmi::StagedPtr *staged) {
+        return tmi::prepare_setting(g->slots[s].tm, win_ms, t_overlap, f_overlap, freq_scale, staged);
+    }));
+    const int rc = requantise_all(g, true, false, nullptr);
     g->revs.invalidate_spectrogram();  // lib.rs:284
     sync_revisions(g);
     return rc;
@@ -358,24 +352,16 @@ TH_API int th_tmg_add_tracks(th_tmg *g, size_t n_tracks, const size_t *ids, cons
     for (uint32_t s = 0; s < n_slots; s++)
         if (!batch[s].ids.empty()) busy.push_back(s);
     // every slot stages its tracks (upload, waveform pyramids, STFT); all commit, or all discard
-    std::vector<tmi::StagedPtr> staged(n_slots);
-    int rc = for_slots(g, busy, [&](uint32_t s) -> int {
+    TH_CHECK(prepare_and_commit(g, busy, [&](uint32_t s, tmi::StagedPtr *staged) {
         const Batch &b = batch[s];
-        std::unique_lock<std::shared_mutex> sl(tmi::rw_of(g->slots[s].tm));
-        return tmi::prepare_add(g->slots[s].tm, b.ids.size(), b.ids.data(), b.srs.data(), b.nch.data(), b.chans.data(), b.ns.data(),
-                                &staged[s]);
-    });
-    if (rc != TH_OK) return rc;  // (staged: discarded on the way out)
-    for (uint32_t s : busy) {
-        std::unique_lock<std::shared_mutex> sl(tmi::rw_of(g->slots[s].tm));
-        tmi::commit(g->slots[s].tm, std::move(staged[s]));
-    }
+        return tmi::prepare_add(g->slots[s].tm, b.ids.size(), b.ids.data(), b.srs.data(), b.nch.data(), b.chans.data(), b.ns.data(), staged);
+    }));
     for (size_t t = 0; t < n_tracks; t++)
         if (last_of[ids[t]] == t) g->where[ids[t]] = th_tmg::Placement{slot_of[t], weight[t]};
     g->revs.invalidate_all();  // lib.rs:192
     sync_revisions(g);
     for (uint32_t s : busy) {
-        rc = tmi::settle(g->slots[s].tm);
+        const int rc = tmi::settle(g->slots[s].tm);
         if (rc != TH_OK) return fail(rc, "slot %u (device %d): %s", s, g->slots[s].device, get_error());
     }
     return TH_OK;
@@ -505,9 +491,9 @@ TH_API int th_tmg_get_audio_render_metadata(th_tmg *g, size_t id, uint32_t ch, d
     TH_CATCH
 }
 
-// The batched readers: check_and_split, one layout, the manager's own revision, the infos and the length published, a short buffer
-// reported; then every owning slot runs its subset side by side and writes its results straight to their places in the caller's
-// buffer (track_manager_internal.h).
+// The batched readers go through br::batched_read (batched_reader.h) with TmgReaders: every owning slot runs its subset side by side and
+// writes its results straight to their places in the caller's buffer.  The tiles return offsets instead of infos and stamp nothing
+// (the headers' revision: every slot carries the manager's), so their entry is written out with the same pieces.
 TH_API int th_tmg_get_spectrogram_tiles(th_tmg *g, const th_tile_request *reqs, size_t n, uint8_t *out, size_t out_capacity,
                                         size_t *offsets, size_t *out_len) {
     TH_TRY
@@ -517,17 +503,20 @@ TH_API int th_tmg_get_spectrogram_tiles(th_tmg *g, const th_tile_request *reqs, 
         if (offsets) offsets[0] = 0;
         return TH_OK;
     }
-    std::shared_lock<std::shared_mutex> rl(g->rw);
+    TmgReaders m{g};
+    const auto rl = m.lock();
     std::vector<tmi::TileInfo> infos(n);
-    Split sp;
-    TH_CHECK(check_and_split(g, n, [&](size_t i) { return reqs[i].id; },
-                             [&](th_tm *tm, size_t i) { return tmi::tile_request_info(tm, reqs[i], &infos[i]); }, &sp));
-    const size_t total = tmi::tiles_layout(infos.data(), n, offsets);  // (the headers' revision: every slot carries the manager's)
+    br::Split sp;
+    TH_CHECK(br::check_and_split(m, n, [&](size_t i) { return reqs[i].id; },
+                                 [&](th_tm *tm, size_t i) { return tmi::tile_request_info(tm, reqs[i], &infos[i]); }, &sp));
+    const size_t total = tmi::tiles_layout(infos.data(), n, offsets);
     *out_len = total;
     if (out_capacity < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
-    for (uint32_t s : sp.busy) TH_CHECK(tmi::ensure_colormap(g->slots[s].tm));
-    return run_on_owners(g, sp, [&](th_tm *tm, const std::vector<size_t> &idx) -> int {
-        return tmi::tiles_run(tm, gather(reqs, idx).data(), idx.size(), gather(infos.data(), idx).data(), out);
+    TH_CHECK(m.before_run(true, sp.busy));
+    return br::run_on_owners(m, sp, [&](th_tm *tm, const std::vector<size_t> &idx) -> int {
+        std::vector<tmi::TileInfo> sub(idx.size());
+        for (size_t j = 0; j < idx.size(); j++) sub[j] = infos[idx[j]];
+        return tmi::tiles_run(tm, idx.size(), sub.data(), out);
     });
     TH_CATCH
 }
@@ -535,25 +524,7 @@ TH_API int th_tmg_get_spectrogram_tiles(th_tmg *g, const th_tile_request *reqs, 
 TH_API int th_tmg_get_spectra(th_tmg *g, const th_spectrum_request *reqs, size_t n, float *out, size_t cap, th_spectrum_info *info,
                               size_t *out_len) {
     TH_TRY
-    TH_REQUIRE(g && out_len && (n == 0 || (reqs && info)), "NULL argument");
-    *out_len = 0;
-    if (n == 0) return TH_OK;
-    std::shared_lock<std::shared_mutex> rl(g->rw);
-    std::vector<tmi::SpectrumInfo> infos(n);
-    Split sp;
-    TH_CHECK(check_and_split(g, n, [&](size_t i) { return reqs[i].id; },
-                             [&](th_tm *tm, size_t i) { return tmi::spectrum_request_info(tm, reqs[i], i, &infos[i]); }, &sp));
-    const size_t total = tmi::spectra_layout(infos.data(), n);
-    const uint64_t revision = revisions(g).second;
-    for (size_t i = 0; i < n; i++) {
-        infos[i].spectrogram_revision = revision;
-        info[i] = infos[i];
-    }
-    *out_len = total;
-    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu floats", total);
-    return run_on_owners(g, sp, [&](th_tm *tm, const std::vector<size_t> &idx) -> int {
-        return tmi::spectra_run(tm, gather(reqs, idx).data(), idx.size(), gather(infos.data(), idx).data(), out);
-    });
+    return br::batched_read<tmi::SpectrumReader>(TmgReaders{g}, reqs, n, out, cap, info, out_len);
     TH_CATCH
 }
 
@@ -563,41 +534,15 @@ TH_API int th_tmg_get_spectrum(th_tmg *g, size_t id, uint32_t ch, int kind, doub
     TH_REQUIRE(g, "tmg is NULL");
     TH_REQUIRE(kind >= 0, "unknown spectrum kind %d", kind);
     const th_spectrum_request r{id, ch, (uint32_t)kind, start_sec, end_sec};
-    th_spectrum_info one{};
-    size_t len = 0;
-    const int rc = th_tmg_get_spectra(g, &r, 1, out, cap, &one, &len);
-    if (info && (rc == TH_OK || rc == TH_ERR_BUFFER_TOO_SMALL)) *info = one;
-    return rc;
+    return br::single_read(info, [&](th_spectrum_info *one, size_t *len) { return th_tmg_get_spectra(g, &r, 1, out, cap, one, len); });
     TH_CATCH
 }
 
 TH_API int th_tmg_get_loudness_meters(th_tmg *g, const size_t *ids, size_t n, th_loudness_meter *meters, double *series, size_t cap,
                                       size_t *out_len) {
     TH_TRY
-    TH_REQUIRE(g && meters && out_len && (n == 0 || ids), "NULL argument");
-    *out_len = 0;
-    if (n == 0) return TH_OK;
-    std::shared_lock<std::shared_mutex> rl(g->rw);
-    std::vector<tmi::MeterInfo> ms(n);
-    Split sp;
-    TH_CHECK(check_and_split(g, n, [&](size_t i) { return ids[i]; },
-                             [&](th_tm *tm, size_t i) { return tmi::loudness_meter_info(tm, ids[i], &ms[i]); }, &sp));
-    const size_t total = tmi::meters_layout(ms.data(), n);
-    const uint64_t revision = revisions(g).first;
-    for (size_t i = 0; i < n; i++) {
-        ms[i].waveform_revision = revision;
-        meters[i] = ms[i];
-    }
-    *out_len = total;
-    if (series && cap < total) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu doubles", total);
-    TH_CHECK(run_on_owners(g, sp, [&](th_tm *tm, const std::vector<size_t> &idx) -> int {
-        std::vector<tmi::MeterInfo> sub = gather(ms.data(), idx);
-        TH_CHECK(tmi::meters_run(tm, gather(ids, idx).data(), idx.size(), sub.data(), series));
-        for (size_t j = 0; j < idx.size(); j++) ms[idx[j]] = sub[j];
-        return TH_OK;
-    }));
-    for (size_t i = 0; i < n; i++) meters[i] = ms[i];
-    return TH_OK;
+    TH_REQUIRE(meters, "NULL argument");  // (also for n == 0)
+    return br::batched_read<tmi::MeterReader>(TmgReaders{g}, ids, n, series, cap, meters, out_len);
     TH_CATCH
 }
 
@@ -609,67 +554,35 @@ TH_API int th_tmg_get_loudness_meter(th_tmg *g, size_t id, th_loudness_meter *me
     TH_CATCH
 }
 
-// Export: the same shape; a slot also writes the zero padding behind each of its requests, and its two counts come back into infos
-namespace {
-int export_on_slots(th_tmg *g, const Split &sp, const tmi::ExportReq *reqs, std::vector<tmi::ExportInfo> &infos, uint8_t *out) {
-    return run_on_owners(g, sp, [&](th_tm *tm, const std::vector<size_t> &idx) -> int {
-        std::vector<tmi::ExportInfo> si = gather(infos.data(), idx);
-        TH_CHECK(tmi::export_run(tm, gather(reqs, idx).data(), idx.size(), si.data(), out));
-        for (size_t j = 0; j < idx.size(); j++) {
-            infos[idx[j]].n_clamped = si[j].n_clamped;
-            infos[idx[j]].n_nan = si[j].n_nan;
-        }
-        return TH_OK;
-    });
-}
-
-int export_check_all(th_tmg *g, const tmi::ExportReq *reqs, size_t n, std::vector<tmi::ExportInfo> &infos, Split *sp) {
-    TH_CHECK(check_and_split(g, n, [&](size_t i) { return reqs[i].base.id; },
-                             [&](th_tm *tm, size_t i) { return tmi::export_request_info(tm, reqs[i], i, &infos[i]); }, sp));
-    const uint64_t revision = revisions(g).first;
-    for (tmi::ExportInfo &f : infos) f.waveform_revision = revision;
-    return TH_OK;
-}
-}  // namespace
-
+// Export: a slot also writes the zero padding behind each of its requests, and its two counts come back into infos.  The WAV form is
+// one request behind a header: checked, stamped and run with the same pieces
 namespace {
 int tmg_export_pcm_any(th_tmg *g, const tmi::ExportReq *reqs, size_t n, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
-    TH_REQUIRE(g && out_len && (n == 0 || (reqs && info)), "NULL argument");
-    *out_len = 0;
-    if (n == 0) return TH_OK;
-    std::shared_lock<std::shared_mutex> rl(g->rw);
-    std::vector<tmi::ExportInfo> infos(n);
-    Split sp;
-    TH_CHECK(export_check_all(g, reqs, n, infos, &sp));
-    size_t total = 0;
-    tmi::export_layout(infos.data(), n, &total);
-    for (size_t i = 0; i < n; i++) info[i] = infos[i];
-    *out_len = total;
-    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
-    TH_CHECK(export_on_slots(g, sp, reqs, infos, out));
-    for (size_t i = 0; i < n; i++) info[i] = infos[i];
-    return TH_OK;
+    return br::batched_read<tmi::ExportReader>(TmgReaders{g}, reqs, n, out, cap, info, out_len);
 }
 
 int tmg_export_wav_any(th_tmg *g, const tmi::ExportReq *req, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
     TH_REQUIRE(g && req && out_len, "NULL argument");
     *out_len = 0;
-    std::shared_lock<std::shared_mutex> rl(g->rw);
-    std::vector<tmi::ExportInfo> one(1);
-    Split sp;
-    TH_CHECK(export_check_all(g, req, 1, one, &sp));
+    TmgReaders m{g};
+    const auto rl = m.lock();
+    tmi::ExportInfo one{};
+    br::Split sp;
+    TH_CHECK(br::check_and_split(m, 1, [&](size_t) { return req->base.id; },
+                                 [&](th_tm *tm, size_t i) { return tmi::export_request_info(tm, *req, i, &one); }, &sp));
+    one.waveform_revision = m.revision(br::Revision::waveform);
     uint8_t hdr[TH_WAV_HEADER_MAX];
     size_t hl = 0, pl = 0;
-    TH_CHECK(tmi::wav_header_checked(req->base.format, one[0].sr, one[0].n_channels, one[0].sample_end - one[0].sample_start, hdr, &hl, &pl));
-    one[0].offset = hl;
-    const size_t total = hl + (size_t)one[0].n_bytes + pl;
-    if (info) *info = one[0];
+    TH_CHECK(tmi::wav_header_checked(req->base.format, one.sr, one.n_channels, one.sample_end - one.sample_start, hdr, &hl, &pl));
+    one.offset = hl;
+    const size_t total = hl + (size_t)one.n_bytes + pl;
+    if (info) *info = one;
     *out_len = total;
     if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
-    TH_CHECK(export_on_slots(g, sp, req, one, out));
+    TH_CHECK(br::run_on_owners(m, sp, [&](th_tm *tm, const std::vector<size_t> &) { return tmi::export_run(tm, 1, &one, out); }));
     std::memcpy(out, hdr, hl);
-    if (pl) out[hl + one[0].n_bytes] = 0;
-    if (info) *info = one[0];
+    if (pl) out[hl + one.n_bytes] = 0;
+    if (info) *info = one;
     return TH_OK;
 }
 }  // namespace
@@ -723,41 +636,18 @@ TH_API int th_tmg_export_wav_band(th_tmg *g, const th_export_band_request *req, 
     TH_CATCH
 }
 
-// Figures: the same shape as the spectra; every busy slot needs its device colormap first, as for the tiles
+// Figures: every busy slot needs its device colormap first, as for the tiles
 TH_API int th_tmg_render_figures(th_tmg *g, const th_figure_request *reqs, size_t n, uint8_t *out, size_t cap, th_figure_info *info,
                                  size_t *out_len) {
     TH_TRY
-    TH_REQUIRE(g && out_len && (n == 0 || (reqs && info)), "NULL argument");
-    *out_len = 0;
-    if (n == 0) return TH_OK;
-    std::shared_lock<std::shared_mutex> rl(g->rw);
-    std::vector<tmi::FigureInfo> infos(n);
-    Split sp;
-    TH_CHECK(check_and_split(g, n, [&](size_t i) { return reqs[i].id; },
-                             [&](th_tm *tm, size_t i) { return tmi::figure_request_info(tm, reqs[i], i, &infos[i]); }, &sp));
-    const size_t total = tmi::figures_layout(infos.data(), n);
-    const uint64_t revision = revisions(g).second;
-    for (size_t i = 0; i < n; i++) {
-        infos[i].spectrogram_revision = revision;
-        info[i] = infos[i];
-    }
-    *out_len = total;
-    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
-    for (uint32_t s : sp.busy) TH_CHECK(tmi::ensure_colormap(g->slots[s].tm));
-    return run_on_owners(g, sp, [&](th_tm *tm, const std::vector<size_t> &idx) -> int {
-        return tmi::figures_run(tm, idx.size(), gather(infos.data(), idx).data(), out);
-    });
+    return br::batched_read<tmi::FigureReader>(TmgReaders{g}, reqs, n, out, cap, info, out_len);
     TH_CATCH
 }
 
 TH_API int th_tmg_render_figure(th_tmg *g, const th_figure_request *req, uint8_t *out, size_t cap, th_figure_info *info) {
     TH_TRY
     TH_REQUIRE(g && req, "NULL argument");
-    th_figure_info one{};
-    size_t len = 0;
-    const int rc = th_tmg_render_figures(g, req, 1, out, cap, &one, &len);
-    if (info && (rc == TH_OK || rc == TH_ERR_BUFFER_TOO_SMALL)) *info = one;
-    return rc;
+    return br::single_read(info, [&](th_figure_info *one, size_t *len) { return th_tmg_render_figures(g, req, 1, out, cap, one, len); });
     TH_CATCH
 }
 
@@ -773,17 +663,10 @@ TH_API int th_tmg_figure_box(th_tmg *g, size_t id, uint32_t ch, double start_sec
 // set_common_normalize / set_common_guard_clipping: every slot re-derives its tracks into staged buffers; all commit, or all discard
 namespace {
 int set_common_dynamics_all(th_tmg *g, int kind, float target, int mode) {
-    std::vector<tmi::StagedPtr> staged(g->slots.size());
-    int rc = for_slots(g, all_slots(g), [&](uint32_t s) -> int {
-        std::unique_lock<std::shared_mutex> sl(tmi::rw_of(g->slots[s].tm));
-        return tmi::prepare_dynamics(g->slots[s].tm, kind, target, mode, &staged[s]);
-    });
-    if (rc != TH_OK) return rc;  // (staged: discarded on the way out)
-    for (size_t s = 0; s < staged.size(); s++) {
-        std::unique_lock<std::shared_mutex> sl(tmi::rw_of(g->slots[s].tm));
-        tmi::commit(g->slots[s].tm, std::move(staged[s]));
-    }
-    rc = requantise_all(g, true, false, nullptr);
+    TH_CHECK(prepare_and_commit(g, all_slots(g), [&](uint32_t s, tmi::StagedPtr *staged) {
+        return tmi::prepare_dynamics(g->slots[s].tm, kind, target, mode, staged);
+    }));
+    const int rc = requantise_all(g, true, false, nullptr);
     g->revs.invalidate_all();
     sync_revisions(g);
     return rc;
@@ -870,107 +753,40 @@ TH_API int th_tmg_set_lod_source(th_tmg *g, int per_request) {
     TH_CATCH
 }
 
-// Waveform envelopes and lanes: the same shape as the spectra and the figures; the revision stamped is the manager's own
+// Waveform envelopes and lanes
 TH_API int th_tmg_get_envelopes(th_tmg *g, const th_envelope_request *reqs, size_t n, float *out, size_t cap, th_envelope_info *info,
                                 size_t *out_len) {
     TH_TRY
-    TH_REQUIRE(g && out_len && (n == 0 || (reqs && info)), "NULL argument");
-    *out_len = 0;
-    if (n == 0) return TH_OK;
-    std::shared_lock<std::shared_mutex> rl(g->rw);
-    std::vector<tmi::EnvelopeInfo> infos(n);
-    Split sp;
-    TH_CHECK(check_and_split(g, n, [&](size_t i) { return reqs[i].id; },
-                             [&](th_tm *tm, size_t i) { return tmi::envelope_request_info(tm, reqs[i], i, &infos[i]); }, &sp));
-    const size_t total = tmi::envelopes_layout(infos.data(), n);
-    const uint64_t revision = revisions(g).first;
-    for (size_t i = 0; i < n; i++) {
-        infos[i].waveform_revision = revision;
-        info[i] = infos[i];
-    }
-    *out_len = total;
-    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu floats", total);
-    return run_on_owners(g, sp, [&](th_tm *tm, const std::vector<size_t> &idx) -> int {
-        return tmi::envelopes_run(tm, idx.size(), gather(infos.data(), idx).data(), out);
-    });
+    return br::batched_read<tmi::EnvelopeReader>(TmgReaders{g}, reqs, n, out, cap, info, out_len);
     TH_CATCH
 }
 
 TH_API int th_tmg_get_envelope(th_tmg *g, const th_envelope_request *req, float *out, size_t cap, th_envelope_info *info) {
     TH_TRY
     TH_REQUIRE(g && req, "NULL argument");
-    th_envelope_info one{};
-    size_t len = 0;
-    const int rc = th_tmg_get_envelopes(g, req, 1, out, cap, &one, &len);
-    if (info && (rc == TH_OK || rc == TH_ERR_BUFFER_TOO_SMALL)) *info = one;
-    return rc;
+    return br::single_read(info, [&](th_envelope_info *one, size_t *len) { return th_tmg_get_envelopes(g, req, 1, out, cap, one, len); });
     TH_CATCH
 }
 
-// Formant candidates: the same shape; a slot's two counts come back into infos
+// Formant candidates: a slot's two counts come back into infos
 TH_API int th_tmg_get_formants(th_tmg *g, const th_formant_request *reqs, size_t n, double *out, size_t cap, th_formant_info *info,
                                size_t *out_len) {
     TH_TRY
-    TH_REQUIRE(g && out_len && (n == 0 || (reqs && info)), "NULL argument");
-    *out_len = 0;
-    if (n == 0) return TH_OK;
-    std::shared_lock<std::shared_mutex> rl(g->rw);
-    std::vector<tmi::FormantInfo> infos(n);
-    Split sp;
-    TH_CHECK(check_and_split(g, n, [&](size_t i) { return reqs[i].id; },
-                             [&](th_tm *tm, size_t i) { return tmi::formant_request_info(tm, reqs[i], i, &infos[i]); }, &sp));
-    const size_t total = tmi::formants_layout(infos.data(), n);
-    const uint64_t revision = revisions(g).first;
-    for (size_t i = 0; i < n; i++) {
-        infos[i].waveform_revision = revision;
-        info[i] = infos[i];
-    }
-    *out_len = total;
-    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu doubles", total);
-    TH_CHECK(run_on_owners(g, sp, [&](th_tm *tm, const std::vector<size_t> &idx) -> int {
-        std::vector<tmi::FormantInfo> sub = gather(infos.data(), idx);
-        TH_CHECK(tmi::formants_run(tm, idx.size(), sub.data(), out));
-        for (size_t j = 0; j < idx.size(); j++) infos[idx[j]] = sub[j];
-        return TH_OK;
-    }));
-    for (size_t i = 0; i < n; i++) info[i] = infos[i];
-    return TH_OK;
+    return br::batched_read<tmi::FormantReader>(TmgReaders{g}, reqs, n, out, cap, info, out_len);
     TH_CATCH
 }
 
 TH_API int th_tmg_get_formant_track(th_tmg *g, const th_formant_request *req, double *out, size_t cap, th_formant_info *info) {
     TH_TRY
     TH_REQUIRE(g && req, "NULL argument");
-    th_formant_info one{};
-    size_t len = 0;
-    const int rc = th_tmg_get_formants(g, req, 1, out, cap, &one, &len);
-    if (info && (rc == TH_OK || rc == TH_ERR_BUFFER_TOO_SMALL)) *info = one;
-    return rc;
+    return br::single_read(info, [&](th_formant_info *one, size_t *len) { return th_tmg_get_formants(g, req, 1, out, cap, one, len); });
     TH_CATCH
 }
 
 TH_API int th_tmg_render_waveform_figures(th_tmg *g, const th_waveform_figure_request *reqs, size_t n, uint8_t *out, size_t cap,
                                           th_waveform_figure_info *info, size_t *out_len) {
     TH_TRY
-    TH_REQUIRE(g && out_len && (n == 0 || (reqs && info)), "NULL argument");
-    *out_len = 0;
-    if (n == 0) return TH_OK;
-    std::shared_lock<std::shared_mutex> rl(g->rw);
-    std::vector<tmi::WaveformFigureInfo> infos(n);
-    Split sp;
-    TH_CHECK(check_and_split(g, n, [&](size_t i) { return reqs[i].env.id; },
-                             [&](th_tm *tm, size_t i) { return tmi::waveform_figure_request_info(tm, reqs[i], i, &infos[i]); }, &sp));
-    const size_t total = tmi::waveform_figures_layout(infos.data(), n);
-    const uint64_t revision = revisions(g).first;
-    for (size_t i = 0; i < n; i++) {
-        infos[i].waveform_revision = revision;
-        info[i] = infos[i];
-    }
-    *out_len = total;
-    if (cap < total || !out) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %zu bytes", total);
-    return run_on_owners(g, sp, [&](th_tm *tm, const std::vector<size_t> &idx) -> int {
-        return tmi::waveform_figures_run(tm, idx.size(), gather(infos.data(), idx).data(), out);
-    });
+    return br::batched_read<tmi::WaveformFigureReader>(TmgReaders{g}, reqs, n, out, cap, info, out_len);
     TH_CATCH
 }
 
@@ -978,10 +794,7 @@ TH_API int th_tmg_render_waveform_figure(th_tmg *g, const th_waveform_figure_req
                                          th_waveform_figure_info *info) {
     TH_TRY
     TH_REQUIRE(g && req, "NULL argument");
-    th_waveform_figure_info one{};
-    size_t len = 0;
-    const int rc = th_tmg_render_waveform_figures(g, req, 1, out, cap, &one, &len);
-    if (info && (rc == TH_OK || rc == TH_ERR_BUFFER_TOO_SMALL)) *info = one;
-    return rc;
+    return br::single_read(info,
+                           [&](th_waveform_figure_info *one, size_t *len) { return th_tmg_render_waveform_figures(g, req, 1, out, cap, one, len); });
     TH_CATCH
 }
