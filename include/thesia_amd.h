@@ -886,6 +886,56 @@ TH_API int th_tm_export_pcm_band(th_tm *tm, const th_export_band_request *reqs, 
 TH_API int th_tm_export_wav_band(th_tm *tm, const th_export_band_request *req, uint8_t *out, size_t cap_bytes,
                                  th_export_info *info /* may be NULL */, size_t *out_len);
 
+/* ---------------------------------------------------------------- FLAC export: a lossless encoder for resident audio */
+/* th_tm_export_flac: request i as a complete FLAC file image of the request's time range, encoded on the device (blocks are
+ * independent, so the encoder is block-parallel integer work, and the file that crosses the bus is the small one).  The request is
+ * th_export_request with the same sample-range rule and the same error order; format is TH_PCM_S16 or TH_PCM_S24 (TH_PCM_F32:
+ * TH_ERR_INVALID_ARG).  The samples that are coded are exactly the integers th_export_quantize gives (absolute-index dither, clamp,
+ * NaN -> 0, counted in n_clamped / n_nan), so the file DECODES TO THE BYTES th_tm_export_pcm RETURNS for the same request.  FLAC is
+ * an entry, not a format value: no existing entry, format or error code changes.
+ *   The stream (a subset of RFC 9639, every choice fixed so that the bytes are a function of the samples):
+ *   Stream header, 42 bytes: "fLaC", one STREAMINFO block with the last-block flag: minimum and maximum block size 4096 / 4096, the
+ *   minimum and maximum frame size actually produced (24 bits each; 0 0 without frames), sr (20 bits), channels - 1 (3), bits per
+ *   sample - 1 (5), total samples (36), MD5 all zero ("not computed").
+ *   Limits: sr > 1 048 575, more than 8 channels, 2^36 or more samples: TH_ERR_UNSUPPORTED.  An empty range is the header alone.
+ *   Frames: fixed block size TH_FLAC_BLOCK = 4096; block b holds samples s0 + 4096 b .. of the range and its frame number is b; the
+ *   last block may be shorter.  Frame header: sync 0xFFF8; block-size code 1100 for 4096, else 0110 (n <= 256, 8 bits of n - 1) or 0111
+ *   (16 bits of n - 1); rate code from the table where the rate is in it (88.2, 176.4, 192, 8, 16, 22.05, 24, 32, 44.1, 48, 96 kHz ->
+ *   0001 .. 1011), else 1101 (sr <= 65 535, 16 bits of Hz), else 1110 (sr a multiple of 10 and sr / 10 <= 65 535, 16 bits), else
+ *   0000; channel assignment n_ch - 1 (independent); size code 100 (16 bit) or 110 (24 bit); the frame number in the UTF-8-like form;
+ *   CRC-8.  Then the subframes in channel order, zero bits to the byte boundary, CRC-16 of the whole frame.
+ *   Subframe of n samples (no wasted bits, no escape codes; all costs exact 64-bit integers): CONSTANT when all n samples are equal.
+ *   Else, for n >= 5, the fixed predictors of order o = 0 .. 4: residuals e from sample o on, u = zigzag(e) = (e << 1) ^ (e >> 31);
+ *   partition order p = the largest p <= 6 with 2^p | n and (n >> p) >= 5; a partition's Rice parameter is the smallest k minimising
+ *   sum(u >> k) + m (k + 1) over its m residuals, k in 0 .. 14 with 4-bit parameters (coding method 0) at 16 bit, 0 .. 30 with 5-bit
+ *   parameters (method 1) at 24 bit; cost(o) = o bps + 6 + sum over the partitions of (parameter bits + residual bits); the lowest
+ *   order of the smallest cost wins.  VERBATIM when that cost >= n bps, and always for n <= 4 unless CONSTANT.
+ *   Not in the stream: LPC subframes, stereo decorrelation, a searched partition order, the MD5, seek tables and comments.
+ * Layout.  Sizes are not known before encoding, so the offsets come from bounds: offset[0] = 0, offset[i + 1] = offset[i] +
+ * th_flac_bound(request i) rounded up to 16, with th_flac_bound = 42 + per block (16 bytes of frame header at most + n_ch x (1 +
+ * n bps / 8) bytes of verbatim subframes + 1 byte of padding + 2 of CRC-16).  A size query (out == NULL or cap_bytes too small:
+ * TH_ERR_BUFFER_TOO_SMALL) returns in *out_len the last offset + the last bound and in info[i].n_bytes the bounds.  A successful call
+ * sets info[i].n_bytes to the ACTUAL file length and *out_len to the last offset + that request's n_bytes.  Bytes between a file's
+ * end and the next offset are unspecified; nothing is written at or beyond the last request's bound.  Errors, first faulty request
+ * and revision: as th_tm_export_pcm.
+ * A reader like th_tm_export_pcm: shared lock, a reader slot's streams, pieces of whole blocks whose bound stays within
+ * TH_EXPORT_PIECE_BYTES through two device buffers (piece p + 1 is encoded while piece p is copied out).  A slot's FLAC scratch is
+ * made on its first FLAC call and never exceeds two staging buffers of TH_EXPORT_PIECE_BYTES, one piece of subframe slots (at most
+ * TH_EXPORT_PIECE_BYTES + 4 bytes x 65 536 units), two tables of 65 536 words and the job table of the largest call; a manager that
+ * never exports FLAC holds none.  A file depends on the track's audio and the request alone.
+ * Host functions.  th_flac_bound: the bound above.  th_flac_frame_header: sync .. CRC-8 of one frame (1 <= block_len <= 4096,
+ * frame_number < 2^36).  th_flac_encode_i32: the same stream made on the host, byte for byte, from n_ch planar int32 channels of n
+ * samples, each inside the format's range (else TH_ERR_INVALID_ARG); cap must hold th_flac_bound (else TH_ERR_BUFFER_TOO_SMALL with
+ * the bound in *out_len), *out_len = the file's length. */
+#define TH_FLAC_BLOCK 4096
+TH_API int th_flac_bound(uint64_t n_frames, uint32_t n_ch, uint32_t format, uint64_t *bytes);
+TH_API int th_flac_frame_header(uint32_t sr, uint32_t n_ch, uint32_t format, uint64_t frame_number, uint32_t block_len,
+                                uint8_t out[16], size_t *len);
+TH_API int th_flac_encode_i32(const int32_t *const *chan, uint32_t n_ch, uint64_t n, uint32_t format, uint32_t sr, uint8_t *out,
+                              size_t cap, size_t *out_len);
+TH_API int th_tm_export_flac(th_tm *tm, const th_export_request *reqs, size_t n, uint8_t *out, size_t cap_bytes,
+                             th_export_info *info /* n */, size_t *out_len);
+
 /* ---------------------------------------------------------------- Export as figures: a spectrogram region at any pixel size */
 /* Any region of a channel's resident u16 image, resampled on the device to any pixel size and coloured (or left as 16-bit grey): what
  * a host saves as a figure, without fetching tiles, stitching them and resampling a second time (upstream's roadmap item "export as
@@ -1248,6 +1298,9 @@ TH_API int th_tmg_export_pcm_band(th_tmg *tmg, const th_export_band_request *req
                                   th_export_info *info /* n */, size_t *out_len);
 TH_API int th_tmg_export_wav_band(th_tmg *tmg, const th_export_band_request *req, uint8_t *out, size_t cap_bytes,
                                   th_export_info *info /* may be NULL */, size_t *out_len);
+/* FLAC export: as above; every slot keeps its own FLAC scratch, files and infos are those of one th_tm */
+TH_API int th_tmg_export_flac(th_tmg *tmg, const th_export_request *reqs, size_t n, uint8_t *out, size_t cap_bytes,
+                              th_export_info *info /* n */, size_t *out_len);
 
 /* figures: every request goes to its owning slot and the slots are served side by side, each copying its records straight into the
  * caller's buffer; bytes, offsets and infos are those of one th_tm, the revision stamped is the manager's own */

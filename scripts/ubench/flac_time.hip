@@ -1,0 +1,127 @@
+// flac_time.hip — the three kernels of th_tm_export_flac timed apart by hipEvents: flac_subframe_kernel, flac_scan_kernel and
+// flac_frame_kernel, compiled from the product's sources, on the plan the reader itself makes (plan_flac / bind_flac) for T stereo
+// tracks x S seconds at 48 kHz, 16 bit TPDF, on music-like (decaying partials over a noise floor) or noise input.  Per repetition
+// the times are summed over the call's pieces; the median over the repetitions is printed.  A child process of
+// scripts/bench_flac.py; prints one JSON line.  From the repository root (one line):
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off scripts/ubench/flac_time.hip thesia_amd/csrc/flac_plan.cpp
+//         -o scripts/ubench/flac_time
+// Usage: flac_time [music|noise] [seconds 30] [tracks 64] [reps 9]
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../../thesia_amd/csrc/kernels_flac.hip"
+
+using namespace th;
+
+#define HIP(call)                                                                          \
+    do {                                                                                   \
+        hipError_t e_ = (call);                                                            \
+        if (e_ != hipSuccess) {                                                            \
+            std::fprintf(stderr, "%s failed: %s\n", #call, hipGetErrorString(e_));         \
+            return 1;                                                                      \
+        }                                                                                  \
+    } while (0)
+
+static double median(std::vector<double> v) {
+    std::sort(v.begin(), v.end());
+    return v[v.size() / 2];
+}
+
+int main(int argc, char **argv) {
+    const bool noise = argc > 1 && std::strcmp(argv[1], "noise") == 0;
+    const double seconds = argc > 2 ? std::atof(argv[2]) : 30.0;
+    const size_t tracks = argc > 3 ? (size_t)std::atoi(argv[3]) : 64;
+    const int reps = argc > 4 ? std::max(7, std::atoi(argv[4])) : 9;
+    const uint32_t sr = 48000, n_ch = 2;
+    const uint64_t n = (uint64_t)(seconds * sr);
+    if (n == 0 || tracks == 0) return 1;
+
+    // two channels on the host, every track its own copy on the device
+    std::vector<float> host(n_ch * n);
+    uint32_t s = 1;
+    auto rnd = [&]() { s = s * 1664525u + 1013904223u; return (double)(s >> 8) / 8388608.0 - 1.0; };
+    const double f[6] = {110.0, 220.0, 277.2, 329.6, 440.0, 659.3}, amp[6] = {0.2, 0.15, 0.1, 0.1, 0.08, 0.05};
+    for (uint64_t i = 0; i < n; i++) {
+        const double t = (double)i / sr;
+        double x = 0;
+        for (int k = 0; k < 6 && !noise; k++) x += amp[k] * std::sin(2.0 * 3.14159265358979323846 * f[k] * t + k) * std::exp(-std::fmod(t * 2.0, 1.0) * 3.0);
+        host[i] = (float)(noise ? 0.9 * rnd() : x + 3e-4 * rnd());
+        host[n + i] = (float)(noise ? 0.9 * rnd() : 0.8 * x + 3e-4 * rnd());
+    }
+    float *d_audio = nullptr;
+    HIP(hipMalloc((void **)&d_audio, tracks * n_ch * n * sizeof(float)));
+    HIP(hipMemcpy(d_audio, host.data(), n_ch * n * sizeof(float), hipMemcpyHostToDevice));
+    for (size_t t = 1; t < tracks; t++) HIP(hipMemcpy(d_audio + t * n_ch * n, d_audio, n_ch * n * sizeof(float), hipMemcpyDeviceToDevice));
+
+    std::vector<FlacPlanRequest> reqs(tracks);
+    std::vector<const float *> chan;
+    uint64_t at = 0;
+    for (size_t t = 0; t < tracks; t++) {
+        reqs[t] = FlacPlanRequest{n_ch, TH_PCM_S16, TH_DITHER_TPDF, 1u, sr, 0, n, at};
+        at += (flac_stream_bound(n, n_ch, 16) + 15) & ~(uint64_t)15;
+        for (uint32_t c = 0; c < n_ch; c++) chan.push_back(d_audio + (t * n_ch + c) * n);
+    }
+    FlacPlan pl = plan_flac(reqs.data(), tracks, TH_EXPORT_PIECE_BYTES);
+    if (pl.err != 0) return 1;
+    uint8_t *d_stage[2] = {nullptr, nullptr};
+    uint32_t *d_slots = nullptr, *d_bits = nullptr, *d_foff = nullptr;
+    FlacJobResult *d_res = nullptr;
+    unsigned char *d_tab = nullptr;
+    unsigned long long *d_cnt = nullptr;
+    for (int b = 0; b < 2; b++) HIP(hipMalloc((void **)&d_stage[b], std::max<uint64_t>(pl.stage_need[b], 16)));
+    HIP(hipMalloc((void **)&d_slots, pl.slot_need * 4));
+    HIP(hipMalloc((void **)&d_bits, (size_t)pl.unit_need * 4));
+    HIP(hipMalloc((void **)&d_foff, (size_t)pl.block_need * 4));
+    HIP(hipMalloc((void **)&d_res, pl.runs.size() * sizeof(FlacJobResult)));
+    HIP(hipMalloc((void **)&d_tab, pl.tab_bytes));
+    HIP(hipMalloc((void **)&d_cnt, tracks * 2 * sizeof(unsigned long long)));
+    HIP(hipMemset(d_cnt, 0, tracks * 2 * sizeof(unsigned long long)));
+    const std::vector<unsigned char> tab = bind_flac(pl, FlacBases{{d_stage[0], d_stage[1]}, d_slots, d_bits, d_foff, d_res, d_tab, d_cnt}, reqs.data(), tracks, chan.data());
+    HIP(hipMemcpy(d_tab, tab.data(), tab.size(), hipMemcpyHostToDevice));
+    const FlacJob *d_jobs = reinterpret_cast<const FlacJob *>(d_tab);
+
+    hipEvent_t ev[4];
+    for (auto &e : ev) HIP(hipEventCreate(&e));
+    std::vector<double> ts[3];
+    uint32_t units = 0, blocks = 0;
+    for (int rep = -1; rep < reps; rep++) {  // (rep -1 warms up)
+        double sum[3] = {0, 0, 0};
+        units = blocks = 0;
+        for (size_t p = 0; p < pl.pieces.size(); p++) {
+            const FlacPiece &pc = pl.pieces[p];
+            const uint32_t nj = (uint32_t)(pc.run1 - pc.run0);
+            HIP(hipEventRecord(ev[0], nullptr));
+            HIP(launch_flac_subframes(d_jobs + pc.run0, nj, pc.n_units, nullptr));
+            HIP(hipEventRecord(ev[1], nullptr));
+            HIP(launch_flac_scan(d_jobs + pc.run0, nj, nullptr));
+            HIP(hipEventRecord(ev[2], nullptr));
+            HIP(launch_flac_frames(d_jobs + pc.run0, nj, pc.n_blocks, nullptr));
+            HIP(hipEventRecord(ev[3], nullptr));
+            HIP(hipEventSynchronize(ev[3]));
+            for (int k = 0; k < 3; k++) {
+                float ms = 0;
+                HIP(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+                sum[k] += ms;
+            }
+            units += pc.n_units;
+            blocks += pc.n_blocks;
+        }
+        if (rep >= 0)
+            for (int k = 0; k < 3; k++) ts[k].push_back(sum[k]);
+    }
+    std::vector<FlacJobResult> res(pl.runs.size());
+    HIP(hipMemcpy(res.data(), d_res, res.size() * sizeof(FlacJobResult), hipMemcpyDeviceToHost));
+    unsigned long long bytes = 0;
+    for (const FlacJobResult &r : res) bytes += r.bytes;
+    std::printf("{\"input\": \"%s\", \"tracks\": %zu, \"samples\": %llu, \"pieces\": %zu, \"units\": %u, \"frames\": %u, \"reps\": %d, "
+                "\"subframe_kernel_ms\": %.3f, \"scan_kernel_ms\": %.3f, \"frame_kernel_ms\": %.3f, \"frame_bytes\": %llu, \"pcm_bytes\": %llu}\n",
+                noise ? "noise" : "music", tracks, (unsigned long long)(tracks * n_ch * n), pl.pieces.size(), units, blocks, reps, median(ts[0]),
+                median(ts[1]), median(ts[2]), bytes, (unsigned long long)(tracks * n_ch * n * 2));
+    return 0;
+}

@@ -350,6 +350,60 @@ class _ExportMethods:
         return out.tobytes(), _export_info_dict(info)
 
 
+    def export_flac(self, requests, out: Optional[np.ndarray] = None):
+        """th_tm_export_flac: requests as export_pcm (fmt PCM_S16 or PCM_S24) -> (uint8 buffer, list of info dicts); request i's
+        complete FLAC file image is buffer[offset: offset + n_bytes], lossless for the bytes export_pcm returns for the same request"""
+        reqs = [_export_request(r) for r in requests]
+        n = len(reqs)
+        if n == 0:
+            return np.empty(0, np.uint8), []
+        arr = (_ffi.ExportRequest * n)(*reqs)
+        info = (_ffi.ExportInfo * n)()
+        need = C.c_size_t()
+        fn = getattr(lib, self._PFX + "export_flac")
+        if out is None:
+            rc = fn(self.handle, arr, n, None, 0, info, C.byref(need))
+            if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+                check(rc)
+            out = np.empty(max(need.value, 1), np.uint8)
+        check(fn(self.handle, arr, n, out.ctypes.data, out.size, info, C.byref(need)))
+        return out[:need.value], [_export_info_dict(o) for o in info]
+
+
+FLAC_BLOCK = 4096
+
+
+def flac_bound(n_frames: int, n_channels: int, fmt: int) -> int:
+    """th_flac_bound: the most bytes a FLAC file image of n_frames frames can take (host)"""
+    b = C.c_uint64()
+    check(lib.th_flac_bound(n_frames, n_channels, fmt, C.byref(b)))
+    return b.value
+
+
+def flac_frame_header(sr: int, n_channels: int, fmt: int, frame_number: int, block_len: int) -> bytes:
+    """th_flac_frame_header: sync .. CRC-8 of one frame of the export's FLAC stream (host)"""
+    out = (C.c_uint8 * 16)()
+    ln = C.c_size_t()
+    check(lib.th_flac_frame_header(sr, n_channels, fmt, frame_number, block_len, out, C.byref(ln)))
+    return bytes(out[:ln.value])
+
+
+def flac_encode_i32(channels, fmt: int, sr: int) -> bytes:
+    """th_flac_encode_i32: planar int32 channels (n_ch, n) -> the FLAC file image th_tm_export_flac makes of those integers (host)"""
+    x = np.ascontiguousarray(channels, dtype=np.int32)
+    if x.ndim == 1:
+        x = x[None, :]
+    n_ch, n = x.shape
+    ptrs = (C.POINTER(C.c_int32) * max(n_ch, 1))(*[x[c].ctypes.data_as(C.POINTER(C.c_int32)) for c in range(n_ch)])
+    need = C.c_size_t()
+    rc = lib.th_flac_encode_i32(ptrs, n_ch, n, fmt, sr, None, 0, C.byref(need))
+    if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+        check(rc)
+    out = np.empty(max(need.value, 1), np.uint8)
+    check(lib.th_flac_encode_i32(ptrs, n_ch, n, fmt, sr, out.ctypes.data, out.size, C.byref(need)))
+    return out[:need.value].tobytes()
+
+
 def resample_plan(sr_in: int, sr_out: int) -> dict:
     """th_resample_plan_for -> {L, M, half_taps, rho, cutoff} of the polyphase resampler sr_in -> sr_out (host)"""
     p = _ffi.ResamplePlan()

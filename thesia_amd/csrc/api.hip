@@ -2,6 +2,7 @@
 // device-pointer ("layer A") entry points.  The TrackManager mirror lives in track_manager.hip.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -12,6 +13,7 @@
 #include "common.h"
 #include "context.h"
 #include "export_core.h"
+#include "flac_block.h"
 #include "host_math.h"
 #include "kernels.h"
 #include "mel_fuse.h"
@@ -1523,6 +1525,85 @@ TH_API int th_wav_header(uint32_t format, uint32_t sr, uint32_t n_ch, uint64_t n
                          size_t *header_len, size_t *pad_len) {
     TH_TRY
     return tmi::wav_header_checked(format, sr, n_ch, n_frames, out, header_len, pad_len);
+    TH_CATCH
+}
+
+// ---- the FLAC stream on the host (flac_core.h and flac_block.h are what the kernels run too)
+namespace th {
+namespace tmi {
+int flac_stream_checked(uint32_t sr, uint32_t n_ch, uint32_t format, uint64_t n_frames) {
+    TH_REQUIRE(format == TH_PCM_S16 || format == TH_PCM_S24, "a FLAC stream is TH_PCM_S16 or TH_PCM_S24 (format %u)", format);
+    TH_REQUIRE(n_ch != 0 && sr != 0, "a FLAC stream needs at least one channel and a sample rate (%u channels at %u Hz)", n_ch, sr);
+    if (n_ch > FLAC_MAX_CHANNELS || sr > FLAC_MAX_RATE || n_frames >= FLAC_MAX_SAMPLES)
+        return fail(TH_ERR_UNSUPPORTED, "%llu frames of %u channels at %u Hz do not fit a FLAC stream (8 channels, 1048575 Hz, 2^36 - 1 frames)",
+                    (unsigned long long)n_frames, n_ch, sr);
+    return TH_OK;
+}
+}  // namespace tmi
+}  // namespace th
+
+TH_API int th_flac_bound(uint64_t n_frames, uint32_t n_ch, uint32_t format, uint64_t *bytes) {
+    TH_TRY
+    TH_REQUIRE(bytes, "NULL argument");
+    TH_CHECK(tmi::flac_stream_checked(1, n_ch, format, n_frames));
+    *bytes = flac_stream_bound(n_frames, n_ch, flac_bps(format));
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_flac_frame_header(uint32_t sr, uint32_t n_ch, uint32_t format, uint64_t frame_number, uint32_t block_len, uint8_t out[16],
+                                size_t *len) {
+    TH_TRY
+    TH_REQUIRE(out && len, "NULL argument");
+    TH_CHECK(tmi::flac_stream_checked(sr, n_ch, format, 0));
+    TH_REQUIRE(block_len >= 1 && block_len <= FLAC_BLOCK, "a block of %u samples (1 .. %u)", block_len, FLAC_BLOCK);
+    TH_REQUIRE(frame_number < FLAC_MAX_SAMPLES, "frame number %llu (below 2^36)", (unsigned long long)frame_number);
+    *len = flac_frame_header(sr, n_ch, flac_bps(format), frame_number, block_len, out);
+    return TH_OK;
+    TH_CATCH
+}
+
+TH_API int th_flac_encode_i32(const int32_t *const *chan, uint32_t n_ch, uint64_t n, uint32_t format, uint32_t sr, uint8_t *out, size_t cap,
+                              size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(out_len && (n == 0 || chan), "NULL argument");
+    *out_len = 0;
+    TH_CHECK(tmi::flac_stream_checked(sr, n_ch, format, n));
+    const uint32_t bps = flac_bps(format);
+    const int32_t lim = 1 << (bps - 1);
+    for (uint32_t c = 0; c < n_ch && n; c++) {
+        TH_REQUIRE(chan[c], "NULL argument");
+        for (uint64_t i = 0; i < n; i++)
+            TH_REQUIRE(chan[c][i] >= -lim && chan[c][i] < lim, "channel %u sample %llu is not a %u-bit integer", c, (unsigned long long)i, bps);
+    }
+    const uint64_t bound = flac_stream_bound(n, n_ch, bps);
+    *out_len = (size_t)bound;
+    if (!out || cap < bound) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %llu bytes", (unsigned long long)bound);
+    // the device's pipeline, run by run: pieces, slots, tables and staging of the plan's sizes
+    const FlacPlanRequest pr{n_ch, format, TH_DITHER_NONE, 0u, sr, 0, n, 0};
+    FlacPlan pl = plan_flac(&pr, 1, TH_EXPORT_PIECE_BYTES);
+    if (pl.err != TH_OK) return fail(pl.err, "%s", pl.err_text.c_str());
+    uint64_t at = FLAC_STREAM_HEADER;
+    uint32_t mn = 0xffffffffu, mx = 0;
+    for (size_t pi = 0; pi < pl.pieces.size(); pi++) {
+        const FlacPiece &pc = pl.pieces[pi];
+        std::vector<uint8_t> stage(pc.bound);
+        std::vector<uint32_t> slots(pc.slot_words), bits(pc.n_units), foff(pc.n_blocks);
+        std::vector<FlacJobResult> res(pl.runs.size());
+        std::vector<unsigned char> tab_mem(pl.tab_bytes);
+        bind_flac(pl, FlacBases{{stage.data(), stage.data()}, slots.data(), bits.data(), foff.data(), res.data(), tab_mem.data(), nullptr}, &pr, 1,
+                  nullptr);
+        for (size_t k = pc.run0; k < pc.run1; k++) {
+            flac_run_job_host(pl.jobs[k], chan, nullptr);
+            std::memcpy(out + at, pl.jobs[k].dst, res[k].bytes);
+            at += res[k].bytes;
+            mn = std::min(mn, res[k].min_frame);
+            mx = std::max(mx, res[k].max_frame);
+        }
+    }
+    flac_stream_header(sr, n_ch, bps, n, mx ? mn : 0u, mx, out);
+    *out_len = (size_t)at;
+    return TH_OK;
     TH_CATCH
 }
 

@@ -13,6 +13,7 @@
 #include "stft_core.h"
 #include "envelope_plan.h"  // EnvJob, LaneSpanJob, LaneRasterJob, ENV_* (the chunk grid of kernels_envelope.hip)
 #include "formant_plan.h"  // FormantJob
+#include "flac_plan.h"  // FlacJob
 #include "figure_plan.h"  // FigHJob, FigVJob, FIG_* (the tile shape of kernels_figure.hip)
 #include "reader_plan.h"  // LoudJob, LoudTrackJob, TruePeakJob, ExportJob, ResampleJob, ResampleTiling and their constants
 #include "stft_plan.h"  // WavePostJob, MelJob, MEL_TILE_FRAMES, MEL_ROWS_*
@@ -288,6 +289,12 @@ hipError_t launch_resample(const ResampleJob *d_jobs, uint32_t n_jobs, uint32_t 
 // ---- kernels_band.hip: one FIR row for every output (BandJob, BandTiling: reader_plan.h)
 // row: t.taps floats (host_math.h band_row); n_blocks: the sum over the jobs
 hipError_t launch_band(const BandJob *d_jobs, uint32_t n_jobs, uint32_t n_blocks, const float *d_row, const BandTiling &t, hipStream_t s);
+
+// ---- kernels_flac.hip: the FLAC encoder of a piece (FlacJob: flac_plan.h), three launches in stream order.  n_units: the piece's
+// (block, channel) pairs; n_blocks: its blocks
+hipError_t launch_flac_subframes(const FlacJob *d_jobs, uint32_t n_jobs, uint32_t n_units, hipStream_t s);
+hipError_t launch_flac_scan(const FlacJob *d_jobs, uint32_t n_jobs, hipStream_t s);
+hipError_t launch_flac_frames(const FlacJob *d_jobs, uint32_t n_jobs, uint32_t n_blocks, hipStream_t s);
 
 // ---- kernels_figure.hip: a region of a u16 image at any pixel size (FigHJob, FigVJob: figure_plan.h).  n_blocks: the sum over the jobs
 hipError_t launch_figure_hpass(const FigHJob *d_jobs, uint32_t n_jobs, uint32_t n_blocks, hipStream_t s);

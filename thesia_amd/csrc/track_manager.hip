@@ -30,6 +30,8 @@
 #include "context.h"
 #include "export_core.h"
 #include "figure_plan.h"
+#include "flac_core.h"
+#include "flac_plan.h"
 #include "host_math.h"
 #include "kernels.h"
 #include "resample_core.h"
@@ -98,6 +100,12 @@ struct ReaderSlot {
     size_t band_table_cap = 0;  // floats
     uint32_t band_sr = 0;       // the rate and the plan band_table holds (0: none)
     th_band_plan band{};
+    // th_tm_export_flac: the subframe slots of one piece (words; at most a piece's bound and a word per unit), the call's table (jobs,
+    // channel pointers) and the piece's tables with the call's results (bit lengths, frame offsets, one FlacJobResult per job).  The
+    // staging buffers, counters, copy stream and events are the export's.  Empty until the slot's first FLAC call
+    th::DeviceBuf<uint32_t> flac_slots;
+    size_t flac_slots_cap = 0;  // words
+    th::DeviceTable flac_tab, flac_aux;
     // th_tm_render_figures: two staging buffers (each at most TH_FIGURE_PIECE_BYTES), the horizontal pass's intermediate of one piece
     // (u16; at most TH_FIGURE_TMP_BYTES unless one output row alone needs more) and the call's table (tap tables, then the job tables).
     // The copy stream and its events are the export's.  Empty until the slot's first figure
@@ -2771,6 +2779,155 @@ TH_API int th_tm_export_wav_band(th_tm *tm, const th_export_band_request *req, u
     TH_REQUIRE(req, "NULL argument");
     const tmi::ExportReq one = tmi::export_req(*req);
     return export_wav_any(tm, &one, out, cap, info, out_len);
+    TH_CATCH
+}
+
+// ---------------------------------------------------------------------------------------------- FLAC export
+// th_tm_export_flac: a reader.  plan_flac (flac_plan.h) cuts the requests into pieces of whole blocks and bind_flac gives the jobs
+// their addresses; what is left here is the slot, its buffers, the upload and the pipeline of the two streams: per piece the three
+// launches of kernels_flac.hip into staging buffer p & 1, the jobs' lengths read back on the copy stream, then one copy per job to
+// where its request's file has got to, while the next piece is encoded.  The host writes the 42 header bytes of each file last.
+namespace th {
+namespace tmi {
+int flac_request_info(th_tm *tm, const th_export_request &r, size_t i, ExportInfo *info) {
+    // (where the export checks the format: behind the track and `which`)
+    if (tm->tracks.count(r.id) && r.which <= 2) TH_REQUIRE(r.format != TH_PCM_F32, "request %zu: FLAC is TH_PCM_S16 or TH_PCM_S24", i);
+    TH_CHECK(export_request_info(tm, export_req(r), i, info));
+    const uint64_t frames = info->sample_end - info->sample_start;
+    TH_CHECK(flac_stream_checked(info->sr, info->n_channels, r.format, frames));
+    info->n_bytes = flac_stream_bound(frames, info->n_channels, flac_bps(r.format));
+    return TH_OK;
+}
+
+size_t FlacReader::layout(ExportInfo *info, size_t n) {
+    uint64_t at = 0, end = 0;
+    for (size_t i = 0; i < n; i++) {
+        info[i].offset = at;
+        info[i].pad = 0;
+        end = at + info[i].n_bytes;
+        at = (end + 15) & ~(uint64_t)15;
+    }
+    return (size_t)end;
+}
+
+namespace {
+struct FlacProgress {  // per request: the file's length so far, its smallest and largest frame
+    uint64_t at = FLAC_STREAM_HEADER;
+    uint32_t mn = 0xffffffffu, mx = 0;
+};
+int flac_run_pieces(th_tm *tm, FlacPlan &pl, const std::vector<FlacPlanRequest> &prs, const std::vector<const float *> &chan, ExportInfo *info,
+                    uint8_t *out, std::vector<FlacProgress> &prog) {
+    const size_t n = prs.size();
+    const std::vector<FlacPiece> &pieces = pl.pieces;
+    TH_HIP(hipSetDevice(tm->ctx->device));
+    SlotLease lease{tm, nullptr};
+    int rc = acquire_slot(tm, &lease.slot);
+    if (rc != TH_OK) return rc;
+    ReaderSlot &sl = *lease.slot;
+    if (!sl.exp_copy) {
+        TH_HIP(hipStreamCreateWithFlags(&sl.exp_copy, hipStreamNonBlocking));
+        for (int b = 0; b < 2; b++) {
+            TH_HIP(hipEventCreateWithFlags(&sl.exp_done[b], hipEventDisableTiming));
+            TH_HIP(hipEventCreateWithFlags(&sl.exp_copied[b], hipEventDisableTiming));
+        }
+    }
+    std::vector<FlacJobResult> res(pl.runs.size());  // (behind the drain: alive until the copies are done)
+    ExportDrain drain{&sl};
+    for (int b = 0; b < 2; b++)
+        TH_CHECK(grow_export_buf(sl, sl.exp_stage[b], sl.exp_stage_cap[b], pl.stage_need[b], 1 << 20, EXPORT_STAGE_MAX, sl.exp_copy));
+    // (words) powers of two from 1 MiB, never above a piece's bound and a word per unit (a slot is its subframe's verbatim size
+    // rounded up to a word: the planner cannot ask for more)
+    constexpr size_t slot_ceil = (size_t)TH_EXPORT_PIECE_BYTES / 4 + 2 * (size_t)FLAC_PIECE_MAX_UNITS;
+    if (pl.slot_need > slot_ceil || pl.stage_need[0] > EXPORT_STAGE_MAX || pl.stage_need[1] > EXPORT_STAGE_MAX)
+        return fail(TH_ERR_INTERNAL, "a FLAC piece of %llu slot words and %llu / %llu staged bytes is beyond the slot's bounds",
+                    (unsigned long long)pl.slot_need, (unsigned long long)pl.stage_need[0], (unsigned long long)pl.stage_need[1]);
+    TH_CHECK(grow_export_buf(sl, sl.flac_slots, sl.flac_slots_cap, pl.slot_need, 1 << 18, slot_ceil, nullptr));
+    const size_t o_foff = (size_t)pl.unit_need * 4, o_res = (o_foff + (size_t)pl.block_need * 4 + 15) & ~(size_t)15;
+    TH_CHECK(sl.flac_aux.ensure(o_res + pl.runs.size() * sizeof(FlacJobResult)));
+    TH_CHECK(sl.flac_tab.ensure(pl.tab_bytes));
+    TH_CHECK(sl.exp_cnt.ensure(n * 2 * sizeof(unsigned long long)));
+    unsigned char *d_tab = static_cast<unsigned char *>(sl.flac_tab.dptr), *d_aux = static_cast<unsigned char *>(sl.flac_aux.dptr);
+    unsigned long long *d_cnt = static_cast<unsigned long long *>(sl.exp_cnt.dptr);
+    FlacJobResult *d_res = reinterpret_cast<FlacJobResult *>(d_aux + o_res);
+    const std::vector<unsigned char> tab =
+        bind_flac(pl, FlacBases{{sl.exp_stage[0].get(), sl.exp_stage[1].get()}, sl.flac_slots.get(), reinterpret_cast<uint32_t *>(d_aux),
+                                reinterpret_cast<uint32_t *>(d_aux + o_foff), d_res, d_tab, d_cnt}, prs.data(), n, chan.data());
+    TH_CHECK(sl.flac_tab.upload(sl.stream, tab.data(), tab.size()));
+    TH_HIP(hipMemsetAsync(d_cnt, 0, n * 2 * sizeof(unsigned long long), sl.stream));
+    const FlacJob *d_jobs = reinterpret_cast<const FlacJob *>(d_tab);
+    auto launch_piece = [&](size_t p) -> int {
+        const FlacPiece &pc = pieces[p];
+        const uint32_t nj = (uint32_t)(pc.run1 - pc.run0);
+        if (p >= 2) TH_HIP(hipStreamWaitEvent(sl.stream, sl.exp_copied[p & 1], 0));  // (the buffer's last piece has left it)
+        TH_HIP(launch_flac_subframes(d_jobs + pc.run0, nj, pc.n_units, sl.stream));
+        TH_HIP(launch_flac_scan(d_jobs + pc.run0, nj, sl.stream));
+        TH_HIP(launch_flac_frames(d_jobs + pc.run0, nj, pc.n_blocks, sl.stream));
+        TH_HIP(hipEventRecord(sl.exp_done[p & 1], sl.stream));
+        return TH_OK;
+    };
+    TH_CHECK(launch_piece(0));
+    for (size_t p = 0; p < pieces.size(); p++) {
+        const FlacPiece &pc = pieces[p];
+        if (p + 1 < pieces.size()) TH_CHECK(launch_piece(p + 1));  // (ahead of the read-back, which holds the host)
+        TH_HIP(hipStreamWaitEvent(sl.exp_copy, sl.exp_done[p & 1], 0));
+        TH_HIP(hipMemcpyAsync(res.data() + pc.run0, d_res + pc.run0, (pc.run1 - pc.run0) * sizeof(FlacJobResult), hipMemcpyDeviceToHost, sl.exp_copy));
+        TH_HIP(hipStreamSynchronize(sl.exp_copy));
+        for (size_t k = pc.run0; k < pc.run1; k++) {
+            const FlacRun &run = pl.runs[k];
+            FlacProgress &pg = prog[run.req];
+            if (res[k].bytes > run.bound || pg.at + res[k].bytes > info[run.req].n_bytes)
+                return fail(TH_ERR_INTERNAL, "request %zu: a FLAC job of %llu bytes against a bound of %llu", run.req, res[k].bytes,
+                            (unsigned long long)run.bound);
+            TH_HIP(hipMemcpyAsync(out + info[run.req].offset + pg.at, sl.exp_stage[p & 1].get() + run.stage_at, res[k].bytes, hipMemcpyDeviceToHost,
+                                  sl.exp_copy));
+            pg.at += res[k].bytes;
+            pg.mn = std::min(pg.mn, res[k].min_frame);
+            pg.mx = std::max(pg.mx, res[k].max_frame);
+        }
+        TH_HIP(hipEventRecord(sl.exp_copied[p & 1], sl.exp_copy));
+    }
+    std::vector<unsigned long long> cnt(n * 2);
+    TH_HIP(hipMemcpyAsync(cnt.data(), d_cnt, cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, sl.stream));
+    TH_HIP(hipStreamSynchronize(sl.stream));
+    TH_HIP(hipStreamSynchronize(sl.exp_copy));
+    for (size_t i = 0; i < n; i++) {
+        info[i].n_clamped = cnt[2 * i];
+        info[i].n_nan = cnt[2 * i + 1];
+    }
+    return TH_OK;
+}
+}  // namespace
+
+int flac_run(th_tm *tm, size_t n, ExportInfo *info, uint8_t *out) {
+    std::vector<FlacPlanRequest> prs(n);
+    std::vector<const float *> chan;
+    for (size_t i = 0; i < n; i++) {
+        const th_export_request &r = info[i].req;
+        const Track &tr = *static_cast<const Track *>(info[i].track);
+        prs[i] = FlacPlanRequest{info[i].n_channels, r.format, r.dither, r.seed, tr.sr, info[i].sample_start, info[i].sample_end, info[i].offset};
+        for (const Channel &c : tr.ch) chan.push_back(r.which == 0 ? c.d_wav : r.which == 1 ? c.d_draw : c.d_orig);
+        info[i].n_clamped = info[i].n_nan = 0;
+    }
+    FlacPlan pl = plan_flac(prs.data(), n, TH_EXPORT_PIECE_BYTES);
+    if (pl.err != TH_OK) return fail(pl.err, "%s", pl.err_text.c_str());
+    std::vector<FlacProgress> prog(n);
+    if (!pl.pieces.empty()) TH_CHECK(flac_run_pieces(tm, pl, prs, chan, info, out, prog));
+    for (size_t i = 0; i < n; i++) {  // (the frames are in place: their sizes are known)
+        flac_stream_header(prs[i].sr, prs[i].n_ch, flac_bps(prs[i].format), prs[i].s1 - prs[i].s0, prog[i].mx ? prog[i].mn : 0u, prog[i].mx,
+                           out + info[i].offset);
+        info[i].n_bytes = prog[i].at;
+    }
+    return TH_OK;
+}
+}  // namespace tmi
+}  // namespace th
+
+TH_API int th_tm_export_flac(th_tm *tm, const th_export_request *reqs, size_t n, uint8_t *out, size_t cap, th_export_info *info,
+                             size_t *out_len) {
+    TH_TRY
+    const int rc = br::batched_read<tmi::FlacReader>(TmReaders{tm}, reqs, n, out, cap, info, out_len);
+    tmi::flac_out_len(rc, info, n, out_len);
+    return rc;
     TH_CATCH
 }
 

@@ -189,6 +189,30 @@ std::vector<ExportReq> export_requests(const R *reqs, size_t n) {
 int wav_header_checked(uint32_t format, uint32_t sr, uint32_t n_ch, uint64_t n_frames, uint8_t out[TH_WAV_HEADER_MAX], size_t *header_len,
                        size_t *pad_len);
 
+// FLAC export.  check: the export's own for the same request (F32 refused where the format is checked), then the stream's limits;
+// n_bytes = th_flac_bound.  layout: offsets that are multiples of 16, from the bounds; returns the last offset + the last bound.
+// flac_run: request i's file image to out + info[i].offset, its actual length into info[i].n_bytes, its two counts into info[i].
+// flac_out_len: what *out_len is after a successful call (the last request's offset + its actual length)
+int flac_stream_checked(uint32_t sr, uint32_t n_ch, uint32_t format, uint64_t n_frames);
+int flac_request_info(th_tm *tm, const th_export_request &r, size_t i, ExportInfo *info);
+int flac_run(th_tm *tm, size_t n, ExportInfo *info, uint8_t *out);
+struct FlacReader : br::ReaderDefaults {
+    using Request = th_export_request;
+    using Info = ExportInfo;
+    using Public = th_export_info;
+    using Out = uint8_t;
+    static constexpr const char *unit = "bytes";
+    static constexpr Revision revision = Revision::waveform;
+    static constexpr bool needs_colormap = false, run_updates_infos = true;
+    static size_t id_of(const Request &r) { return r.id; }
+    static int check(th_tm *tm, const Request &r, size_t i, Info *info) { return flac_request_info(tm, r, i, info); }
+    static size_t layout(Info *info, size_t n);
+    static int run(th_tm *tm, size_t n, Info *info, Out *out) { return flac_run(tm, n, info, out); }
+};
+inline void flac_out_len(int rc, const th_export_info *info, size_t n, size_t *out_len) {
+    if (rc == TH_OK && n) *out_len = (size_t)(info[n - 1].offset + info[n - 1].n_bytes);
+}
+
 // Figures.  *info: the record's size and what the plan needs of the request (the resident image; its offset is the layout's to set).
 // layout: offsets that are multiples of 64; returns the last record's end.  figures_run: request i's record to
 // out + info[i].offset, nothing between the records.  The device colormap must exist (ensure_colormap, before the shared lock)

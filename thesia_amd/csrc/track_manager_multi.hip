@@ -603,6 +603,16 @@ TH_API int th_tmg_export_wav(th_tmg *g, const th_export_request *req, uint8_t *o
     TH_CATCH
 }
 
+// FLAC: a slot writes its requests' files at the batch's offsets; the actual lengths and the counts come back into infos
+TH_API int th_tmg_export_flac(th_tmg *g, const th_export_request *reqs, size_t n, uint8_t *out, size_t cap, th_export_info *info,
+                              size_t *out_len) {
+    TH_TRY
+    const int rc = br::batched_read<tmi::FlacReader>(TmgReaders{g}, reqs, n, out, cap, info, out_len);
+    tmi::flac_out_len(rc, info, n, out_len);
+    return rc;
+    TH_CATCH
+}
+
 TH_API int th_tmg_export_pcm_at(th_tmg *g, const th_export_at_request *reqs, size_t n, uint8_t *out, size_t cap, th_export_info *info,
                                 size_t *out_len) {
     TH_TRY
