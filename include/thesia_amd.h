@@ -910,7 +910,8 @@ TH_API int th_tm_export_wav_band(th_tm *tm, const th_export_band_request *req, u
  *   sum(u >> k) + m (k + 1) over its m residuals, k in 0 .. 14 with 4-bit parameters (coding method 0) at 16 bit, 0 .. 30 with 5-bit
  *   parameters (method 1) at 24 bit; cost(o) = o bps + 6 + sum over the partitions of (parameter bits + residual bits); the lowest
  *   order of the smallest cost wins.  VERBATIM when that cost >= n bps, and always for n <= 4 unless CONSTANT.
- *   Not in the stream: LPC subframes, stereo decorrelation, a searched partition order, the MD5, seek tables and comments.
+ *   Not in this stream: LPC subframes and stereo decorrelation (the _ex entries below add them by flags), a searched partition
+ *   order, the MD5, seek tables and comments.
  * Layout.  Sizes are not known before encoding, so the offsets come from bounds: offset[0] = 0, offset[i + 1] = offset[i] +
  * th_flac_bound(request i) rounded up to 16, with th_flac_bound = 42 + per block (16 bytes of frame header at most + n_ch x (1 +
  * n bps / 8) bytes of verbatim subframes + 1 byte of padding + 2 of CRC-16).  A size query (out == NULL or cap_bytes too small:
@@ -935,6 +936,48 @@ TH_API int th_flac_encode_i32(const int32_t *const *chan, uint32_t n_ch, uint64_
                               size_t cap, size_t *out_len);
 TH_API int th_tm_export_flac(th_tm *tm, const th_export_request *reqs, size_t n, uint8_t *out, size_t cap_bytes,
                              th_export_info *info /* n */, size_t *out_len);
+
+/* The _ex entries: the same export with two more coding tools, chosen by flags.  flags == 0 gives the bytes of the entries above, byte
+ * for byte; a bit outside TH_FLAC_LPC | TH_FLAC_STEREO is TH_ERR_INVALID_ARG (checked where the format is).  Request, sample-range
+ * rule, error order, offsets from th_flac_bound, size query, info, revision, pieces and reader slot: those of th_tm_export_flac.  The
+ * stream is a function of the samples and the flags alone, and th_flac_encode_i32_ex is the same source run on the host: the same
+ * file, byte for byte.  All rules are integer arithmetic, or f64 in a fixed serial order (one rounded operation after the other, no
+ * fused multiply-add).
+ *   TH_FLAC_LPC: per subframe, LPC predictors of order 1 .. TH_FLAC_LPC_MAX_ORDER join the candidates, wherever the fixed predictors
+ *   are tried (n >= 5, not CONSTANT).  For a block s[0 .. n) of one coded channel:
+ *   1. Window: w[i] = (((2 i + 1) (2 n - 2 i - 1)) << 14) / (n n) in unsigned 64-bit division (Welch, 0 <= w <= 2^14).  L = the bit
+ *      length of max |s[i]|, sh = max(0, L - 8), x[i] = (s[i] w[i]) >> sh (arithmetic, 64 bit), so |x| < 2^22 at any level.
+ *   2. Autocorrelation r[m] = sum x[i] x[i + m], m = 0 .. min(8, n - 1), exact in int64 (|r| < 2^56).  r[0] == 0: no LPC candidates.
+ *   3. Levinson-Durbin in f64: E = (double)r[0]; for m = 1 ..: acc = (double)r[m], then acc = acc - a[j - 1] (double)r[m - j] for
+ *      j = 1 .. m - 1; k = acc / E; the new a[j - 1] = a[j - 1] - k a[m - j - 1] (from the old ones), a[m - 1] = k; E = E (1 - k k).
+ *      When E is not finite or not > 0, order m and all higher orders are no candidates.
+ *   4. Order m's coefficients in P bits, P = 12 for 16-bit files and 14 for 24-bit files: cmax = max |a|; zero or non-finite: no
+ *      candidate.  e = cmax's binary exponent as frexp gives it; shift = P - e - 1, above 15 set to 15, below 0 no candidate.  With
+ *      fb = 0, for j = 1 .. m: fb = fb + a[j - 1] 2^shift; q[j] = floor(fb + 0.5) clamped to [-2^(P-1), 2^(P-1) - 1]; fb = fb - q[j].
+ *   5. Residual e[i] = s[i] - ((sum over j = 1 .. m of q[j] s[i - j]) >> shift) for i >= m, exact in int64, arithmetic shift.  If any
+ *      e[i] lies outside [-(2^31 - 1), 2^31 - 1], order m is no candidate (checked on every residual).
+ *   6. Cost, exact: partition order p = the largest p <= 6 with 2^p | n and (n >> p) >= max(5, m + 1); Rice parameters as for the
+ *      fixed predictors (all k, the file's coding method); cost(LPC m) = m bps + 4 + 5 + m P + 6 + the partitions.
+ *   7. The candidates are fixed 0 .. 4, then LPC 1 .. 8: the smallest cost wins, the earlier one on ties; VERBATIM when that cost is
+ *      >= n bps.  The subframe (RFC 9639 9.2.6): type 1xxxxx with order - 1, the warm-up samples, 4 bits of P - 1, 5 bits of shift,
+ *      the coefficients q[1] .. q[m] as P-bit two's complement, then the residual as in a FIXED subframe.
+ *   TH_FLAC_STEREO: files of exactly 2 channels only (no effect on others).  Per block four channels are coded from the quantised
+ *   integers: L and R at bps bits, M = (L + R) >> 1 at bps bits, S = L - R at bps + 1 bits, each by the rules above (LPC candidates
+ *   only with TH_FLAC_LPC; for S, warm-up, CONSTANT and VERBATIM sizes and the VERBATIM threshold use bps + 1; the Rice method and P
+ *   stay the file's).  The frame takes the assignment of the fewest subframe bits, the earlier one on ties: independent L R (code
+ *   0001), left/side L S (1000), side/right S R (1001), mid/side M S (1010).  Only the header's assignment bits and CRC-8 change.
+ *   Every subframe is a minimum over a superset of the flags == 0 candidates and "independent" is among the assignments, so no
+ *   frame is longer than the flags == 0 frame: th_flac_bound, the offsets and the size query are unchanged and still bounds, and the
+ *   decoded samples are the bytes th_tm_export_pcm returns whatever the flags.  A slot's subframe scratch with TH_FLAC_STEREO: four
+ *   units per stereo block, each of the side channel's verbatim size (at most 3 x TH_EXPORT_PIECE_BYTES + 4 bytes x 65 536 units).
+ *   Not in the stream: a searched partition order, orders above 8, the MD5, seek tables and comments. */
+#define TH_FLAC_LPC 1u    /* LPC subframes of order 1 .. TH_FLAC_LPC_MAX_ORDER among the candidates */
+#define TH_FLAC_STEREO 2u /* for 2-channel files: the cheapest of the four channel assignments per frame */
+#define TH_FLAC_LPC_MAX_ORDER 8
+TH_API int th_flac_encode_i32_ex(const int32_t *const *chan, uint32_t n_ch, uint64_t n, uint32_t format, uint32_t sr, uint32_t flags,
+                                 uint8_t *out, size_t cap, size_t *out_len);
+TH_API int th_tm_export_flac_ex(th_tm *tm, const th_export_request *reqs, size_t n, uint32_t flags, uint8_t *out, size_t cap_bytes,
+                                th_export_info *info /* n */, size_t *out_len);
 
 /* ---------------------------------------------------------------- Export as figures: a spectrogram region at any pixel size */
 /* Any region of a channel's resident u16 image, resampled on the device to any pixel size and coloured (or left as 16-bit grey): what
@@ -1301,6 +1344,8 @@ TH_API int th_tmg_export_wav_band(th_tmg *tmg, const th_export_band_request *req
 /* FLAC export: as above; every slot keeps its own FLAC scratch, files and infos are those of one th_tm */
 TH_API int th_tmg_export_flac(th_tmg *tmg, const th_export_request *reqs, size_t n, uint8_t *out, size_t cap_bytes,
                               th_export_info *info /* n */, size_t *out_len);
+TH_API int th_tmg_export_flac_ex(th_tmg *tmg, const th_export_request *reqs, size_t n, uint32_t flags, uint8_t *out, size_t cap_bytes,
+                                 th_export_info *info /* n */, size_t *out_len);
 
 /* figures: every request goes to its owning slot and the slots are served side by side, each copying its records straight into the
  * caller's buffer; bytes, offsets and infos are those of one th_tm, the revision stamped is the manager's own */

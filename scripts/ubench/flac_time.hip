@@ -1,11 +1,11 @@
-// flac_time.hip — the three kernels of th_tm_export_flac timed apart by hipEvents: flac_subframe_kernel, flac_scan_kernel and
+// flac_time.hip — the three kernels of th_tm_export_flac / th_tm_export_flac_ex timed apart by hipEvents: flac_subframe_kernel, flac_scan_kernel and
 // flac_frame_kernel, compiled from the product's sources, on the plan the reader itself makes (plan_flac / bind_flac) for T stereo
 // tracks x S seconds at 48 kHz, 16 bit TPDF, on music-like (decaying partials over a noise floor) or noise input.  Per repetition
 // the times are summed over the call's pieces; the median over the repetitions is printed.  A child process of
 // scripts/bench_flac.py; prints one JSON line.  From the repository root (one line):
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off scripts/ubench/flac_time.hip thesia_amd/csrc/flac_plan.cpp
 //         -o scripts/ubench/flac_time
-// Usage: flac_time [music|noise] [seconds 30] [tracks 64] [reps 9]
+// Usage: flac_time [music|noise] [seconds 30] [tracks 64] [reps 9] [flags 0]   (flags: TH_FLAC_LPC 1 | TH_FLAC_STEREO 2)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -38,6 +38,7 @@ int main(int argc, char **argv) {
     const double seconds = argc > 2 ? std::atof(argv[2]) : 30.0;
     const size_t tracks = argc > 3 ? (size_t)std::atoi(argv[3]) : 64;
     const int reps = argc > 4 ? std::max(7, std::atoi(argv[4])) : 9;
+    const uint32_t flags = argc > 5 ? (uint32_t)std::atoi(argv[5]) & FLAC_FLAGS : 0u;
     const uint32_t sr = 48000, n_ch = 2;
     const uint64_t n = (uint64_t)(seconds * sr);
     if (n == 0 || tracks == 0) return 1;
@@ -63,7 +64,7 @@ int main(int argc, char **argv) {
     std::vector<const float *> chan;
     uint64_t at = 0;
     for (size_t t = 0; t < tracks; t++) {
-        reqs[t] = FlacPlanRequest{n_ch, TH_PCM_S16, TH_DITHER_TPDF, 1u, sr, 0, n, at};
+        reqs[t] = FlacPlanRequest{n_ch, TH_PCM_S16, TH_DITHER_TPDF, 1u, sr, 0, n, at, flags};
         at += (flac_stream_bound(n, n_ch, 16) + 15) & ~(uint64_t)15;
         for (uint32_t c = 0; c < n_ch; c++) chan.push_back(d_audio + (t * n_ch + c) * n);
     }
@@ -97,7 +98,7 @@ int main(int argc, char **argv) {
             const FlacPiece &pc = pl.pieces[p];
             const uint32_t nj = (uint32_t)(pc.run1 - pc.run0);
             HIP(hipEventRecord(ev[0], nullptr));
-            HIP(launch_flac_subframes(d_jobs + pc.run0, nj, pc.n_units, nullptr));
+            HIP(launch_flac_subframes(d_jobs + pc.run0, nj, pc.n_units, flags, nullptr));
             HIP(hipEventRecord(ev[1], nullptr));
             HIP(launch_flac_scan(d_jobs + pc.run0, nj, nullptr));
             HIP(hipEventRecord(ev[2], nullptr));
@@ -119,9 +120,9 @@ int main(int argc, char **argv) {
     HIP(hipMemcpy(res.data(), d_res, res.size() * sizeof(FlacJobResult), hipMemcpyDeviceToHost));
     unsigned long long bytes = 0;
     for (const FlacJobResult &r : res) bytes += r.bytes;
-    std::printf("{\"input\": \"%s\", \"tracks\": %zu, \"samples\": %llu, \"pieces\": %zu, \"units\": %u, \"frames\": %u, \"reps\": %d, "
+    std::printf("{\"input\": \"%s\", \"flags\": %u, \"tracks\": %zu, \"samples\": %llu, \"pieces\": %zu, \"units\": %u, \"frames\": %u, \"reps\": %d, "
                 "\"subframe_kernel_ms\": %.3f, \"scan_kernel_ms\": %.3f, \"frame_kernel_ms\": %.3f, \"frame_bytes\": %llu, \"pcm_bytes\": %llu}\n",
-                noise ? "noise" : "music", tracks, (unsigned long long)(tracks * n_ch * n), pl.pieces.size(), units, blocks, reps, median(ts[0]),
+                noise ? "noise" : "music", flags, tracks, (unsigned long long)(tracks * n_ch * n), pl.pieces.size(), units, blocks, reps, median(ts[0]),
                 median(ts[1]), median(ts[2]), bytes, (unsigned long long)(tracks * n_ch * n * 2));
     return 0;
 }

@@ -8,7 +8,7 @@ from ._ffi import LIB_PATH, ThError, ChanDesc, ImgDesc, RasterDesc, WaveDesc, Ti
 from .api import (LINEAR, MEL, SPECTRUM_MAX, SPECTRUM_MEAN_AMP, SPECTRUM_MEAN_POWER, Context, ab_variants, DeviceBuffer, Graph, MultiTrackManager, Plan, TileCache, TrackManager, calc_framing_params,  # noqa: F401
                   calc_mel_fb, calc_normalized_win, device_count, gated_loudness, global_db_range, hz_range_to_idx, k_weighting,
                   limiter_params, loudness_n_blocks, loudness_n_short_term, loudness_range, true_peak_filter, normalize_gain, mel_default_n_mel, pitch_f32, pitch_u16, shard_assign, spectrogram_tile_geometry, spectrum_frame_range, stft_n_frames, waveform_tile_geometry,
-                  PCM_S16, PCM_S24, PCM_F32, DITHER_NONE, DITHER_TPDF, audio_sample_range, export_chunk_frames, export_dither, export_quantize, wav_header, FLAC_BLOCK, flac_bound, flac_frame_header, flac_encode_i32,
+                  PCM_S16, PCM_S24, PCM_F32, DITHER_NONE, DITHER_TPDF, audio_sample_range, export_chunk_frames, export_dither, export_quantize, wav_header, FLAC_BLOCK, FLAC_LPC, FLAC_STEREO, FLAC_LPC_MAX_ORDER, flac_bound, flac_frame_header, flac_encode_i32,
                   resample_plan, resample_n_out, resample_coefs, resample_f32, resample_tile,
                   BAND_PASS, BAND_STOP, band_plan, band_coefs, band_response, band_f32,
                   FIGURE_RGBA, FIGURE_GREY16, figure_axis, figure_box,
@@ -19,7 +19,7 @@ from .api import (LINEAR, MEL, SPECTRUM_MAX, SPECTRUM_MEAN_AMP, SPECTRUM_MEAN_PO
 __all__ = ["LINEAR", "MEL", "SPECTRUM_MEAN_AMP", "SPECTRUM_MEAN_POWER", "SPECTRUM_MAX", "Context", "ab_variants", "DeviceBuffer", "Graph", "MultiTrackManager", "Plan", "TileCache", "TrackManager", "ThError", "calc_framing_params",
            "calc_mel_fb", "calc_normalized_win", "device_count", "gated_loudness", "global_db_range", "hz_range_to_idx", "k_weighting",
            "limiter_params", "loudness_n_blocks", "loudness_n_short_term", "loudness_range", "true_peak_filter", "normalize_gain", "mel_default_n_mel", "pitch_f32", "pitch_u16", "shard_assign", "spectrogram_tile_geometry", "spectrum_frame_range", "stft_n_frames", "waveform_tile_geometry",
-           "PCM_S16", "PCM_S24", "PCM_F32", "DITHER_NONE", "DITHER_TPDF", "audio_sample_range", "export_chunk_frames", "export_dither", "export_quantize", "wav_header", "FLAC_BLOCK", "flac_bound", "flac_frame_header", "flac_encode_i32",
+           "PCM_S16", "PCM_S24", "PCM_F32", "DITHER_NONE", "DITHER_TPDF", "audio_sample_range", "export_chunk_frames", "export_dither", "export_quantize", "wav_header", "FLAC_BLOCK", "FLAC_LPC", "FLAC_STEREO", "FLAC_LPC_MAX_ORDER", "flac_bound", "flac_frame_header", "flac_encode_i32",
            "resample_plan", "resample_n_out", "resample_coefs", "resample_f32", "resample_tile",
            "BAND_PASS", "BAND_STOP", "band_plan", "band_coefs", "band_response", "band_f32",
            "FIGURE_RGBA", "FIGURE_GREY16", "figure_axis", "figure_box",

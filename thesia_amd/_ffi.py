@@ -392,6 +392,9 @@ _SIGS = {
     "th_flac_bound": [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)],
     "th_flac_frame_header": [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, c_u8p, c_szp],
     "th_flac_encode_i32": [C.POINTER(C.POINTER(C.c_int32)), C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, c_szp],
+    "th_flac_encode_i32_ex": [C.POINTER(C.POINTER(C.c_int32)), C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, c_szp],
+    "th_tm_export_flac_ex": [vp, C.POINTER(ExportRequest), C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(ExportInfo), c_szp],
+    "th_tmg_export_flac_ex": [vp, C.POINTER(ExportRequest), C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(ExportInfo), c_szp],
     "th_tm_export_flac": [vp, C.POINTER(ExportRequest), C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(ExportInfo), c_szp],
     "th_tmg_export_flac": [vp, C.POINTER(ExportRequest), C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(ExportInfo), c_szp],
     "th_resample_plan_for": [C.c_uint32, C.c_uint32, C.POINTER(ResamplePlan)],

@@ -350,9 +350,10 @@ class _ExportMethods:
         return out.tobytes(), _export_info_dict(info)
 
 
-    def export_flac(self, requests, out: Optional[np.ndarray] = None):
+    def export_flac(self, requests, out: Optional[np.ndarray] = None, flags: Optional[int] = None):
         """th_tm_export_flac: requests as export_pcm (fmt PCM_S16 or PCM_S24) -> (uint8 buffer, list of info dicts); request i's
-        complete FLAC file image is buffer[offset: offset + n_bytes], lossless for the bytes export_pcm returns for the same request"""
+        complete FLAC file image is buffer[offset: offset + n_bytes], lossless for the bytes export_pcm returns for the same request.
+        flags (FLAC_LPC | FLAC_STEREO, or 0): th_tm_export_flac_ex, the smaller files of LPC subframes and stereo decorrelation"""
         reqs = [_export_request(r) for r in requests]
         n = len(reqs)
         if n == 0:
@@ -361,6 +362,9 @@ class _ExportMethods:
         info = (_ffi.ExportInfo * n)()
         need = C.c_size_t()
         fn = getattr(lib, self._PFX + "export_flac")
+        if flags is not None:
+            ex = getattr(lib, self._PFX + "export_flac_ex")
+            fn = lambda h, a, m, o, cap, inf, ln: ex(h, a, m, flags, o, cap, inf, ln)  # noqa: E731
         if out is None:
             rc = fn(self.handle, arr, n, None, 0, info, C.byref(need))
             if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
@@ -371,6 +375,7 @@ class _ExportMethods:
 
 
 FLAC_BLOCK = 4096
+FLAC_LPC, FLAC_STEREO, FLAC_LPC_MAX_ORDER = 1, 2, 8
 
 
 def flac_bound(n_frames: int, n_channels: int, fmt: int) -> int:
@@ -388,19 +393,23 @@ def flac_frame_header(sr: int, n_channels: int, fmt: int, frame_number: int, blo
     return bytes(out[:ln.value])
 
 
-def flac_encode_i32(channels, fmt: int, sr: int) -> bytes:
-    """th_flac_encode_i32: planar int32 channels (n_ch, n) -> the FLAC file image th_tm_export_flac makes of those integers (host)"""
+def flac_encode_i32(channels, fmt: int, sr: int, flags: Optional[int] = None) -> bytes:
+    """th_flac_encode_i32: planar int32 channels (n_ch, n) -> the FLAC file image th_tm_export_flac makes of those integers (host);
+    with flags (FLAC_LPC | FLAC_STEREO, or 0) th_flac_encode_i32_ex, the image of th_tm_export_flac_ex"""
     x = np.ascontiguousarray(channels, dtype=np.int32)
     if x.ndim == 1:
         x = x[None, :]
     n_ch, n = x.shape
     ptrs = (C.POINTER(C.c_int32) * max(n_ch, 1))(*[x[c].ctypes.data_as(C.POINTER(C.c_int32)) for c in range(n_ch)])
     need = C.c_size_t()
-    rc = lib.th_flac_encode_i32(ptrs, n_ch, n, fmt, sr, None, 0, C.byref(need))
+    fn = lib.th_flac_encode_i32
+    if flags is not None:
+        fn = lambda p, c, m, f, r, o, cap, ln: lib.th_flac_encode_i32_ex(p, c, m, f, r, flags, o, cap, ln)  # noqa: E731
+    rc = fn(ptrs, n_ch, n, fmt, sr, None, 0, C.byref(need))
     if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
         check(rc)
     out = np.empty(max(need.value, 1), np.uint8)
-    check(lib.th_flac_encode_i32(ptrs, n_ch, n, fmt, sr, out.ctypes.data, out.size, C.byref(need)))
+    check(fn(ptrs, n_ch, n, fmt, sr, out.ctypes.data, out.size, C.byref(need)))
     return out[:need.value].tobytes()
 
 

@@ -1565,9 +1565,16 @@ TH_API int th_flac_frame_header(uint32_t sr, uint32_t n_ch, uint32_t format, uin
 
 TH_API int th_flac_encode_i32(const int32_t *const *chan, uint32_t n_ch, uint64_t n, uint32_t format, uint32_t sr, uint8_t *out, size_t cap,
                               size_t *out_len) {
+    return th_flac_encode_i32_ex(chan, n_ch, n, format, sr, 0u, out, cap, out_len);
+}
+
+TH_API int th_flac_encode_i32_ex(const int32_t *const *chan, uint32_t n_ch, uint64_t n, uint32_t format, uint32_t sr, uint32_t flags,
+                                 uint8_t *out, size_t cap, size_t *out_len) {
     TH_TRY
     TH_REQUIRE(out_len && (n == 0 || chan), "NULL argument");
     *out_len = 0;
+    TH_REQUIRE(format == TH_PCM_S16 || format == TH_PCM_S24, "a FLAC stream is TH_PCM_S16 or TH_PCM_S24 (format %u)", format);
+    TH_REQUIRE((flags & ~FLAC_FLAGS) == 0, "FLAC flags %#x (TH_FLAC_LPC | TH_FLAC_STEREO)", flags);
     TH_CHECK(tmi::flac_stream_checked(sr, n_ch, format, n));
     const uint32_t bps = flac_bps(format);
     const int32_t lim = 1 << (bps - 1);
@@ -1580,7 +1587,7 @@ TH_API int th_flac_encode_i32(const int32_t *const *chan, uint32_t n_ch, uint64_
     *out_len = (size_t)bound;
     if (!out || cap < bound) return fail(TH_ERR_BUFFER_TOO_SMALL, "need %llu bytes", (unsigned long long)bound);
     // the device's pipeline, run by run: pieces, slots, tables and staging of the plan's sizes
-    const FlacPlanRequest pr{n_ch, format, TH_DITHER_NONE, 0u, sr, 0, n, 0};
+    const FlacPlanRequest pr{n_ch, format, TH_DITHER_NONE, 0u, sr, 0, n, 0, flags};
     FlacPlan pl = plan_flac(&pr, 1, TH_EXPORT_PIECE_BYTES);
     if (pl.err != TH_OK) return fail(pl.err, "%s", pl.err_text.c_str());
     uint64_t at = FLAC_STREAM_HEADER;

@@ -28,19 +28,21 @@ FlacPlan plan_flac(const FlacPlanRequest *reqs, size_t n, uint64_t piece_bytes) 
         const FlacPlanRequest &r = reqs[i];
         pl.chan0[i] = n_ptrs;
         n_ptrs += r.n_ch;
-        if (r.n_ch == 0 || r.n_ch > FLAC_MAX_CHANNELS || r.s1 < r.s0) {
+        if (r.n_ch == 0 || r.n_ch > FLAC_MAX_CHANNELS || r.s1 < r.s0 || (r.flags & ~FLAC_FLAGS)) {
             pl.err = TH_ERR_INTERNAL;
             pl.err_text = "a FLAC request reached the planner unchecked";
             return pl;
         }
         const uint32_t bps = flac_bps(r.format);
+        // units of a block, and the sample size that sizes their slots: a stereo block's four are all as wide as its side channel
+        const uint32_t upb = flac_units_per_block(r.n_ch, r.flags), slot_bps = upb == r.n_ch ? bps : bps + 1u;
         const uint64_t len = r.s1 - r.s0, n_full = len / FLAC_BLOCK;
         const uint32_t rest = (uint32_t)(len % FLAC_BLOCK);
         const uint64_t n_blk = n_full + (rest ? 1 : 0), fb = flac_frame_bound(FLAC_BLOCK, r.n_ch, bps);
         uint64_t b = 0;
         while (b < n_blk) {
             const uint64_t room = piece_bytes > cur.bound ? piece_bytes - cur.bound : 0;
-            const uint64_t units = (FLAC_PIECE_MAX_UNITS - cur.n_units) / r.n_ch;
+            const uint64_t units = (FLAC_PIECE_MAX_UNITS - cur.n_units) / upb;
             uint64_t full = b < n_full ? std::min({n_full - b, room / fb, units}) : 0;
             uint64_t bound = full * fb;
             uint32_t tail = 0;  // the request's short last block, when it comes next and fits
@@ -62,15 +64,15 @@ FlacPlan plan_flac(const FlacPlanRequest *reqs, size_t n, uint64_t piece_bytes) 
                 run.nb = nb;
                 run.first_unit = cur.n_units;
                 run.first_block = cur.n_blocks;
-                run.slot_words = flac_slot_words(n_block, bps);
+                run.slot_words = flac_slot_words(n_block, slot_bps);
                 run.slot_at = cur.slot_words;
                 run.stage_at = cur.bound;
                 run.bound = run_bound;
                 pl.runs.push_back(run);
                 cur.run1 = pl.runs.size();
-                cur.n_units += nb * r.n_ch;
+                cur.n_units += nb * upb;
                 cur.n_blocks += nb;
-                cur.slot_words += (uint64_t)nb * r.n_ch * run.slot_words;
+                cur.slot_words += (uint64_t)nb * upb * run.slot_words;
                 cur.bound += run_bound;
             };
             if (full) push(b, (uint32_t)full, FLAC_BLOCK, bound);
@@ -110,6 +112,7 @@ std::vector<unsigned char> bind_flac(FlacPlan &p, const FlacBases &b, const Flac
             j.seed = r.seed;
             j.sr = r.sr;
             j.slot_words = run.slot_words;
+            j.flags = r.flags;
         }
     }
     size_t n_ptrs = 0;

@@ -19,7 +19,8 @@ static_assert(sizeof(FlacJobResult) == 16, "FlacJobResult must have no implicit 
 
 // ---- kernels_flac.hip.  A job is blocks [b0, b0 + nb) of one request: the whole request, or the part of it that lies in one piece.
 // Block b holds samples s0 + 4096 b .. of the range [s0, s1) and is frame b of the stream.  The subframe kernel runs one workgroup per
-// unit (block-major: unit = block x n_ch + channel), the scan kernel one per job, the frame kernel one per block.
+// unit (block-major: unit = block x units per block + coded channel), the scan kernel one per job, the frame kernel one per block.
+// A block has n_ch units, one per channel; with TH_FLAC_STEREO a 2-channel block has four, L R M S, of which the frame joins two.
 struct FlacJob {
     const float *const *chan;  // n_ch planar f32 channels, indexed by the track's ABSOLUTE sample
     uint32_t *slots;           // the job's units: slot_words words each (the subframe's bits, big-endian in the word)
@@ -34,7 +35,8 @@ struct FlacJob {
     uint32_t first_unit, first_block;  // the job's first workgroup in the subframe / frame kernel's grid
     uint32_t n_ch, format, dither, seed, sr;
     uint32_t slot_words;
-    uint32_t pad_[3];
+    uint32_t flags;            // TH_FLAC_LPC | TH_FLAC_STEREO (0: th_tm_export_flac's stream)
+    uint32_t pad_[2];
 };
 static_assert(sizeof(FlacJob) == 128, "FlacJob must have no implicit padding");
 
@@ -43,6 +45,7 @@ struct FlacPlanRequest {
     uint32_t n_ch, format, dither, seed, sr;
     uint64_t s0, s1;
     uint64_t offset;  // into out
+    uint32_t flags;   // of the call (the _ex entries)
 };
 struct FlacRun {       // a job before it has addresses
     size_t req;

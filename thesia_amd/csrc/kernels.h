@@ -291,8 +291,9 @@ hipError_t launch_resample(const ResampleJob *d_jobs, uint32_t n_jobs, uint32_t 
 hipError_t launch_band(const BandJob *d_jobs, uint32_t n_jobs, uint32_t n_blocks, const float *d_row, const BandTiling &t, hipStream_t s);
 
 // ---- kernels_flac.hip: the FLAC encoder of a piece (FlacJob: flac_plan.h), three launches in stream order.  n_units: the piece's
-// (block, channel) pairs; n_blocks: its blocks
-hipError_t launch_flac_subframes(const FlacJob *d_jobs, uint32_t n_jobs, uint32_t n_units, hipStream_t s);
+// (block, coded channel) pairs; n_blocks: its blocks; flags: the call's TH_FLAC_* (every job of the table carries the same; 0 runs the
+// kernel instance that is compiled without LPC and stereo)
+hipError_t launch_flac_subframes(const FlacJob *d_jobs, uint32_t n_jobs, uint32_t n_units, uint32_t flags, hipStream_t s);
 hipError_t launch_flac_scan(const FlacJob *d_jobs, uint32_t n_jobs, hipStream_t s);
 hipError_t launch_flac_frames(const FlacJob *d_jobs, uint32_t n_jobs, uint32_t n_blocks, hipStream_t s);
 

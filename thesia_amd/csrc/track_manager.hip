@@ -100,7 +100,8 @@ struct ReaderSlot {
     size_t band_table_cap = 0;  // floats
     uint32_t band_sr = 0;       // the rate and the plan band_table holds (0: none)
     th_band_plan band{};
-    // th_tm_export_flac: the subframe slots of one piece (words; at most a piece's bound and a word per unit), the call's table (jobs,
+    // th_tm_export_flac: the subframe slots of one piece (words; at most a piece's bound and a word per unit; with TH_FLAC_STEREO three
+    // times the bound, for a stereo block's four units of the side channel's size), the call's table (jobs,
     // channel pointers) and the piece's tables with the call's results (bit lengths, frame offsets, one FlacJobResult per job).  The
     // staging buffers, counters, copy stream and events are the export's.  Empty until the slot's first FLAC call
     th::DeviceBuf<uint32_t> flac_slots;
@@ -2789,17 +2790,21 @@ TH_API int th_tm_export_wav_band(th_tm *tm, const th_export_band_request *req, u
 // where its request's file has got to, while the next piece is encoded.  The host writes the 42 header bytes of each file last.
 namespace th {
 namespace tmi {
-int flac_request_info(th_tm *tm, const th_export_request &r, size_t i, ExportInfo *info) {
+int flac_request_info(th_tm *tm, const th_export_request &r, uint32_t flags, size_t i, ExportInfo *info) {
     // (where the export checks the format: behind the track and `which`)
-    if (tm->tracks.count(r.id) && r.which <= 2) TH_REQUIRE(r.format != TH_PCM_F32, "request %zu: FLAC is TH_PCM_S16 or TH_PCM_S24", i);
+    if (tm->tracks.count(r.id) && r.which <= 2) {
+        TH_REQUIRE(r.format != TH_PCM_F32, "request %zu: FLAC is TH_PCM_S16 or TH_PCM_S24", i);
+        TH_REQUIRE((flags & ~FLAC_FLAGS) == 0, "request %zu: unknown FLAC flags (TH_FLAC_LPC | TH_FLAC_STEREO)", i);
+    }
     TH_CHECK(export_request_info(tm, export_req(r), i, info));
+    info->flac_flags = flags;
     const uint64_t frames = info->sample_end - info->sample_start;
     TH_CHECK(flac_stream_checked(info->sr, info->n_channels, r.format, frames));
     info->n_bytes = flac_stream_bound(frames, info->n_channels, flac_bps(r.format));
     return TH_OK;
 }
 
-size_t FlacReader::layout(ExportInfo *info, size_t n) {
+size_t flac_layout(ExportInfo *info, size_t n) {
     uint64_t at = 0, end = 0;
     for (size_t i = 0; i < n; i++) {
         info[i].offset = at;
@@ -2836,8 +2841,11 @@ int flac_run_pieces(th_tm *tm, FlacPlan &pl, const std::vector<FlacPlanRequest> 
     for (int b = 0; b < 2; b++)
         TH_CHECK(grow_export_buf(sl, sl.exp_stage[b], sl.exp_stage_cap[b], pl.stage_need[b], 1 << 20, EXPORT_STAGE_MAX, sl.exp_copy));
     // (words) powers of two from 1 MiB, never above a piece's bound and a word per unit (a slot is its subframe's verbatim size
-    // rounded up to a word: the planner cannot ask for more)
-    constexpr size_t slot_ceil = (size_t)TH_EXPORT_PIECE_BYTES / 4 + 2 * (size_t)FLAC_PIECE_MAX_UNITS;
+    // rounded up to a word: the planner cannot ask for more); a stereo block's four units of bps + 1 bits are at most 4 x 17 / (2 x 16)
+    // of the block's bound: three pieces' worth
+    bool four_units = false;
+    for (const FlacPlanRequest &r : prs) four_units |= flac_units_per_block(r.n_ch, r.flags) != r.n_ch;
+    const size_t slot_ceil = (size_t)TH_EXPORT_PIECE_BYTES / 4 * (four_units ? 3 : 1) + 2 * (size_t)FLAC_PIECE_MAX_UNITS;
     if (pl.slot_need > slot_ceil || pl.stage_need[0] > EXPORT_STAGE_MAX || pl.stage_need[1] > EXPORT_STAGE_MAX)
         return fail(TH_ERR_INTERNAL, "a FLAC piece of %llu slot words and %llu / %llu staged bytes is beyond the slot's bounds",
                     (unsigned long long)pl.slot_need, (unsigned long long)pl.stage_need[0], (unsigned long long)pl.stage_need[1]);
@@ -2859,7 +2867,7 @@ int flac_run_pieces(th_tm *tm, FlacPlan &pl, const std::vector<FlacPlanRequest> 
         const FlacPiece &pc = pieces[p];
         const uint32_t nj = (uint32_t)(pc.run1 - pc.run0);
         if (p >= 2) TH_HIP(hipStreamWaitEvent(sl.stream, sl.exp_copied[p & 1], 0));  // (the buffer's last piece has left it)
-        TH_HIP(launch_flac_subframes(d_jobs + pc.run0, nj, pc.n_units, sl.stream));
+        TH_HIP(launch_flac_subframes(d_jobs + pc.run0, nj, pc.n_units, prs[0].flags, sl.stream));  // (one call, one flags value)
         TH_HIP(launch_flac_scan(d_jobs + pc.run0, nj, sl.stream));
         TH_HIP(launch_flac_frames(d_jobs + pc.run0, nj, pc.n_blocks, sl.stream));
         TH_HIP(hipEventRecord(sl.exp_done[p & 1], sl.stream));
@@ -2904,7 +2912,8 @@ int flac_run(th_tm *tm, size_t n, ExportInfo *info, uint8_t *out) {
     for (size_t i = 0; i < n; i++) {
         const th_export_request &r = info[i].req;
         const Track &tr = *static_cast<const Track *>(info[i].track);
-        prs[i] = FlacPlanRequest{info[i].n_channels, r.format, r.dither, r.seed, tr.sr, info[i].sample_start, info[i].sample_end, info[i].offset};
+        prs[i] = FlacPlanRequest{info[i].n_channels, r.format, r.dither, r.seed, tr.sr, info[i].sample_start, info[i].sample_end, info[i].offset,
+                                 info[i].flac_flags};
         for (const Channel &c : tr.ch) chan.push_back(r.which == 0 ? c.d_wav : r.which == 1 ? c.d_draw : c.d_orig);
         info[i].n_clamped = info[i].n_nan = 0;
     }
@@ -2925,9 +2934,14 @@ int flac_run(th_tm *tm, size_t n, ExportInfo *info, uint8_t *out) {
 TH_API int th_tm_export_flac(th_tm *tm, const th_export_request *reqs, size_t n, uint8_t *out, size_t cap, th_export_info *info,
                              size_t *out_len) {
     TH_TRY
-    const int rc = br::batched_read<tmi::FlacReader>(TmReaders{tm}, reqs, n, out, cap, info, out_len);
-    tmi::flac_out_len(rc, info, n, out_len);
-    return rc;
+    return tmi::flac_read(TmReaders{tm}, reqs, n, 0u, out, cap, info, out_len);
+    TH_CATCH
+}
+
+TH_API int th_tm_export_flac_ex(th_tm *tm, const th_export_request *reqs, size_t n, uint32_t flags, uint8_t *out, size_t cap,
+                                th_export_info *info, size_t *out_len) {
+    TH_TRY
+    return tmi::flac_read(TmReaders{tm}, reqs, n, flags, out, cap, info, out_len);
     TH_CATCH
 }
 

@@ -160,6 +160,7 @@ struct ExportInfo : th_export_info {  // + the request, the track (a Track of tr
     size_t n_out;
     th_band_plan band;      // half_taps == 0: no filter
     uint32_t pad;
+    uint32_t flac_flags;    // the FLAC reader's: TH_FLAC_* of the call
 };
 int export_request_info(th_tm *tm, const ExportReq &r, size_t i, ExportInfo *info);
 int export_run(th_tm *tm, size_t n, ExportInfo *info, uint8_t *out);
@@ -192,11 +193,16 @@ int wav_header_checked(uint32_t format, uint32_t sr, uint32_t n_ch, uint64_t n_f
 // FLAC export.  check: the export's own for the same request (F32 refused where the format is checked), then the stream's limits;
 // n_bytes = th_flac_bound.  layout: offsets that are multiples of 16, from the bounds; returns the last offset + the last bound.
 // flac_run: request i's file image to out + info[i].offset, its actual length into info[i].n_bytes, its two counts into info[i].
-// flac_out_len: what *out_len is after a successful call (the last request's offset + its actual length)
+// flac_out_len: what *out_len is after a successful call (the last request's offset + its actual length).
+// The call's flags (th_tm_export_flac: 0) are checked where the format is.  They are the reader's template argument, so every entry
+// hands the caller's requests to the driver as they are: FlacReaderOf<0 .. 3>, and FLAC_FLAGS_UNKNOWN for any other value
 int flac_stream_checked(uint32_t sr, uint32_t n_ch, uint32_t format, uint64_t n_frames);
-int flac_request_info(th_tm *tm, const th_export_request &r, size_t i, ExportInfo *info);
+int flac_request_info(th_tm *tm, const th_export_request &r, uint32_t flags, size_t i, ExportInfo *info);
+size_t flac_layout(ExportInfo *info, size_t n);
 int flac_run(th_tm *tm, size_t n, ExportInfo *info, uint8_t *out);
-struct FlacReader : br::ReaderDefaults {
+constexpr uint32_t FLAC_FLAGS_UNKNOWN = ~0u;
+template <uint32_t FLAGS>
+struct FlacReaderOf : br::ReaderDefaults {
     using Request = th_export_request;
     using Info = ExportInfo;
     using Public = th_export_info;
@@ -205,12 +211,27 @@ struct FlacReader : br::ReaderDefaults {
     static constexpr Revision revision = Revision::waveform;
     static constexpr bool needs_colormap = false, run_updates_infos = true;
     static size_t id_of(const Request &r) { return r.id; }
-    static int check(th_tm *tm, const Request &r, size_t i, Info *info) { return flac_request_info(tm, r, i, info); }
-    static size_t layout(Info *info, size_t n);
+    static int check(th_tm *tm, const Request &r, size_t i, Info *info) { return flac_request_info(tm, r, FLAGS, i, info); }
+    static size_t layout(Info *info, size_t n) { return flac_layout(info, n); }
     static int run(th_tm *tm, size_t n, Info *info, Out *out) { return flac_run(tm, n, info, out); }
 };
+using FlacReader = FlacReaderOf<0u>;
 inline void flac_out_len(int rc, const th_export_info *info, size_t n, size_t *out_len) {
     if (rc == TH_OK && n) *out_len = (size_t)(info[n - 1].offset + info[n - 1].n_bytes);
+}
+// the entry of either manager (m: its adaptor for batched_read)
+template <class M>
+int flac_read(M m, const th_export_request *reqs, size_t n, uint32_t flags, uint8_t *out, size_t cap, th_export_info *info, size_t *out_len) {
+    int rc;
+    switch (flags) {
+        case 0u: rc = br::batched_read<FlacReaderOf<0u>>(m, reqs, n, out, cap, info, out_len); break;
+        case 1u: rc = br::batched_read<FlacReaderOf<1u>>(m, reqs, n, out, cap, info, out_len); break;
+        case 2u: rc = br::batched_read<FlacReaderOf<2u>>(m, reqs, n, out, cap, info, out_len); break;
+        case 3u: rc = br::batched_read<FlacReaderOf<3u>>(m, reqs, n, out, cap, info, out_len); break;
+        default: rc = br::batched_read<FlacReaderOf<FLAC_FLAGS_UNKNOWN>>(m, reqs, n, out, cap, info, out_len); break;
+    }
+    flac_out_len(rc, info, n, out_len);
+    return rc;
 }
 
 // Figures.  *info: the record's size and what the plan needs of the request (the resident image; its offset is the layout's to set).

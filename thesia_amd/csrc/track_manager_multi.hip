@@ -607,9 +607,13 @@ TH_API int th_tmg_export_wav(th_tmg *g, const th_export_request *req, uint8_t *o
 TH_API int th_tmg_export_flac(th_tmg *g, const th_export_request *reqs, size_t n, uint8_t *out, size_t cap, th_export_info *info,
                               size_t *out_len) {
     TH_TRY
-    const int rc = br::batched_read<tmi::FlacReader>(TmgReaders{g}, reqs, n, out, cap, info, out_len);
-    tmi::flac_out_len(rc, info, n, out_len);
-    return rc;
+    return tmi::flac_read(TmgReaders{g}, reqs, n, 0u, out, cap, info, out_len);
+    TH_CATCH
+}
+TH_API int th_tmg_export_flac_ex(th_tmg *g, const th_export_request *reqs, size_t n, uint32_t flags, uint8_t *out, size_t cap,
+                                 th_export_info *info, size_t *out_len) {
+    TH_TRY
+    return tmi::flac_read(TmgReaders{g}, reqs, n, flags, out, cap, info, out_len);
     TH_CATCH
 }
 
