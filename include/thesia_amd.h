@@ -1247,6 +1247,100 @@ TH_API int th_tm_get_formants(th_tm *tm, const th_formant_request *reqs, size_t 
                               th_formant_info *info /* n */, size_t *out_len);
 TH_API int th_tm_get_formant_track(th_tm *tm, const th_formant_request *req, double *out, size_t cap_doubles, th_formant_info *info);
 
+/* ---------------------------------------------------------------- Align two tracks: lag, gain and null depth */
+/* By how many samples a PROBE channel is shifted against a REFERENCE channel, with what gain it matches it, and how deep the two
+ * null once shifted and scaled: the time-domain cross-correlation of a range of the reference with the probe over the lags
+ * -D .. D, in f64, on the resident audio.  No reference implementation exists; these definitions are the contract.
+ *   SIGN CONVENTION.  A positive lag means the probe is LATE: probe[n + l*] matches reference[n].  A host that wants the two on one
+ *   time axis subtracts l* / sr seconds from the probe's time arguments (or draws the probe l* / sr seconds to the left).
+ *   Request and plan.  th_align_request: the reference (ref_id, ref_ch, ref_which) and the probe (id, ch, which), `which` as
+ *   th_tm_copy_audio; the two may be the same track, even the same channel.  [start_sec, end_sec) is a range of the REFERENCE;
+ *   max_lag_sec >= 0, finite; kind TH_ALIGN_OUT_*; flags: TH_ALIGN_ABS or 0.  th_align_plan_for(sr_ref, n_ref, sr, n, req, &plan)
+ *   (host) is the one place where numbers are made from seconds, all in C double: [s0, s1) = th_audio_sample_range(sr_ref, n_ref,
+ *   start_sec, end_sec), N = s1 - s0; D = rint(max_lag_sec sr); the lags are l = -D .. D, n_lags = 2 D + 1, and an empty range has
+ *   n_lags = 0.  TH_ERR_INVALID_ARG: a NaN anywhere, a bad range (as th_audio_sample_range), a negative or infinite max_lag_sec, an
+ *   unknown kind, which or flag bit, a zero rate.  Then TH_ERR_UNSUPPORTED: sr_ref != sr; N > TH_ALIGN_MAX_REF; D >
+ *   TH_ALIGN_MAX_LAG; N n_lags > TH_ALIGN_MAX_WORK.
+ *   Arithmetic.  a[k] = ref[s0 + k], k < N; b[n] = the probe, +0 outside [0, n_b); indices are signed 64-bit.
+ *     r[l] = sum over k < N of (double)a[k] (double)b[s0 + k + l].
+ *   The product of two f32 is exact in f64, so whether a product and its addition are fused changes no bit.  Products with b outside
+ *   the track are formed (with b = +0).  The ORDER of the additions depends on k alone: block j = k div TH_ALIGN_BLOCK (4096);
+ *   inside a block, partial sum q = k mod 4 takes its terms in ascending k, from +0; the block's value is (p0 + p1) + (p2 + p3);
+ *   group g = j div TH_ALIGN_GROUP_BLOCKS (32) adds its blocks' values in ascending j, from +0; r adds the groups' values in ascending
+ *   g, from +0.  It does not depend on the lag, the piece, the batch, the reader slot, or th_tm against th_tmg.
+ *   E(x, first, N): the same order over (double)x[first + k] (double)x[first + k] (x = +0 outside its track).  E_ref = E(ref, s0, N);
+ *   E_probe = E(probe, s0 + l*, N).
+ *   The host's step, on the read-back r, in C double with libm's sqrt and log10 (th_align_peak and the lines below it):
+ *     the result is INVALID when n_lags = 0, when any r[l] or E_ref is not finite, or when E_ref <= 0;
+ *     m = r (with TH_ALIGN_ABS: |r|, so that an inverted copy aligns too); l* = the smallest l at which m is largest;
+ *     polarity = -1 when r[l*] < 0, else +1;
+ *     delta (a parabola's vertex through m at l* - 1, l*, l* + 1): at the first or the last searched lag 0; otherwise den =
+ *     (m- - 2 m0) + m+ and delta = den < 0 ? (0.5 (m- - m+)) / den : 0;
+ *     r* = r[l*]; gain = r* / E_ref; resid = E_probe - r* gain (the product rounded, then the difference), 0 when that is negative;
+ *     rho = r* / sqrt(E_ref E_probe); null_dB = 10 log10(resid / E_probe).
+ *   gain is the factor by which the reference, shifted by l*, best matches the probe in the least-squares sense; null_dB is the energy
+ *   of what is left of the probe's window after that match is subtracted, relative to the window's own energy (-inf: a perfect null).
+ *   Output: doubles, requests back to back in request order.  TH_ALIGN_SUMMARY_DOUBLES = 10 per request: status (0 valid, 1
+ *   invalid), l*, delta, r*, E_ref, E_probe, rho, gain, null_dB, polarity; an invalid result has status 1 and NaN in the other nine.
+ *   kind TH_ALIGN_OUT_CURVE: the n_lags values r[-D .. D] follow (whatever the status).  r is additive over channels: a host that
+ *   wants a joint fit over a track's channels adds their curves.  Where this text says "the same bits", a NaN is a NaN: its sign and
+ *   payload are the machine's.
+ *   info[i]: offset and length in doubles, sr, max_lag = D, [sample_start, sample_end) = [s0, s1), waveform_revision.
+ *   Host functions, which run the kernel's own arithmetic (align_core.h) and give the reader's bits: th_xcorr_f64: r[i] = sum over k <
+ *   n_a of a[k] b[first + i + k] for i < n_lags (a: the reference's range; b: the whole probe; first = s0 + the first lag);
+ *   th_align_energy_f64: E(x, first, n_sum); th_align_peak: the step above up to delta (status, the peak's index into r, delta,
+ *   polarity); th_align_f64: a whole request from two host channels (ids and channels of the request are not looked at).
+ * th_tm_align_tracks / th_tm_align_track: a reader like th_tm_get_formants: shared lock, a reader slot's own stream; out == NULL or a
+ * cap below *out_len: TH_ERR_BUFFER_TOO_SMALL with info and *out_len filled.  The first faulty request in request order decides; of
+ * one request: an unknown probe id, then an unknown reference id: TH_ERR_NOT_FOUND; a bad channel or argument: TH_ERR_INVALID_ARG;
+ * then TH_ERR_UNSUPPORTED as above.  On any error nothing is written to out.
+ * Device memory is BOUNDED.  A request is cut into pieces of at most TH_ALIGN_PIECE_LAGS lags; a piece is one launch of the
+ * correlation kernel (a workgroup: a tile of lags x one group of the reference, its group values into a scratch of n_groups x lags
+ * doubles, at most 16 MiB), one of the fold over the groups into one of two record buffers, and one copy; piece k + 1 computes while
+ * piece k is copied.  The two energies are small launches of the same order, E_probe after the host has found l*. */
+#define TH_ALIGN_MAX_REF (1u << 22)
+#define TH_ALIGN_MAX_LAG (1u << 20)
+#define TH_ALIGN_MAX_WORK (1ull << 40)
+#define TH_ALIGN_PIECE_LAGS 65536u
+#define TH_ALIGN_BLOCK 4096u
+#define TH_ALIGN_GROUP_BLOCKS 32u
+#define TH_ALIGN_SUMMARY_DOUBLES 10u
+#define TH_ALIGN_OUT_SUMMARY 0
+#define TH_ALIGN_OUT_CURVE 1
+#define TH_ALIGN_ABS 1u
+typedef struct {
+    size_t ref_id;
+    uint32_t ref_ch, ref_which; /* which: 0 audio, 1 drawn, 2 original */
+    size_t id;
+    uint32_t ch, which;
+    double start_sec, end_sec;  /* a range of the reference */
+    double max_lag_sec;
+    uint32_t kind, flags;       /* TH_ALIGN_OUT_*; TH_ALIGN_ABS or 0 */
+} th_align_request;
+typedef struct {
+    uint32_t sr, max_lag;       /* max_lag = D */
+    uint32_t kind, flags;
+    uint64_t sample_start, sample_end; /* [s0, s1) of the reference */
+    uint64_t n_lags;            /* 2 D + 1; 0 for an empty range */
+    uint64_t length;            /* doubles of output: TH_ALIGN_SUMMARY_DOUBLES (+ n_lags for TH_ALIGN_OUT_CURVE) */
+} th_align_plan;
+typedef struct {
+    uint64_t offset, length;    /* into out, doubles */
+    uint32_t sr, max_lag;
+    uint64_t sample_start, sample_end;
+    uint64_t waveform_revision;
+} th_align_info;
+TH_API int th_align_plan_for(uint32_t sr_ref, size_t n_ref, uint32_t sr, size_t n, const th_align_request *req, th_align_plan *plan);
+TH_API int th_xcorr_f64(const float *a, size_t n_a, const float *b, size_t n_b, int64_t first, size_t n_lags, double *r /* n_lags */);
+TH_API int th_align_energy_f64(const float *x, size_t n, int64_t first, size_t n_sum, double *energy);
+TH_API int th_align_peak(const double *r, size_t n_lags, uint32_t flags, double e_ref, uint32_t *status, size_t *peak, double *delta,
+                         double *polarity);
+TH_API int th_align_f64(const float *ref, size_t n_ref, uint32_t sr_ref, const float *probe, size_t n, uint32_t sr,
+                        const th_align_request *req, double *out, size_t cap_doubles, size_t *out_len);
+TH_API int th_tm_align_tracks(th_tm *tm, const th_align_request *reqs, size_t n, double *out, size_t cap_doubles,
+                              th_align_info *info /* n */, size_t *out_len);
+TH_API int th_tm_align_track(th_tm *tm, const th_align_request *req, double *out, size_t cap_doubles, th_align_info *info);
+
 /* ---------------------------------------------------------------- TrackManager over several devices (one process) */
 /* th_tmg: the th_tm_* calls above, call for call, with a th_tmg * in place of the th_tm *; a multi-GPU host swaps one for
  * the other.  Every result — updated ids, max_sr, db state, revisions, specs, images, tile bytes, batch offsets, render
@@ -1368,6 +1462,13 @@ TH_API int th_tmg_render_waveform_figure(th_tmg *tmg, const th_waveform_figure_r
 TH_API int th_tmg_get_formants(th_tmg *tmg, const th_formant_request *reqs, size_t n, double *out, size_t cap_doubles,
                                th_formant_info *info /* n */, size_t *out_len);
 TH_API int th_tmg_get_formant_track(th_tmg *tmg, const th_formant_request *req, double *out, size_t cap_doubles, th_formant_info *info);
+
+/* alignment: the same; the probe's slot runs a request.  A reference that lives on another slot is copied, its range only (at most
+ * TH_ALIGN_MAX_REF floats), through pinned host memory into the probe's slot before the run, so a request's doubles are those of one
+ * th_tm, bit for bit */
+TH_API int th_tmg_align_tracks(th_tmg *tmg, const th_align_request *reqs, size_t n, double *out, size_t cap_doubles,
+                               th_align_info *info /* n */, size_t *out_len);
+TH_API int th_tmg_align_track(th_tmg *tmg, const th_align_request *req, double *out, size_t cap_doubles, th_align_info *info);
 
 /* Test and measurement entry points (kernel selectors for A/B runs, per-launch kernel timing, replacing a resident image
  * with given pixels) are NOT part of this interface: include/thesia_amd_testing.h declares them; a thesia host binds none. */

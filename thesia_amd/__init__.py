@@ -14,7 +14,9 @@ from .api import (LINEAR, MEL, SPECTRUM_MAX, SPECTRUM_MEAN_AMP, SPECTRUM_MEAN_PO
                   FIGURE_RGBA, FIGURE_GREY16, figure_axis, figure_box,
                   edges, envelope_edges, waveform_figure_span,
                   FORMANT_WIN_GAUSS, FORMANT_WIN_RECT, FORMANT_OUT_FORMANTS, FORMANT_OUT_LPC, formant_request, formant_plan, formant_window,
-                  formant_start_points, formants_f64, formant_frame_f64)
+                  formant_start_points, formants_f64, formant_frame_f64,
+                  ALIGN_OUT_SUMMARY, ALIGN_OUT_CURVE, ALIGN_ABS, ALIGN_SUMMARY_DOUBLES, align_request, align_plan, xcorr_f64, align_energy_f64,
+                  align_peak, align_f64, align_summary)
 
 __all__ = ["LINEAR", "MEL", "SPECTRUM_MEAN_AMP", "SPECTRUM_MEAN_POWER", "SPECTRUM_MAX", "Context", "ab_variants", "DeviceBuffer", "Graph", "MultiTrackManager", "Plan", "TileCache", "TrackManager", "ThError", "calc_framing_params",
            "calc_mel_fb", "calc_normalized_win", "device_count", "gated_loudness", "global_db_range", "hz_range_to_idx", "k_weighting",
@@ -26,4 +28,6 @@ __all__ = ["LINEAR", "MEL", "SPECTRUM_MEAN_AMP", "SPECTRUM_MEAN_POWER", "SPECTRU
            "edges", "envelope_edges", "waveform_figure_span",
            "FORMANT_WIN_GAUSS", "FORMANT_WIN_RECT", "FORMANT_OUT_FORMANTS", "FORMANT_OUT_LPC", "formant_request", "formant_plan", "formant_window",
            "formant_start_points", "formants_f64", "formant_frame_f64",
+           "ALIGN_OUT_SUMMARY", "ALIGN_OUT_CURVE", "ALIGN_ABS", "ALIGN_SUMMARY_DOUBLES", "align_request", "align_plan", "xcorr_f64", "align_energy_f64",
+           "align_peak", "align_f64", "align_summary",
            "ChanDesc", "ImgDesc", "RasterDesc", "WaveDesc", "TileGeom", "LIB_PATH"]

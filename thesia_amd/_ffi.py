@@ -178,6 +178,22 @@ class FormantInfo(C.Structure):  # th_formant_info
                 ("n_invalid", C.c_uint64), ("n_unconverged", C.c_uint64), ("waveform_revision", C.c_uint64)]
 
 
+class AlignRequest(C.Structure):  # th_align_request
+    _fields_ = [("ref_id", C.c_size_t), ("ref_ch", C.c_uint32), ("ref_which", C.c_uint32), ("id", C.c_size_t), ("ch", C.c_uint32),
+                ("which", C.c_uint32), ("start_sec", C.c_double), ("end_sec", C.c_double), ("max_lag_sec", C.c_double),
+                ("kind", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class AlignPlan(C.Structure):  # th_align_plan
+    _fields_ = [("sr", C.c_uint32), ("max_lag", C.c_uint32), ("kind", C.c_uint32), ("flags", C.c_uint32), ("sample_start", C.c_uint64),
+                ("sample_end", C.c_uint64), ("n_lags", C.c_uint64), ("length", C.c_uint64)]
+
+
+class AlignInfo(C.Structure):  # th_align_info
+    _fields_ = [("offset", C.c_uint64), ("length", C.c_uint64), ("sr", C.c_uint32), ("max_lag", C.c_uint32), ("sample_start", C.c_uint64),
+                ("sample_end", C.c_uint64), ("waveform_revision", C.c_uint64)]
+
+
 class WaveformFigureRequest(C.Structure):  # th_waveform_figure_request
     _fields_ = [("env", EnvelopeRequest), ("out_h", C.c_uint32), ("amp_lo", C.c_float), ("amp_hi", C.c_float), ("thickness", C.c_uint32),
                 ("fill", C.c_uint8 * 4), ("background", C.c_uint8 * 4)]
@@ -445,6 +461,17 @@ _SIGS = {
     "th_tm_get_formant_track": [vp, C.POINTER(FormantRequest), C.POINTER(C.c_double), C.c_size_t, C.POINTER(FormantInfo)],
     "th_tmg_get_formants": [vp, C.POINTER(FormantRequest), C.c_size_t, C.POINTER(C.c_double), C.c_size_t, C.POINTER(FormantInfo), c_szp],
     "th_tmg_get_formant_track": [vp, C.POINTER(FormantRequest), C.POINTER(C.c_double), C.c_size_t, C.POINTER(FormantInfo)],
+    "th_align_plan_for": [C.c_uint32, C.c_size_t, C.c_uint32, C.c_size_t, C.POINTER(AlignRequest), C.POINTER(AlignPlan)],
+    "th_xcorr_f64": [c_f32p, C.c_size_t, c_f32p, C.c_size_t, C.c_int64, C.c_size_t, C.POINTER(C.c_double)],
+    "th_align_energy_f64": [c_f32p, C.c_size_t, C.c_int64, C.c_size_t, C.POINTER(C.c_double)],
+    "th_align_peak": [C.POINTER(C.c_double), C.c_size_t, C.c_uint32, C.c_double, C.POINTER(C.c_uint32), c_szp, C.POINTER(C.c_double),
+                      C.POINTER(C.c_double)],
+    "th_align_f64": [c_f32p, C.c_size_t, C.c_uint32, c_f32p, C.c_size_t, C.c_uint32, C.POINTER(AlignRequest), C.POINTER(C.c_double),
+                     C.c_size_t, c_szp],
+    "th_tm_align_tracks": [vp, C.POINTER(AlignRequest), C.c_size_t, C.POINTER(C.c_double), C.c_size_t, C.POINTER(AlignInfo), c_szp],
+    "th_tm_align_track": [vp, C.POINTER(AlignRequest), C.POINTER(C.c_double), C.c_size_t, C.POINTER(AlignInfo)],
+    "th_tmg_align_tracks": [vp, C.POINTER(AlignRequest), C.c_size_t, C.POINTER(C.c_double), C.c_size_t, C.POINTER(AlignInfo), c_szp],
+    "th_tmg_align_track": [vp, C.POINTER(AlignRequest), C.POINTER(C.c_double), C.c_size_t, C.POINTER(AlignInfo)],
     "th_tm_render_waveform_figures": [vp, C.POINTER(WaveformFigureRequest), C.c_size_t, C.c_void_p, C.c_size_t,
                                       C.POINTER(WaveformFigureInfo), c_szp],
     "th_tm_render_waveform_figure": [vp, C.POINTER(WaveformFigureRequest), C.c_void_p, C.c_size_t, C.POINTER(WaveformFigureInfo)],

@@ -913,6 +913,110 @@ class _FormantMethods:
         return out[:info.length].reshape(-1, 2 + req.n_poles), _export_info_dict(info)
 
 
+ALIGN_OUT_SUMMARY, ALIGN_OUT_CURVE = 0, 1
+ALIGN_ABS = 1
+ALIGN_SUMMARY_DOUBLES = 10
+ALIGN_MAX_REF, ALIGN_MAX_LAG, ALIGN_MAX_WORK, ALIGN_PIECE_LAGS = 1 << 22, 1 << 20, 1 << 40, 65536
+ALIGN_SUMMARY_FIELDS = ("status", "lag", "delta", "r", "e_ref", "e_probe", "rho", "gain", "null_dB", "polarity")
+
+
+def align_request(ref_id: int = 0, ref_ch: int = 0, track_id: int = 0, ch: int = 0, start_sec: float = 0.0, end_sec: float = float("inf"),
+                  max_lag_sec: float = 0.0, kind: int = ALIGN_OUT_SUMMARY, flags: int = 0, ref_which: int = 0, which: int = 0) -> "_ffi.AlignRequest":
+    """th_align_request: the reference (ref_id, ref_ch, ref_which), the probe (track_id, ch, which), a range of the reference, the
+    largest lag searched, ALIGN_OUT_*, ALIGN_ABS or 0"""
+    return _ffi.AlignRequest(ref_id, ref_ch, ref_which, track_id, ch, which, start_sec, end_sec, max_lag_sec, kind, flags)
+
+
+def _align_request(r) -> "_ffi.AlignRequest":
+    """an AlignRequest (align_request), or a dict of its keywords"""
+    return r if isinstance(r, _ffi.AlignRequest) else align_request(**r)
+
+
+def align_plan(sr_ref: int, n_ref: int, sr: int, n: int, req) -> dict:
+    """th_align_plan_for -> the numbers of a request as a dict (host)"""
+    req, pl = _align_request(req), _ffi.AlignPlan()
+    check(lib.th_align_plan_for(sr_ref, n_ref, sr, n, C.byref(req), C.byref(pl)))
+    return {k: getattr(pl, k) for k, _ in pl._fields_}
+
+
+def xcorr_f64(a, b, first: int, n_lags: int) -> np.ndarray:
+    """th_xcorr_f64: r[i] = sum_k a[k] b[first + i + k], i < n_lags, in the reader's order (host) -> float64[n_lags]"""
+    a, b = _f32(a).ravel(), _f32(b).ravel()
+    r = np.empty(max(int(n_lags), 1), np.float64)
+    check(lib.th_xcorr_f64(_ptr(a, c_f32p), a.size, _ptr(b, c_f32p), b.size, first, n_lags, _ptr(r, c_f64p)))
+    return r[:n_lags]
+
+
+def align_energy_f64(x, first: int, n_sum: int) -> float:
+    """th_align_energy_f64: E(x, first, n_sum) in the reader's order (host)"""
+    x, e = _f32(x).ravel(), C.c_double()
+    check(lib.th_align_energy_f64(_ptr(x, c_f32p), x.size, first, n_sum, C.byref(e)))
+    return e.value
+
+
+def align_peak(r, flags: int, e_ref: float) -> dict:
+    """th_align_peak: the host's step on a curve -> dict(status, peak (index into r), delta, polarity)"""
+    r = np.ascontiguousarray(r, np.float64).ravel()
+    st, pk, de, po = C.c_uint32(), C.c_size_t(), C.c_double(), C.c_double()
+    check(lib.th_align_peak(_ptr(r, c_f64p), r.size, flags, e_ref, C.byref(st), C.byref(pk), C.byref(de), C.byref(po)))
+    return {"status": st.value, "peak": pk.value, "delta": de.value, "polarity": po.value}
+
+
+def align_f64(ref, sr_ref: int, probe, sr: int, req) -> np.ndarray:
+    """th_align_f64: a whole request from two host channels, the reader's bits -> float64[ALIGN_SUMMARY_DOUBLES (+ n_lags)]"""
+    ref, probe, req = _f32(ref).ravel(), _f32(probe).ravel(), _align_request(req)
+    need = C.c_size_t()
+    rc = lib.th_align_f64(_ptr(ref, c_f32p), ref.size, sr_ref, _ptr(probe, c_f32p), probe.size, sr, C.byref(req), None, 0, C.byref(need))
+    if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+        check(rc)
+    out = np.empty(max(need.value, 1), np.float64)
+    check(lib.th_align_f64(_ptr(ref, c_f32p), ref.size, sr_ref, _ptr(probe, c_f32p), probe.size, sr, C.byref(req), _ptr(out, c_f64p), out.size,
+                           C.byref(need)))
+    return out[:need.value]
+
+
+def align_summary(rec) -> dict:
+    """the first ALIGN_SUMMARY_DOUBLES doubles of a request's record as a dict (ALIGN_SUMMARY_FIELDS)"""
+    return dict(zip(ALIGN_SUMMARY_FIELDS, (float(v) for v in rec[:ALIGN_SUMMARY_DOUBLES])))
+
+
+class _AlignMethods:
+    """lag, gain and null depth of a probe channel against a range of a reference channel (th_tm_* and th_tmg_*: _PFX).  A positive lag:
+    the probe is late; subtract lag / sr from the probe's time arguments"""
+
+    def align_tracks(self, requests, out: Optional[np.ndarray] = None):
+        """th_tm_align_tracks: requests = iterable of align_request(...) or dicts of its keywords -> (list of float64 records: the ten
+        summary doubles, then the curve for ALIGN_OUT_CURVE; list of info dicts).  out: a float64 array to fill instead of a new one;
+        the records are then views into it."""
+        reqs = [_align_request(r) for r in requests]
+        n = len(reqs)
+        if n == 0:
+            return [], []
+        arr = (_ffi.AlignRequest * n)(*reqs)
+        info = (_ffi.AlignInfo * n)()
+        need = C.c_size_t()
+        fn = getattr(lib, self._PFX + "align_tracks")
+        if out is None:
+            rc = fn(self.handle, arr, n, None, 0, info, C.byref(need))
+            if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+                check(rc)
+            out = np.empty(max(need.value, 1), np.float64)
+        check(fn(self.handle, arr, n, _ptr(out, c_f64p), out.size, info, C.byref(need)))
+        return [out[o.offset: o.offset + o.length] for o in info], [_export_info_dict(o) for o in info]
+
+    def align_track(self, ref_id: int, ref_ch: int, track_id: int, ch: int, **kw):
+        """th_tm_align_track -> (float64 record, info dict) of one request (keywords: align_request)"""
+        req = align_request(ref_id, ref_ch, track_id, ch, **kw)
+        info = _ffi.AlignInfo()
+        fn = getattr(lib, self._PFX + "align_track")
+        rc = fn(self.handle, C.byref(req), None, 0, C.byref(info))
+        if rc not in (_ffi.OK, _ffi.ERR_BUFFER_TOO_SMALL):
+            check(rc)
+        out = np.empty(max(info.length, 1), np.float64)
+        check(fn(self.handle, C.byref(req), _ptr(out, c_f64p), out.size, C.byref(info)))
+        return out[:info.length], _export_info_dict(info)
+
+
 def true_peak_filter(sr: int):
     """-> (factor, coef f64, phase, delay) of the kept taps of the true-peak interpolator at rate sr, ascending tap index (host)"""
     f, n = C.c_uint32(), C.c_uint32()
@@ -1426,7 +1530,7 @@ class TileCache:
                 "spectrogram_revision": sr.value, "hits": h.value, "misses": m.value}
 
 
-class TrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods, _ExportAtMethods, _ExportBandMethods, _FigureMethods, _EnvelopeMethods, _FormantMethods):
+class TrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods, _ExportAtMethods, _ExportBandMethods, _FigureMethods, _EnvelopeMethods, _FormantMethods, _AlignMethods):
     """th_tm: mirror of core/mod.rs TrackManager with HBM-resident audio / specs / images."""
     _PFX = "th_tm_"
 
@@ -1626,7 +1730,7 @@ class TrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _E
         return out[: n.value].tobytes()
 
 
-class MultiTrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods, _ExportAtMethods, _ExportBandMethods, _FigureMethods, _EnvelopeMethods, _FormantMethods):
+class MultiTrackManager(_DynamicsMethods, _SpectrumMethods, _LoudnessMeterMethods, _ExportMethods, _ExportAtMethods, _ExportBandMethods, _FigureMethods, _EnvelopeMethods, _FormantMethods, _AlignMethods):
     """th_tmg: the TrackManager over several devices of one process (duplicates allowed: [0, 0] is two slots on one card).
     Same method names as TrackManager; results are bit-identical to one TrackManager holding every track."""
     _PFX = "th_tmg_"

@@ -13,6 +13,7 @@
 #include "stft_core.h"
 #include "envelope_plan.h"  // EnvJob, LaneSpanJob, LaneRasterJob, ENV_* (the chunk grid of kernels_envelope.hip)
 #include "formant_plan.h"  // FormantJob
+#include "align_plan.h"  // AlignJob, ALIGN_* (the tile shape of kernels_align.hip)
 #include "flac_plan.h"  // FlacJob
 #include "figure_plan.h"  // FigHJob, FigVJob, FIG_* (the tile shape of kernels_figure.hip)
 #include "reader_plan.h"  // LoudJob, LoudTrackJob, TruePeakJob, ExportJob, ResampleJob, ResampleTiling and their constants
@@ -314,5 +315,11 @@ hipError_t launch_lane_raster(const LaneRasterJob *d_jobs, uint32_t n_jobs, uint
 // ---- kernels_formant.hip: the raw LPC / root record of every frame of a piece (FormantJob: formant_plan.h).  n_blocks: the piece's
 // frames; max_W, max_p: the largest of its jobs (they size the launch's LDS)
 hipError_t launch_formants(const FormantJob *d_jobs, uint32_t n_jobs, uint32_t n_blocks, uint32_t max_W, uint32_t max_p, hipStream_t s);
+
+// ---- kernels_align.hip: the cross-correlation of one piece (AlignJob: align_plan.h; passed by value, no device table): the group
+// values into job.scratch, then their fold over the groups, job.n_lags doubles, into d_rec.  launch_align_energy: the group values of
+// E(x, first, N) (x: a track of n samples, +0 outside) into d_groups[0 .. align_n_groups(N)); the host folds them (align_fold)
+hipError_t launch_align_xcorr(const AlignJob &job, double *d_rec, hipStream_t s);
+hipError_t launch_align_energy(const float *d_x, uint64_t n, int64_t first, uint64_t N, double *d_groups, hipStream_t s);
 
 }  // namespace th

@@ -126,6 +126,16 @@ struct ReaderSlot {
     th::DeviceTable fm_tab;
     th::DeviceBuf<double> fm_rec[2];
     size_t fm_rec_cap[2] = {0, 0};  // doubles
+    // th_tm_align_tracks: the group values of one piece (n_groups x lags doubles, at most 32 x TH_ALIGN_PIECE_LAGS = 16 MiB), the folded
+    // curve of two pieces (each at most TH_ALIGN_PIECE_LAGS doubles) and the group values of the two energies (2 x 32 doubles); under
+    // th_tmg the range of a reference that lives in another manager (at most TH_ALIGN_MAX_REF floats) and the pinned host buffer it
+    // comes through.  The copy stream and its events are the export's.  Empty until the slot's first alignment
+    th::DeviceBuf<double> al_scratch, al_rec[2], al_en;
+    size_t al_scratch_cap = 0, al_rec_cap[2] = {0, 0};  // doubles
+    th::DeviceBuf<float> al_ref;
+    size_t al_ref_cap = 0;  // floats
+    float *al_ref_host = nullptr;  // pinned
+    size_t al_ref_host_cap = 0;    // floats
 };
 constexpr size_t TILE_BYTES_MAX = 520 * 520 * 4;  // 512 core + 2 x 4 gutter (render_tiles.rs:15-16); >= 1024 * 12 waveform bins
 constexpr size_t MAX_READER_SLOTS = 16;
@@ -896,6 +906,7 @@ TH_API int th_tm_destroy(th_tm *tm) {
         (void)hipStreamSynchronize(sp->stream);
         (void)hipStreamDestroy(sp->stream);
         (void)hipHostFree(sp->h_tile);
+        if (sp->al_ref_host) (void)hipHostFree(sp->al_ref_host);
         if (sp->exp_copy) (void)hipStreamDestroy(sp->exp_copy);
         for (int b = 0; b < 2; b++) {
             if (sp->exp_done[b]) (void)hipEventDestroy(sp->exp_done[b]);
@@ -3373,6 +3384,169 @@ int formants_run(th_tm *tm, size_t n, FormantInfo *info, double *out) {
     TH_HIP(hipStreamSynchronize(sl.stream));
     return TH_OK;
 }
+
+// ---------------------------------------------------------------------------------------------- alignment of two tracks
+// th_tm_align_tracks: a reader.  align_plan_for checks a request and makes its numbers; plan_align (align_plan.h) cuts a request into
+// pieces of lags; what is left here is the slot, its buffers and, request after request: the reference's energy, per piece the
+// correlation kernel and its fold into record buffer p & 1 and one copy on the slot's copy stream while the next piece computes, then
+// the host's step on the curve, the probe's energy at the lag it found, and the summary.
+int align_request_info(th_tm *tm, const AlignReq &ar, size_t i, AlignInfo *info) {
+    const th_align_request &r = ar.r;
+    *info = AlignInfo{};
+    auto it = tm->tracks.find(r.id);
+    if (it == tm->tracks.end()) return fail(TH_ERR_NOT_FOUND, "request %zu: Track %zu does not exist", i, r.id);
+    th_tm *home = ar.home_of ? ar.home_of(ar.who, r.ref_id) : tm;
+    const Track *rt = nullptr;
+    if (home) {
+        auto ir = home->tracks.find(r.ref_id);
+        if (ir != home->tracks.end()) rt = &ir->second;
+    }
+    if (!rt) return fail(TH_ERR_NOT_FOUND, "request %zu: reference Track %zu does not exist", i, r.ref_id);
+    const Track &pt = it->second;
+    TH_REQUIRE(r.ch < pt.ch.size(), "request %zu: Track %zu has no channel %u", i, r.id, r.ch);
+    TH_REQUIRE(r.ref_ch < rt->ch.size(), "request %zu: reference Track %zu has no channel %u", i, r.ref_id, r.ref_ch);
+    TH_REQUIRE(r.which <= 2 && r.ref_which <= 2, "request %zu: which must be 0 (audio), 1 (drawn) or 2 (original)", i);
+    const Channel &pc = pt.ch[r.ch], &rc = rt->ch[r.ref_ch];
+    const int rcode = align_plan_for(rt->sr, rc.n, pt.sr, pc.n, r, &info->pl);
+    TH_REQUIRE(rcode != 1, "request %zu: bad alignment request: [%g, %g) s of the reference at %u Hz, lags up to %g s, kind %u, flags %u", i,
+               r.start_sec, r.end_sec, rt->sr, r.max_lag_sec, r.kind, r.flags);
+    if (rcode != 0)
+        return fail(TH_ERR_UNSUPPORTED,
+                    "request %zu: [%g, %g) s at %u Hz against %u Hz over %g s of lag: the rates must be equal, the range at most %u samples, "
+                    "the lag at most %u samples, their product at most 2^40",
+                    i, r.start_sec, r.end_sec, rt->sr, pt.sr, r.max_lag_sec, TH_ALIGN_MAX_REF, TH_ALIGN_MAX_LAG);
+    const th_align_plan &pl = info->pl;
+    info->ref = r.ref_which == 0 ? rc.d_wav : r.ref_which == 1 ? rc.d_draw : rc.d_orig;
+    info->probe = r.which == 0 ? pc.d_wav : r.which == 1 ? pc.d_draw : pc.d_orig;
+    info->n_probe = pc.n;
+    info->ref_home = home;
+    info->length = pl.length;
+    info->sr = pl.sr;
+    info->max_lag = pl.max_lag;
+    info->sample_start = pl.sample_start;
+    info->sample_end = pl.sample_end;
+    info->waveform_revision = tm->waveform_revision();
+    return TH_OK;
+}
+
+namespace {
+// the calling thread's device goes back to the slot's own when the reference's manager has been read
+struct DeviceBack {
+    int device;
+    ~DeviceBack() { (void)hipSetDevice(device); }
+};
+
+// n samples at src, in manager `home` (another one than the slot's: a slot of the same th_tmg, whose lock the caller holds, so no writer
+// is in either), into the slot's al_ref: by home's device into pinned host memory, from there up on the slot's stream
+int align_stage_ref(th_tm *tm, ReaderSlot &sl, th_tm *home, const float *src, size_t n) {
+    if (sl.al_ref_host_cap < n) {
+        size_t want = 1 << 16;
+        while (want < n) want <<= 1;
+        if (sl.al_ref_host) TH_HIP(hipHostFree(sl.al_ref_host));
+        sl.al_ref_host = nullptr;
+        sl.al_ref_host_cap = 0;
+        TH_HIP(hipHostMalloc((void **)&sl.al_ref_host, want * sizeof(float), hipHostMallocPortable));
+        sl.al_ref_host_cap = want;
+    }
+    TH_CHECK(grow_export_buf(sl, sl.al_ref, sl.al_ref_cap, n, 1 << 16, TH_ALIGN_MAX_REF, nullptr));
+    {
+        std::shared_lock<std::shared_mutex> hl(home->rw);
+        DeviceBack back{tm->ctx->device};
+        TH_HIP(hipSetDevice(home->ctx->device));
+        TH_HIP(hipMemcpy(sl.al_ref_host, src, n * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    TH_HIP(hipMemcpyAsync(sl.al_ref.get(), sl.al_ref_host, n * sizeof(float), hipMemcpyHostToDevice, sl.stream));
+    TH_HIP(hipStreamSynchronize(sl.stream));  // (the pinned buffer is the next staged request's too)
+    return TH_OK;
+}
+}  // namespace
+
+int align_run(th_tm *tm, size_t n, AlignInfo *info, double *out) {
+    TH_HIP(hipSetDevice(tm->ctx->device));
+    SlotLease lease{tm, nullptr};
+    int rc = acquire_slot(tm, &lease.slot);
+    if (rc != TH_OK) return rc;
+    ReaderSlot &sl = *lease.slot;
+    if (!sl.exp_copy) {
+        TH_HIP(hipStreamCreateWithFlags(&sl.exp_copy, hipStreamNonBlocking));
+        for (int b = 0; b < 2; b++) {
+            TH_HIP(hipEventCreateWithFlags(&sl.exp_done[b], hipEventDisableTiming));
+            TH_HIP(hipEventCreateWithFlags(&sl.exp_copied[b], hipEventDisableTiming));
+        }
+    }
+    std::vector<double> curve;  // (behind the drain: alive until the copies are done)
+    double h_en[2 * ALIGN_GROUP_BLOCKS];
+    ExportDrain drain{&sl};
+    if (!sl.al_en.get()) TH_HIP(sl.al_en.alloc(sizeof h_en));
+    for (size_t i = 0; i < n; i++) {
+        const th_align_plan &pl = info[i].pl;
+        const uint64_t s0 = pl.sample_start, N = pl.sample_end - pl.sample_start;
+        const uint32_t D = pl.max_lag, n_groups = (uint32_t)align_n_groups(N);
+        double *dst = out + info[i].offset;
+        AlignPeak pk{1u, 0, 0.0, 1.0};
+        if (pl.n_lags == 0) {  // (an empty range: nothing to launch)
+            align_summary(pk, nullptr, D, 0.0, 0.0, dst);
+            continue;
+        }
+        double *r = dst + TH_ALIGN_SUMMARY_DOUBLES;
+        if (pl.kind != TH_ALIGN_OUT_CURVE) {
+            curve.resize((size_t)pl.n_lags);
+            r = curve.data();
+        }
+        const float *a = info[i].ref + s0;
+        if (info[i].ref_home != tm) {
+            TH_CHECK(align_stage_ref(tm, sl, info[i].ref_home, a, (size_t)N));
+            a = sl.al_ref.get();
+        }
+        const AlignPieces ap = plan_align(N, pl.n_lags);
+        const std::vector<AlignPiece> &pieces = ap.pieces;
+        TH_CHECK(grow_export_buf(sl, sl.al_scratch, sl.al_scratch_cap, (size_t)ap.scratch_doubles, 1 << 16,
+                                 (size_t)ALIGN_GROUP_BLOCKS * TH_ALIGN_PIECE_LAGS, nullptr));
+        for (int b = 0; b < 2; b++)  // (the copy stream reads them too)
+            if ((size_t)b < pieces.size())
+                TH_CHECK(grow_export_buf(sl, sl.al_rec[b], sl.al_rec_cap[b], (size_t)ap.rec_doubles, 1 << 12, TH_ALIGN_PIECE_LAGS, sl.exp_copy));
+        TH_HIP(launch_align_energy(a, N, 0, N, sl.al_en.get(), sl.stream));
+        auto launch_piece = [&](size_t p) -> int {
+            const AlignPiece &pc = pieces[p];
+            AlignJob job{};
+            job.a = a;
+            job.b = info[i].probe;
+            job.scratch = sl.al_scratch.get();
+            job.N = N;
+            job.n_b = info[i].n_probe;
+            job.first = (int64_t)s0 - (int64_t)D + (int64_t)pc.lag0;
+            job.n_lags = pc.n_lags;
+            job.n_tiles = pc.n_tiles;
+            job.n_groups = pc.n_groups;
+            TH_HIP(launch_align_xcorr(job, sl.al_rec[p & 1].get(), sl.stream));
+            TH_HIP(hipEventRecord(sl.exp_done[p & 1], sl.stream));
+            return TH_OK;
+        };
+        TH_CHECK(launch_piece(0));
+        for (size_t p = 0; p < pieces.size(); p++) {
+            // (piece p + 1 goes into the other buffer; the copy of piece p - 1 out of it has been waited for below)
+            if (p + 1 < pieces.size()) TH_CHECK(launch_piece(p + 1));
+            TH_HIP(hipStreamWaitEvent(sl.exp_copy, sl.exp_done[p & 1], 0));
+            TH_HIP(hipMemcpyAsync(r + pieces[p].lag0, sl.al_rec[p & 1].get(), (size_t)pieces[p].n_lags * sizeof(double), hipMemcpyDeviceToHost,
+                                  sl.exp_copy));
+            TH_HIP(hipStreamSynchronize(sl.exp_copy));
+        }
+        TH_HIP(hipMemcpyAsync(h_en, sl.al_en.get(), n_groups * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
+        TH_HIP(hipStreamSynchronize(sl.stream));
+        const double e_ref = align_fold(h_en, n_groups, 1);
+        pk = align_peak(r, pl.n_lags, pl.flags, e_ref);
+        double e_probe = 0.0;
+        if (pk.status == 0) {  // (the probe's energy where the peak was found)
+            double *d_en = sl.al_en.get() + ALIGN_GROUP_BLOCKS, *h = h_en + ALIGN_GROUP_BLOCKS;
+            TH_HIP(launch_align_energy(info[i].probe, info[i].n_probe, (int64_t)s0 + (int64_t)pk.index - (int64_t)D, N, d_en, sl.stream));
+            TH_HIP(hipMemcpyAsync(h, d_en, n_groups * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
+            TH_HIP(hipStreamSynchronize(sl.stream));
+            e_probe = align_fold(h, n_groups, 1);
+        }
+        align_summary(pk, r, D, e_ref, e_probe, dst);
+    }
+    return TH_OK;
+}
 }  // namespace tmi
 }  // namespace th
 
@@ -3421,6 +3595,20 @@ TH_API int th_tm_get_formant_track(th_tm *tm, const th_formant_request *req, dou
     TH_TRY
     TH_REQUIRE(tm && req, "NULL argument");
     return br::single_read(info, [&](th_formant_info *one, size_t *len) { return th_tm_get_formants(tm, req, 1, out, cap, one, len); });
+    TH_CATCH
+}
+
+TH_API int th_tm_align_tracks(th_tm *tm, const th_align_request *reqs, size_t n, double *out, size_t cap, th_align_info *info, size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(n == 0 || reqs, "NULL argument");
+    return br::batched_read<tmi::AlignReader>(TmReaders{tm}, tmi::align_requests(reqs, n, nullptr, nullptr).data(), n, out, cap, info, out_len);
+    TH_CATCH
+}
+
+TH_API int th_tm_align_track(th_tm *tm, const th_align_request *req, double *out, size_t cap, th_align_info *info) {
+    TH_TRY
+    TH_REQUIRE(tm && req, "NULL argument");
+    return br::single_read(info, [&](th_align_info *one, size_t *len) { return th_tm_align_tracks(tm, req, 1, out, cap, one, len); });
     TH_CATCH
 }
 

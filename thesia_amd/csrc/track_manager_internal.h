@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "batched_reader.h"
+#include "align_plan.h"
 #include "common.h"
 #include "envelope_plan.h"
 #include "figure_plan.h"
@@ -55,7 +56,7 @@ int prepare_dynamics(th_tm *tm, int kind, float target, int mode, StagedPtr *out
 void get_common_dynamics(th_tm *tm, int *kind, float *target, int *mode);
 void commit(th_tm *tm, StagedPtr staged);
 
-// The batched readers (spectra, loudness meters, export, figures, envelopes, waveform figures, formants): each is a traits struct,
+// The batched readers (spectra, loudness meters, export, figures, envelopes, waveform figures, formants, alignment): each is a traits struct,
 // beside its Info, that batched_reader.h's br::batched_read drives over either manager: NULL arguments, n == 0, the shared lock, every
 // request checked in request order, the layout, the manager's revision stamped, the infos and the length published, a short buffer
 // reported, the run, the infos published again where the run updates them.  th_tm is one owner: every request is checked against it
@@ -320,6 +321,51 @@ struct FormantReader : br::ReaderDefaults {
     static size_t layout(Info *info, size_t n) { return br::layout_back_to_back(info, n, &Info::length); }
     static int run(th_tm *tm, size_t n, Info *info, Out *out) { return formants_run(tm, n, info, out); }
 };
+
+// Alignment of two tracks.  A request names two tracks; the probe's decides the owner, and the reference is looked for in the manager
+// home_of(who, ref_id) returns (NULL: no manager holds it), or, with home_of == NULL, in the owner itself: th_tm passes none, th_tmg
+// its own track table, so that check reports one request's faults in one order for both.  *info: the plan, the two resident channels
+// and the reference's manager; where that is not the run's own manager the run stages the reference's range (it takes that manager's
+// shared lock for the copy; the caller holds the lock that keeps writers out of both).  Requests back to back, in doubles.
+// align_run: request i's doubles to out + info[i].offset
+struct AlignReq {
+    th_align_request r;
+    th_tm *(*home_of)(void *who, size_t id);
+    void *who;
+};
+struct AlignInfo : th_align_info {
+    th_align_plan pl;
+    const float *ref, *probe;  // the whole channels (ref: in ref_home's device memory)
+    uint64_t n_probe;
+    th_tm *ref_home;
+};
+int align_request_info(th_tm *tm, const AlignReq &r, size_t i, AlignInfo *info);
+int align_run(th_tm *tm, size_t n, AlignInfo *info, double *out);
+struct AlignReader : br::ReaderDefaults {
+    using Request = AlignReq;
+    using Info = AlignInfo;
+    using Public = th_align_info;
+    using Out = double;
+    static constexpr const char *unit = "doubles";
+    static constexpr Revision revision = Revision::waveform;
+    static constexpr bool needs_colormap = false, run_updates_infos = false;
+    static size_t id_of(const Request &r) { return r.r.id; }
+    static int check(th_tm *tm, const Request &r, size_t i, Info *info) { return align_request_info(tm, r, i, info); }
+    static size_t layout(Info *info, size_t n) {
+        uint64_t at = 0;
+        for (size_t i = 0; i < n; i++) {
+            info[i].offset = at;
+            at += info[i].length;
+        }
+        return (size_t)at;
+    }
+    static int run(th_tm *tm, size_t n, Info *info, Out *out) { return align_run(tm, n, info, out); }
+};
+inline std::vector<AlignReq> align_requests(const th_align_request *reqs, size_t n, th_tm *(*home_of)(void *, size_t), void *who) {
+    std::vector<AlignReq> out(n);
+    for (size_t i = 0; i < n; i++) out[i] = AlignReq{reqs[i], home_of, who};
+    return out;
+}
 
 // update_spec_imgs against `global` (NULL: the manager's own tracks, as th_tm_* does), then the writer's final wait:
 // for the images only (apply_track_list_changes, set_dB_range) or for everything (set_setting, set_colormap)

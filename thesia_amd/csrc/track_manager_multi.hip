@@ -797,6 +797,30 @@ TH_API int th_tmg_get_formant_track(th_tmg *g, const th_formant_request *req, do
     TH_CATCH
 }
 
+// Alignment: the probe's slot owns a request; the reference is found in the manager's track table (under g->rw, which the driver
+// holds from the check to the run) and, where it lives on another slot, staged by the run
+namespace {
+th_tm *align_home_of(void *who, size_t id) {
+    const th_tmg *g = static_cast<const th_tmg *>(who);
+    const th_tmg::Placement *p = find_track(g, id);
+    return p ? g->slots[p->slot].tm : nullptr;
+}
+}  // namespace
+
+TH_API int th_tmg_align_tracks(th_tmg *g, const th_align_request *reqs, size_t n, double *out, size_t cap, th_align_info *info, size_t *out_len) {
+    TH_TRY
+    TH_REQUIRE(n == 0 || reqs, "NULL argument");
+    return br::batched_read<tmi::AlignReader>(TmgReaders{g}, tmi::align_requests(reqs, n, align_home_of, g).data(), n, out, cap, info, out_len);
+    TH_CATCH
+}
+
+TH_API int th_tmg_align_track(th_tmg *g, const th_align_request *req, double *out, size_t cap, th_align_info *info) {
+    TH_TRY
+    TH_REQUIRE(g && req, "NULL argument");
+    return br::single_read(info, [&](th_align_info *one, size_t *len) { return th_tmg_align_tracks(g, req, 1, out, cap, one, len); });
+    TH_CATCH
+}
+
 TH_API int th_tmg_render_waveform_figures(th_tmg *g, const th_waveform_figure_request *reqs, size_t n, uint8_t *out, size_t cap,
                                           th_waveform_figure_info *info, size_t *out_len) {
     TH_TRY
